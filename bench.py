@@ -11,14 +11,24 @@ RMSProp, on synthetic 84x84x4 uint8 frames generated on the device; value = env-
 slowest rank's wall time (weak scaling: 32 envs per GPU).  Workload at N=1 = BASELINE configs[1]
 (Breakout action set, Nature net, 32 envs, t_max=5).
 
-The timed region is repeated: consecutive windows of exactly K steps, each bracketed by barrier + synchronize on both
-sides and reduced with MAX over ranks; `value` / `ms_per_step` are the MEDIAN window's, all windows are listed in
-`windows_ms`.  `--windows` fixes their number; by default there are at least 9 and as many more as it takes to time a
-quarter of a second (at most 51): a 20-step window is 4.5 ms and the GPU clock is still ramping through the first three
+A plain run sets up, runs the W warm-up steps, times exactly K steps in one window bracketed by barrier + synchronize on
+both sides (reduced with MAX over ranks), writes the outputs of the last step if --dump-outputs is given, and prints the
+JSON line; `ms_per_step` is that window's time / K.  Everything else it can measure is behind --full.
+
+--windows N times N consecutive K-step windows instead; `value` / `ms_per_step` are then the MEDIAN window's, all windows
+are listed in `windows_ms`.  --windows 0 (the default with --full) times at least 9 and as many more as it takes to time
+a quarter of a second (at most 51): a 20-step window is 4.5 ms and the GPU clock is still ramping through the first three
 or four of them, so with nine short windows the median itself sat on the ramp (707 k against 719 k from 300-step windows
 on the same box).
 
-Extra objects on the JSON line:
+--dump-outputs DIR writes, after the timed steps and before anything --full adds, what the last timed step computed on
+rank 0 as float32 .npy files: the weights and the RMSProp mean-square slot after its update (param_<tensor>.npy,
+rms_<tensor>.npy), its rollout (actions, values, rewards, masks: [t_max, envs]), n-step returns and advantages
+([t_max * envs]), the policy of its last acting step ([envs, actions]), loss terms (loss, actor, critic, entropy), learning
+rate and gradient norm.  Inputs are seeded, so the same arguments give the same inputs from run to run.  An array larger
+than its share of 64 MB is replaced by a fixed, seeded sample of its elements (a line on stderr names each one).
+
+Extra objects on the JSON line (--full only; null in a plain run):
   roofline     -- the kernel family with the largest share of the cycle, timed with HIP events attached to the
                   kernel dispatches (hipExtLaunchKernelGGL start/stop events on the launch stream) in a second,
                   eager (graph-free) pass over the same K steps; achieved = algorithmic FLOPs (or bytes) per
@@ -26,8 +36,8 @@ Extra objects on the JSON line:
   cpu_baseline -- oracle/cpu_learner.py (torch-CPU port of the reference loop; the reference's TF path cannot
                   run here) on a bounded sample, rank 0, N=1 only: thread count calibrated once, then the median of
                   three equal windows.
-  host_plugin_loop (only with --host-envs) -- the same workload with the environments as host BaseEnvironment
-                  plugins (PAACLearner._train_host: per step 32 x 28 KB observations H2D + the action indices D2H,
+  host_plugin_loop (only with --host-envs, with or without --full) -- the same workload with the environments as host
+                  BaseEnvironment plugins (PAACLearner._train_host: per step 32 x 28 KB observations H2D + the action indices D2H,
                   eager launches): the PCIe-inclusive rate a real emulator would see.  Reported beside `value`, never as it.
 """
 import argparse
@@ -123,6 +133,37 @@ def time_host_plugin_loop(a, train, PAACLearner, np, cycles=60, warm=10):
                      "eager launches; PCIe-inclusive, not `value`")
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(folder, ro, learner, np):
+    """What the last run cycle computed (rank 0's shard), as float32 .npy files in `folder`; arrays too large for their
+    share of DUMP_BUDGET_BYTES are replaced by a sorted sample of their flattened elements (RandomState(0), no repeats)."""
+    ro.synchronize()
+    L = learner
+    out = [("param_" + k, v) for k, v in L.network.get_parameters().items()]
+    out += [("rms_" + k, v) for k, v in L.network.get_parameters(L.rms).items()]
+    for name, t in (("actions", ro.actions), ("values", ro.values), ("rewards", ro.rewards), ("masks", ro.masks),
+                    ("returns", ro.y), ("advantages", ro.adv), ("policy", ro.probs), ("loss", L.loss_dev),
+                    ("lr", L.lr_dev), ("grad_norm", L.gnorm_dev)):
+        out.append((name, t.detach().cpu().numpy()))
+    out = [(name, np.ascontiguousarray(a, dtype=np.float32)) for name, a in out]
+    # water-filling: the smaller arrays are kept whole, the largest share what is left equally (256 B per file for the
+    # .npy header)
+    left, keep = (DUMP_BUDGET_BYTES - 256 * len(out)) // 4, {}
+    by_size = sorted(out, key=lambda na: na[1].size)
+    for i, (name, a) in enumerate(by_size):
+        keep[name] = min(a.size, left // (len(by_size) - i))
+        left -= keep[name]
+    os.makedirs(folder, exist_ok=True)
+    for name, a in out:
+        if keep[name] < a.size:
+            print("bench.py: %s.npy holds %d of %d elements (sorted sample, RandomState(0))" % (name, keep[name], a.size),
+                  file=sys.stderr)
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep[name], replace=False))]
+        np.save(os.path.join(folder, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -135,15 +176,21 @@ def main():
     ap.add_argument("--sampler", default="numpy", choices=["numpy", "philox"])
     ap.add_argument("--raw-frames", action="store_true", help="path B: raw 210x160 frame pairs + GPU preprocess")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the event-timed roofline pass, the CPU baseline and, unless --windows is given, repeated windows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the event-timed roofline pass")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--windows", type=int, default=0,
+    ap.add_argument("--windows", type=int, default=None,
                     help="consecutive K-step windows, the median one is reported; 0 = at least 9, more while they add up to "
-                         "less than 0.25 s (at most 51)")
+                         "less than 0.25 s (at most 51); default 1, with --full 0")
     ap.add_argument("--host-envs", action="store_true",
                     help="also time the host-plugin loop (PCIe-inclusive) on the same workload; reported beside value")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     a = ap.parse_args()
+    if a.windows is None:
+        a.windows = 0 if a.full else 1
 
     # stdout carries ONE JSON line: whatever libraries print on the way (RCCL 2.26 writes a version banner to stdout when
     # its communicator comes up) goes to stderr -- file descriptor 1 points at stderr until the line is ready
@@ -257,11 +304,13 @@ def main():
     elapsed = sorted(windows)[len(windows) // 2]          # the median window
     value = world * N * T * a.steps / elapsed
     finite = bool(torch.isfinite(learner.network.params).all().item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ro, learner, np)
 
     roofline = None
     kernels = None
     per = {}
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # every rank runs the event-timed pass (with N > 1 each cycle contains collectives); rank 0 reports
         learner.ctx.prof_enable(True)
         ro.use_graph = False
@@ -350,7 +399,7 @@ def main():
                             avg_launch_us=dom["avg_us"], traffic=traffic)
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from oracle import cpu_learner, network as onet          # the oracle is the baseline leg, never the product
         envs = [env_creator.create_environment(i) for i in range(N)]
         params = onet.init_params(a.arch, A, np.random.RandomState(0), dtype=np.float32)

@@ -484,6 +484,13 @@ def pin_host_array(t):
         return False
 
 
+def unpin_host_array(t):
+    """Undo pin_host_array once nothing on the device reads the memory any more.  A registration left behind outlives the
+    memory it covers: a later allocation at an overlapping address (the multiprocessing heap hands freed shared blocks
+    out again) is then resolved to the stale, smaller registration and copies from it fail with an invalid argument."""
+    torch.cuda.cudart().cudaHostUnregister(t.data_ptr())
+
+
 class Graph(object):
     """hipGraph captured from the launches issued on torch's current stream between begin() and end()."""
 

@@ -785,6 +785,8 @@ class PAACLearner(ActorLearner):
         for g in step_graphs:
             if g is not None:
                 g.close()
+        if not raw_mode and pinned:
+            hip_ops.unpin_host_array(host_states)      # the stream is drained and the graphs copying from it are gone
         logging.debug("Host-plugin loop: %d update cycles, global step %d", counter, self.global_step)
         np.random.set_state(hip_ops.mt_state_to_numpy(mt_state))
 

@@ -164,10 +164,9 @@ def test_runners_host_batching():
 
 def test_checkpoint_keys_are_the_reference_index():
     """The saver's key for every tensor of the NIPS / A=4 layout (and both optimizer slots) == the key set and shapes
-    of /root/reference/pretrained/breakout/checkpoints/-80000000.index (actor_learner.py:26-27,79-82)."""
-    index = "/root/reference/pretrained/breakout/checkpoints/-80000000.index"
-    if not os.path.exists(index):
-        pytest.skip("reference not mounted")
+    of the reference's pretrained/breakout/checkpoints/-80000000.index (actor_learner.py:26-27,79-82), committed as
+    tests/golden/tf_index_breakout.bin."""
+    index = os.path.join(ROOT, "tests", "golden", "tf_index_breakout.bin")
     import tfproto
     from oracle import network as onet
     from paac_amd import _lib

@@ -1,12 +1,12 @@
 """Structural pin of the oracle's TensorFlow half against the one artefact the reference holds for it: the
 serialized NIPS training graph pretrained/breakout/checkpoints/-80000000.meta (TF 1.0.1) and the checkpoint .index
-next to it.  The protobuf / table wire formats are walked by tests/tfproto.py (nothing is executed, TensorFlow is
-not needed) and every assertion is made BY NODE: op type, input wiring, attribute or constant value -- so each
+next to it, committed as data: tests/golden/tf_meta_breakout.bin and tests/golden/tf_index_breakout.bin are those two
+files byte for byte.  The protobuf / table wire formats are walked by tests/tfproto.py (nothing is executed, TensorFlow
+is not needed) and every assertion is made BY NODE: op type, input wiring, attribute or constant value -- so each
 constant and formula oracle/network.py hard-codes is tied to the graph node that carries it.
 
-This is the most /root/reference can give the forward / loss / gradient / clip / RMSProp arithmetic; the VALUES those
-ops produce remain "parity unpinned" (no TensorFlow here, no golden vectors upstream).  Skipped where /root/reference
-is not mounted (the GPU box)."""
+This is the most the reference can give the forward / loss / gradient / clip / RMSProp arithmetic; the VALUES those
+ops produce remain "parity unpinned" (no TensorFlow here, no golden vectors upstream)."""
 import os
 
 import numpy as np
@@ -15,13 +15,14 @@ import pytest
 import tfproto
 from oracle import network as onet
 
-CKPT = "/root/reference/pretrained/breakout/checkpoints/-80000000"
-pytestmark = pytest.mark.skipif(not os.path.exists(CKPT + ".meta"), reason="reference not mounted")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+META = os.path.join(GOLDEN, "tf_meta_breakout.bin")
+INDEX = os.path.join(GOLDEN, "tf_index_breakout.bin")
 
 
 @pytest.fixture(scope="module")
 def nodes():
-    return tfproto.graph_nodes(CKPT + ".meta")
+    return tfproto.graph_nodes(META)
 
 
 def const(nodes, name):
@@ -210,7 +211,7 @@ def test_initialiser_ranges(nodes):
 def test_checkpoint_index_names_and_shapes():
     """The checkpoint .index: 10 variables + two optimizer slots each, the scopes of networks.py:111,144 /
     policy_v_network.py:16 ('local_learning_1' trunk, 'local_learning_2' heads), shapes = oracle.param_shapes."""
-    entries = tfproto.bundle_entries(CKPT + ".index")
+    entries = tfproto.bundle_entries(INDEX)
     want = {}
     for name, shape in onet.param_shapes("NIPS", 4):
         key = "local_learning_%d/%s" % (2 if name.startswith(("actor", "critic")) else 1, name)

@@ -35,7 +35,12 @@ enum { PAAC_ARCH_NIPS = 0, PAAC_ARCH_NATURE = 1,     /* networks.py:138-151 / :1
         * multiple of 256).  An architecture here is a compiled geometry: paac_amd/build.py builds a library for it on
         * demand (-DPAAC_USER_ARCH ...), which then serves PAAC_ARCH_NATURE and PAAC_ARCH_USER (not PAAC_ARCH_NIPS). */
        PAAC_ARCH_USER = 2 };
-enum { PAAC_CLIP_IGNORE = 0, PAAC_CLIP_GLOBAL = 1 }; /* actor_learner.py:51-59 ('local' is broken upstream) */
+/* --clip_norm_type (train.py, actor_learner.py:51-64): IGNORE = no clipping; GLOBAL = tf.clip_by_global_norm over all
+ * gradients; LOCAL = tf.clip_by_norm of every variable's gradient on its own (weights and biases are separate variables).
+ * Upstream's 'local' branch cannot run: actor_learner.py:62-63 hands each (grad, var) tuple to tf.clip_by_norm instead
+ * of the gradient.  LOCAL implements the branch's evident intent (its comment "Clip layer grads by layer norm", the help
+ * text, and the tf.global_norm of the clipped gradients after it). */
+enum { PAAC_CLIP_IGNORE = 0, PAAC_CLIP_GLOBAL = 1, PAAC_CLIP_LOCAL = 2 };
 
 #define PAAC_MAX_TENSORS 12
 #define PAAC_OBS_BYTES 28224 /* 84*84*4 */
@@ -201,13 +206,20 @@ int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t
                                const paac_returns* ret, int batch, float entropy_beta, float* grad, float* loss_out,
                                int forward_done, int phase, paac_stream_t stream);
 
-/* tf.clip_by_global_norm + RMSPropOptimizer.apply_gradients (actor_learner.py:31-34,56-59,70):
+/* Gradient clipping + RMSPropOptimizer.apply_gradients (actor_learner.py:31-34,51-64,70):
  *   g <- grad * grad_scale           (grad_scale = 1/world_size after the sum all-reduce)
- *   gn = sqrt(sum g^2); g <- g * clip_norm*min(1/gn, 1/clip_norm)  (mode GLOBAL)
+ *   mode IGNORE: f = 1
+ *   mode GLOBAL: gn = sqrt(sum g^2); g <- g * f, f = clip_norm*min(1/gn, 1/clip_norm)   (tf.clip_by_global_norm)
+ *   mode LOCAL:  per tensor i of the layout (weights and biases separately): ss_i = sum g_i^2 over its elements;
+ *                g_i <- g_i * f_i, f_i = clip_norm*min(rsqrt(ss_i), 1/clip_norm)        (tf.clip_by_norm, TF 1.0.1);
+ *                ss_i == 0 gives f_i = 1
  *   ms += (g^2 - ms)(1-decay); mom = momentum*mom + lr*g/sqrt(ms+eps); var -= mom
  * lr is read from device memory (*lr_dev) so the call can sit in a replayed graph.
- * gnorm_out (nullable): device float receiving gn.  After paac_loss_backward(phase = 3) on the same `grad` the norm pass
- * first completes the conv part of `grad` (which is therefore written although the parameter is const). */
+ * gnorm_out (nullable): device float receiving the global norm the reference's global_norm tensor holds: of the RAW
+ * gradient g in modes IGNORE and GLOBAL, of the CLIPPED gradient, sqrt(sum_i f_i^2 ss_i), in mode LOCAL.  LOCAL needs
+ * n = the layout's total.  Every mode is two launches (norm pass, update), deterministic (no float atomics).
+ * After paac_loss_backward(phase = 3) on the same `grad` the norm pass first completes the conv part of `grad` (which is
+ * therefore written although the parameter is const). */
 int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms, float* mom, int64_t n,
                       const float* lr_dev, float decay, float momentum, float eps, float clip_norm,
                       int clip_mode, float grad_scale, float* gnorm_out, paac_stream_t stream);
@@ -216,9 +228,16 @@ int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms
  * flat raw gradient and of the flat clipped gradient, plus global_norm): the reductions ride along the norm pass of
  * the LAST paac_clip_rmsprop on this ctx (no extra pass over the gradient); this call only folds its per-block
  * partials.  stats_out: device float[8] = {sum, sum of squares, max, min, number of exact zeros, 0, 0, 0} of the raw
- * flat gradient (g * grad_scale) over the reference's P elements (alignment pads excluded).  The clipped gradient is
- * the raw one times clip_norm*min(1/gn, 1/clip_norm), so its statistics follow.  Call at the logging cadence. */
+ * flat gradient (g * grad_scale) over the reference's P elements (alignment pads excluded), in every mode.  In modes
+ * IGNORE and GLOBAL the clipped gradient is the raw one times one factor, so its statistics follow; in mode LOCAL they
+ * follow from paac_grad_tensor_stats.  Call at the logging cadence. */
 int paac_grad_stats(paac_ctx* ctx, float* stats_out, paac_stream_t stream);
+
+/* Per-tensor summaries of the last paac_clip_rmsprop, which must have run in mode LOCAL (fails otherwise): out: device
+ * float[PAAC_MAX_TENSORS][8], row i = {sum, sum of squares, max, min, exact zeros, factor f_i applied, 0, 0} of tensor
+ * i's raw gradient (g * grad_scale, its alignment pads excluded); rows past the layout's tensors are zero.  The clipped
+ * tensor is the raw one times f_i.  Call at the logging cadence. */
+int paac_grad_tensor_stats(paac_ctx* ctx, float* out, paac_stream_t stream);
 
 /* actor_learner.py:119-123 + paac.py:127: *global_step += increment; *lr_out = f32(lr0 - step*lr0/anneal)
  * (0 beyond anneal); evaluated in fp64 like the reference's Python float. */

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PAAC_HIP_LIB") or os.path.join(HERE, "libpaac_hip.so"
 MAX_TENSORS = 12
 PROF_FAMILIES = 16
 ARCH_NIPS, ARCH_NATURE, ARCH_USER = 0, 1, 2
-CLIP_IGNORE, CLIP_GLOBAL = 0, 1
+CLIP_IGNORE, CLIP_GLOBAL, CLIP_LOCAL = 0, 1, 2
 
 
 class Layout(ctypes.Structure):
@@ -63,6 +63,7 @@ _SIGNATURES = {
     "paac_loss_backward_returns": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Returns), c_int, c_float, c_void_p,
                                            c_void_p, c_int, c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_clip_rmsprop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,
                                   c_float, c_float, c_float, c_int, c_float, c_void_p, c_void_p]),
     "paac_lr_step": (c_int, [c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p]),

@@ -45,9 +45,10 @@ class ActorLearner(object):
         elif self.clip_norm_type == 'global':
             self.clip_mode = _lib.CLIP_GLOBAL
         elif self.clip_norm_type == 'local':
-            # actor_learner.py:62-63 iterates over (grad, var) tuples and hands the tuple to tf.clip_by_norm:
-            # the branch cannot run upstream, so there is no behaviour to reproduce.
-            raise Exception("clip_norm_type 'local' is undefined in the reference (actor_learner.py:62-63)")
+            # tf.clip_by_norm of every variable's gradient on its own (weights and biases separately).  Upstream's branch
+            # cannot run: actor_learner.py:62-63 hands each (grad, var) tuple to tf.clip_by_norm instead of the gradient;
+            # this is the branch's evident intent (its comment, the help text, the global_norm line after it)
+            self.clip_mode = _lib.CLIP_LOCAL
         else:
             raise Exception('Norm type not recognized')
 

@@ -1268,7 +1268,8 @@ __global__ void fill_f32_kernel(float* p, float v, int n) {
 }
 
 // =============================================================================================
-// Global-norm clip + TF RMSProp over the flat parameter buffer (actor_learner.py:31-34,56-59,70).
+// Gradient clip (ignore / global norm / per-tensor norm) + TF RMSProp over the flat parameter buffer
+// (actor_learner.py:31-34,51-64,70).
 constexpr int NORM_BLOCKS = 256;         // tail blocks of norm_kernel
 constexpr int kNormPartialsMax = 1024;   // head blocks + tail blocks; unused slots stay 0 (the optimizer step sums all of them)
 constexpr int NORM_LANES = 8;            // lanes that share one float4 of the head (the slab sums of net_bwd.hip's finalize)
@@ -1298,8 +1299,23 @@ struct NormArgs {
   long tail_begin4;
 };
 
+// Local mode (PAAC_CLIP_LOCAL: tf.clip_by_norm per variable).  Upstream clips every entry of grads_and_vars on its own,
+// so weights and biases are separate tensors with a factor each.  The norm blocks are tensor-aligned: each run of head
+// blocks and each run of tail blocks covers exactly one tensor, so tensor t's partials are the contiguous slots
+// [blk[t], blk[t + 1]) -- no hand-off between workgroups.  The launch has as many blocks as the global mode's
+// (blk[nt] == its block count), so either mode leaves every slot the other one reads in a defined state.
+struct LocalSpec {
+  int nt;                              // tensors of the layout
+  int blk[PAAC_MAX_TENSORS + 1];       // first norm block (= partials slot) of tensor t
+  long off4[PAAC_MAX_TENSORS + 1];     // first float4 of tensor t in the padded layout; off4[nt] = n4
+  float pads[PAAC_MAX_TENSORS];        // alignment pads of tensor t (zeros its partials count that upstream has not)
+  float* factors;                      // [nt]: the factors applied, written by the optimizer step's block 0
+};
+constexpr int kNormFactors = 5 * kNormPartialsMax;   // offset of LocalSpec::factors inside ctx->partials
+
+template <bool LOCAL>
 __global__ __launch_bounds__(256) void norm_kernel(float* __restrict__ g, long n4, float scale, const NormArgs a,
-                                                   float* __restrict__ partials) {
+                                                   const LocalSpec ls, float* __restrict__ partials) {
   float acc = 0.f, sum = 0.f, mx = -INFINITY, mn = INFINITY, zeros = 0.f;
   auto take = [&](const float4 q) {
     const float x = q.x * scale, y = q.y * scale, z = q.z * scale, w = q.w * scale;
@@ -1315,15 +1331,29 @@ __global__ __launch_bounds__(256) void norm_kernel(float* __restrict__ g, long n
     }
   };
   float4* g4 = reinterpret_cast<float4*>(g);
-  if ((int)blockIdx.x < a.head_blocks) {
-    const int r = threadIdx.x % NORM_LANES;
-    long h = (long)blockIdx.x * (256 / NORM_LANES) + threadIdx.x / NORM_LANES;   // float4 inside the concatenated conv tensors
-    NormSeg sg = a.seg[0];
+  const int bid = blockIdx.x;
+  int t = 0;                                     // local mode: the one tensor this block covers
+  if constexpr (LOCAL) {
 #pragma unroll
-    for (int j = 1; j < 6; ++j) {
-      if (j < a.nseg && h >= sg.count4) {
-        h -= sg.count4;
-        sg = a.seg[j];
+    for (int j = 1; j < PAAC_MAX_TENSORS; ++j) t += (j < ls.nt && bid >= ls.blk[j]) ? 1 : 0;
+  }
+  if (LOCAL ? t < a.nseg : bid < a.head_blocks) {
+    const int r = threadIdx.x % NORM_LANES;
+    long h;
+    NormSeg sg = a.seg[0];
+    if constexpr (LOCAL) {
+      h = (long)(bid - ls.blk[t]) * (256 / NORM_LANES) + threadIdx.x / NORM_LANES;   // float4 inside conv tensor t
+#pragma unroll
+      for (int j = 1; j < 6; ++j)
+        if (j == t) sg = a.seg[j];
+    } else {
+      h = (long)bid * (256 / NORM_LANES) + threadIdx.x / NORM_LANES;   // float4 inside the concatenated conv tensors
+#pragma unroll
+      for (int j = 1; j < 6; ++j) {
+        if (j < a.nseg && h >= sg.count4) {
+          h -= sg.count4;
+          sg = a.seg[j];
+        }
       }
     }
     const bool live = h < sg.count4;     // whole lane groups are live or not: the shuffles below stay inside a group
@@ -1352,15 +1382,18 @@ __global__ __launch_bounds__(256) void norm_kernel(float* __restrict__ g, long n
     if (live && r == 0) take(make_float4(v[0], v[1], v[2], v[3]));
   } else {
     // latency-bound (a few float4 per thread): every load of a pass is issued before the first one is consumed
+    // (local mode: the blocks of tail tensor t stride over its padded range only)
     constexpr int U = 8;
-    constexpr long STRIDE = (long)NORM_BLOCKS * 256;
-    for (long i0 = a.tail_begin4 + ((int)blockIdx.x - a.head_blocks) * 256 + threadIdx.x; i0 < n4; i0 += U * STRIDE) {
+    const long STRIDE = LOCAL ? (long)(ls.blk[t + 1] - ls.blk[t]) * 256 : (long)NORM_BLOCKS * 256;
+    const long end = LOCAL ? ls.off4[t + 1] : n4;
+    const long begin = LOCAL ? ls.off4[t] + (long)(bid - ls.blk[t]) * 256 : a.tail_begin4 + (long)(bid - a.head_blocks) * 256;
+    for (long i0 = begin + threadIdx.x; i0 < end; i0 += U * STRIDE) {
       float4 v[U];
       bool live[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const long i = i0 + u * STRIDE;
-        live[u] = i < n4;
+        live[u] = i < end;
         v[u] = live[u] ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
@@ -1391,13 +1424,12 @@ __global__ __launch_bounds__(256) void norm_kernel(float* __restrict__ g, long n
   }
 }
 
-// One workgroup: the partials of the last norm_kernel (np of them) -> out[8] = {sum, sum of squares, max, min, exact zeros
-// among the real (unpadded) elements, 0, 0, 0}.  Launched by the host at the progress-record cadence only.
-__global__ __launch_bounds__(256) void grad_stats_kernel(const float* __restrict__ partials, int np, float pads,
-                                                         float* __restrict__ out) {
+// One workgroup: the partials of the last norm_kernel in slots [lo, hi) -> out[8] = {sum, sum of squares, max, min, exact
+// zeros among the real (unpadded) elements, 0, 0, 0}.  Ends on a barrier (a caller may fold again at once).
+__device__ void fold_norm_partials(const float* __restrict__ partials, int lo, int hi, float pads, float* __restrict__ out) {
   const int t = threadIdx.x;
   float ss = 0.f, sum = 0.f, mx = -INFINITY, mn = INFINITY, zeros = 0.f;
-  for (int i = t; i < np; i += 256) {
+  for (int i = lo + t; i < hi; i += 256) {
     ss += partials[i];
     sum += partials[kNormPartialsMax + i];
     mx = fmaxf(mx, partials[2 * kNormPartialsMax + i]);
@@ -1427,6 +1459,24 @@ __global__ __launch_bounds__(256) void grad_stats_kernel(const float* __restrict
     if (real_zeros > 0.f) { c = fmaxf(c, 0.f); d = fminf(d, 0.f); }
     out[0] = b; out[1] = a; out[2] = c; out[3] = d; out[4] = real_zeros; out[5] = 0.f; out[6] = 0.f; out[7] = 0.f;
   }
+  __syncthreads();
+}
+
+// The whole flat gradient: all np partials.  Launched by the host at the progress-record cadence only.
+__global__ __launch_bounds__(256) void grad_stats_kernel(const float* __restrict__ partials, int np, float pads,
+                                                         float* __restrict__ out) {
+  fold_norm_partials(partials, 0, np, pads, out);
+}
+
+// Per tensor, after a local-mode step (tensor-aligned partials): out[t][8] = the summaries above of tensor t's raw
+// gradient, with out[t][5] = the factor the step applied to it; rows nt .. PAAC_MAX_TENSORS - 1 are zero.
+__global__ __launch_bounds__(256) void grad_tensor_stats_kernel(const float* __restrict__ partials, const LocalSpec ls,
+                                                                float* __restrict__ out) {
+  for (int t = 0; t < ls.nt; ++t) {
+    fold_norm_partials(partials, ls.blk[t], ls.blk[t + 1], ls.pads[t], out + 8 * t);
+    if (threadIdx.x == 0) out[8 * t + 5] = ls.factors[t];
+  }
+  for (int i = 8 * ls.nt + threadIdx.x; i < 8 * PAAC_MAX_TENSORS; i += 256) out[i] = 0.f;
 }
 
 constexpr int RMS_U = 4;   // float4 per thread and array in rmsprop_kernel
@@ -1473,13 +1523,16 @@ __device__ __forceinline__ void rms_update4(float4& gv, float4& m, float4& mo, f
 // Block classes by blockIdx: [0, fc_tiles) one 16 x 256 tile of the fc weights; then one 32 x cout tile of a conv weight
 // tensor each; then flat blocks over everything else.  A tile block streams its rows coalesced like a flat block, then
 // passes the updated values through LDS into the packed order (fragments of fc_heads.h / bf16 planes of tower.h).
-template <bool MOM>
+// LOCAL: clip_mode is PAAC_CLIP_LOCAL -- every block folds the tensor-aligned partials into per-tensor sums of squares in
+// the same fixed order (the same factors everywhere), and each float4 takes the factor of the tensor it lies in.
+template <bool MOM, bool LOCAL>
 __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ var, const float* __restrict__ g,
                                                       float* __restrict__ ms, float* __restrict__ mom, long n4,
                                                       const float* __restrict__ lr_dev, float decay, float momentum,
                                                       float eps, float clip_norm, int clip_mode, float scale,
                                                       const float* __restrict__ partials, float* __restrict__ gnorm_out,
-                                                      const PackSpec pk, const int fc_tiles, const int conv_tiles) {
+                                                      const PackSpec pk, const int fc_tiles, const int conv_tiles,
+                                                      const LocalSpec ls) {
   __shared__ float red[4];
   __shared__ float s_factor;
   __shared__ float tile[32 * 68 > 16 * 260 ? 32 * 68 : 16 * 260];
@@ -1536,27 +1589,78 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ var, c
     v[u] = reinterpret_cast<float4*>(var)[il];
   }
   const float lr = *lr_dev;
-  // every block reduces the same partials in the same order -> identical norm everywhere (unused slots hold 0)
-  float acc = (partials[tid] + partials[tid + 256]) + (partials[tid + 512] + partials[tid + 768]);
+  float fu[RMS_U];       // factor (times scale) of each of this thread's float4s
   static_assert(kNormPartialsMax == 1024, "four partials per thread");
+  if constexpr (LOCAL) {
+    // segmented fold of the partials: 16 lanes per tensor, each summing the slots j, j + 16, ... of its tensor's range,
+    // then a fixed xor tree -- the same order in every block
+    __shared__ float s_p[kNormPartialsMax];
+    __shared__ float s_ss[PAAC_MAX_TENSORS], s_ft[PAAC_MAX_TENSORS];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const float gn = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-    float f = 1.f;
-    if (clip_mode == PAAC_CLIP_GLOBAL) f = clip_norm * fminf(1.0f / gn, 1.0f / clip_norm);
-    s_factor = f;
-    if (gnorm_out && bid == 0) *gnorm_out = gn;
+    for (int k = 0; k < 4; ++k) s_p[tid + 256 * k] = partials[tid + 256 * k];
+    __syncthreads();
+    const int t = tid >> 4, j = tid & 15;
+    int lo = 0, hi = 0;
+#pragma unroll
+    for (int q = 0; q < PAAC_MAX_TENSORS; ++q)
+      if (q == t && q < ls.nt) {
+        lo = ls.blk[q];
+        hi = ls.blk[q + 1];
+      }
+    float acc = 0.f;
+    for (int i = lo + j; i < hi; i += 16) acc += s_p[i];
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 16);
+    if (j == 0 && t < ls.nt) {
+      // TF 1.0.1 clip_by_norm literally: clip_norm * min(rsqrt(ss), 1 / clip_norm); ss == 0 gives 1 (no inf, no NaN)
+      s_ss[t] = acc;
+      s_ft[t] = clip_norm * fminf(1.0f / sqrtf(acc), 1.0f / clip_norm);
+    }
+    __syncthreads();
+    if (tid == 0 && bid == 0) {
+      // tf.global_norm of the CLIPPED gradients (actor_learner.py:64), in a fixed order
+      float c2 = 0.f;
+      for (int q = 0; q < ls.nt; ++q) {
+        c2 += s_ft[q] * s_ft[q] * s_ss[q];
+        ls.factors[q] = s_ft[q];
+      }
+      if (gnorm_out) *gnorm_out = sqrtf(c2);
+    }
+    // a tile block lies inside one tensor; a flat block's float4s may lie in several
+#pragma unroll
+    for (int u = 0; u < RMS_U; ++u) {
+      if (u > 0 && cls != 2) {
+        fu[u] = fu[0];
+        continue;
+      }
+      int tt = 0;
+#pragma unroll
+      for (int q = 1; q < PAAC_MAX_TENSORS; ++q) tt += (q < ls.nt && idx[u] >= ls.off4[q]) ? 1 : 0;
+      fu[u] = s_ft[tt] * scale;
+    }
+  } else {
+    // every block reduces the same partials in the same order -> identical norm everywhere (unused slots hold 0)
+    float acc = (partials[tid] + partials[tid + 256]) + (partials[tid + 512] + partials[tid + 768]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+      const float gn = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+      float f = 1.f;
+      if (clip_mode == PAAC_CLIP_GLOBAL) f = clip_norm * fminf(1.0f / gn, 1.0f / clip_norm);
+      s_factor = f;
+      if (gnorm_out && bid == 0) *gnorm_out = gn;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < RMS_U; ++u) fu[u] = s_factor * scale;
   }
-  __syncthreads();
-  const float f = s_factor * scale;
   const float omd = 1.0f - decay;
 #pragma unroll
   for (int u = 0; u < RMS_U; ++u) {
     if (idx[u] < 0) continue;
-    rms_update4<MOM>(gv[u], m[u], mo[u], v[u], f, lr, omd, momentum, eps);
+    rms_update4<MOM>(gv[u], m[u], mo[u], v[u], fu[u], lr, omd, momentum, eps);
     reinterpret_cast<float4*>(ms)[idx[u]] = m[u];
     reinterpret_cast<float4*>(mom)[idx[u]] = mo[u];
     reinterpret_cast<float4*>(var)[idx[u]] = v[u];
@@ -1670,6 +1774,38 @@ static int fill_norm_args(paac_ctx* ctx, const float* grad, NormArgs* na) {
   if (na->head_blocks + NORM_BLOCKS > kNormPartialsMax) return 0;
   if (pending) ctx->pending_fin_grad = nullptr;
   return na->head_blocks + NORM_BLOCKS;
+}
+
+// Local mode's tensor-aligned blocks, inside the np blocks the global mode launches (fill_norm_args): each conv tensor
+// its own run of head blocks (32 float4 each), each small tail tensor one block per 2048 float4, the fc weights the rest.
+// Returns 0 when they do not fit.
+static int fill_local_spec(const paac_ctx* ctx, const NormArgs& na, int np, LocalSpec* ls) {
+  const paac_layout& L = ctx->layout;
+  memset(ls, 0, sizeof(*ls));
+  ls->nt = L.num_tensors;
+  for (int t = 0; t < L.num_tensors; ++t) {
+    const long end = t + 1 < L.num_tensors ? L.offset[t + 1] : L.total;
+    ls->off4[t] = L.offset[t] / 4;
+    ls->pads[t] = (float)(end - L.offset[t] - L.size[t]);
+  }
+  ls->off4[L.num_tensors] = L.total / 4;
+  const int fc_t = na.nseg;                           // the fc weights: the first tensor after the conv tensors
+  int nb[PAAC_MAX_TENSORS], b = 0;
+  for (int t = 0; t < L.num_tensors; ++t) {
+    const long c4 = ls->off4[t + 1] - ls->off4[t];
+    nb[t] = t < na.nseg ? (int)((c4 + 256 / NORM_LANES - 1) / (256 / NORM_LANES)) : (int)((c4 + 2047) / 2048);
+    if (t != fc_t) b += nb[t];
+  }
+  nb[fc_t] = np - b;
+  if (nb[fc_t] < 1) return 0;
+  b = 0;
+  for (int t = 0; t < L.num_tensors; ++t) {
+    ls->blk[t] = b;
+    b += nb[t];
+  }
+  ls->blk[L.num_tensors] = b;
+  ls->factors = ctx->partials + kNormFactors;
+  return b == np;
 }
 
 // The packed copies the optimizer step maintains and the block classes that go with them (from the ctx's layout).
@@ -2022,28 +2158,48 @@ int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms
                       float grad_scale, float* gnorm_out, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && grad && ms && mom && lr_dev, "paac_clip_rmsprop: null argument");
   PAAC_REQUIRE(n > 0 && (n % 4) == 0, "paac_clip_rmsprop: n=%ld must be a positive multiple of 4 (padded layout)", (long)n);
-  PAAC_REQUIRE(clip_mode == PAAC_CLIP_IGNORE || clip_mode == PAAC_CLIP_GLOBAL,
-               "paac_clip_rmsprop: clip mode %d (the reference's 'local' branch is undefined)", clip_mode);
+  PAAC_REQUIRE(clip_mode == PAAC_CLIP_IGNORE || clip_mode == PAAC_CLIP_GLOBAL || clip_mode == PAAC_CLIP_LOCAL,
+               "paac_clip_rmsprop: clip mode %d (0 ignore, 1 global, 2 local)", clip_mode);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(ctx, F_CLIP_RMSPROP, (int)(n / 4), s);
   const long n4 = n / 4;
+  const bool local = clip_mode == PAAC_CLIP_LOCAL;
   NormArgs na;
+  LocalSpec ls;
+  memset(&ls, 0, sizeof(ls));
+  if (local) {                                        // layout first: a refusal must leave a pending slab reduction pending
+    PAAC_REQUIRE(n == ctx->layout.total, "paac_clip_rmsprop: local mode needs the whole layout (n=%ld, layout %ld floats)",
+                 (long)n, (long)ctx->layout.total);
+    const int np_layout = fill_norm_args(ctx, nullptr, &na);
+    PAAC_REQUIRE(np_layout > 0 && fill_local_spec(ctx, na, np_layout, &ls),
+                 "paac_clip_rmsprop: the layout's tensors do not fit the local mode's norm blocks");
+  }
   const int np = fill_norm_args(ctx, grad, &na);
   PAAC_REQUIRE(np > 0, "paac_clip_rmsprop: a slab reduction is pending for another gradient buffer, or the conv tensors "
                        "need more than %d norm blocks", kNormPartialsMax - NORM_BLOCKS);
-  launch_k(norm_kernel, dim3((unsigned)np), dim3(256), s, PROF_FIRST, const_cast<float*>(grad), n4, grad_scale, na,
-           ctx->partials);
+  if (local)
+    launch_k(norm_kernel<true>, dim3((unsigned)np), dim3(256), s, PROF_FIRST, const_cast<float*>(grad), n4, grad_scale, na,
+             ls, ctx->partials);
+  else
+    launch_k(norm_kernel<false>, dim3((unsigned)np), dim3(256), s, PROF_FIRST, const_cast<float*>(grad), n4, grad_scale, na,
+             ls, ctx->partials);
+  ctx->last_clip_local = local ? 1 : 0;
   PackSpec pk;
   int fc_tiles, conv_tiles;
   long flat4;
   fill_pack_spec(ctx, &pk, &fc_tiles, &conv_tiles, &flat4);
   const dim3 grid((unsigned)(fc_tiles + conv_tiles + (flat4 + 256 * RMS_U - 1) / (256 * RMS_U)));
-  if (momentum != 0.f)
-    launch_k(rmsprop_kernel<true>, grid, dim3(256), s, PROF_LAST, params, grad, ms, mom, n4, lr_dev, decay, momentum, eps,
-             clip_norm, clip_mode, grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles);
-  else
-    launch_k(rmsprop_kernel<false>, grid, dim3(256), s, PROF_LAST, params, grad, ms, mom, n4, lr_dev, decay, momentum, eps,
-             clip_norm, clip_mode, grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles);
+#define PAAC_RMS_LAUNCH(MOM, LOCAL)                                                                                     \
+  launch_k(rmsprop_kernel<MOM, LOCAL>, grid, dim3(256), s, PROF_LAST, params, grad, ms, mom, n4, lr_dev, decay, momentum, \
+           eps, clip_norm, clip_mode, grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles, ls)
+  if (momentum != 0.f) {
+    if (local) PAAC_RMS_LAUNCH(true, true);
+    else PAAC_RMS_LAUNCH(true, false);
+  } else {
+    if (local) PAAC_RMS_LAUNCH(false, true);
+    else PAAC_RMS_LAUNCH(false, false);
+  }
+#undef PAAC_RMS_LAUNCH
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2056,6 +2212,20 @@ int paac_grad_stats(paac_ctx* ctx, float* stats_out, paac_stream_t stream) {
   PAAC_REQUIRE(np > 0, "paac_grad_stats: no norm layout");
   hipLaunchKernelGGL(grad_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ctx->partials, np, pads,
                      stats_out);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_grad_tensor_stats(paac_ctx* ctx, float* out, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && out, "paac_grad_tensor_stats: null argument");
+  PAAC_REQUIRE(ctx->last_clip_local, "paac_grad_tensor_stats: the last paac_clip_rmsprop on this ctx was not a local-mode "
+                                     "step (per-tensor partials exist only after PAAC_CLIP_LOCAL)");
+  NormArgs na;
+  LocalSpec ls;
+  const int np = fill_norm_args(ctx, nullptr, &na);
+  PAAC_REQUIRE(np > 0 && fill_local_spec(ctx, na, np, &ls), "paac_grad_tensor_stats: no local norm layout");
+  hipLaunchKernelGGL(grad_tensor_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ctx->partials, ls,
+                     out);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

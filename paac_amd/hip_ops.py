@@ -263,7 +263,9 @@ class Context(object):
 
     def grad_stats(self, clip_norm, clip_mode):
         """Gradient summaries of the last clip_rmsprop (actor_learner.py:85-87, logger_utils.py:23-33): dict with
-        mean / stddev / max / min of the raw and of the clipped flat gradient, and global_norm.  Synchronises."""
+        mean / stddev / max / min of the raw and of the clipped flat gradient, and global_norm (of the raw gradient,
+        or of the clipped one in local mode, as the reference's global_norm tensor holds).  Local mode adds "tensors":
+        {name: {"norm": raw L2 norm, "factor": factor applied}}.  Synchronises."""
         out = torch.zeros(8, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.paac_grad_stats(self.handle, ctypes.c_void_p(out.data_ptr()), _stream()), "paac_grad_stats")
         s, ss, mx, mn = [float(v) for v in out.cpu().numpy()[:4].astype(np.float64)]
@@ -271,12 +273,33 @@ class Context(object):
         mean = s / n
         std = max(ss / n - mean * mean, 0.0) ** 0.5
         gn = ss ** 0.5
+        raw = {"mean": mean, "stddev": std, "max": mx, "min": mn}
+        if clip_mode == _lib.CLIP_LOCAL:
+            # the clipped gradient is tensor i's raw one times f_i: its summaries are folded from the per-tensor ones
+            ts = self.grad_tensor_stats()
+            f = ts[:, 5]
+            cs, css = float(np.sum(f * ts[:, 0])), float(np.sum(f * f * ts[:, 1]))
+            cmean = cs / n
+            return {"global_norm": css ** 0.5, "raw_gradients": raw,
+                    "clipped_gradients": {"mean": cmean, "stddev": max(css / n - cmean * cmean, 0.0) ** 0.5,
+                                          "max": float(np.max(f * ts[:, 2])), "min": float(np.min(f * ts[:, 3]))},
+                    "tensors": {t["name"]: {"norm": float(ts[i, 1]) ** 0.5, "factor": float(f[i])}
+                                for i, t in enumerate(self.layout["tensors"])}}
         f = 1.0
         if clip_mode == _lib.CLIP_GLOBAL and gn > 0.0:
             f = clip_norm * min(1.0 / gn, 1.0 / clip_norm)
         return {"global_norm": gn,
-                "raw_gradients": {"mean": mean, "stddev": std, "max": mx, "min": mn},
+                "raw_gradients": raw,
                 "clipped_gradients": {"mean": mean * f, "stddev": std * f, "max": mx * f, "min": mn * f}}
+
+    def grad_tensor_stats(self):
+        """Per-tensor summaries of the last clip_rmsprop, which must have run in local mode (include/paac_hip.h:
+        paac_grad_tensor_stats): float64 array [num_tensors, 8], row i = {sum, sum of squares, max, min, real zeros,
+        factor applied, 0, 0} of tensor i's raw gradient.  Synchronises."""
+        out = torch.zeros(_lib.MAX_TENSORS * 8, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.paac_grad_tensor_stats(self.handle, ctypes.c_void_p(out.data_ptr()), _stream()),
+                   "paac_grad_tensor_stats")
+        return out.cpu().numpy().astype(np.float64).reshape(_lib.MAX_TENSORS, 8)[:len(self.layout["tensors"])]
 
     def debug_activation(self, what, batch):
         out = torch.empty(batch * 20 * 20 * 64, dtype=torch.float32, device=self.device)

@@ -39,8 +39,9 @@ REFERENCE_FLAGS = (
      "global steps over which the learning rate falls linearly to zero"),
     (("--entropy",), "entropy_regularisation_strength", 0.02, float, "weight of the policy-entropy bonus"),
     (("--clip_norm",), "clip_norm", 3.0, float, "gradient norm the update is clipped to"),
-    (("--clip_norm_type",), "clip_norm_type", "global", None, "'global' (joint norm), 'ignore' (no clipping); "
-                                                             "'local' is undefined upstream and rejected"),
+    (("--clip_norm_type",), "clip_norm_type", "global", None, "'global' (global norm), 'local' (layer-wise norm: "
+                                                             "each weight and bias tensor clipped on its own), "
+                                                             "'ignore' (no clipping)"),
     (("--gamma",), "gamma", 0.99, float, "discount factor"),
     (("--max_global_steps",), "max_global_steps", 80000000, int, "environment steps to train for"),
     (("--max_local_steps",), "max_local_steps", 5, int, "t_max: steps per environment between updates"),

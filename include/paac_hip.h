@@ -141,6 +141,9 @@ int paac_bootstrap_forward_trunk(paac_ctx* ctx, const float* params, const uint8
  * PIL-nearest resize, history push, reset on terminal) builds stack_out / stack_out2 from them: four launches.
  * stack_out == NULL (with it stack_out2, raw_scratch and the four record pointers): no environment step -- forward + heads
  * finish + sampler only, for environments that live on the host (paac.py:104-110; up to PAAC_ACT_STEP_MAX_ENVS of them).
+ * A geometry without the fc + head partials kernel (a user architecture whose flattened conv output the kernel's waves do
+ * not divide) runs paac_forward (heads finished into probs_out / values_out) and then the sampler [+ environment step]
+ * launch of paac_sample_mt_synth_step instead: same stream, same outputs.
  * Up to PAAC_ACT_STEP_MAX_ENVS environments and N*(A-1) <= 1024 draws: the three launches above.  Beyond, up to
  * PAAC_ACT_STEP_MAX_ENVS_LARGE environments and PAAC_FUSED_SAMPLE_MAX_DRAWS draws (the 128 x 18 and 256 x 4 shards):
  * paac_forward + paac_sample_mt_synth_step in one call (four launches; lend walk_scratch as there), with the sampler's
@@ -327,8 +330,12 @@ int paac_graph_destroy(paac_graph* g);
 /* Test/debug: copy an internal activation to a caller device buffer (async on stream).
  * what: 1..3 = conv outputs a1..a3 [batch,OH,OW,C], 4 = fc activations h [batch,H] of the activation set used
  * last (acting or training); 21..23 / 24 = the same of the TRAINING set explicitly (rows kept by paac_keep_next_forward);
- * 11..13 / 14 = the gradients wrt them.  Returns the element count. */
-int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, paac_stream_t stream);
+ * 11..13 / 14 = the gradients wrt them.  out_capacity: floats `out` holds; a copy larger than that is refused (nothing is
+ * written).  Returns the element count. */
+int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, int64_t out_capacity, paac_stream_t stream);
+/* Test/debug: the element count paac_debug_activation copies for (what, batch) on geometry `arch` of this library (host
+ * only, no device or ctx needed); -1 for a `what` the geometry does not have. */
+int64_t paac_debug_activation_size(int arch, int what, int batch);
 
 /* Test/debug: sampler workgroup `sampler_workgroup` of paac_act_step_mt's large-shard step launch reports an exactly-zero
  * conditional probability it has not seen (-1: off, the default) -- exercises the rare serial path of the distributed zero

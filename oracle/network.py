@@ -172,7 +172,8 @@ def head_grads(pi, v, onehot, y, adv, beta, dtype=np.float64):
 
 
 def loss_and_grads(params, states_u8, onehot, y, adv, beta, arch, dtype=np.float64, relu_masks=None):
-    """Full forward + loss + backward.  Returns (loss dict, grads dict in param order).
+    """Full forward + loss + backward.  Returns (loss dict, grads dict in param order); the loss dict also carries the
+    data gradients "dz1".."dz3" (d loss / d pre-activation of each conv layer, the ReLU mask applied).
     relu_masks (optional): {"a1".."a3", "h"} boolean arrays overriding relu'(.) in the backward pass -- lets a
     test take the masks from the implementation under test so that pre-activations within rounding of 0
     (whose sign legitimately differs between summation orders) do not mask real backward errors."""
@@ -196,12 +197,14 @@ def loss_and_grads(params, states_u8, onehot, y, adv, beta, arch, dtype=np.float
     grads["fc%d_weights" % n] = cache["xf"].T @ dh
     grads["fc%d_biases" % n] = dh.sum(axis=0)
     dx = dh @ params["fc%d_weights" % n].astype(dtype).T
+    dzs = {}
     for i in reversed(range(len(convs))):
         Lc = convs[i]
         a = cache["a%d" % (i + 1)]
         B = a.shape[0]
         m = (a > 0) if relu_masks is None else relu_masks["a%d" % (i + 1)].reshape(a.shape)
         dz = (dx.reshape(a.shape) * m).reshape(-1, Lc["cout"])
+        dzs["dz%d" % (i + 1)] = dz.reshape(a.shape)
         cols = cache["cols%d" % (i + 1)]
         grads["conv%d_weights" % (i + 1)] = (cols.T @ dz).reshape(Lc["kh"], Lc["kw"], Lc["cin"], Lc["cout"])
         grads["conv%d_biases" % (i + 1)] = dz.sum(axis=0)
@@ -213,6 +216,7 @@ def loss_and_grads(params, states_u8, onehot, y, adv, beta, arch, dtype=np.float
     L["pi"] = fw["pi"]
     L["v"] = fw["v"]
     L["logits"] = fw["logits"]
+    L.update(dzs)          # "dz1".."dz3": data gradients wrt each conv layer's pre-activation [B, OH, OW, C] (masked)
     return L, ordered
 
 

@@ -96,7 +96,8 @@ _SIGNATURES = {
     "paac_graph_end": (c_int, [c_void_p, POINTER(c_void_p)]),
     "paac_graph_launch": (c_int, [c_void_p, c_void_p]),
     "paac_graph_destroy": (c_int, [c_void_p]),
-    "paac_debug_activation": (c_int64, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "paac_debug_activation": (c_int64, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "paac_debug_activation_size": (c_int64, [c_int, c_int, c_int]),
     "paac_debug_set_tuning": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "paac_debug_get_tuning": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "paac_debug_clock": (c_int, [c_void_p, c_void_p]),

@@ -134,7 +134,10 @@ def build_user_arch(convs, fc, verbose=False):
     layers = convs + [(0, 3, 1)] * (3 - len(convs))
     flags += ["-DPAAC_USER_K%d=%d" % (i + 1, k) for i, (_, k, _) in enumerate(layers)]
     flags += ["-DPAAC_USER_S%d=%d" % (i + 1, st) for i, (_, _, st) in enumerate(layers)]
-    return build(verbose=verbose, extra_flags=flags, lib_path=lib, obj_suffix=suffix)
+    try:
+        return build(verbose=verbose, extra_flags=flags, lib_path=lib, obj_suffix=suffix)
+    except RuntimeError as exc:
+        raise RuntimeError("building the user architecture %s (fc %d) failed: %s" % (convs, fc, exc)) from exc
 
 
 if __name__ == "__main__":

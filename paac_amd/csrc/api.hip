@@ -375,6 +375,15 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
                  (int64_t)batch * (ctx->cfg.num_actions - 1) <= 1024,
                  "paac_act_step_mt: sampling without an environment step covers up to %d environments and 1024 draws (use "
                  "paac_forward + paac_sample_mt); got %d x %d actions", PAAC_ACT_STEP_MAX_ENVS, batch, ctx->cfg.num_actions);
+    if (!forward_has_fc_heads(ctx)) {
+      // no head partials on this geometry: the plain forward finishes the heads, the sampler reads its probabilities
+      int rc = launch_forward(ctx, 0, params, states, batch, nullptr, probs_out, values_out, (hipStream_t)stream);
+      if (rc) return rc;
+      rc = launch_sample_mt_probs(probs_out, ctx->cfg.num_actions, mt_state, actions, batch, (hipStream_t)stream);
+      if (rc) return rc;
+      PAAC_CHECK_HIP(hipGetLastError());
+      return 0;
+    }
     const float *partial, *ba, *bc;
     int ntiles;
     int rc = launch_forward_trunk(ctx, params, states, batch, &partial, &ntiles, &ba, &bc, (hipStream_t)stream);
@@ -394,6 +403,18 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
                "paac_act_step_mt: N*(A-1) = %ld exceeds %d (use paac_forward + paac_sample_mt + paac_synth_step)",
                (long)batch * (ctx->cfg.num_actions - 1), PAAC_FUSED_SAMPLE_MAX_DRAWS);
   PAAC_REQUIRE(states != stack_out && states != stack_out2, "paac_act_step_mt: the step cannot shift the stacks in place");
+  if (!forward_has_fc_heads(ctx)) {
+    // no head partials on this geometry (fc_heads_waves == 0): paac_forward + paac_sample_mt_synth_step's launch
+    int rc = launch_forward(ctx, 0, params, states, batch, nullptr, probs_out, values_out, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, env_seed, env_offset, batch,
+                                     terminal_threshold, step_base_dev, step_offset, states, stack_out, stack_out2, rewards_out,
+                                     masks_out, ep_reward, ep_len, finished, walk_scratch, walk_scratch_bytes, raw_scratch,
+                                     nullptr, (hipStream_t)stream);
+    if (rc) return rc;
+    PAAC_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   if (batch > PAAC_ACT_STEP_MAX_ENVS || (int64_t)batch * (ctx->cfg.num_actions - 1) > 1024) {
     // the large shards (128 x 18, 256 x 4): policy forward with its heads finish, then the sampler + environment-step launch
     // with the walks spread over several workgroups -- whose MT19937 doubles a spare workgroup of the fc launch makes
@@ -504,31 +525,49 @@ int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t
   return 0;
 }
 
-int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, paac_stream_t stream) {
+// Elements of activation `what` (paac_debug_activation) for `batch` rows of geometry `spec`; -1: no such activation.
+static int64_t debug_activation_elems(const ArchSpec& spec, int what, int batch) {
+  if (what >= 21 && what <= 24) what -= 20;
+  if (what >= 11 && what <= 10 + spec.nconv) what -= 10;
+  if (what >= 1 && what <= spec.nconv) {
+    const ConvSpec& cs = spec.conv[what - 1];
+    return (int64_t)batch * cs.oh * cs.ow * cs.cout;
+  }
+  if (what == 4 || what == 14) return (int64_t)batch * spec.fc;
+  return -1;
+}
+
+int64_t paac_debug_activation_size(int arch, int what, int batch) {
+  PAAC_REQUIRE(batch > 0, "paac_debug_activation_size: batch %d", batch);
+  const int64_t n = debug_activation_elems(arch_spec(arch), what, batch);
+  if (n < 0) {
+    set_error("paac_debug_activation_size: what=%d", what);
+    return -1;
+  }
+  return n;
+}
+
+int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, int64_t out_capacity, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && out && batch > 0 && batch <= ctx->max_batch, "paac_debug_activation: bad arguments");
-  const float* src = nullptr;
-  int64_t n = 0;
-  const bool training_set = what >= 21 && what <= 24;      // 21..24: a1..a3 / h of the TRAINING set whichever was used last
-  if (training_set) what -= 20;
-  const Workspace& W = ctx->ws[training_set ? 1 : ctx->last_ws];
-  if (what >= 1 && what <= ctx->spec.nconv) {
-    const ConvSpec& cs = ctx->spec.conv[what - 1];
-    src = W.act[what - 1];
-    n = (int64_t)batch * cs.oh * cs.ow * cs.cout;
-  } else if (what == 4) {
-    src = W.h;
-    n = (int64_t)batch * ctx->spec.fc;
-  } else if (what >= 11 && what <= 10 + ctx->spec.nconv) {
-    const ConvSpec& cs = ctx->spec.conv[what - 11];
-    src = ctx->dact[what - 11];
-    n = (int64_t)batch * cs.oh * cs.ow * cs.cout;
-  } else if (what == 14) {
-    src = ctx->dh;
-    n = (int64_t)batch * ctx->spec.fc;
-  } else {
+  const int64_t n = debug_activation_elems(ctx->spec, what, batch);
+  if (n < 0) {
     set_error("paac_debug_activation: what=%d", what);
     return -1;
   }
+  PAAC_REQUIRE(n <= out_capacity, "paac_debug_activation: what=%d needs %ld floats, out holds %ld", what, (long)n,
+               (long)out_capacity);
+  const bool training_set = what >= 21 && what <= 24;      // 21..24: a1..a3 / h of the TRAINING set whichever was used last
+  if (training_set) what -= 20;
+  const Workspace& W = ctx->ws[training_set ? 1 : ctx->last_ws];
+  const float* src;
+  if (what >= 1 && what <= ctx->spec.nconv)
+    src = W.act[what - 1];
+  else if (what == 4)
+    src = W.h;
+  else if (what >= 11 && what <= 10 + ctx->spec.nconv)
+    src = ctx->dact[what - 11];
+  else
+    src = ctx->dh;
   PAAC_CHECK_HIP(hipMemcpyAsync(out, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return n;
 }

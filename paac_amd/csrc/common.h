@@ -240,6 +240,14 @@ int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, i
                                 float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, void* walk_scratch,
                                 int64_t walk_scratch_bytes, uint8_t* raw_scratch, const void* mt_ahead, hipStream_t stream,
                                 const HeadsPartials* heads = nullptr);
+// sampler only, from finished probabilities (no environment step): N <= 64 environments, N * (A - 1) <= 1024 draws
+int launch_sample_mt_probs(const float* probs, int A, uint32_t* mt_state, int32_t* actions, int N, hipStream_t stream);
+// false: the geometry of ctx's arch has no fc + head partials kernel (fc_heads.h: fc_heads_waves == 0), so no acting
+// forward leaves head partials for a later launch (launch_forward_trunk)
+bool forward_has_fc_heads(const paac_ctx* ctx);
+// the conv weight gradients fit the head blocks of paac_clip_rmsprop's norm pass, which can then finish their slab
+// reduction (paac_loss_backward phase 3); false for user architectures with large conv layers
+bool norm_head_fits(const paac_ctx* ctx);
 int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row, hipStream_t s);
 int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, const float** partial,
                          int* ntiles, const float** ba, const float** bc, hipStream_t s);

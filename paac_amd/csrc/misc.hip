@@ -1141,8 +1141,9 @@ __global__ __launch_bounds__(256) void synth_step_a_mt_kernel(const float* __res
     __shared__ int16_t act_s[mt_lds_d(LDSC)];
     // the running episode totals do not depend on the sampler: request them before it (first 256 environments)
     const int e0 = threadIdx.x < N ? threadIdx.x : 0;
-    const float ep_reward0 = ep_reward[e0];
-    const int32_t ep_len0 = ep_len[e0];
+    const bool env_step = rewards_out != nullptr;    // false: sampler only (launch_sample_mt_probs; one workgroup)
+    const float ep_reward0 = env_step ? ep_reward[e0] : 0.f;
+    const int32_t ep_len0 = env_step ? ep_len[e0] : 0;
     // (ends past a barrier; with several sampler workgroups only the one that finishes the walks goes on)
     // hs.partial: the heads were NOT finished by a launch of their own -- every sampler workgroup finishes those of the
     // environments its walks visit (paac_act_step_mt, large shards); otherwise `probs` holds all of them
@@ -1154,7 +1155,7 @@ __global__ __launch_bounds__(256) void synth_step_a_mt_kernel(const float* __res
     else
       go_on = sample_mt_body<LDSC>(probs, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, nullptr, nullptr,
                                    NoProbsHook(), mw, ahead);
-    if (!go_on) return;
+    if (!go_on || !env_step) return;
     MISC_STAMP(7);
     for (int e = threadIdx.x; e < N; e += 256) {
       const uint32_t key = synth_key(seed, env_offset + (uint32_t)e, id);
@@ -1771,9 +1772,23 @@ static int fill_norm_args(paac_ctx* ctx, const float* grad, NormArgs* na) {
   na->head_blocks = (int)((total4 + 256 / NORM_LANES - 1) / (256 / NORM_LANES));
   na->tail_begin4 = L.offset[nconv_t] / 4;
   if (na->tail_begin4 != total4) return 0;            // the conv tensors are contiguous from 0 (no pads among them)
-  if (na->head_blocks + NORM_BLOCKS > kNormPartialsMax) return 0;
+  if (na->head_blocks + NORM_BLOCKS > kNormPartialsMax) {
+    // conv tensors larger than the head blocks cover (user architectures with large conv layers): no head, the tail blocks
+    // stride over the whole gradient -- the backward has reduced the slabs itself (norm_head_fits), global mode only
+    if (pending) return 0;
+    na->nseg = 0;
+    na->head_blocks = 0;
+    na->tail_begin4 = 0;
+    return NORM_BLOCKS;
+  }
   if (pending) ctx->pending_fin_grad = nullptr;
   return na->head_blocks + NORM_BLOCKS;
+}
+
+bool norm_head_fits(const paac_ctx* ctx) {
+  long total4 = 0;
+  for (int i = 0; i < 2 * ctx->spec.nconv; ++i) total4 += ctx->layout.size[i] / 4;
+  return (total4 + 256 / NORM_LANES - 1) / (256 / NORM_LANES) + NORM_BLOCKS <= kNormPartialsMax;
 }
 
 // Local mode's tensor-aligned blocks, inside the np blocks the global mode launches (fill_norm_args): each conv tensor
@@ -2090,6 +2105,21 @@ bool sampler_folds_heads(int N, int A, const void* walk_scratch) {
   return sampler_is_large(N, A) && walk_scratch != nullptr && mw_walks(N, A) <= 16384 && N <= 256 && A <= 32;
 }
 
+int launch_sample_mt_probs(const float* probs, int A, uint32_t* mt_state, int32_t* actions, int N, hipStream_t stream) {
+  PAAC_REQUIRE(probs && mt_state && actions && N > 0 && N <= 64 && A >= 2 && A <= 32 && (int64_t)N * (A - 1) <= MT_LDS_D,
+               "launch_sample_mt_probs: N=%d A=%d", N, A);
+  {
+    ProfScope ps(g_prof_ctx, F_SAMPLE_ENV_STEP, N, stream);
+    launch_k(synth_step_a_mt_kernel<1>, dim3(1), dim3(256), stream, PROF_WHOLE, probs, A, mt_state, actions, (uint64_t)0,
+             (uint32_t)0, N, (uint32_t)0, (const uint64_t*)nullptr, (uint64_t)0, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+             (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (int32_t*)nullptr, (FinishedRing*)nullptr,
+             MultiWalk{nullptr, nullptr, nullptr, 0}, (uint32_t*)nullptr, (const MtAhead*)nullptr,
+             RowsHeadsHook{nullptr, 0, N, A, nullptr, nullptr, nullptr, nullptr});
+  }
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // mt_ahead (nullable): the record a spare workgroup of the preceding fc launch left (csrc/mt_ahead.h)
 int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, int32_t* actions, uint64_t seed, uint32_t env_offset,
                                 int N, uint32_t terminal_threshold, const uint64_t* step_base_dev, uint64_t step_offset,
@@ -2171,7 +2201,7 @@ int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms
     PAAC_REQUIRE(n == ctx->layout.total, "paac_clip_rmsprop: local mode needs the whole layout (n=%ld, layout %ld floats)",
                  (long)n, (long)ctx->layout.total);
     const int np_layout = fill_norm_args(ctx, nullptr, &na);
-    PAAC_REQUIRE(np_layout > 0 && fill_local_spec(ctx, na, np_layout, &ls),
+    PAAC_REQUIRE(np_layout > 0 && na.head_blocks > 0 && fill_local_spec(ctx, na, np_layout, &ls),
                  "paac_clip_rmsprop: the layout's tensors do not fit the local mode's norm blocks");
   }
   const int np = fill_norm_args(ctx, grad, &na);

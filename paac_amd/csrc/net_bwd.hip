@@ -498,7 +498,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     wgrad_out(i_w1, feats, NT::C1, slab, splits);
   }
   ctx->pending_fin_grad = nullptr;
-  if (phase == 3) {
+  if (phase == 3 && norm_head_fits(ctx)) {     // (else the optimizer step's norm pass cannot take the slabs over)
     ctx->pending_fin = fin;
     ctx->pending_fin_grad = grad;
   } else {

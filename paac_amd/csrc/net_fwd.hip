@@ -485,6 +485,10 @@ int launch_deferred_heads(paac_ctx* ctx, const float* params, hipStream_t s) {
   return 0;
 }
 
+bool forward_has_fc_heads(const paac_ctx* ctx) {
+  return fc_heads_waves(ctx->cfg.arch == PAAC_ARCH_NATURE ? NatureNet::FLAT : OtherNet::FLAT) > 0;
+}
+
 // Acting trunk up to the per-tile head partials (fc_heads.h); the caller's sampler launch finishes the heads.
 int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, const float** partial,
                          int* ntiles, const float** ba, const float** bc, hipStream_t s) {

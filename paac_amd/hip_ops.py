@@ -37,6 +37,39 @@ def _ptr(t, dtype, numel=None, name="tensor", optional=False):
     return ctypes.c_void_p(t.data_ptr())
 
 
+# (filters, kernel size, stride) of the stock trunks' conv layers and their fc width (networks.py)
+STOCK_GEOMETRY = {_lib.ARCH_NATURE: ([(32, 8, 4), (64, 4, 2), (64, 3, 1)], 512),
+                  _lib.ARCH_NIPS: ([(16, 8, 4), (32, 4, 2)], 256)}
+
+
+def arch_geometry(arch):
+    """-> (convs [(filters, size, stride), ...], fc width) of `arch` in the loaded library."""
+    if int(arch) == _lib.ARCH_USER:
+        g = _lib.user_arch()
+        if g is None:
+            raise _lib.PaacHipError("the loaded library has no user architecture")
+        return g
+    return STOCK_GEOMETRY[int(arch)]
+
+
+def activation_size(convs, fc, what, batch):
+    """Floats paac_debug_activation copies for `what` (include/paac_hip.h) over `batch` rows of the geometry (convs, fc):
+    VALID convolutions over 84 x 84; None for a `what` the geometry does not have."""
+    what = int(what)
+    if 21 <= what <= 24:
+        what -= 20
+    elif 11 <= what <= 14:
+        what -= 10
+    if what == 4:
+        return int(batch) * int(fc)
+    if not 1 <= what <= len(convs):
+        return None
+    size = 84
+    for _, k, s in convs[:what]:
+        size = (size - k) // s + 1
+    return int(batch) * size * size * int(convs[what - 1][0])
+
+
 class Context(object):
     """Owns one paac_ctx (activation workspace for one network on one GPU)."""
 
@@ -302,8 +335,12 @@ class Context(object):
         return out.cpu().numpy().astype(np.float64).reshape(_lib.MAX_TENSORS, 8)[:len(self.layout["tensors"])]
 
     def debug_activation(self, what, batch):
-        out = torch.empty(batch * 20 * 20 * 64, dtype=torch.float32, device=self.device)
-        n = self.lib.paac_debug_activation(self.handle, int(what), int(batch), ctypes.c_void_p(out.data_ptr()), _stream())
+        convs, fc = arch_geometry(self.arch)
+        cap = activation_size(convs, fc, what, batch)
+        if cap is None:
+            raise ValueError("debug_activation: what=%d is not an activation of this geometry" % what)
+        out = torch.empty(cap, dtype=torch.float32, device=self.device)
+        n = self.lib.paac_debug_activation(self.handle, int(what), int(batch), ctypes.c_void_p(out.data_ptr()), cap, _stream())
         _lib.check(n, "paac_debug_activation")
         return out[:n].clone()
 

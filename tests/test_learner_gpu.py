@@ -23,12 +23,13 @@ def make_args(**kw):
     return args
 
 
-def build_learner(args, params_seed=0):
+def build_learner(args, params_seed=0, arch=None):
+    """arch: the oracle's name of the network (a user architecture's registered ARCHS key); default args.arch's trunk."""
     from paac_amd import train
     from paac_amd.paac import PAACLearner
     network_creator, env_creator = train.get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)
-    arch = "NIPS" if args.arch == "NIPS" else "NATURE"
+    arch = arch or ("NIPS" if args.arch == "NIPS" else "NATURE")
     params = onet.init_params(arch, args.num_actions, np.random.RandomState(params_seed), dtype=np.float32)
     learner.network.set_parameters(params)
     learner.network.init = lambda folder, saver, session: 0      # keep the injected weights
@@ -168,12 +169,17 @@ def test_device_loop_matches_oracle(game, N, T, cycles, arch, raw):
     """The device-resident cycle (hipGraph replay, numpy-parity sampler) against the CPU restatement of paac.py:99-165
     on the same synthetic environments and np.random stream: observations and actions bit for bit, values / returns /
     weights within the float tolerance."""
+    check_device_loop_matches_oracle(game, N, T, cycles, arch, raw)
+
+
+def check_device_loop_matches_oracle(game, N, T, cycles, arch, raw, user_arch=""):
+    """test_device_loop_matches_oracle's body; user_arch: a --user_arch spec, `arch` then names its oracle ARCHS entry."""
     from paac_amd import hip_ops
     from paac_amd.paac import DeviceRollout
-    args = make_args(game=game, arch=arch, emulator_counts=N, emulator_workers=0, max_local_steps=T,
-                     max_global_steps=1 << 40, synthetic_terminal_p=0.05, sampler="numpy", test_seed=11,
-                     synthetic_raw_frames=raw)
-    learner, params, env_creator = build_learner(args)
+    args = make_args(game=game, arch="NATURE" if user_arch else arch, emulator_counts=N, emulator_workers=0,
+                     max_local_steps=T, max_global_steps=1 << 40, synthetic_terminal_p=0.05, sampler="numpy", test_seed=11,
+                     synthetic_raw_frames=raw, user_arch=user_arch)
+    learner, params, env_creator = build_learner(args, arch=arch)
     A = args.num_actions
     assert N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS       # every BASELINE shard runs the fused sampler + env step
     np.random.seed(args.test_seed)
@@ -333,9 +339,13 @@ def test_batched_graph_launches_equal_single_cycles():
 def test_philox_step_inside_heads_equals_separate_calls(arch, A, N):
     """paac_forward_sample_synth_step (row i's heads workgroup also does environment i's bookkeeping, extra workgroups
     shift the stacks) == paac_forward_sample followed by paac_synth_step, bit for bit, over consecutive steps."""
+    check_philox_step_equals_separate_calls({"NIPS": 0, "NATURE": 1}[arch], arch, A, N)
+
+
+def check_philox_step_equals_separate_calls(arch_id, arch, A, N):
+    """test_philox_step_inside_heads_equals_separate_calls's body (arch: the oracle's name of the network)."""
     from paac_amd import hip_ops
     from paac_amd.synthetic import terminal_threshold
-    arch_id = {"NIPS": 0, "NATURE": 1}[arch]
     ctx = hip_ops.Context(arch_id, A, max_batch=N)
     host = onet.init_params(arch, A, np.random.RandomState(1), dtype=np.float32)
     flat = np.zeros(ctx.layout["total"], dtype=np.float32)

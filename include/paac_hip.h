@@ -162,9 +162,9 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
  * planes (an internal copy owned by the ctx).  By default every paac_forward* / paac_train_forward / paac_loss_backward
  * call refreshes that copy from `params` first (one small extra launch), so a caller may change `params` at any time.
  * A caller that owns every write to `params` can switch to managed mode: paac_set_managed_weights(ctx, 1) -- then the
- * copy is refreshed only by paac_clip_rmsprop (right behind the optimizer step) and by an explicit paac_pack_weights
- * (call it after initialising, restoring or broadcasting `params`); in managed mode the acting forwards also stop
- * keeping the conv1 / conv2 activations (only the training forward keeps them, for the backward pass). */
+ * copy is refreshed only by paac_clip_rmsprop / paac_clip_adam (right behind the optimizer step) and by an explicit
+ * paac_pack_weights (call it after initialising, restoring or broadcasting `params`); in managed mode the acting
+ * forwards also stop keeping the conv1 / conv2 activations (only the training forward keeps them, for the backward pass). */
 int paac_pack_weights(paac_ctx* ctx, const float* params, paac_stream_t stream);
 int paac_set_managed_weights(paac_ctx* ctx, int on);
 
@@ -174,8 +174,8 @@ int paac_set_managed_weights(paac_ctx* ctx, int on);
  * phase: 0 = everything; 1 = forward (unless done) + heads + fc layer -> the gradients of fc_w .. critic_b, i.e. the
  * contiguous tail [offset(fc_w), total) of the flat buffer (95 % of its bytes); 2 = conv layers -> the head
  * [0, offset(fc_w)).  A data-parallel caller all-reduces the tail while phase 2 still runs.  3 = everything, except that
- * the split-K slabs of the conv weight gradients are summed into `grad` by the NEXT paac_clip_rmsprop on this ctx and
- * this `grad` (its norm pass does it, in the same order, so norm and update are bit-identical to phase 0; one launch
+ * the split-K slabs of the conv weight gradients are summed into `grad` by the NEXT paac_clip_rmsprop or paac_clip_adam
+ * on this ctx and this `grad` (its norm pass does it, in the same order, so norm and update are bit-identical to phase 0; one launch
  * less): until then the conv part of `grad` is not valid -- for a caller that goes straight to the optimizer step.
  * actions = sampled action index per row (the one-hot's argmax,
  * paac.py:27), y = critic target, adv = advantage, batch rows t-major (paac.py:151-154).
@@ -227,17 +227,34 @@ int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms
                       const float* lr_dev, float decay, float momentum, float eps, float clip_norm,
                       int clip_mode, float grad_scale, float* gnorm_out, paac_stream_t stream);
 
+/* Gradient clipping + tf.train.AdamOptimizer(lr, beta1, beta2, epsilon=eps).apply_gradients (TF 1.0.1 ApplyAdam), the
+ * alternative update rule to paac_clip_rmsprop's on the same clipped gradient g (grad_scale and the modes IGNORE /
+ * GLOBAL / LOCAL exactly as there):
+ *   alpha = lr * sqrt(1 - beta2_power) / (1 - beta1_power)
+ *   m += (g - m)(1-beta1); v += (g^2 - v)(1-beta2); var -= m*alpha / (sqrt(v) + eps)
+ *   beta1_power *= beta1; beta2_power *= beta2      (fp32 products, after the update: Adam's _finish)
+ * beta_powers: device float[2] = {beta1_power, beta2_power}, read and advanced on the device (start them at {beta1, beta2}
+ * and the zeros for m and v).  lr is read from device memory (*lr_dev) like paac_clip_rmsprop's, so the call can sit
+ * in a replayed graph.  Two launches: the norm pass's first workgroup also turns lr and the powers into alpha (a ctx scratch
+ * float) and advances the powers; the update reads alpha.  beta1 and beta2 must lie in [0, 1), eps must be positive.
+ * Everything else is paac_clip_rmsprop's contract: n % 4 == 0, LOCAL needs the whole layout, a pending phase-3 slab
+ * reduction of `grad` is completed, the packed weights are refreshed in managed mode, gnorm_out, paac_grad_stats and
+ * paac_grad_tensor_stats report this step. */
+int paac_clip_adam(paac_ctx* ctx, float* params, const float* grad, float* m, float* v, float* beta_powers, int64_t n,
+                   const float* lr_dev, float beta1, float beta2, float eps, float clip_norm, int clip_mode,
+                   float grad_scale, float* gnorm_out, paac_stream_t stream);
+
 /* The reference's gradient summaries (actor_learner.py:85-87 -> logger_utils.py:23-33: mean, stddev, max, min of the
  * flat raw gradient and of the flat clipped gradient, plus global_norm): the reductions ride along the norm pass of
- * the LAST paac_clip_rmsprop on this ctx (no extra pass over the gradient); this call only folds its per-block
- * partials.  stats_out: device float[8] = {sum, sum of squares, max, min, number of exact zeros, 0, 0, 0} of the raw
+ * the LAST paac_clip_rmsprop / paac_clip_adam on this ctx (no extra pass over the gradient); this call only folds its
+ * per-block partials.  stats_out: device float[8] = {sum, sum of squares, max, min, number of exact zeros, 0, 0, 0} of the raw
  * flat gradient (g * grad_scale) over the reference's P elements (alignment pads excluded), in every mode.  In modes
  * IGNORE and GLOBAL the clipped gradient is the raw one times one factor, so its statistics follow; in mode LOCAL they
  * follow from paac_grad_tensor_stats.  Call at the logging cadence. */
 int paac_grad_stats(paac_ctx* ctx, float* stats_out, paac_stream_t stream);
 
-/* Per-tensor summaries of the last paac_clip_rmsprop, which must have run in mode LOCAL (fails otherwise): out: device
- * float[PAAC_MAX_TENSORS][8], row i = {sum, sum of squares, max, min, exact zeros, factor f_i applied, 0, 0} of tensor
+/* Per-tensor summaries of the last paac_clip_rmsprop / paac_clip_adam, which must have run in mode LOCAL (fails
+ * otherwise): out: device float[PAAC_MAX_TENSORS][8], row i = {sum, sum of squares, max, min, exact zeros, factor f_i applied, 0, 0} of tensor
  * i's raw gradient (g * grad_scale, its alignment pads excluded); rows past the layout's tensors are zero.  The clipped
  * tensor is the raw one times f_i.  Call at the logging cadence. */
 int paac_grad_tensor_stats(paac_ctx* ctx, float* out, paac_stream_t stream);

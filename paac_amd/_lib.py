@@ -66,6 +66,8 @@ _SIGNATURES = {
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_clip_rmsprop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,
                                   c_float, c_float, c_float, c_int, c_float, c_void_p, c_void_p]),
+    "paac_clip_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,
+                               c_float, c_float, c_float, c_int, c_float, c_void_p, c_void_p]),
     "paac_lr_step": (c_int, [c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p]),
     "paac_nstep_returns": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p,
                                    c_void_p, c_void_p]),

@@ -1,9 +1,9 @@
 """Base learner (mirrors reference actor_learner.py:11-127).
 
 Holds what the reference's ActorLearner holds -- hyper-parameters, the environments, the network, the
-RMSProp optimizer state, savers, lr schedule, reward clipping, checkpoint cadence -- with the TensorFlow
-optimizer graph (compute_gradients / clip_by_global_norm / apply_gradients, :31-70) replaced by
-paac_loss_backward + paac_clip_rmsprop on a flat parameter buffer.
+optimizer state (RMSProp, or Adam with --optimizer adam), savers, lr schedule, reward clipping, checkpoint cadence --
+with the TensorFlow optimizer graph (compute_gradients / clip_by_global_norm / apply_gradients, :31-70) replaced by
+paac_loss_backward + paac_clip_rmsprop (paac_clip_adam) on a flat parameter buffer.
 """
 import logging
 import os
@@ -33,11 +33,21 @@ class ActorLearner(object):
         self.optimizer_checkpoint_folder = os.path.join(self.debugging_folder, 'optimizer_checkpoints/')
         self.last_saving_step = 0
 
-        # RMSPropOptimizer(lr, decay=alpha, epsilon=e): momentum 0.0, rms slot init 1.0 (actor_learner.py:31-34)
+        # RMSPropOptimizer(lr, decay=alpha, epsilon=e): momentum 0.0, rms slot init 1.0 (actor_learner.py:31-34); or
+        # --optimizer adam: AdamOptimizer(lr, beta1, beta2, epsilon=e), the alternative train.py's --e help names
+        # (args.json files and Namespaces from before the flag lack the fields: RMSProp)
         self.learning_rate = Placeholder('learning_rate')
+        self.optimizer = getattr(args, "optimizer", "rmsprop")
+        if self.optimizer not in ("rmsprop", "adam"):
+            raise ValueError("optimizer %r: expected 'rmsprop' or 'adam'" % (self.optimizer,))
         self.alpha = args.alpha
         self.e = args.e
         self.momentum = 0.0
+        self.beta1 = float(getattr(args, "beta1", 0.9))
+        self.beta2 = float(getattr(args, "beta2", 0.999))
+        if self.optimizer == "adam" and not (0.0 <= self.beta1 < 1.0 and 0.0 <= self.beta2 < 1.0 and self.e > 0.0):
+            raise ValueError("Adam needs 0 <= beta1, beta2 < 1 and e > 0 (beta1=%r, beta2=%r, e=%r)"
+                             % (self.beta1, self.beta2, self.e))
         self.clip_norm = args.clip_norm
         self.clip_norm_type = args.clip_norm_type
         if self.clip_norm_type == 'ignore':
@@ -66,8 +76,19 @@ class ActorLearner(object):
         self.torch_device = dev
         n = self.network.layout["total"]
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.rms = torch.ones(n, dtype=torch.float32, device=dev)         # .meta: OptimizerVariables init 1.0
-        self.mom = torch.zeros(n, dtype=torch.float32, device=dev)        # .meta: OptimizerVariables_1 zeros
+        if self.optimizer == "adam":
+            # slots m, v (zeros) and the fp32 bias-correction powers {beta1_power, beta2_power}, advanced on the device
+            self.adam_m = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.adam_v = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.beta_powers = torch.tensor([self.beta1, self.beta2], dtype=torch.float32, device=dev)
+            self.optimizer_state = [("m", self.adam_m), ("v", self.adam_v), ("beta_powers", self.beta_powers)]
+        else:
+            self.rms = torch.ones(n, dtype=torch.float32, device=dev)     # .meta: OptimizerVariables init 1.0
+            self.mom = torch.zeros(n, dtype=torch.float32, device=dev)    # .meta: OptimizerVariables_1 zeros
+            self.optimizer_state = [("rms", self.rms), ("mom", self.mom)]
+        # the ONE list of what an optimizer step reads and writes besides the gradient: replica checks, the data-parallel
+        # broadcast, the graph-replay snapshot and the checkpoints' consistency all go through it
+        self.update_state = [("params", self.network.params)] + self.optimizer_state
         self.lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.gnorm_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_dev = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -95,31 +116,65 @@ class ActorLearner(object):
             self.network_saver.get_arrays = lambda: dict(variables(), **self._get_optimizer_arrays())
 
     # -- optimizer slots under the reference's names ('<var>/OptimizerVariables', '<var>/OptimizerVariables_1') ----
+    # Both optimizers are named 'OptimizerVariables', so TF gives their two slots the same keys: RMSProp ms / momentum,
+    # Adam m / v.  Adam's beta1_power / beta2_power are top-level variables ('beta1_power', 'beta2_power').  Upstream's
+    # optimizer saver keeps only variables whose name contains 'OptimizerVariables' and would drop them -- a resumed run
+    # would restart bias correction from step 1 with trained moments.  This build writes them to the optimizer checkpoint
+    # (and, with --checkpoint_format tf, to the all-variables network bundle), deliberately.
+    ADAM_POWER_KEYS = ("beta1_power", "beta2_power")
+
+    def _slot_tensors(self):
+        if self.optimizer == "adam":
+            return (("OptimizerVariables", self.adam_m), ("OptimizerVariables_1", self.adam_v))
+        return (("OptimizerVariables", self.rms), ("OptimizerVariables_1", self.mom))
+
     def _get_optimizer_arrays(self):
         scope = self.network.name
         out = {}
-        for slot, flat in (("OptimizerVariables", self.rms), ("OptimizerVariables_1", self.mom)):
+        for slot, flat in self._slot_tensors():
             for k, v in self.network.get_parameters(flat).items():
                 out[checkpoint_key(scope, k, slot)] = v
+        if self.optimizer == "adam":
+            powers = self.beta_powers.cpu().numpy()
+            for i, key in enumerate(self.ADAM_POWER_KEYS):
+                out[key] = np.float32(powers[i]).reshape(())
         return out
 
     def _set_optimizer_arrays(self, d):
         lay = self.network.layout
-        host = {"OptimizerVariables": np.ones(lay["total"], dtype=np.float32),
+        adam = self.optimizer == "adam"
+        if adam and not all(k in d for k in self.ADAM_POWER_KEYS):
+            raise KeyError("optimizer checkpoint has no beta1_power / beta2_power: it was written by an RMSProp run "
+                           "(--optimizer rmsprop), and this learner runs Adam (--optimizer adam) -- its slots would be "
+                           "read as Adam's moments")
+        host = {"OptimizerVariables": (np.zeros if adam else np.ones)(lay["total"], dtype=np.float32),
                 "OptimizerVariables_1": np.zeros(lay["total"], dtype=np.float32)}
         where = {t["name"]: t for t in lay["tensors"]}
         seen = set()
         for key, value in d.items():
             name, slot = tensor_of_key(key)
-            if slot is None:         # a bundle of all variables (the reference's network saver): the slots are taken from it
+            if slot is None:         # a variable (the reference's all-variables bundle) or Adam's powers: not a slot
                 continue
             t = where[name]
             host[slot][t["offset"]:t["offset"] + t["size"]] = np.asarray(value, dtype=np.float32).reshape(-1)
             seen.add((name, slot))
         if len(seen) != 2 * len(where):
             raise KeyError("optimizer checkpoint holds %d of %d slot tensors" % (len(seen), 2 * len(where)))
-        self.rms.copy_(torch.from_numpy(host["OptimizerVariables"]))
-        self.mom.copy_(torch.from_numpy(host["OptimizerVariables_1"]))
+        for slot, flat in self._slot_tensors():
+            flat.copy_(torch.from_numpy(host[slot]))
+        if adam:
+            powers = [np.float32(np.asarray(d[k], dtype=np.float32).reshape(())) for k in self.ADAM_POWER_KEYS]
+            self.beta_powers.copy_(torch.from_numpy(np.array(powers, dtype=np.float32)))
+
+    # -- the optimizer step on self.grad (already all-reduced): one place for the loops and the feed-dict path ----
+    def apply_gradients(self):
+        net = self.network
+        if self.optimizer == "adam":
+            self.ctx.clip_adam(net.params, self.grad, self.adam_m, self.adam_v, self.beta_powers, self.lr_dev, self.beta1,
+                               self.beta2, self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
+        else:
+            self.ctx.clip_rmsprop(net.params, self.grad, self.rms, self.mom, self.lr_dev, self.alpha, self.momentum,
+                                  self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
 
     # -- one optimizer step from a reference-style feed dict (Session.run([train_step, ...], feed)) ----
     def _train_step_from_feed(self, feed_dict):
@@ -133,8 +188,7 @@ class ActorLearner(object):
         self.lr_dev.fill_(float(np.float32(feed_dict[self.learning_rate])))
         self.ctx.loss_backward(net.params, states, actions, y, adv, self.entropy_beta, self.grad, self.loss_dev)
         self._allreduce_grad()
-        self.ctx.clip_rmsprop(net.params, self.grad, self.rms, self.mom, self.lr_dev, self.alpha, self.momentum,
-                              self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
+        self.apply_gradients()
 
     # -- data parallel: one sum all-reduce of the flat gradient per update (paac_amd/parallel.py) ------
     @staticmethod
@@ -155,7 +209,7 @@ class ActorLearner(object):
         if not due:
             return
         self.last_saving_step = self.global_step
-        self._sync_device()                    # nothing in flight: weights, rms and mom belong to the same update
+        self._sync_device()                    # nothing in flight: weights and optimizer state belong to the same update
         if parallel.rank() == 0:
             for saver, folder in ((self.network_saver, self.network_checkpoint_folder),
                                   (self.optimizer_saver, self.optimizer_checkpoint_folder)):
@@ -185,10 +239,10 @@ class ActorLearner(object):
             optimizer_step = Saver.step_of(optimizer_checkpoint)
             if optimizer_step is not None and optimizer_step != int(resumed_step):
                 logging.warning('Optimizer checkpoint is from step %d, network checkpoint from step %d: resuming with '
-                                'weights and RMSProp statistics of different updates', optimizer_step, int(resumed_step))
+                                'weights and optimizer statistics of different updates', optimizer_step, int(resumed_step))
         if parallel.world_size() > 1:
             step = torch.tensor([int(resumed_step)], dtype=torch.int64, device=self.torch_device)
-            for t in (self.network.params, self.rms, self.mom, step):
+            for t in [t for _, t in self.update_state] + [step]:
                 parallel.broadcast_(t, src=0)
             self.network.weights_changed()
             resumed_step = int(step.item())

@@ -112,9 +112,9 @@ struct paac_ctx {
   float* dh;       // [max_batch][H]
   float* wslab;    // wgrad split-K slabs (all layers)
   int64_t wslab_floats;
-  float* partials; // norm / gradient-summary partials of the last paac_clip_rmsprop (5 x kNormPartialsMax floats), then
-                   // the per-tensor factors of a local-mode step
-  int last_clip_local;             // 1: the last paac_clip_rmsprop ran in PAAC_CLIP_LOCAL (tensor-aligned partials)
+  float* partials; // norm / gradient-summary partials of the last paac_clip_rmsprop / paac_clip_adam (5 x kNormPartialsMax
+                   // floats), then the per-tensor factors of a local-mode step, then Adam's step size (misc.hip: kAdamAlpha)
+  int last_clip_local;             // 1: the last optimizer step ran in PAAC_CLIP_LOCAL (tensor-aligned partials)
   // paac_loss_backward(phase = 3) leaves the slab reduction of the conv weight gradients to the next paac_clip_rmsprop on
   // the same gradient buffer (its norm pass does it): the segments, and the buffer they belong to
   paac::FinalizeArgs pending_fin;

@@ -1313,10 +1313,31 @@ struct LocalSpec {
   float* factors;                      // [nt]: the factors applied, written by the optimizer step's block 0
 };
 constexpr int kNormFactors = 5 * kNormPartialsMax;   // offset of LocalSpec::factors inside ctx->partials
+constexpr int kAdamAlpha = kNormFactors + PAAC_MAX_TENSORS;   // offset of the Adam step size inside ctx->partials (8192 floats)
 
-template <bool LOCAL>
+// Adam's bias-correction powers (TF 1.0.1 AdamOptimizer: fp32 variables beta1_power / beta2_power, advanced by one fp32
+// product each in _finish, after the update that used them).  Every block of the update launch reads the step size they
+// give, so they cannot be advanced inside it: block 0 of the norm pass (ADAM) reads them with *lr, writes TF ApplyAdam's
+//   alpha = lr * sqrt(1 - beta2_power) / (1 - beta1_power)
+// to a scratch float of the ctx and stores the advanced powers.  The launch boundary orders this before every reader.
+struct AdamPowers {
+  float* powers;          // device float[2] {beta1_power, beta2_power}, in/out
+  const float* lr;
+  float* alpha;           // ctx->partials + kAdamAlpha
+  float beta1, beta2;
+};
+
+template <bool LOCAL, bool ADAM>
 __global__ __launch_bounds__(256) void norm_kernel(float* __restrict__ g, long n4, float scale, const NormArgs a,
-                                                   const LocalSpec ls, float* __restrict__ partials) {
+                                                   const LocalSpec ls, float* __restrict__ partials, const AdamPowers ap) {
+  if constexpr (ADAM) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      const float b1p = ap.powers[0], b2p = ap.powers[1];
+      *ap.alpha = *ap.lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
+      ap.powers[0] = b1p * ap.beta1;
+      ap.powers[1] = b2p * ap.beta2;
+    }
+  }
   float acc = 0.f, sum = 0.f, mx = -INFINITY, mn = INFINITY, zeros = 0.f;
   auto take = [&](const float4 q) {
     const float x = q.x * scale, y = q.y * scale, z = q.z * scale, w = q.w * scale;
@@ -1480,7 +1501,7 @@ __global__ __launch_bounds__(256) void grad_tensor_stats_kernel(const float* __r
   for (int i = 8 * ls.nt + threadIdx.x; i < 8 * PAAC_MAX_TENSORS; i += 256) out[i] = 0.f;
 }
 
-constexpr int RMS_U = 4;   // float4 per thread and array in rmsprop_kernel
+constexpr int RMS_U = 4;   // float4 per thread and array in update_kernel
 
 // What the optimizer step also maintains (csrc/tower.h, csrc/fc_heads.h): the pre-split bf16 planes of the Nature conv
 // weights and the fragment-ordered copy of the fc weights -- written by the workgroup that has just updated the values, so
@@ -1519,21 +1540,39 @@ __device__ __forceinline__ void rms_update4(float4& gv, float4& m, float4& mo, f
 #undef PAAC_RMS
 }
 
-// MOM = false: momentum == 0 (the reference's setting, actor_learner.py:31-34): the momentum slot is written (it
-// is checkpointed as OptimizerVariables_1) but not read.
+// One optimizer element update (TF ApplyAdam): m = first moment, s = second moment, alpha = the bias-corrected step size
+// (norm_kernel<., true>).  eps lies outside the sqrt: an exact-zero gradient on zero moments gives 0 / eps = 0.
+__device__ __forceinline__ void adam_update4(float4& gv, float4& m, float4& s, float4& v, const float f, const float alpha,
+                                             const float omb1, const float omb2, const float eps) {
+#define PAAC_ADAM(c)                                       \
+  {                                                        \
+    const float gg = gv.c * f;                             \
+    m.c = m.c + (gg - m.c) * omb1;                         \
+    s.c = s.c + (gg * gg - s.c) * omb2;                    \
+    v.c = v.c - (m.c * alpha) / (sqrtf(s.c) + eps);        \
+  }
+  PAAC_ADAM(x) PAAC_ADAM(y) PAAC_ADAM(z) PAAC_ADAM(w)
+#undef PAAC_ADAM
+}
+
+// The update rules of update_kernel.  RULE_RMSPROP: momentum == 0 (the reference's setting, actor_learner.py:31-34): the
+// momentum slot is written (it is checkpointed as OptimizerVariables_1) but not read.  RULE_ADAM: ms / mom are Adam's m /
+// v, lr_dev points at the alpha norm_kernel<., true> wrote in the same step, (decay, momentum) carry (beta1, beta2).
 // Block classes by blockIdx: [0, fc_tiles) one 16 x 256 tile of the fc weights; then one 32 x cout tile of a conv weight
 // tensor each; then flat blocks over everything else.  A tile block streams its rows coalesced like a flat block, then
 // passes the updated values through LDS into the packed order (fragments of fc_heads.h / bf16 planes of tower.h).
 // LOCAL: clip_mode is PAAC_CLIP_LOCAL -- every block folds the tensor-aligned partials into per-tensor sums of squares in
 // the same fixed order (the same factors everywhere), and each float4 takes the factor of the tensor it lies in.
-template <bool MOM, bool LOCAL>
-__global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ var, const float* __restrict__ g,
-                                                      float* __restrict__ ms, float* __restrict__ mom, long n4,
-                                                      const float* __restrict__ lr_dev, float decay, float momentum,
-                                                      float eps, float clip_norm, int clip_mode, float scale,
-                                                      const float* __restrict__ partials, float* __restrict__ gnorm_out,
-                                                      const PackSpec pk, const int fc_tiles, const int conv_tiles,
-                                                      const LocalSpec ls) {
+enum { RULE_RMSPROP = 0, RULE_RMSPROP_MOM = 1, RULE_ADAM = 2 };
+template <int RULE, bool LOCAL>
+__global__ __launch_bounds__(256) void update_kernel(float* __restrict__ var, const float* __restrict__ g,
+                                                     float* __restrict__ ms, float* __restrict__ mom, long n4,
+                                                     const float* __restrict__ lr_dev, float decay, float momentum,
+                                                     float eps, float clip_norm, int clip_mode, float scale,
+                                                     const float* __restrict__ partials, float* __restrict__ gnorm_out,
+                                                     const PackSpec pk, const int fc_tiles, const int conv_tiles,
+                                                     const LocalSpec ls) {
+  constexpr bool MOM = RULE == RULE_RMSPROP_MOM;
   __shared__ float red[4];
   __shared__ float s_factor;
   __shared__ float tile[32 * 68 > 16 * 260 ? 32 * 68 : 16 * 260];
@@ -1586,7 +1625,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ var, c
     gv[u] = reinterpret_cast<const float4*>(g)[il];
     m[u] = reinterpret_cast<float4*>(ms)[il];
     mo[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (MOM) mo[u] = reinterpret_cast<float4*>(mom)[il];
+    if constexpr (RULE != RULE_RMSPROP) mo[u] = reinterpret_cast<float4*>(mom)[il];
     v[u] = reinterpret_cast<float4*>(var)[il];
   }
   const float lr = *lr_dev;
@@ -1661,7 +1700,8 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ var, c
 #pragma unroll
   for (int u = 0; u < RMS_U; ++u) {
     if (idx[u] < 0) continue;
-    rms_update4<MOM>(gv[u], m[u], mo[u], v[u], fu[u], lr, omd, momentum, eps);
+    if constexpr (RULE == RULE_ADAM) adam_update4(gv[u], m[u], mo[u], v[u], fu[u], lr, omd, 1.0f - momentum, eps);
+    else rms_update4<MOM>(gv[u], m[u], mo[u], v[u], fu[u], lr, omd, momentum, eps);
     reinterpret_cast<float4*>(ms)[idx[u]] = m[u];
     reinterpret_cast<float4*>(mom)[idx[u]] = mo[u];
     reinterpret_cast<float4*>(var)[idx[u]] = v[u];
@@ -2181,57 +2221,90 @@ int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, i
 }
 }  // namespace paac
 
-extern "C" {
-
-int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms, float* mom, int64_t n,
-                      const float* lr_dev, float decay, float momentum, float eps, float clip_norm, int clip_mode,
-                      float grad_scale, float* gnorm_out, paac_stream_t stream) {
-  PAAC_REQUIRE(ctx && params && grad && ms && mom && lr_dev, "paac_clip_rmsprop: null argument");
-  PAAC_REQUIRE(n > 0 && (n % 4) == 0, "paac_clip_rmsprop: n=%ld must be a positive multiple of 4 (padded layout)", (long)n);
+// paac_clip_rmsprop / paac_clip_adam: one norm pass, one update launch.  ap == nullptr: RMSProp (s1 = ms, s2 = mom, h1 =
+// decay, h2 = momentum, step_dev = lr); otherwise Adam (s1 = m, s2 = v, h1 = beta1, h2 = beta2; the norm pass turns *lr_dev
+// and the powers into alpha, which the update reads).
+static int clip_step(const char* fn, paac_ctx* ctx, float* params, const float* grad, float* s1, float* s2, int64_t n,
+                     const float* lr_dev, float h1, float h2, float eps, float clip_norm, int clip_mode, float grad_scale,
+                     float* gnorm_out, const AdamPowers* ap, hipStream_t s) {
+  PAAC_REQUIRE(n > 0 && (n % 4) == 0, "%s: n=%ld must be a positive multiple of 4 (padded layout)", fn, (long)n);
   PAAC_REQUIRE(clip_mode == PAAC_CLIP_IGNORE || clip_mode == PAAC_CLIP_GLOBAL || clip_mode == PAAC_CLIP_LOCAL,
-               "paac_clip_rmsprop: clip mode %d (0 ignore, 1 global, 2 local)", clip_mode);
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(ctx, F_CLIP_RMSPROP, (int)(n / 4), s);
+               "%s: clip mode %d (0 ignore, 1 global, 2 local)", fn, clip_mode);
+  ProfScope ps(ctx, F_CLIP_RMSPROP, (int)(n / 4), s);   // the optimizer step's family, either rule
   const long n4 = n / 4;
   const bool local = clip_mode == PAAC_CLIP_LOCAL;
   NormArgs na;
   LocalSpec ls;
   memset(&ls, 0, sizeof(ls));
   if (local) {                                        // layout first: a refusal must leave a pending slab reduction pending
-    PAAC_REQUIRE(n == ctx->layout.total, "paac_clip_rmsprop: local mode needs the whole layout (n=%ld, layout %ld floats)",
-                 (long)n, (long)ctx->layout.total);
+    PAAC_REQUIRE(n == ctx->layout.total, "%s: local mode needs the whole layout (n=%ld, layout %ld floats)", fn, (long)n,
+                 (long)ctx->layout.total);
     const int np_layout = fill_norm_args(ctx, nullptr, &na);
     PAAC_REQUIRE(np_layout > 0 && na.head_blocks > 0 && fill_local_spec(ctx, na, np_layout, &ls),
-                 "paac_clip_rmsprop: the layout's tensors do not fit the local mode's norm blocks");
+                 "%s: the layout's tensors do not fit the local mode's norm blocks", fn);
   }
   const int np = fill_norm_args(ctx, grad, &na);
-  PAAC_REQUIRE(np > 0, "paac_clip_rmsprop: a slab reduction is pending for another gradient buffer, or the conv tensors "
-                       "need more than %d norm blocks", kNormPartialsMax - NORM_BLOCKS);
-  if (local)
-    launch_k(norm_kernel<true>, dim3((unsigned)np), dim3(256), s, PROF_FIRST, const_cast<float*>(grad), n4, grad_scale, na,
-             ls, ctx->partials);
-  else
-    launch_k(norm_kernel<false>, dim3((unsigned)np), dim3(256), s, PROF_FIRST, const_cast<float*>(grad), n4, grad_scale, na,
-             ls, ctx->partials);
+  PAAC_REQUIRE(np > 0, "%s: a slab reduction is pending for another gradient buffer, or the conv tensors need more than %d "
+                       "norm blocks", fn, kNormPartialsMax - NORM_BLOCKS);
+  float* g = const_cast<float*>(grad);
+  AdamPowers none;
+  memset(&none, 0, sizeof(none));
+  const AdamPowers& pw = ap != nullptr ? *ap : none;
+#define PAAC_NORM_LAUNCH(KERNEL) \
+  launch_k(KERNEL, dim3((unsigned)np), dim3(256), s, PROF_FIRST, g, n4, grad_scale, na, ls, ctx->partials, pw)
+  if (ap != nullptr) {
+    if (local) PAAC_NORM_LAUNCH((norm_kernel<true, true>));
+    else PAAC_NORM_LAUNCH((norm_kernel<false, true>));
+  } else {
+    if (local) PAAC_NORM_LAUNCH((norm_kernel<true, false>));
+    else PAAC_NORM_LAUNCH((norm_kernel<false, false>));
+  }
+#undef PAAC_NORM_LAUNCH
   ctx->last_clip_local = local ? 1 : 0;
   PackSpec pk;
   int fc_tiles, conv_tiles;
   long flat4;
   fill_pack_spec(ctx, &pk, &fc_tiles, &conv_tiles, &flat4);
   const dim3 grid((unsigned)(fc_tiles + conv_tiles + (flat4 + 256 * RMS_U - 1) / (256 * RMS_U)));
-#define PAAC_RMS_LAUNCH(MOM, LOCAL)                                                                                     \
-  launch_k(rmsprop_kernel<MOM, LOCAL>, grid, dim3(256), s, PROF_LAST, params, grad, ms, mom, n4, lr_dev, decay, momentum, \
-           eps, clip_norm, clip_mode, grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles, ls)
-  if (momentum != 0.f) {
-    if (local) PAAC_RMS_LAUNCH(true, true);
-    else PAAC_RMS_LAUNCH(true, false);
+  const float* step_dev = ap != nullptr ? ap->alpha : lr_dev;
+#define PAAC_UPDATE_LAUNCH(KERNEL)                                                                                       \
+  launch_k(KERNEL, grid, dim3(256), s, PROF_LAST, params, grad, s1, s2, n4, step_dev, h1, h2, eps, clip_norm, clip_mode, \
+           grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles, ls)
+  if (ap != nullptr) {
+    if (local) PAAC_UPDATE_LAUNCH((update_kernel<RULE_ADAM, true>));
+    else PAAC_UPDATE_LAUNCH((update_kernel<RULE_ADAM, false>));
+  } else if (h2 != 0.f) {
+    if (local) PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP_MOM, true>));
+    else PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP_MOM, false>));
   } else {
-    if (local) PAAC_RMS_LAUNCH(false, true);
-    else PAAC_RMS_LAUNCH(false, false);
+    if (local) PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP, true>));
+    else PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP, false>));
   }
-#undef PAAC_RMS_LAUNCH
+#undef PAAC_UPDATE_LAUNCH
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" {
+
+int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms, float* mom, int64_t n,
+                      const float* lr_dev, float decay, float momentum, float eps, float clip_norm, int clip_mode,
+                      float grad_scale, float* gnorm_out, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && grad && ms && mom && lr_dev, "paac_clip_rmsprop: null argument");
+  return clip_step("paac_clip_rmsprop", ctx, params, grad, ms, mom, n, lr_dev, decay, momentum, eps, clip_norm, clip_mode,
+                   grad_scale, gnorm_out, nullptr, (hipStream_t)stream);
+}
+
+int paac_clip_adam(paac_ctx* ctx, float* params, const float* grad, float* m, float* v, float* beta_powers, int64_t n,
+                   const float* lr_dev, float beta1, float beta2, float eps, float clip_norm, int clip_mode,
+                   float grad_scale, float* gnorm_out, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && grad && m && v && beta_powers && lr_dev, "paac_clip_adam: null argument");
+  PAAC_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f,
+               "paac_clip_adam: beta1=%g and beta2=%g must lie in [0, 1)", (double)beta1, (double)beta2);
+  PAAC_REQUIRE(eps > 0.f, "paac_clip_adam: eps=%g must be positive", (double)eps);
+  const AdamPowers ap{beta_powers, lr_dev, ctx->partials + kAdamAlpha, beta1, beta2};
+  return clip_step("paac_clip_adam", ctx, params, grad, m, v, n, lr_dev, beta1, beta2, eps, clip_norm, clip_mode, grad_scale,
+                   gnorm_out, &ap, (hipStream_t)stream);
 }
 
 int paac_grad_stats(paac_ctx* ctx, float* stats_out, paac_stream_t stream) {

@@ -228,6 +228,19 @@ class Context(object):
                                               _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), _stream()),
                    "paac_clip_rmsprop")
 
+    def clip_adam(self, params, grad, m, v, beta_powers, lr_dev, beta1, beta2, eps, clip_norm, clip_mode, grad_scale=1.0,
+                  gnorm_out=None):
+        """The same clipped gradient through TF Adam instead of RMSProp (include/paac_hip.h: paac_clip_adam); beta_powers is
+        the device float32[2] {beta1_power, beta2_power} the step reads and advances."""
+        n = self.layout["total"]
+        _lib.check(self.lib.paac_clip_adam(self.handle, _ptr(params, torch.float32, n, "params"),
+                                           _ptr(grad, torch.float32, n, "grad"), _ptr(m, torch.float32, n, "m"),
+                                           _ptr(v, torch.float32, n, "v"), _ptr(beta_powers, torch.float32, 2, "beta_powers"),
+                                           n, _ptr(lr_dev, torch.float32, 1, "lr_dev"), float(beta1), float(beta2),
+                                           float(eps), float(clip_norm), int(clip_mode), float(grad_scale),
+                                           _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), _stream()),
+                   "paac_clip_adam")
+
     def keep_next_forward(self, train_row):
         """The next acting forward also leaves its rows' activations at rows [train_row, train_row + batch) of the training
         activation set (include/paac_hip.h: paac_keep_next_forward); -1 cancels."""

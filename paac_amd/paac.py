@@ -197,9 +197,7 @@ class DeviceRollout(object):
                             L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=2)
 
     def _update(self):
-        L = self.L
-        L.ctx.clip_rmsprop(L.network.params, L.grad, L.rms, L.mom, L.lr_dev, L.alpha, L.momentum, L.e, L.clip_norm,
-                           L.clip_mode, L._grad_scale(), L.gnorm_dev)
+        self.L.apply_gradients()
 
     def capture(self):
         """Capture the cycle into hipGraphs: one per observation-ring parity (and a separate update graph when a
@@ -275,11 +273,12 @@ class DeviceRollout(object):
 
     # -- trust, but verify: the captured exchange ---------------------------------------------------------
     def _cycle_state(self):
-        """Every tensor one cycle reads and writes (the rollout's and the learner's): a snapshot of them is a restart point."""
+        """Every tensor one cycle reads and writes (the rollout's and the learner's): a snapshot of them is a restart point.
+        (The optimizer state includes Adam's bias-correction powers: left out, a replayed check would advance them twice.)"""
         L = self.L
         ts = [self.states, self.actions, self.values, self.rewards, self.masks, self.probs, self.y, self.adv, self.ep_reward,
-              self.ep_len, self.finished, self.tick, self.global_step_dev, L.network.params, L.rms, L.mom, L.grad, L.lr_dev,
-              L.gnorm_dev, L.loss_dev]
+              self.ep_len, self.finished, self.tick, self.global_step_dev] + [t for _, t in L.update_state] + \
+             [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev]
         for name in ("raw", "walk_scratch", "mt_state"):
             t = getattr(self, name, None)
             if t is not None:
@@ -315,8 +314,8 @@ class DeviceRollout(object):
         all-reduced gradient, identical update).  Raises parallel.ReplicaMismatch on every rank when they do not."""
         L = self.L
         self.synchronize()
-        names = ("params", "rms", "mom") if what == "weights" else ("grad",)
-        tensors = [L.network.params, L.rms, L.mom] if what == "weights" else [L.grad]
+        named = L.update_state if what == "weights" else [("grad", L.grad)]
+        names, tensors = [n for n, _ in named], [t for _, t in named]
         with torch.cuda.stream(self.stream):
             ok, same = parallel.replicas_identical(tensors)
         if not ok:
@@ -755,8 +754,7 @@ class PAACLearner(ActorLearner):
             self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv,
                                    self.entropy_beta, self.grad, self.loss_dev)
             self._allreduce_grad()
-            self.ctx.clip_rmsprop(params, self.grad, self.rms, self.mom, self.lr_dev, self.alpha, self.momentum, self.e,
-                                  self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
+            self.apply_gradients()
             if getattr(self.args, "record_feeds", False):
                 self.last_feed = dict(states=d_states.view(T * N, 84, 84, 4).cpu().numpy(), y=d_y.cpu().numpy(),
                                       adv=d_adv.cpu().numpy(), actions=d_actions.view(-1).cpu().numpy(), lr=lr,
@@ -767,10 +765,10 @@ class PAACLearner(ActorLearner):
                 self.args.cycle_callback(self.global_step)
             counter += 1
             if parallel.collectives_active() and (counter == 1 or counter % check_every == 0):
-                ok, same = parallel.replicas_identical([params, self.rms, self.mom])
+                ok, same = parallel.replicas_identical([t for _, t in self.update_state])
                 if not ok:
                     raise parallel.ReplicaMismatch("data-parallel replicas diverged after %d updates: %s differ between ranks"
-                                                   % (counter, ", ".join(n for n, s in zip(("params", "rms", "mom"), same) if not s)))
+                                                   % (counter, ", ".join(n for (n, _), s in zip(self.update_state, same) if not s)))
             if counter % (2048 / self.emulator_counts) == 0:
                 curr_time = time.time()
                 last_ten = 0.0 if len(total_rewards) < 1 else np.mean(total_rewards[-10:])
@@ -793,7 +791,7 @@ class PAACLearner(ActorLearner):
     def _sync_device(self):
         """Everything issued so far has completed -- graph-replayed cycles still running on the rollout's own stream and
         a data-parallel optimizer step still waiting to ride in front of the next cycle included -- so a checkpoint
-        taken now holds weights, rms and mom of one and the same update."""
+        taken now holds the weights and the optimizer state (update_state) of one and the same update."""
         if self.rollout is not None:
             self.rollout.synchronize()
         super(PAACLearner, self)._sync_device()

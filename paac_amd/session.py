@@ -24,15 +24,19 @@ def variable_scope(scope, tensor_name):
 
 
 def checkpoint_key(scope, tensor_name, slot=None):
-    """slot: None (the variable), 'OptimizerVariables' (RMSProp ms) or 'OptimizerVariables_1' (momentum)
+    """slot: None (the variable), 'OptimizerVariables' (RMSProp ms, Adam m) or 'OptimizerVariables_1' (momentum, Adam v)
     (actor_learner.py:31-34: RMSPropOptimizer(..., name='OptimizerVariables') names its slots after itself)."""
     key = "%s/%s" % (variable_scope(scope, tensor_name), tensor_name)
     return key if slot is None else "%s/%s" % (key, slot)
 
 
 def tensor_of_key(key):
-    """-> (tensor name, slot or None); also accepts the un-numbered '<scope>/<tensor>' keys of round-1 checkpoints."""
+    """-> (tensor name, slot or None); also accepts the un-numbered '<scope>/<tensor>' keys of round-1 checkpoints.  A key
+    without a scope is a top-level variable that belongs to no tensor of the network (Adam's 'beta1_power' /
+    'beta2_power'): (None, None)."""
     parts = key.split("/")
+    if len(parts) < 2:
+        return None, None
     slot = parts[2] if len(parts) > 2 else None
     return parts[1], slot
 

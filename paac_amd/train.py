@@ -32,8 +32,9 @@ REFERENCE_FLAGS = (
     (("-d", "--device"), "device", "/gpu:0", str, "'/gpu:N' selects the MI355X; '/cpu:0' is rejected (no CPU path)"),
     (("--rom_path",), "rom_path", "./atari_roms", None, "directory with the game ROMs (ALE environments only)"),
     (("-v", "--visualize"), "visualize", False, bool_arg, "call on_new_frame with every emulator screen"),
-    (("--e",), "e", 0.1, float, "RMSProp epsilon"),
-    (("--alpha",), "alpha", 0.99, float, "RMSProp decay of the squared-gradient average"),
+    (("--e",), "e", 0.1, float, "Epsilon for the Rmsprop and Adam optimizers (textbook Adam uses 1e-8; with Adam it is "
+                                "added outside the square root)"),
+    (("--alpha",), "alpha", 0.99, float, "RMSProp decay of the squared-gradient average (ignored by Adam)"),
     (("-lr", "--initial_lr"), "initial_lr", 0.0224, float, "learning rate at step 0"),
     (("-lra", "--lr_annealing_steps"), "lr_annealing_steps", 80000000, int,
      "global steps over which the learning rate falls linearly to zero"),
@@ -70,6 +71,11 @@ BUILD_FLAGS = (
      "a user architecture instead of --arch (compiled on first use): filter counts of the 2 or 3 conv layers of the "
      "reference trunks' shapes (8x8/4, 4x4/2[, 3x3/1]) and the fc width, e.g. 32,64,64,1024 -- or filters:size:stride per "
      "layer, e.g. 32:8:4,64:5:2,64:3:1,512"),
+    (("--optimizer",), "optimizer", "rmsprop", None,
+     "update rule applied to the clipped gradients: 'rmsprop' (the reference's) or 'adam' (TF AdamOptimizer with --beta1, "
+     "--beta2 and --e; --alpha is ignored)"),
+    (("--beta1",), "beta1", 0.9, float, "Adam decay of the first-moment average"),
+    (("--beta2",), "beta2", 0.999, float, "Adam decay of the second-moment average"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),
@@ -82,9 +88,9 @@ def get_arg_parser():
         kwargs = dict(dest=dest, default=default, help=text)
         if kind is not None:
             kwargs["type"] = kind
-        if dest in ("sampler", "emulator", "checkpoint_format"):
+        if dest in ("sampler", "emulator", "checkpoint_format", "optimizer"):
             kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "ale"],
-                                 "checkpoint_format": ["npz", "tf"]}[dest]
+                                 "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"]}[dest]
         parser.add_argument(*options, **kwargs)
     return parser
 

@@ -5,7 +5,7 @@ import csv, glob, os, re, sys
 src = sys.argv[1]
 trace = glob.glob(os.path.join(src, "**", "*_kernel_trace.csv"), recursive=True)[0]
 rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r['Start_Timestamp']))
-marks = [i for i, r in enumerate(rows) if 'rmsprop_kernel' in r['Kernel_Name']]
+marks = [i for i, r in enumerate(rows) if 'rmsprop_kernel' in r['Kernel_Name'] or 'update_kernel' in r['Kernel_Name']]
 k0 = len(marks) // 3
 
 

@@ -19,7 +19,7 @@ stats = glob.glob(os.path.join(src, "stats", "*", "*_kernel_stats.csv"))[0]
 shutil.copy(stats, "profiles/%s_rocprofv3_kernel_stats.csv" % tag)
 trace = glob.glob(os.path.join(src, "stats", "*", "*_kernel_trace.csv"))[0]
 rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r['Start_Timestamp']))
-marks = [i for i, r in enumerate(rows) if 'rmsprop_kernel' in r['Kernel_Name']]
+marks = [i for i, r in enumerate(rows) if 'rmsprop_kernel' in r['Kernel_Name'] or 'update_kernel' in r['Kernel_Name']]
 k0 = len(marks) // 3         # steady-state part of the hipGraph phase (the tail of the trace is the eager, event-bracketed pass)
 # the profiler occasionally stalls the queue for milliseconds while it drains its buffers: take the shortest of a few
 # consecutive cycles
@@ -126,7 +126,7 @@ for name, pat, b in FUSED:
             fam["conv_tower[batch=%d]" % bb] = traffic["%s|%s" % k]
     elif ks:
         fam["%s[batch=%d]" % (name, b)] = traffic["%s|%s" % ks[-1]]
-rk = [k for k in fe if "rmsprop_kernel" in k[0] or "sumsq_kernel" in k[0] or "norm_kernel" in k[0]]
+rk = [k for k in fe if "rmsprop_kernel" in k[0] or "update_kernel" in k[0] or "sumsq_kernel" in k[0] or "norm_kernel" in k[0]]
 if rk:
     fam["clip_rmsprop[batch=%d]" % 0] = sum(traffic["%s|%s" % k] for k in rk)
 json.dump({"workload": meta["config"]["workload"], "bytes_per_launch": fam,

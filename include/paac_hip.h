@@ -184,10 +184,14 @@ int paac_loss_backward(paac_ctx* ctx, const float* params, const uint8_t* states
                        const float* y, const float* adv, int batch, float entropy_beta,
                        float* grad, float* loss_out, int forward_done, int phase, paac_stream_t stream);
 
+/* Advantage estimator of paac_loss_backward_returns.  NSTEP: paac_nstep_returns.  GAE: paac_gae_returns with gae_lambda. */
+enum { PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1 };
+
 /* paac_nstep_returns_tick + paac_loss_backward with the returns computed inside the backward's first launch (the heads
  * gradient kernel derives y / adv of every row from the rollout records; its last workgroup writes y_out / adv_out and
  * does the global_step / lr / frame-counter bookkeeping): one launch less per update, same values bit for bit.
- * batch must equal T*N (rows t-major, paac.py:151-154).  With phase == 2 (conv part only) `ret` is not used. */
+ * batch must equal T*N (rows t-major, paac.py:151-154).  With phase == 2 (conv part only) `ret` is not used.
+ * estimator = PAAC_RETURNS_GAE: == paac_gae_returns_tick + paac_loss_backward instead, bit for bit again. */
 typedef struct {
   const float* v_boot;        /* [N] bootstrap values (float32 network output, paac.py:140-142) */
   const float* rewards;       /* [T,N] clipped rewards */
@@ -204,6 +208,8 @@ typedef struct {
   float* lr_out_dev;
   uint64_t* tick_dev;         /* nullable */
   uint64_t tick_inc;
+  int32_t estimator;          /* PAAC_RETURNS_NSTEP (0: the n-step return above) or PAAC_RETURNS_GAE */
+  double gae_lambda;          /* in [0, 1]; read by PAAC_RETURNS_GAE only.  Both zero = a struct from before these fields */
 } paac_returns;
 int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                                const paac_returns* ret, int batch, float entropy_beta, float* grad, float* loss_out,
@@ -276,6 +282,22 @@ int paac_nstep_returns_tick(const float* v_boot, const float* rewards, const flo
                             int64_t increment, double initial_lr, int64_t lr_annealing_steps, float* lr_out_dev,
                             uint64_t* tick_dev, uint64_t tick_inc, paac_stream_t stream);
 
+/* Generalized advantage estimation (Schulman et al., arXiv 1506.02438) on the same records, beside the reference's n-step
+ * return.  With V_T = v_boot, the fp32 inputs promoted to fp64 and every operation a separate round-to-nearest fp64
+ * operation (gl = gamma * gae_lambda, one fp64 product):
+ *   A = 0; for t = T-1..0: delta = (r_t + (gamma*V_{t+1})*m_t) - V_t; A = delta + (gl*A)*m_t;
+ *                          adv_t = f32(A); y_t = f32(A + V_t)
+ * gae_lambda in [0, 1]: 0 = the one-step TD error; 1 = the n-step return up to the last place (use paac_nstep_returns
+ * for the reference's values bit for bit). */
+int paac_gae_returns(const float* v_boot, const float* rewards, const float* masks, const float* values,
+                     int T, int N, double gamma, double gae_lambda, float* y, float* adv, paac_stream_t stream);
+
+/* paac_gae_returns + the bookkeeping of paac_nstep_returns_tick in ONE launch. */
+int paac_gae_returns_tick(const float* v_boot, const float* rewards, const float* masks, const float* values,
+                          int T, int N, double gamma, double gae_lambda, float* y, float* adv, int64_t* global_step_dev,
+                          int64_t increment, double initial_lr, int64_t lr_annealing_steps, float* lr_out_dev,
+                          uint64_t* tick_dev, uint64_t tick_inc, paac_stream_t stream);
+
 /* paac.py:34-45 bit-exact: probs - float32.epsneg, then numpy legacy multinomial(1, p) per env in
  * index order on ONE MT19937 stream.  mt_state: device uint32[625] = numpy key[624] + pos, advanced
  * in place (import/export with np.random.get_state()/set_state()).  scratch: device, >=
@@ -347,7 +369,8 @@ int paac_graph_destroy(paac_graph* g);
 /* Test/debug: copy an internal activation to a caller device buffer (async on stream).
  * what: 1..3 = conv outputs a1..a3 [batch,OH,OW,C], 4 = fc activations h [batch,H] of the activation set used
  * last (acting or training); 21..23 / 24 = the same of the TRAINING set explicitly (rows kept by paac_keep_next_forward);
- * 11..13 / 14 = the gradients wrt them.  out_capacity: floats `out` holds; a copy larger than that is refused (nothing is
+ * 11..13 / 14 = the gradients wrt them; 25 = the value head's outputs [batch] of the TRAINING set (after an update whose
+ * returns took the bootstrap values from the training forward, rows [T*N, T*N + N) are those values).  out_capacity: floats `out` holds; a copy larger than that is refused (nothing is
  * written).  Returns the element count. */
 int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, int64_t out_capacity, paac_stream_t stream);
 /* Test/debug: the element count paac_debug_activation copies for (what, batch) on geometry `arch` of this library (host

@@ -14,6 +14,7 @@ MAX_TENSORS = 12
 PROF_FAMILIES = 16
 ARCH_NIPS, ARCH_NATURE, ARCH_USER = 0, 1, 2
 CLIP_IGNORE, CLIP_GLOBAL, CLIP_LOCAL = 0, 1, 2
+RETURNS_NSTEP, RETURNS_GAE = 0, 1
 
 
 class Layout(ctypes.Structure):
@@ -36,7 +37,8 @@ class Returns(ctypes.Structure):
     _fields_ = [("v_boot", c_void_p), ("rewards", c_void_p), ("masks", c_void_p), ("values", c_void_p),
                 ("T", c_int32), ("N", c_int32), ("gamma", ctypes.c_double), ("y_out", c_void_p), ("adv_out", c_void_p),
                 ("global_step_dev", c_void_p), ("increment", c_int64), ("initial_lr", ctypes.c_double),
-                ("lr_annealing_steps", c_int64), ("lr_out_dev", c_void_p), ("tick_dev", c_void_p), ("tick_inc", c_uint64)]
+                ("lr_annealing_steps", c_int64), ("lr_out_dev", c_void_p), ("tick_dev", c_void_p), ("tick_inc", c_uint64),
+                ("estimator", c_int32), ("gae_lambda", ctypes.c_double)]
 
 
 class PaacHipError(RuntimeError):
@@ -74,6 +76,11 @@ _SIGNATURES = {
     "paac_nstep_returns_tick": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p,
                                         c_void_p, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_uint64,
                                         c_void_p]),
+    "paac_gae_returns": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p,
+                                 c_void_p, c_void_p]),
+    "paac_gae_returns_tick": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_uint64,
+                                      c_void_p]),
     "paac_sample_mt_scratch_bytes": (c_int64, [c_int, c_int]),
     "paac_sample_mt": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "paac_sample_philox": (c_int, [c_void_p, c_int, c_int, c_uint64, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),

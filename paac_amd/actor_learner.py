@@ -48,6 +48,11 @@ class ActorLearner(object):
         if self.optimizer == "adam" and not (0.0 <= self.beta1 < 1.0 and 0.0 <= self.beta2 < 1.0 and self.e > 0.0):
             raise ValueError("Adam needs 0 <= beta1, beta2 < 1 and e > 0 (beta1=%r, beta2=%r, e=%r)"
                              % (self.beta1, self.beta2, self.e))
+        # --gae_lambda: 1.0 (and Namespaces / args.json files from before the flag) = the reference's n-step return through
+        # the n-step kernels; anything else in [0, 1] = GAE(lambda) (hip_ops.uses_gae is the one routing rule)
+        self.gae_lambda = float(getattr(args, "gae_lambda", 1.0))
+        if not 0.0 <= self.gae_lambda <= 1.0:           # (NaN fails both comparisons)
+            raise ValueError("gae_lambda %r: expected a value in [0, 1]" % (self.gae_lambda,))
         self.clip_norm = args.clip_norm
         self.clip_norm_type = args.clip_norm_type
         if self.clip_norm_type == 'ignore':

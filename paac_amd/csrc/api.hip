@@ -510,6 +510,10 @@ int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t
   PAAC_REQUIRE(ret->v_boot || (forward_done && batch + ret->N <= ctx->max_batch),
                "paac_loss_backward_returns: v_boot == NULL takes the bootstrap values from rows [batch, batch + N) of a "
                "training forward that has already run over batch + N rows");
+  PAAC_REQUIRE(ret->estimator == PAAC_RETURNS_NSTEP || ret->estimator == PAAC_RETURNS_GAE,
+               "paac_loss_backward_returns: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", ret->estimator);
+  PAAC_REQUIRE(ret->gae_lambda >= 0.0 && ret->gae_lambda <= 1.0, "paac_loss_backward_returns: gae_lambda %g outside [0, 1]",
+               ret->gae_lambda);
   PAAC_REQUIRE(!ret->global_step_dev || (ret->lr_out_dev && ret->lr_annealing_steps > 0),
                "paac_loss_backward_returns: schedule bookkeeping needs lr_out_dev and lr_annealing_steps");
   int rc = 0;
@@ -527,6 +531,7 @@ int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t
 
 // Elements of activation `what` (paac_debug_activation) for `batch` rows of geometry `spec`; -1: no such activation.
 static int64_t debug_activation_elems(const ArchSpec& spec, int what, int batch) {
+  if (what == 25) return batch;
   if (what >= 21 && what <= 24) what -= 20;
   if (what >= 11 && what <= 10 + spec.nconv) what -= 10;
   if (what >= 1 && what <= spec.nconv) {
@@ -556,6 +561,10 @@ int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, in
   }
   PAAC_REQUIRE(n <= out_capacity, "paac_debug_activation: what=%d needs %ld floats, out holds %ld", what, (long)n,
                (long)out_capacity);
+  if (what == 25) {                                        // value head outputs of the TRAINING set
+    PAAC_CHECK_HIP(hipMemcpyAsync(out, ctx->ws[1].values, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return n;
+  }
   const bool training_set = what >= 21 && what <= 24;      // 21..24: a1..a3 / h of the TRAINING set whichever was used last
   if (training_set) what -= 20;
   const Workspace& W = ctx->ws[training_set ? 1 : ctx->last_ws];

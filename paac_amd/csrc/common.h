@@ -247,6 +247,14 @@ int launch_sample_mt_probs(const float* probs, int A, uint32_t* mt_state, int32_
 bool forward_has_fc_heads(const paac_ctx* ctx);
 // the conv weight gradients fit the head blocks of paac_clip_rmsprop's norm pass, which can then finish their slab
 // reduction (paac_loss_backward phase 3); false for user architectures with large conv layers
+// One step of the generalized-advantage scan (heads.h has the contract): V = V_t, Vn = V_{t+1}, A = A_{t+1} -> A_t.  Separate
+// round-to-nearest fp64 operations: no FMA contraction, so the scan equals its IEEE restatement bit for bit.
+__device__ __forceinline__ void gae_step(const double gamma, const double gl, const float rw, const float mk, const double V,
+                                         const double Vn, double& A) {
+  const double delta = __dsub_rn(__dadd_rn((double)rw, __dmul_rn(__dmul_rn(gamma, Vn), (double)mk)), V);
+  A = __dadd_rn(delta, __dmul_rn(__dmul_rn(gl, A), (double)mk));
+}
+
 bool norm_head_fits(const paac_ctx* ctx);
 int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row, hipStream_t s);
 int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, const float** partial,

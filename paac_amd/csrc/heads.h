@@ -323,18 +323,103 @@ __device__ __forceinline__ void nstep_row(const ReturnsArgs& r, const int i, flo
   nstep_row_from(r, i, r.v_boot[i % r.N], y, adv);
 }
 
-template <int AP>
+// Generalized advantage estimation (Schulman et al., arXiv 1506.02438) as the alternative estimator, selected at compile
+// time: the kernels below take the estimator as a template flag and the GAE instantiations this argument block, so the
+// n-step instantiations keep their arguments and their code.  With V_T = v_boot, every operation a separate
+// round-to-nearest fp64 operation on the promoted fp32 inputs (no fp32 first product: that is numpy's promotion in the
+// reference's n-step loop, and there is no reference loop here):
+//   delta_t = (r_t + (gamma V_{t+1}) m_t) - V_t;  A_t = delta_t + (gl A_{t+1}) m_t;  adv_t = f32(A_t);  y_t = f32(A_t + V_t)
+// gl = gamma * lambda, formed once on the host.  One step is gae_step (common.h), shared with gae_returns_kernel (csrc/misc.hip).
+constexpr int kEstNstep = 0, kEstGae = 1;      // == PAAC_RETURNS_NSTEP, PAAC_RETURNS_GAE (include/paac_hip.h)
+struct GaeArgs : ReturnsArgs {
+  double gl;
+};
+template <int EST> struct ReturnsOf { using type = ReturnsArgs; };
+template <> struct ReturnsOf<kEstGae> { using type = GaeArgs; };
+
+__device__ __forceinline__ void gae_row_from(const GaeArgs& r, const int i, const float vb, float& y, float& adv) {
+  const int t = i / r.N, e = i - t * r.N;
+  double A = 0.0, Vn = (double)vb, V = Vn;
+  for (int tt = r.T - 1; tt >= t; --tt) {       // t <= T - 1: at least one step, V ends as V_t
+    const long k = (long)tt * r.N + e;
+    V = (double)r.values_act[k];
+    gae_step(r.gamma, r.gl, r.rewards[k], r.masks[k], V, Vn, A);
+    Vn = V;
+  }
+  adv = (float)A;
+  y = (float)__dadd_rn(A, V);
+}
+// The preloaded form (see NstepPre): the later steps' acting values are requested with their rewards and masks, in the
+// same memory round trip.
+struct GaePre {
+  float rw[kNstepPre], mk[kNstepPre], va[kNstepPre];
+};
+__device__ __forceinline__ GaePre gae_preload(const GaeArgs& r, const int i) {
+  GaePre p;
+  const int t = i / r.N, e = i - t * r.N;
+#pragma unroll
+  for (int k = 0; k < kNstepPre; ++k) {
+    const int tt = r.T - 1 - k;
+    const long at = (long)(tt >= t ? tt : t) * r.N + e;
+    p.rw[k] = r.rewards[at];
+    p.mk[k] = r.masks[at];
+    p.va[k] = r.values_act[at];
+  }
+  return p;
+}
+__device__ __forceinline__ void gae_row_from(const GaeArgs& r, const int i, const float vb, const GaePre& p, float& y,
+                                             float& adv) {
+  const int t = i / r.N, e = i - t * r.N;
+  double A = 0.0, Vn = (double)vb, V = Vn;
+#pragma unroll
+  for (int k = 0; k < kNstepPre; ++k) {
+    const int tt = r.T - 1 - k;
+    if (tt >= t) {
+      V = (double)p.va[k];
+      gae_step(r.gamma, r.gl, p.rw[k], p.mk[k], V, Vn, A);
+      Vn = V;
+    }
+  }
+  for (int tt = r.T - 1 - kNstepPre; tt >= t; --tt) {
+    const long k = (long)tt * r.N + e;
+    V = (double)r.values_act[k];
+    gae_step(r.gamma, r.gl, r.rewards[k], r.masks[k], V, Vn, A);
+    Vn = V;
+  }
+  adv = (float)A;
+  y = (float)__dadd_rn(A, V);
+}
+
+// One spelling for both estimators inside the kernels: the argument block's type picks the scan.
+template <int EST> struct PreOf { using type = NstepPre; };
+template <> struct PreOf<kEstGae> { using type = GaePre; };
+__device__ __forceinline__ void returns_row(const ReturnsArgs& r, const int i, float& y, float& adv) { nstep_row(r, i, y, adv); }
+__device__ __forceinline__ void returns_row(const GaeArgs& r, const int i, float& y, float& adv) {
+  gae_row_from(r, i, r.v_boot[i % r.N], y, adv);
+}
+__device__ __forceinline__ NstepPre returns_preload(const ReturnsArgs& r, const int i) { return nstep_preload(r, i); }
+__device__ __forceinline__ GaePre returns_preload(const GaeArgs& r, const int i) { return gae_preload(r, i); }
+__device__ __forceinline__ void returns_row_from(const ReturnsArgs& r, const int i, const float vb, const NstepPre& p,
+                                                 float& y, float& adv) {
+  nstep_row_from(r, i, vb, p, y, adv);
+}
+__device__ __forceinline__ void returns_row_from(const GaeArgs& r, const int i, const float vb, const GaePre& p, float& y,
+                                                 float& adv) {
+  gae_row_from(r, i, vb, p, y, adv);
+}
+
+template <int AP, class RT>
 __device__ __forceinline__ void load_row_and_grad(const float* __restrict__ probs, const float* __restrict__ values,
                                                   const int32_t* __restrict__ actions, const float* __restrict__ y,
                                                   const float* __restrict__ adv, int i, int A, float beta, float s,
-                                                  float (&out)[AP + 1], float* stats, const ReturnsArgs& rt,
+                                                  float (&out)[AP + 1], float* stats, const RT& rt,
                                                   float* yv_out = nullptr, float* av_out = nullptr) {
   float pi[AP];
 #pragma unroll
   for (int a = 0; a < AP; ++a) pi[a] = probs[(long)i * A + (a < A ? a : 0)];
   float yv, av;
   if (rt.v_boot) {
-    nstep_row(rt, i, yv, av);
+    returns_row(rt, i, yv, av);
   } else {
     yv = y[i];
     av = adv[i];
@@ -352,7 +437,7 @@ __device__ __forceinline__ void load_row_and_grad(const float* __restrict__ prob
 //                   recomputed into LDS in chunks of 256 rows, h rows loaded in batches
 //   B + H/32        head bias gradients + loss scalars
 constexpr int HB_CHUNK = 256;
-template <int H, int AP>
+template <int H, int AP, int EST>
 __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ values,
                                                         const int32_t* __restrict__ actions, const float* __restrict__ y,
                                                         const float* __restrict__ adv, const float* __restrict__ h,
@@ -360,7 +445,8 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
                                                         int A, int B, float beta, float* __restrict__ dH,
                                                         float* __restrict__ gWa, float* __restrict__ gba,
                                                         float* __restrict__ gWc, float* __restrict__ gbc,
-                                                        float* __restrict__ loss_out, const ReturnsArgs rt) {
+                                                        float* __restrict__ loss_out,
+                                                        const typename ReturnsOf<EST>::type rt) {
   constexpr int NV = AP + 1;
   constexpr int NS = NV + 3;                       // + 3 loss statistics (role 3)
   const int tid = threadIdx.x;
@@ -497,7 +583,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
 // dgrad_tower_kernel).  One launch less per update; every value bit-identical to the separate launches.
 static_assert(kDlStride == MAXA + 1 + 3, "floats per row in the dl buffer: AP + 1 gradients (padded to 33) + 3 loss terms");
 
-template <int H, int AP>
+template <int H, int AP, int EST>
 __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restrict__ slab, int splits, long slab_stride,
                                                           const float* __restrict__ fc_b, const float* __restrict__ Wa,
                                                           const float* __restrict__ ba, const float* __restrict__ Wc,
@@ -506,7 +592,8 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
                                                           float* __restrict__ probs_ws, float* __restrict__ values_ws,
                                                           const int32_t* __restrict__ actions, const float* __restrict__ y,
                                                           const float* __restrict__ adv, float beta, float* __restrict__ dH,
-                                                          float* __restrict__ dl_buf, const ReturnsArgs rt) {
+                                                          float* __restrict__ dl_buf,
+                                                          const typename ReturnsOf<EST>::type rt) {
   constexpr int JPT = H / 256;
   constexpr int NV = AP + 1;                 // A logits (padded) + value
   constexpr int NB = NV + 1;                 // + the bootstrap row's value
@@ -538,9 +625,9 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
     for (int a = 0; a < AP; ++a) waj[jj][a] = Wa[j * A + (a < A ? a : 0)];
   }
   const int act = actions[i];
-  // (the row's n-step scan runs on thread 0 further down: its inputs are wave-uniform addresses, requested here)
-  NstepPre npre;
-  if (rt.rewards) npre = nstep_preload(rt, i);
+  // (the row's returns scan runs on thread 0 further down: its inputs are wave-uniform addresses, requested here)
+  typename PreOf<EST>::type npre;
+  if (rt.rewards) npre = returns_preload(rt, i);
   float part[NB], hv[JPT];
 #pragma unroll
   for (int a = 0; a < NB; ++a) part[a] = 0.f;
@@ -591,7 +678,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
     values_ws[i] = lg[AP];
     float yv, av;
     if (rt.rewards) {
-      nstep_row_from(rt, i, boot ? lg[NV] : rt.v_boot[i % rt.N], npre, yv, av);
+      returns_row_from(rt, i, boot ? lg[NV] : rt.v_boot[i % rt.N], npre, yv, av);
       rt.y_out[i] = yv;                      // the learner's records of the returns (paac.py:151-154 feed layout)
       rt.adv_out[i] = av;
       if (boot && i < rt.N) values_ws[B + i] = lg[NV];
@@ -725,19 +812,19 @@ inline void launch_heads_fwd(int A, dim3 grid, hipStream_t s, Args... args) {
   else if (A <= 20) launch_k(heads_fwd_kernel<H, 20>, grid, dim3(256), s, PROF_WHOLE, args...);
   else launch_k(heads_fwd_kernel<H, 32>, grid, dim3(256), s, PROF_WHOLE, args...);
 }
-template <int H, class... Args>
+template <int H, int EST, class... Args>
 inline void launch_heads_train(int A, dim3 grid, hipStream_t s, Args... args) {
-  if (A <= 4) launch_k(heads_train_kernel<H, 4>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 8) launch_k(heads_train_kernel<H, 8>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 20) launch_k(heads_train_kernel<H, 20>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else launch_k(heads_train_kernel<H, 32>, grid, dim3(256), s, PROF_WHOLE, args...);
+  if (A <= 4) launch_k(heads_train_kernel<H, 4, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 8) launch_k(heads_train_kernel<H, 8, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 20) launch_k(heads_train_kernel<H, 20, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else launch_k(heads_train_kernel<H, 32, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
 }
-template <int H, class... Args>
+template <int H, int EST, class... Args>
 inline void launch_heads_bwd(int A, dim3 grid, hipStream_t s, Args... args) {
-  if (A <= 4) launch_k(heads_bwd_kernel<H, 4>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 8) launch_k(heads_bwd_kernel<H, 8>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 20) launch_k(heads_bwd_kernel<H, 20>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else launch_k(heads_bwd_kernel<H, 32>, grid, dim3(256), s, PROF_WHOLE, args...);
+  if (A <= 4) launch_k(heads_bwd_kernel<H, 4, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 8) launch_k(heads_bwd_kernel<H, 8, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 20) launch_k(heads_bwd_kernel<H, 20, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else launch_k(heads_bwd_kernel<H, 32, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
 }
 
 }  // namespace paac

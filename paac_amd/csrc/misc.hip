@@ -84,6 +84,54 @@ __global__ void nstep_returns_kernel(const float* __restrict__ v_boot, const flo
   }
 }
 
+// The GAE sibling (heads.h: gae_step is the arithmetic contract): same chunked loads, same bookkeeping wave.  gl = gamma *
+// lambda.  V_{t+1} of a chunk's first step is the previous chunk's last value (the bootstrap value at t = T - 1).
+__global__ void gae_returns_kernel(const float* __restrict__ v_boot, const float* __restrict__ rewards,
+                                   const float* __restrict__ masks, const float* __restrict__ values, int T, int N,
+                                   double gamma, double gl, float* __restrict__ y, float* __restrict__ adv,
+                                   const CycleTick ct) {
+  const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (threadIdx.x >= 64) {
+    if (blockIdx.x == 0 && threadIdx.x == 64) {
+      if (ct.global_step) {
+        const int64_t step = *ct.global_step + ct.step_inc;
+        *ct.global_step = step;
+        double lr = 0.0;
+        if (step <= ct.anneal) lr = ct.lr0 - ((double)step * ct.lr0 / (double)ct.anneal);
+        *ct.lr_out = (float)lr;
+      }
+      if (ct.tick) *ct.tick += ct.tick_inc;
+    }
+    return;
+  }
+  if (e >= N) return;
+  constexpr int CH = 8;
+  double A = 0.0, Vn = (double)v_boot[e];
+  for (int t0 = T - 1; t0 >= 0; t0 -= CH) {
+    float r[CH], m[CH], v[CH];
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      const int t = t0 - u;
+      const long i = (long)(t >= 0 ? t : 0) * N + e;
+      r[u] = rewards[i];
+      m[u] = masks[i];
+      v[u] = values[i];
+    }
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      const int t = t0 - u;
+      if (t >= 0) {
+        const long i = (long)t * N + e;
+        const double V = (double)v[u];
+        gae_step(gamma, gl, r[u], m[u], V, Vn, A);
+        adv[i] = (float)A;
+        y[i] = (float)__dadd_rn(A, V);
+        Vn = V;
+      }
+    }
+  }
+}
+
 // actor_learner.py:119-123 evaluated after the cycle's increments (paac.py:127,156).
 __global__ void lr_step_kernel(int64_t* global_step, int64_t inc, double lr0, int64_t anneal, float* lr_out) {
   const int64_t step = *global_step + inc;
@@ -1978,6 +2026,36 @@ int paac_nstep_returns_tick(const float* v_boot, const float* rewards, const flo
   ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
   launch_k(nstep_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
            values, T, N, gamma, y, adv, ct);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_gae_returns(const float* v_boot, const float* rewards, const float* masks, const float* values, int T, int N,
+                     double gamma, double gae_lambda, float* y, float* adv, paac_stream_t stream) {
+  PAAC_REQUIRE(T > 0 && N > 0, "paac_gae_returns: T=%d N=%d", T, N);
+  PAAC_REQUIRE(gae_lambda >= 0.0 && gae_lambda <= 1.0, "paac_gae_returns: gae_lambda %g outside [0, 1]", gae_lambda);
+  CycleTick ct;
+  memset(&ct, 0, sizeof(ct));
+  ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
+  launch_k(gae_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
+           values, T, N, gamma, gamma * gae_lambda, y, adv, ct);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_gae_returns_tick(const float* v_boot, const float* rewards, const float* masks, const float* values, int T,
+                          int N, double gamma, double gae_lambda, float* y, float* adv, int64_t* global_step_dev,
+                          int64_t increment, double initial_lr, int64_t lr_annealing_steps, float* lr_out_dev,
+                          uint64_t* tick_dev, uint64_t tick_inc, paac_stream_t stream) {
+  PAAC_REQUIRE(T > 0 && N > 0, "paac_gae_returns_tick: T=%d N=%d", T, N);
+  PAAC_REQUIRE(gae_lambda >= 0.0 && gae_lambda <= 1.0, "paac_gae_returns_tick: gae_lambda %g outside [0, 1]", gae_lambda);
+  PAAC_REQUIRE(global_step_dev && lr_out_dev && lr_annealing_steps > 0, "paac_gae_returns_tick: bad arguments");
+  CycleTick ct;
+  ct.global_step = global_step_dev; ct.step_inc = increment; ct.lr0 = initial_lr; ct.anneal = lr_annealing_steps;
+  ct.lr_out = lr_out_dev; ct.tick = tick_dev; ct.tick_inc = tick_inc;
+  ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
+  launch_k(gae_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
+           values, T, N, gamma, gamma * gae_lambda, y, adv, ct);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

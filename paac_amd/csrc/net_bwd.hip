@@ -221,7 +221,7 @@ int launch_pack_dgrad(paac_ctx* ctx, const float* params, hipStream_t s) {
 template <class NT>
 static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                          const float* y, const float* adv, int batch, float beta, float* grad, float* loss_out,
-                         int phase, const ReturnsArgs& rt, hipStream_t s) {
+                         int phase, const GaeArgs& rt, int estimator, hipStream_t s) {
   const paac_layout& L = ctx->layout;
   Workspace& W = ctx->ws[1];
   const int cls = batch_class(batch);
@@ -249,7 +249,8 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       if (rc) return rc;
     }
   }
-  ReturnsArgs rtl = rt;
+  GaeArgs rtl = rt;                            // (the n-step kernels take its ReturnsArgs part: estimator chosen below)
+  const ReturnsArgs& rtn = rtl;
   if (rtl.boot_in_fwd && !fused_heads) {       // the separate heads launch has produced the bootstrap rows' values
     rtl.v_boot = W.values + batch;
     rtl.boot_in_fwd = 0;
@@ -259,16 +260,27 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     ProfScope ps(ctx, F_HEADS_BWD, batch, s);
     const int rows = ctx->heads_pending_rows;
     // (rows kept by the acting forwards hold finished fc activations: one "slab", zero bias -- fmaxf(h + 0, 0) == h)
-    launch_heads_train<NT::H>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
-                              ctx->heads_pending_h ? (const float*)ctx->zeros : params + L.offset[i_wf + 1], wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
-                              batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, rtl);
+    const float* fc_b = ctx->heads_pending_h ? (const float*)ctx->zeros : params + L.offset[i_wf + 1];
+    if (estimator == kEstGae)
+      launch_heads_train<NT::H, kEstGae>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
+                                         fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
+                                         batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, rtl);
+    else
+      launch_heads_train<NT::H, kEstNstep>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
+                                           fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
+                                           batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, rtn);
     ctx->heads_pending_rows = 0;
     ctx->heads_pending_h = 0;
   } else if (do_fc) {
     ProfScope ps(ctx, F_HEADS_BWD, batch, s);
-    launch_heads_bwd<NT::H>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
-                            adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
-                            grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, rtl);
+    if (estimator == kEstGae)
+      launch_heads_bwd<NT::H, kEstGae>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
+                                       adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
+                                       grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, rtl);
+    else
+      launch_heads_bwd<NT::H, kEstNstep>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
+                                         adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
+                                         grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, rtn);
   }
   const float* xf = (NT::NCONV == 3) ? W.act[2] : W.act[1];   // flattened last conv output
   float* dxf = (NT::NCONV == 3) ? ctx->dact[2] : ctx->dact[1];
@@ -513,17 +525,20 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
 int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
                     const float* adv, int batch, float beta, float* grad, float* loss_out, int phase, hipStream_t s,
                     const paac_returns* ret) {
-  ReturnsArgs rt;
+  GaeArgs rt;
   memset(&rt, 0, sizeof(rt));
+  int estimator = kEstNstep;
   if (ret) {
+    estimator = ret->estimator;              // (validated by paac_loss_backward_returns)
+    if (estimator == kEstGae) rt.gl = ret->gamma * ret->gae_lambda;
     rt.v_boot = ret->v_boot; rt.boot_in_fwd = ret->v_boot ? 0 : 1; rt.rewards = ret->rewards; rt.masks = ret->masks; rt.values_act = ret->values;
     rt.T = ret->T; rt.N = ret->N; rt.gamma = ret->gamma; rt.y_out = ret->y_out; rt.adv_out = ret->adv_out;
     rt.global_step = ret->global_step_dev; rt.step_inc = ret->increment; rt.lr0 = ret->initial_lr;
     rt.anneal = ret->lr_annealing_steps; rt.lr_out = ret->lr_out_dev; rt.tick = ret->tick_dev; rt.tick_inc = ret->tick_inc;
   }
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, s);
-  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, s);
+    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, s);
+  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, s);
 }
 
 int64_t wslab_floats_needed(int arch) {

@@ -56,6 +56,8 @@ def activation_size(convs, fc, what, batch):
     """Floats paac_debug_activation copies for `what` (include/paac_hip.h) over `batch` rows of the geometry (convs, fc):
     VALID convolutions over 84 x 84; None for a `what` the geometry does not have."""
     what = int(what)
+    if what == 25:
+        return int(batch)
     if 21 <= what <= 24:
         what -= 20
     elif 11 <= what <= 14:
@@ -194,10 +196,12 @@ class Context(object):
 
     def loss_backward_returns(self, params, states, actions, v_boot, rewards, masks, values, gamma, y_out, adv_out,
                               entropy_beta, grad, loss_out=None, forward_done=False, phase=0, global_step_dev=None,
-                              increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None, tick_dev=None, tick_inc=0):
+                              increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None, tick_dev=None, tick_inc=0,
+                              gae_lambda=None):
         """n-step returns (+ the cycle's schedule bookkeeping) inside the backward's first launch
         (include/paac_hip.h: paac_loss_backward_returns) == nstep_returns_tick followed by loss_backward.
-        v_boot=None: the bootstrap values are rows [B, B + N) of the training forward that has already run."""
+        v_boot=None: the bootstrap values are rows [B, B + N) of the training forward that has already run.
+        gae_lambda: None or 1.0 = the n-step return; anything else = GAE(lambda) instead (uses_gae)."""
         B = self._check_states(states)
         T, N = rewards.shape
         if T * N != B:
@@ -209,7 +213,9 @@ class Context(object):
             global_step_dev=_ptr(global_step_dev, torch.int64, 1, "global_step", True), increment=int(increment),
             initial_lr=float(initial_lr), lr_annealing_steps=int(lr_annealing_steps),
             lr_out_dev=_ptr(lr_out_dev, torch.float32, 1, "lr_out", True),
-            tick_dev=_ptr(tick_dev, torch.int64, 1, "tick", True), tick_inc=int(tick_inc))
+            tick_dev=_ptr(tick_dev, torch.int64, 1, "tick", True), tick_inc=int(tick_inc),
+            estimator=_lib.RETURNS_GAE if uses_gae(gae_lambda) else _lib.RETURNS_NSTEP,
+            gae_lambda=float(gae_lambda) if uses_gae(gae_lambda) else 0.0)
         _lib.check(self.lib.paac_loss_backward_returns(
             self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
             _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"), ctypes.byref(ret), B,
@@ -386,6 +392,45 @@ def lr_step(global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_d
     _lib.check(lib.paac_lr_step(_ptr(global_step_dev, torch.int64, 1, "global_step"), int(increment), float(initial_lr),
                                 int(lr_annealing_steps), _ptr(lr_out_dev, torch.float32, 1, "lr_out"), _stream()),
                "paac_lr_step")
+
+
+def uses_gae(gae_lambda):
+    """THE routing rule of --gae_lambda: None (not given) and exactly 1.0 mean the reference's n-step return through the
+    n-step kernels -- GAE(1) is the same quantity only up to the last place -- and every other value the GAE kernels."""
+    return gae_lambda is not None and float(gae_lambda) != 1.0
+
+
+def returns(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None):
+    """nstep_returns or gae_returns by the routing rule (uses_gae)."""
+    if uses_gae(gae_lambda):
+        gae_returns(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv)
+    else:
+        nstep_returns(v_boot, rewards, masks, values, gamma, y, adv)
+
+
+def gae_returns(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv):
+    """Generalized advantage estimation on the rollout records (include/paac_hip.h: paac_gae_returns)."""
+    T, N = rewards.shape
+    lib = _lib.load()
+    _lib.check(lib.paac_gae_returns(_ptr(v_boot, torch.float32, N, "v_boot"), _ptr(rewards, torch.float32, T * N, "rewards"),
+                                    _ptr(masks, torch.float32, T * N, "masks"), _ptr(values, torch.float32, T * N, "values"),
+                                    T, N, float(gamma), float(gae_lambda), _ptr(y, torch.float32, T * N, "y"),
+                                    _ptr(adv, torch.float32, T * N, "adv"), _stream()), "paac_gae_returns")
+
+
+def gae_returns_tick(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv, global_step_dev, increment, initial_lr,
+                     lr_annealing_steps, lr_out_dev, tick_dev=None, tick_inc=0):
+    T, N = rewards.shape
+    lib = _lib.load()
+    _lib.check(lib.paac_gae_returns_tick(_ptr(v_boot, torch.float32, N, "v_boot"), _ptr(rewards, torch.float32, T * N, "rewards"),
+                                         _ptr(masks, torch.float32, T * N, "masks"), _ptr(values, torch.float32, T * N, "values"),
+                                         T, N, float(gamma), float(gae_lambda), _ptr(y, torch.float32, T * N, "y"),
+                                         _ptr(adv, torch.float32, T * N, "adv"),
+                                         _ptr(global_step_dev, torch.int64, 1, "global_step"), int(increment),
+                                         float(initial_lr), int(lr_annealing_steps),
+                                         _ptr(lr_out_dev, torch.float32, 1, "lr_out"),
+                                         _ptr(tick_dev, torch.int64, 1, "tick", True), int(tick_inc), _stream()),
+               "paac_gae_returns_tick")
 
 
 def nstep_returns(v_boot, rewards, masks, values, gamma, y, adv):

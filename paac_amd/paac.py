@@ -189,7 +189,7 @@ class DeviceRollout(object):
                                     phase=(0 if self.single_exchange else 1) if self.phased else 3,
                                     global_step_dev=self.global_step_dev, increment=self.total_envs * T,
                                     initial_lr=L.initial_lr, lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev,
-                                    tick_dev=self.tick, tick_inc=T)
+                                    tick_dev=self.tick, tick_inc=T, gae_lambda=L.gae_lambda)
 
     def _backward_conv(self, parity):
         L = self.L
@@ -748,7 +748,7 @@ class PAACLearner(ActorLearner):
             self.ctx.forward(params, d_cur, values=d_vboot)
             d_rewards.copy_(torch.from_numpy(rewards))
             d_masks.copy_(torch.from_numpy(masks))
-            hip_ops.nstep_returns(d_vboot, d_rewards, d_masks, d_values, self.gamma, d_y, d_adv)
+            hip_ops.returns(d_vboot, d_rewards, d_masks, d_values, self.gamma, d_y, d_adv, self.gae_lambda)
             lr = self.get_lr()
             self.lr_dev.fill_(float(np.float32(lr)))
             self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv,
@@ -758,7 +758,9 @@ class PAACLearner(ActorLearner):
             if getattr(self.args, "record_feeds", False):
                 self.last_feed = dict(states=d_states.view(T * N, 84, 84, 4).cpu().numpy(), y=d_y.cpu().numpy(),
                                       adv=d_adv.cpu().numpy(), actions=d_actions.view(-1).cpu().numpy(), lr=lr,
-                                      values=d_values.cpu().numpy(), global_step=self.global_step)
+                                      values=d_values.cpu().numpy(), global_step=self.global_step,
+                                      rewards=d_rewards.cpu().numpy(), masks=d_masks.cpu().numpy(),
+                                      v_boot=d_vboot.cpu().numpy())
                 if getattr(self.args, "feed_callback", None):
                     self.args.feed_callback(self.last_feed)
             if getattr(self.args, "cycle_callback", None):      # bench hook: one call per finished cycle, nothing copied

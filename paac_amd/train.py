@@ -76,6 +76,9 @@ BUILD_FLAGS = (
      "--beta2 and --e; --alpha is ignored)"),
     (("--beta1",), "beta1", 0.9, float, "Adam decay of the first-moment average"),
     (("--beta2",), "beta2", 0.999, float, "Adam decay of the second-moment average"),
+    (("--gae_lambda",), "gae_lambda", 1.0, float,
+     "advantage estimator: 1.0 = the reference's n-step return (bit for bit); a value in [0, 1) = generalized advantage "
+     "estimation GAE(lambda) on the same rollout records, 0 being the one-step TD error"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),

@@ -215,6 +215,43 @@ int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t
                                const paac_returns* ret, int batch, float entropy_beta, float* grad, float* loss_out,
                                int forward_done, int phase, paac_stream_t stream);
 
+/* --ppo_epochs K / --ppo_clip EPS: PPO's clipped-surrogate epochs (Schulman et al., arXiv 1707.06347) on one rollout.  The
+ * reference has no counterpart; this is the contract.
+ *   K = 1 (the default) is the update above, through the same kernels, whatever EPS says.  K > 1 (up to PAAC_PPO_EPOCHS_MAX)
+ *   is K optimizer steps per rollout; EPS in (0, 1) is read only then.
+ *   Epoch 1 is the update above (either estimator; global_step / lr / frame counter advance once per cycle, here) and also
+ *   records p_old[i] = pi(a_i | s_i): the fp32 probability its own training-side heads computed, the value they write to the
+ *   ctx's probabilities at [i, a_i] -- paac_loss_backward_returns_record, or paac_loss_backward_record.  The
+ *   ratio of epoch 1 is therefore identically 1 on every route, it needs no ratio arithmetic, and its gradient is
+ *   paac_loss_backward's bit for bit.  y, adv and p_old are frozen for the rest of the cycle.
+ *   Epochs 2..K: paac_train_forward_trunk over the T*N rollout rows (no bootstrap rows) on the current weights, then
+ *   paac_loss_backward_ppo(forward_done = 1), then the same exchange, clip and optimizer step with the same lr (Adam's powers
+ *   advance per step).  Per row, fp32, no contraction, with eps = 1e-30f and s = 5/B:
+ *     p = pi[act]; invq = 1/(p_old + eps); r = p*invq
+ *     active = !((adv > 0 && r > 1 + EPS) || (adv < 0 && r < 1 - EPS))
+ *     g_a = -(adv*(active ? 1 : 0)*1[a = act]*invq - beta*(log(pi_a + eps) + pi_a/(pi_a + eps)))
+ *     dlogit_a = s*pi_a*(g_a - sum_j g_j pi_j); dv = s*0.5*(v - y)
+ *     actor term = -(min(r*adv, clamp(r, 1 - EPS, 1 + EPS)*adv) + beta*entropy); entropy and critic terms unchanged
+ *   (the gradient of the reference loss at the effective advantage adv*active*(p + eps)/(p_old + eps)).
+ * paac_loss_backward_ppo: y / adv / p_old device float[batch]; loss_out as paac_loss_backward's (its actor entry = the mean
+ * actor term above); ppo_stats_out (nullable): device float[2] = {clip_fraction = mean of !active, approx_kl = mean of
+ * log(p_old + eps) - log(p + eps)}, reduced in a fixed order (one small launch), written unless phase == 2.  forward_done
+ * and every phase as paac_loss_backward.  clip_eps outside (0, 1) (NaN included) and a NULL p_old are refused.
+ * paac_loss_backward_record: paac_loss_backward that also writes p_old_out[batch] (not in phase 2): the recording epoch of a
+ * caller that computes y / adv itself.  Gradient and loss equal paac_loss_backward's bit for bit.
+ * paac_loss_backward_returns_record: the same for paac_loss_backward_returns (either estimator; paac_returns is unchanged). */
+#define PAAC_PPO_EPOCHS_MAX 16
+int paac_loss_backward_record(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                              const float* y, const float* adv, float* p_old_out, int batch, float entropy_beta,
+                              float* grad, float* loss_out, int forward_done, int phase, paac_stream_t stream);
+int paac_loss_backward_returns_record(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                                      const paac_returns* ret, float* p_old_out, int batch, float entropy_beta,
+                                      float* grad, float* loss_out, int forward_done, int phase, paac_stream_t stream);
+int paac_loss_backward_ppo(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                           const float* y, const float* adv, const float* p_old, float clip_eps, int batch,
+                           float entropy_beta, float* grad, float* loss_out, float* ppo_stats_out, int forward_done,
+                           int phase, paac_stream_t stream);
+
 /* Gradient clipping + RMSPropOptimizer.apply_gradients (actor_learner.py:31-34,51-64,70):
  *   g <- grad * grad_scale           (grad_scale = 1/world_size after the sum all-reduce)
  *   mode IGNORE: f = 1
@@ -370,7 +407,9 @@ int paac_graph_destroy(paac_graph* g);
  * what: 1..3 = conv outputs a1..a3 [batch,OH,OW,C], 4 = fc activations h [batch,H] of the activation set used
  * last (acting or training); 21..23 / 24 = the same of the TRAINING set explicitly (rows kept by paac_keep_next_forward);
  * 11..13 / 14 = the gradients wrt them; 25 = the value head's outputs [batch] of the TRAINING set (after an update whose
- * returns took the bootstrap values from the training forward, rows [T*N, T*N + N) are those values).  out_capacity: floats `out` holds; a copy larger than that is refused (nothing is
+ * returns took the bootstrap values from the training forward, rows [T*N, T*N + N) are those values); 26 = the policy
+ * head's probabilities [batch, A] of the TRAINING set (what p_old is recorded from; needs the ctx for A, so
+ * paac_debug_activation_size does not know it).  out_capacity: floats `out` holds; a copy larger than that is refused (nothing is
  * written).  Returns the element count. */
 int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, int64_t out_capacity, paac_stream_t stream);
 /* Test/debug: the element count paac_debug_activation copies for (what, batch) on geometry `arch` of this library (host

@@ -15,6 +15,7 @@ PROF_FAMILIES = 16
 ARCH_NIPS, ARCH_NATURE, ARCH_USER = 0, 1, 2
 CLIP_IGNORE, CLIP_GLOBAL, CLIP_LOCAL = 0, 1, 2
 RETURNS_NSTEP, RETURNS_GAE = 0, 1
+PPO_EPOCHS_MAX = 16            # PAAC_PPO_EPOCHS_MAX
 
 
 class Layout(ctypes.Structure):
@@ -64,6 +65,12 @@ _SIGNATURES = {
     "paac_set_managed_weights": (c_int, [c_void_p, c_int]),
     "paac_loss_backward_returns": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Returns), c_int, c_float, c_void_p,
                                            c_void_p, c_int, c_int, c_void_p]),
+    "paac_loss_backward_returns_record": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Returns), c_void_p, c_int,
+                                                  c_float, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "paac_loss_backward_record": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                          c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "paac_loss_backward_ppo": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
+                                       c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_clip_rmsprop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,

@@ -53,6 +53,17 @@ class ActorLearner(object):
         self.gae_lambda = float(getattr(args, "gae_lambda", 1.0))
         if not 0.0 <= self.gae_lambda <= 1.0:           # (NaN fails both comparisons)
             raise ValueError("gae_lambda %r: expected a value in [0, 1]" % (self.gae_lambda,))
+        # --ppo_epochs K / --ppo_clip EPS (include/paac_hip.h has the contract): K = 1 (and Namespaces / args.json files from
+        # before the flags) = one update per rollout through today's calls; EPS is read only when K > 1
+        self.ppo_epochs = getattr(args, "ppo_epochs", 1)
+        if isinstance(self.ppo_epochs, bool) or self.ppo_epochs != int(self.ppo_epochs) or \
+                not 1 <= int(self.ppo_epochs) <= _lib.PPO_EPOCHS_MAX:
+            raise ValueError("ppo_epochs %r: expected an integer in [1, %d] (a captured cycle grows by about ten launches per "
+                             "epoch)" % (self.ppo_epochs, _lib.PPO_EPOCHS_MAX))
+        self.ppo_epochs = int(self.ppo_epochs)
+        self.ppo_clip = float(getattr(args, "ppo_clip", 0.2))
+        if not 0.0 < self.ppo_clip < 1.0:               # (NaN fails both comparisons)
+            raise ValueError("ppo_clip %r: expected a value in (0, 1)" % (self.ppo_clip,))
         self.clip_norm = args.clip_norm
         self.clip_norm_type = args.clip_norm_type
         if self.clip_norm_type == 'ignore':
@@ -97,6 +108,14 @@ class ActorLearner(object):
         self.lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.gnorm_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+        # --ppo_epochs: per-cycle scratch, nothing of it is checkpointed.  p_old [T*N]; row k of ppo_loss / ppo_stats = the
+        # loss scalars / {clip_fraction, approx_kl} of epoch k + 1 (row 0 stays zero: epoch 1 reports through loss_dev, and its
+        # ratio is identically 1)
+        self.p_old = self.ppo_loss = self.ppo_stats = None
+        if self.ppo_epochs > 1:
+            self.p_old = torch.zeros(self.emulator_counts * self.max_local_steps, dtype=torch.float32, device=dev)
+            self.ppo_loss = torch.zeros((self.ppo_epochs, 4), dtype=torch.float32, device=dev)
+            self.ppo_stats = torch.zeros((self.ppo_epochs, 2), dtype=torch.float32, device=dev)
         self.train_step = Placeholder('train_step')
 
         self.ctx = hip_ops.Context(self.network.arch_id, self.num_actions,
@@ -180,6 +199,14 @@ class ActorLearner(object):
         else:
             self.ctx.clip_rmsprop(net.params, self.grad, self.rms, self.mom, self.lr_dev, self.alpha, self.momentum,
                                   self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
+
+    def ppo_epoch_backward(self, k, states, actions, y, adv, phase):
+        """Epoch k + 1 (k = 1 .. ppo_epochs - 1) up to its gradient: training forward (trunk) over the rollout rows on the
+        current weights, then the clipped-surrogate backward on the frozen y / adv / p_old."""
+        params = self.network.params
+        self.ctx.train_forward_trunk(params, states)
+        self.ctx.loss_backward_ppo(params, states, actions, y, adv, self.p_old, self.ppo_clip, self.entropy_beta, self.grad,
+                                   self.ppo_loss[k], self.ppo_stats[k], forward_done=True, phase=phase)
 
     # -- one optimizer step from a reference-style feed dict (Session.run([train_step, ...], feed)) ----
     def _train_step_from_feed(self, feed_dict):

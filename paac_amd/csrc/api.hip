@@ -194,6 +194,7 @@ int paac_create(const paac_cfg* cfg, paac_ctx** out) {
   }
   PAAC_CHECK_HIP(hipMalloc(&c->dh, (size_t)B * c->spec.fc * sizeof(float)));
   PAAC_CHECK_HIP(hipMalloc(&c->dl_buf, (size_t)B * paac::kDlStride * sizeof(float)));
+  PAAC_CHECK_HIP(hipMalloc(&c->ppo_rows, (size_t)B * 2 * sizeof(float)));
   c->wslab_floats = wslab_floats_needed(cfg->arch);
   PAAC_CHECK_HIP(hipMalloc(&c->wslab, (size_t)c->wslab_floats * sizeof(float)));
   PAAC_CHECK_HIP(hipMalloc(&c->partials, 8192 * sizeof(float)));
@@ -244,7 +245,7 @@ int paac_destroy(paac_ctx* c) {
   }
   for (int i = 0; i < 3; ++i)
     if (c->dact[i]) (void)hipFree(c->dact[i]);
-  float* bufs[] = {c->dh, c->wslab, c->partials, c->dl_buf, c->zeros};
+  float* bufs[] = {c->dh, c->wslab, c->partials, c->dl_buf, c->zeros, c->ppo_rows};
   for (float* b : bufs)
     if (b) (void)hipFree(b);
   if (c->mt_ahead) (void)hipFree(c->mt_ahead);
@@ -496,9 +497,9 @@ int paac_loss_backward(paac_ctx* ctx, const float* params, const uint8_t* states
   return 0;
 }
 
-int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
-                               const paac_returns* ret, int batch, float entropy_beta, float* grad, float* loss_out,
-                               int forward_done, int phase, paac_stream_t stream) {
+static int loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                                 const paac_returns* ret, float* p_old_out, int batch, float entropy_beta, float* grad,
+                                 float* loss_out, int forward_done, int phase, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && states && actions && ret && grad, "paac_loss_backward_returns: null argument");
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_returns: batch %d outside (0, max_batch=%d]", batch,
                ctx->max_batch);
@@ -522,8 +523,67 @@ int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t
     if (rc) return rc;
   }
   ctx->last_ws = 1;
+  // (p_old_out: this is epoch 1 of a --ppo_epochs cycle -- the same arithmetic, plus the store of p_old)
   rc = launch_backward(ctx, params, states, actions, ret->y_out, ret->adv_out, batch, entropy_beta, grad, loss_out, phase,
-                       (hipStream_t)stream, ret);
+                       (hipStream_t)stream, ret, p_old_out ? 1 : 0, p_old_out);
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                               const paac_returns* ret, int batch, float entropy_beta, float* grad, float* loss_out,
+                               int forward_done, int phase, paac_stream_t stream) {
+  return loss_backward_returns(ctx, params, states, actions, ret, nullptr, batch, entropy_beta, grad, loss_out, forward_done,
+                               phase, stream);
+}
+
+int paac_loss_backward_returns_record(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                                      const paac_returns* ret, float* p_old_out, int batch, float entropy_beta, float* grad,
+                                      float* loss_out, int forward_done, int phase, paac_stream_t stream) {
+  PAAC_REQUIRE(p_old_out, "paac_loss_backward_returns_record: null p_old_out");
+  return loss_backward_returns(ctx, params, states, actions, ret, p_old_out, batch, entropy_beta, grad, loss_out, forward_done,
+                               phase, stream);
+}
+
+int paac_loss_backward_record(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                              const float* y, const float* adv, float* p_old_out, int batch, float entropy_beta, float* grad,
+                              float* loss_out, int forward_done, int phase, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && states && actions && y && adv && grad, "paac_loss_backward_record: null argument");
+  PAAC_REQUIRE(p_old_out, "paac_loss_backward_record: null p_old_out");
+  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_record: batch %d outside (0, max_batch=%d]", batch,
+               ctx->max_batch);
+  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward_record: phase %d", phase);
+  int rc = 0;
+  if (!forward_done && phase != 2) {
+    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  ctx->last_ws = 1;
+  rc = launch_backward(ctx, params, states, actions, y, adv, batch, entropy_beta, grad, loss_out, phase, (hipStream_t)stream,
+                       nullptr, 1, p_old_out);
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_loss_backward_ppo(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
+                           const float* adv, const float* p_old, float clip_eps, int batch, float entropy_beta, float* grad,
+                           float* loss_out, float* ppo_stats_out, int forward_done, int phase, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && states && actions && y && adv && grad, "paac_loss_backward_ppo: null argument");
+  PAAC_REQUIRE(p_old, "paac_loss_backward_ppo: null p_old");
+  PAAC_REQUIRE(clip_eps > 0.f && clip_eps < 1.f, "paac_loss_backward_ppo: clip_eps %g outside (0, 1)", (double)clip_eps);   // (NaN fails)
+  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_ppo: batch %d outside (0, max_batch=%d]", batch,
+               ctx->max_batch);
+  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward_ppo: phase %d", phase);
+  int rc = 0;
+  if (!forward_done && phase != 2) {
+    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  ctx->last_ws = 1;
+  rc = launch_backward(ctx, params, states, actions, y, adv, batch, entropy_beta, grad, loss_out, phase, (hipStream_t)stream,
+                       nullptr, 2, const_cast<float*>(p_old), clip_eps, ppo_stats_out);
   if (rc) return rc;
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
@@ -554,6 +614,12 @@ int64_t paac_debug_activation_size(int arch, int what, int batch) {
 
 int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, int64_t out_capacity, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && out && batch > 0 && batch <= ctx->max_batch, "paac_debug_activation: bad arguments");
+  if (what == 26) {                                        // policy outputs [batch, A] of the TRAINING set
+    const int64_t np = (int64_t)batch * ctx->cfg.num_actions;
+    PAAC_REQUIRE(np <= out_capacity, "paac_debug_activation: what=26 needs %ld floats, out holds %ld", (long)np, (long)out_capacity);
+    PAAC_CHECK_HIP(hipMemcpyAsync(out, ctx->ws[1].probs, (size_t)np * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return np;
+  }
   const int64_t n = debug_activation_elems(ctx->spec, what, batch);
   if (n < 0) {
     set_error("paac_debug_activation: what=%d", what);

@@ -135,6 +135,7 @@ struct paac_ctx {
   const uint32_t* ahead_state;     // one shot, set by paac_act_step_mt: the MT19937 state to work ahead from (nullptr: off)
   int ahead_D;                     // doubles the step can consume at most: N * (A - 1)
   float* dl_buf;                   // [max_batch][kDlStride] per-row head gradients + loss terms (heads.h)
+  float* ppo_rows;                 // [max_batch][2] per-row clip / KL terms of paac_loss_backward_ppo (heads.h: ppo_stats_kernel)
   int fc_splits_max;
   // conv tower (csrc/tower.h, Nature only): conv weights pre-split into bf16 planes in MFMA operand order
   void* tower_pack;      // kTowerPackVecs x 16 bytes, nullptr when the tower is off
@@ -267,6 +268,7 @@ int launch_sample_env_step_heads(const float* partial, int ntiles, const float* 
                                  const void* mt_ahead, hipStream_t s);
 int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
                     const float* adv, int batch, float beta, float* grad, float* loss_out, int phase, hipStream_t s,
-                    const paac_returns* ret = nullptr);
+                    const paac_returns* ret = nullptr, int loss = 0, float* p_old = nullptr, float clip_eps = 0.f,
+                    float* ppo_stats_out = nullptr);   // loss: heads.h kLossA3c / kLossA3cRecord / kLossPpo
 
 }  // namespace paac

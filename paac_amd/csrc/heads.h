@@ -215,13 +215,33 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
 //   s = 5/B; dv = s*0.5*(v - y); g_a = -(adv*1[a=act]/(pi_a+eps) - beta*(log(pi_a+eps) + pi_a/(pi_a+eps)))
 //   dlogit_a = s*pi_a*(g_a - sum_j g_j pi_j)
 // out[0..AP) = dlogits (0 beyond A), out[AP] = dv.  stats (optional): actor term, critic term, entropy.
-template <int AP>
+// LOSS (compile time, the sibling of the kernels' EST flag; include/paac_hip.h has the contract):
+//   kLossA3c        the reference's loss above
+//   kLossA3cRecord  the same arithmetic; the kernels also store p_old[i] = pi[act] (epoch 1 of a --ppo_epochs cycle)
+//   kLossPpo        PPO's clipped surrogate (Schulman et al., arXiv 1707.06347) in place of the actor term, on frozen y / adv /
+//                   p_old:  invq = 1/(p_old+eps); r = pi[act]*invq; active = !((adv > 0 && r > 1+EPS) || (adv < 0 && r < 1-EPS))
+//                   g_a = -(adv*active*1[a=act]*invq - beta*(...));  actor term = -(min(r adv, clamp(r, 1-EPS, 1+EPS) adv) + beta H)
+//                   pstats: {1 - active, log(p_old+eps) - log(pi[act]+eps)} (clip fraction and approximate KL of the row).
+//                   With p_old = pi[act] the row is active, invq is the plain loss's 1/(pi_a+eps), and every gradient bit is its.
+constexpr int kLossA3c = 0, kLossA3cRecord = 1, kLossPpo = 2;
+template <int AP, int LOSS = kLossA3c>
 __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, int act, float y, float adv, float beta,
-                                              float s, int A, float (&out)[AP + 1], float* stats) {
+                                              float s, int A, float (&out)[AP + 1], float* stats, float p_old = 0.f,
+                                              float clip_eps = 0.f, float* pstats = nullptr) {
 #pragma clang fp contract(off)   // inlined into several kernels that must produce the same bits: no context-dependent fma
   const float eps = 1e-30f;
   float g[AP];
   float dot = 0.f, ent = 0.f, logp = 0.f;
+  float invq = 0.f, ratio = 0.f, af = 1.f;
+  if constexpr (LOSS == kLossPpo) {
+    float pact = 0.f;
+#pragma unroll
+    for (int a = 0; a < AP; ++a) pact = (a == act) ? pi[a] : pact;
+    invq = 1.0f / (p_old + eps);
+    ratio = pact * invq;
+    const bool clipped = (adv > 0.f && ratio > 1.0f + clip_eps) || (adv < 0.f && ratio < 1.0f - clip_eps);
+    af = clipped ? 0.f : 1.f;
+  }
 #pragma unroll
   for (int a = 0; a < AP; ++a) {
     const bool on = a < A;
@@ -229,7 +249,10 @@ __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, in
     const float lp = logf(p + eps);
     const float inv = 1.0f / (p + eps);
     const float oh = (a == act) ? 1.f : 0.f;
-    g[a] = on ? -(adv * oh * inv - beta * (lp + p * inv)) : 0.f;
+    if constexpr (LOSS == kLossPpo)
+      g[a] = on ? -(adv * af * oh * invq - beta * (lp + p * inv)) : 0.f;
+    else
+      g[a] = on ? -(adv * oh * inv - beta * (lp + p * inv)) : 0.f;
     dot += on ? g[a] * p : 0.f;
     ent -= on ? p * lp : 0.f;
     logp += on ? oh * lp : 0.f;
@@ -238,9 +261,20 @@ __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, in
   for (int a = 0; a < AP; ++a) out[a] = (a < A) ? s * pi[a] * (g[a] - dot) : 0.f;
   out[AP] = s * 0.5f * (v - y);
   if (stats) {
-    stats[0] = -(logp * adv + beta * ent);   // actor objective term
+    if constexpr (LOSS == kLossPpo) {
+      const float rc = fminf(fmaxf(ratio, 1.0f - clip_eps), 1.0f + clip_eps);
+      stats[0] = -(fminf(ratio * adv, rc * adv) + beta * ent);   // clipped surrogate + entropy bonus
+    } else {
+      stats[0] = -(logp * adv + beta * ent);   // actor objective term
+    }
     stats[1] = 0.25f * (y - v) * (y - v);    // critic term
     stats[2] = ent;
+  }
+  if constexpr (LOSS == kLossPpo) {
+    if (pstats) {
+      pstats[0] = 1.f - af;
+      pstats[1] = logf(p_old + eps) - logp;
+    }
   }
 }
 
@@ -408,16 +442,32 @@ __device__ __forceinline__ void returns_row_from(const GaeArgs& r, const int i, 
   gae_row_from(r, i, vb, p, y, adv);
 }
 
-template <int AP, class RT>
+// The LOSS != kLossA3c instantiations carry three more arguments behind their estimator's block (every kLossA3c
+// instantiation keeps its block, and with it its arguments and its code).
+struct PpoArgs {
+  float* p_old;         // [B]: written by kLossA3cRecord, read by kLossPpo
+  float clip_eps;       // kLossPpo
+  float* stat_rows;     // kLossPpo: [B][2] per-row {clipped, log(p_old+eps) - log(p+eps)}, summed by ppo_stats_kernel
+};
+template <class Base> struct WithPpo : Base { PpoArgs ppo; };
+template <int EST, int LOSS> struct ArgsOf { using type = WithPpo<typename ReturnsOf<EST>::type>; };
+template <int EST> struct ArgsOf<EST, kLossA3c> { using type = typename ReturnsOf<EST>::type; };
+
+template <int AP, int LOSS = kLossA3c, class RT>
 __device__ __forceinline__ void load_row_and_grad(const float* __restrict__ probs, const float* __restrict__ values,
                                                   const int32_t* __restrict__ actions, const float* __restrict__ y,
                                                   const float* __restrict__ adv, int i, int A, float beta, float s,
                                                   float (&out)[AP + 1], float* stats, const RT& rt,
-                                                  float* yv_out = nullptr, float* av_out = nullptr) {
+                                                  float* yv_out = nullptr, float* av_out = nullptr,
+                                                  float* pstats = nullptr) {
   float pi[AP];
 #pragma unroll
   for (int a = 0; a < AP; ++a) pi[a] = probs[(long)i * A + (a < A ? a : 0)];
-  float yv, av;
+  float yv, av, pold = 0.f, ceps = 0.f;
+  if constexpr (LOSS == kLossPpo) {
+    pold = rt.ppo.p_old[i];
+    ceps = rt.ppo.clip_eps;
+  }
   if (rt.v_boot) {
     returns_row(rt, i, yv, av);
   } else {
@@ -428,7 +478,10 @@ __device__ __forceinline__ void load_row_and_grad(const float* __restrict__ prob
     *yv_out = yv;
     *av_out = av;
   }
-  head_grad_row<AP>(pi, values[i], actions[i], yv, av, beta, s, A, out, stats);
+  if constexpr (LOSS == kLossPpo)
+    head_grad_row<AP, kLossPpo>(pi, values[i], actions[i], yv, av, beta, s, A, out, stats, pold, ceps, pstats);
+  else
+    head_grad_row<AP>(pi, values[i], actions[i], yv, av, beta, s, A, out, stats);
 }
 
 // One launch, three roles by blockIdx:
@@ -437,7 +490,7 @@ __device__ __forceinline__ void load_row_and_grad(const float* __restrict__ prob
 //                   recomputed into LDS in chunks of 256 rows, h rows loaded in batches
 //   B + H/32        head bias gradients + loss scalars
 constexpr int HB_CHUNK = 256;
-template <int H, int AP, int EST>
+template <int H, int AP, int EST, int LOSS = kLossA3c>
 __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ values,
                                                         const int32_t* __restrict__ actions, const float* __restrict__ y,
                                                         const float* __restrict__ adv, const float* __restrict__ h,
@@ -446,7 +499,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
                                                         float* __restrict__ gWa, float* __restrict__ gba,
                                                         float* __restrict__ gWc, float* __restrict__ gbc,
                                                         float* __restrict__ loss_out,
-                                                        const typename ReturnsOf<EST>::type rt) {
+                                                        const typename ArgsOf<EST, LOSS>::type rt) {
   constexpr int NV = AP + 1;
   constexpr int NS = NV + 3;                       // + 3 loss statistics (role 3)
   const int tid = threadIdx.x;
@@ -469,7 +522,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
       for (int a = 0; a < AP; ++a) waj[jj][a] = Wa[j * A + (a < A ? a : 0)];
     }
     float dl[NV];
-    load_row_and_grad<AP>(probs, values, actions, y, adv, i, A, beta, s, dl, nullptr, rt);   // every thread: same row
+    load_row_and_grad<AP, LOSS>(probs, values, actions, y, adv, i, A, beta, s, dl, nullptr, rt);   // every thread: same row
 #pragma unroll
     for (int jj = 0; jj < JPT; ++jj) {
       const int j = tid + jj * 256;
@@ -500,7 +553,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
       __syncthreads();
       if (tid < cnt) {
         float dl[NV];
-        load_row_and_grad<AP>(probs, values, actions, y, adv, i0 + tid, A, beta, s, dl, nullptr, rt);
+        load_row_and_grad<AP, LOSS>(probs, values, actions, y, adv, i0 + tid, A, beta, s, dl, nullptr, rt);
 #pragma unroll
         for (int a = 0; a < NV; ++a) smem[tid * NV + a] = dl[a];
       }
@@ -539,10 +592,19 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
   for (int i = tid; i < B; i += 256) {
     float dl[NV], stats[3];
     float yv, av;
-    load_row_and_grad<AP>(probs, values, actions, y, adv, i, A, beta, s, dl, stats, rt, &yv, &av);
+    float pst[2];
+    load_row_and_grad<AP, LOSS>(probs, values, actions, y, adv, i, A, beta, s, dl, stats, rt, &yv, &av, pst);
     if (rt.v_boot) {          // the learner's records of the returns (paac.py:151-154 feed layout)
       rt.y_out[i] = yv;
       rt.adv_out[i] = av;
+    }
+    if constexpr (LOSS == kLossA3cRecord) {
+      const int ai = actions[i];
+      rt.ppo.p_old[i] = probs[(long)i * A + (ai >= 0 && ai < A ? ai : 0)];   // (an action outside [0, A) reads no other row)
+    }
+    if constexpr (LOSS == kLossPpo) {
+      rt.ppo.stat_rows[2 * i] = pst[0];
+      rt.ppo.stat_rows[2 * i + 1] = pst[1];
     }
 #pragma unroll
     for (int a = 0; a < NV; ++a) accv[a] += dl[a];
@@ -583,7 +645,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
 // dgrad_tower_kernel).  One launch less per update; every value bit-identical to the separate launches.
 static_assert(kDlStride == MAXA + 1 + 3, "floats per row in the dl buffer: AP + 1 gradients (padded to 33) + 3 loss terms");
 
-template <int H, int AP, int EST>
+template <int H, int AP, int EST, int LOSS = kLossA3c>
 __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restrict__ slab, int splits, long slab_stride,
                                                           const float* __restrict__ fc_b, const float* __restrict__ Wa,
                                                           const float* __restrict__ ba, const float* __restrict__ Wc,
@@ -593,7 +655,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
                                                           const int32_t* __restrict__ actions, const float* __restrict__ y,
                                                           const float* __restrict__ adv, float beta, float* __restrict__ dH,
                                                           float* __restrict__ dl_buf,
-                                                          const typename ReturnsOf<EST>::type rt) {
+                                                          const typename ArgsOf<EST, LOSS>::type rt) {
   constexpr int JPT = H / 256;
   constexpr int NV = AP + 1;                 // A logits (padded) + value
   constexpr int NB = NV + 1;                 // + the bootstrap row's value
@@ -625,6 +687,12 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
     for (int a = 0; a < AP; ++a) waj[jj][a] = Wa[j * A + (a < A ? a : 0)];
   }
   const int act = actions[i];
+  float pold = 0.f, ypre = 0.f, apre = 0.f;     // kLossPpo: the row's frozen p_old / y / adv, wave-uniform like act
+  if constexpr (LOSS == kLossPpo) {
+    pold = rt.ppo.p_old[i];
+    ypre = y[i];
+    apre = adv[i];
+  }
   // (the row's returns scan runs on thread 0 further down: its inputs are wave-uniform addresses, requested here)
   typename PreOf<EST>::type npre;
   if (rt.rewards) npre = returns_preload(rt, i);
@@ -673,11 +741,17 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
       if (a < A) {
         probs_ws[(long)i * A + a] = pa;
         logits_ws[(long)i * A + a] = lg[a];
+        if constexpr (LOSS == kLossA3cRecord) {
+          if (a == act) rt.ppo.p_old[i] = pa;
+        }
       }
     }
     values_ws[i] = lg[AP];
     float yv, av;
-    if (rt.rewards) {
+    if constexpr (LOSS == kLossPpo) {
+      yv = ypre;
+      av = apre;
+    } else if (rt.rewards) {
       returns_row_from(rt, i, boot ? lg[NV] : rt.v_boot[i % rt.N], npre, yv, av);
       rt.y_out[i] = yv;                      // the learner's records of the returns (paac.py:151-154 feed layout)
       rt.adv_out[i] = av;
@@ -703,7 +777,17 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
   float pi[AP], dl[NV], stats[3];
 #pragma unroll
   for (int a = 0; a < AP; ++a) pi[a] = row_s[a];
-  head_grad_row<AP>(pi, lg[AP], act, row_s[AP], row_s[AP + 1], beta, 5.0f / (float)B, A, dl, stats);   // every thread: same row
+  if constexpr (LOSS == kLossPpo) {
+    float pst[2];
+    head_grad_row<AP, kLossPpo>(pi, lg[AP], act, row_s[AP], row_s[AP + 1], beta, 5.0f / (float)B, A, dl, stats, pold,
+                                rt.ppo.clip_eps, pst);
+    if (tid == 0) {
+      rt.ppo.stat_rows[2 * i] = pst[0];
+      rt.ppo.stat_rows[2 * i + 1] = pst[1];
+    }
+  } else {
+    head_grad_row<AP>(pi, lg[AP], act, row_s[AP], row_s[AP + 1], beta, 5.0f / (float)B, A, dl, stats);   // every thread: same row
+  }
   if (tid == 0) {
 #pragma unroll
     for (int a = 0; a < NV; ++a) dl_buf[(long)i * kDlStride + a] = dl[a];
@@ -812,19 +896,19 @@ inline void launch_heads_fwd(int A, dim3 grid, hipStream_t s, Args... args) {
   else if (A <= 20) launch_k(heads_fwd_kernel<H, 20>, grid, dim3(256), s, PROF_WHOLE, args...);
   else launch_k(heads_fwd_kernel<H, 32>, grid, dim3(256), s, PROF_WHOLE, args...);
 }
-template <int H, int EST, class... Args>
+template <int H, int EST, int LOSS = kLossA3c, class... Args>
 inline void launch_heads_train(int A, dim3 grid, hipStream_t s, Args... args) {
-  if (A <= 4) launch_k(heads_train_kernel<H, 4, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 8) launch_k(heads_train_kernel<H, 8, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 20) launch_k(heads_train_kernel<H, 20, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else launch_k(heads_train_kernel<H, 32, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  if (A <= 4) launch_k(heads_train_kernel<H, 4, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 8) launch_k(heads_train_kernel<H, 8, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 20) launch_k(heads_train_kernel<H, 20, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else launch_k(heads_train_kernel<H, 32, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
 }
-template <int H, int EST, class... Args>
+template <int H, int EST, int LOSS = kLossA3c, class... Args>
 inline void launch_heads_bwd(int A, dim3 grid, hipStream_t s, Args... args) {
-  if (A <= 4) launch_k(heads_bwd_kernel<H, 4, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 8) launch_k(heads_bwd_kernel<H, 8, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else if (A <= 20) launch_k(heads_bwd_kernel<H, 20, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
-  else launch_k(heads_bwd_kernel<H, 32, EST>, grid, dim3(256), s, PROF_WHOLE, args...);
+  if (A <= 4) launch_k(heads_bwd_kernel<H, 4, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 8) launch_k(heads_bwd_kernel<H, 8, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else if (A <= 20) launch_k(heads_bwd_kernel<H, 20, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
+  else launch_k(heads_bwd_kernel<H, 32, EST, LOSS>, grid, dim3(256), s, PROF_WHOLE, args...);
 }
 
 }  // namespace paac

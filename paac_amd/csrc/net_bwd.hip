@@ -1,4 +1,6 @@
 // Backward half of the actor-critic network (see net_fwd.hip): dgrad / wgrad launches, slab finalize, launch tuning.
+#include <type_traits>
+
 #include "net_common.h"
 #include "dgrad_tower.h"
 #include "gemm3.h"
@@ -218,10 +220,44 @@ int launch_pack_dgrad(paac_ctx* ctx, const float* params, hipStream_t s) {
 // buffer, 95 % of its bytes); 2 = conv layers (the head of the flat buffer) + slab finalize.  The split lets a
 // data-parallel caller all-reduce the tail while phase 2 still computes.  3 = whole backward with the slab finalize
 // left to the norm pass of the next paac_clip_rmsprop on `grad` (one launch less; the same sums in the same order).
+// kLossPpo: clip fraction and approximate KL of the update = means over the rows of stat_rows, summed in block_sums_256's
+// fixed order (one workgroup; the rows were written by whichever heads kernel ran, so every route gives the same bits).
+__global__ __launch_bounds__(256) void ppo_stats_kernel(const float* __restrict__ stat_rows, int B, float* __restrict__ out2) {
+  __shared__ float smem[2 * 256 + 2 * 8];
+  __shared__ float red[2];
+  float acc[2] = {0.f, 0.f};
+  for (int i = threadIdx.x; i < B; i += 256) {
+    acc[0] += stat_rows[2 * i];
+    acc[1] += stat_rows[2 * i + 1];
+  }
+  block_sums_256<2>(acc, smem, red);
+  if (threadIdx.x < 2) out2[threadIdx.x] = red[threadIdx.x] / (float)B;
+}
+
+// The heads launch of a LOSS != kLossA3c instantiation: its estimator's argument block with the PPO fields behind it.
+// (kLossPpo reads y / adv from the arrays whatever estimator made them: one instantiation, under the n-step block.)
+template <class Go>
+static void launch_ppo_heads(Go&& go, int loss, int estimator, const GaeArgs& rt, const PpoArgs& ppo) {
+  using std::integral_constant;
+  if (loss == kLossA3cRecord && estimator == kEstGae) {
+    WithPpo<GaeArgs> ra;
+    static_cast<GaeArgs&>(ra) = rt;
+    ra.ppo = ppo;
+    go(integral_constant<int, kEstGae>{}, integral_constant<int, kLossA3cRecord>{}, ra);
+    return;
+  }
+  WithPpo<ReturnsArgs> ra;
+  static_cast<ReturnsArgs&>(ra) = rt;
+  ra.ppo = ppo;
+  if (loss == kLossA3cRecord) go(integral_constant<int, kEstNstep>{}, integral_constant<int, kLossA3cRecord>{}, ra);
+  else go(integral_constant<int, kEstNstep>{}, integral_constant<int, kLossPpo>{}, ra);
+}
+
 template <class NT>
 static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                          const float* y, const float* adv, int batch, float beta, float* grad, float* loss_out,
-                         int phase, const GaeArgs& rt, int estimator, hipStream_t s) {
+                         int phase, const GaeArgs& rt, int estimator, int loss, const PpoArgs& ppo, float* ppo_stats_out,
+                         hipStream_t s) {
   const paac_layout& L = ctx->layout;
   Workspace& W = ctx->ws[1];
   const int cls = batch_class(batch);
@@ -261,7 +297,16 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     const int rows = ctx->heads_pending_rows;
     // (rows kept by the acting forwards hold finished fc activations: one "slab", zero bias -- fmaxf(h + 0, 0) == h)
     const float* fc_b = ctx->heads_pending_h ? (const float*)ctx->zeros : params + L.offset[i_wf + 1];
-    if (estimator == kEstGae)
+    if (loss != kLossA3c) {
+      // (--ppo_epochs: epoch 1 also stores p_old; later epochs run the clipped surrogate on the frozen y / adv / p_old arrays)
+      auto go = [&](auto est, auto lossc, const auto& ra) {
+        launch_heads_train<NT::H, decltype(est)::value, decltype(lossc)::value>(
+            A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H, fc_b, wa,
+            params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A, batch, W.h, W.logits, W.probs, W.values, actions, y,
+            adv, beta, ctx->dh, ctx->dl_buf, ra);
+      };
+      launch_ppo_heads(go, loss, estimator, rtl, ppo);
+    } else if (estimator == kEstGae)
       launch_heads_train<NT::H, kEstGae>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
                                          fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
                                          batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, rtl);
@@ -273,7 +318,15 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     ctx->heads_pending_h = 0;
   } else if (do_fc) {
     ProfScope ps(ctx, F_HEADS_BWD, batch, s);
-    if (estimator == kEstGae)
+    if (loss != kLossA3c) {
+      auto go = [&](auto est, auto lossc, const auto& ra) {
+        launch_heads_bwd<NT::H, decltype(est)::value, decltype(lossc)::value>(
+            A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y, adv, (const float*)W.h,
+            wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa], grad + L.offset[i_wa + 1], grad + L.offset[i_wc],
+            grad + L.offset[i_wc + 1], loss_out, ra);
+      };
+      launch_ppo_heads(go, loss, estimator, rtl, ppo);
+    } else if (estimator == kEstGae)
       launch_heads_bwd<NT::H, kEstGae>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
                                        adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
                                        grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, rtl);
@@ -282,6 +335,8 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
                                          adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
                                          grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, rtn);
   }
+  if (do_fc && loss == kLossPpo && ppo_stats_out)
+    launch_k(ppo_stats_kernel, dim3(1), dim3(256), s, PROF_NONE, (const float*)ppo.stat_rows, batch, ppo_stats_out);
   const float* xf = (NT::NCONV == 3) ? W.act[2] : W.act[1];   // flattened last conv output
   float* dxf = (NT::NCONV == 3) ? ctx->dact[2] : ctx->dact[1];
   FinalizeArgs fin;
@@ -524,7 +579,11 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
 
 int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
                     const float* adv, int batch, float beta, float* grad, float* loss_out, int phase, hipStream_t s,
-                    const paac_returns* ret) {
+                    const paac_returns* ret, int loss, float* p_old, float clip_eps, float* ppo_stats_out) {
+  PpoArgs ppo;
+  ppo.p_old = p_old;
+  ppo.clip_eps = clip_eps;
+  ppo.stat_rows = ctx->ppo_rows;
   GaeArgs rt;
   memset(&rt, 0, sizeof(rt));
   int estimator = kEstNstep;
@@ -537,8 +596,8 @@ int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, c
     rt.anneal = ret->lr_annealing_steps; rt.lr_out = ret->lr_out_dev; rt.tick = ret->tick_dev; rt.tick_inc = ret->tick_inc;
   }
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, s);
-  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, s);
+    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, ppo_stats_out, s);
+  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, ppo_stats_out, s);
 }
 
 int64_t wslab_floats_needed(int arch) {

@@ -197,11 +197,12 @@ class Context(object):
     def loss_backward_returns(self, params, states, actions, v_boot, rewards, masks, values, gamma, y_out, adv_out,
                               entropy_beta, grad, loss_out=None, forward_done=False, phase=0, global_step_dev=None,
                               increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None, tick_dev=None, tick_inc=0,
-                              gae_lambda=None):
+                              gae_lambda=None, p_old_out=None):
         """n-step returns (+ the cycle's schedule bookkeeping) inside the backward's first launch
         (include/paac_hip.h: paac_loss_backward_returns) == nstep_returns_tick followed by loss_backward.
         v_boot=None: the bootstrap values are rows [B, B + N) of the training forward that has already run.
-        gae_lambda: None or 1.0 = the n-step return; anything else = GAE(lambda) instead (uses_gae)."""
+        gae_lambda: None or 1.0 = the n-step return; anything else = GAE(lambda) instead (uses_gae).
+        p_old_out: float32[B], also receives p_old (epoch 1 of a --ppo_epochs cycle); gradient and loss are unchanged."""
         B = self._check_states(states)
         T, N = rewards.shape
         if T * N != B:
@@ -216,12 +217,46 @@ class Context(object):
             tick_dev=_ptr(tick_dev, torch.int64, 1, "tick", True), tick_inc=int(tick_inc),
             estimator=_lib.RETURNS_GAE if uses_gae(gae_lambda) else _lib.RETURNS_NSTEP,
             gae_lambda=float(gae_lambda) if uses_gae(gae_lambda) else 0.0)
+        if p_old_out is not None:          # include/paac_hip.h: paac_loss_backward_returns_record
+            _lib.check(self.lib.paac_loss_backward_returns_record(
+                self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
+                _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"), ctypes.byref(ret),
+                _ptr(p_old_out, torch.float32, B, "p_old_out"), B, float(entropy_beta),
+                _ptr(grad, torch.float32, self.layout["total"], "grad"), _ptr(loss_out, torch.float32, 4, "loss_out", True),
+                1 if forward_done else 0, int(phase), _stream()), "paac_loss_backward_returns_record")
+            return
         _lib.check(self.lib.paac_loss_backward_returns(
             self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
             _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"), ctypes.byref(ret), B,
             float(entropy_beta), _ptr(grad, torch.float32, self.layout["total"], "grad"),
             _ptr(loss_out, torch.float32, 4, "loss_out", True), 1 if forward_done else 0, int(phase), _stream()),
             "paac_loss_backward_returns")
+
+    def loss_backward_record(self, params, states, actions, y, adv, p_old_out, entropy_beta, grad, loss_out=None,
+                             forward_done=False, phase=0):
+        """loss_backward that also writes p_old_out[i] = pi(a_i | s_i) as its own heads computed it (include/paac_hip.h:
+        paac_loss_backward_record): epoch 1 of a --ppo_epochs cycle for a caller that computes y / adv itself."""
+        B = self._check_states(states)
+        _lib.check(self.lib.paac_loss_backward_record(
+            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
+            _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"),
+            _ptr(y, torch.float32, B, "y"), _ptr(adv, torch.float32, B, "adv"), _ptr(p_old_out, torch.float32, B, "p_old_out"),
+            B, float(entropy_beta), _ptr(grad, torch.float32, self.layout["total"], "grad"),
+            _ptr(loss_out, torch.float32, 4, "loss_out", True), 1 if forward_done else 0, int(phase), _stream()),
+            "paac_loss_backward_record")
+
+    def loss_backward_ppo(self, params, states, actions, y, adv, p_old, clip_eps, entropy_beta, grad, loss_out=None,
+                          ppo_stats_out=None, forward_done=False, phase=0):
+        """Epochs 2..K of a --ppo_epochs cycle: the clipped surrogate on the frozen y / adv / p_old (include/paac_hip.h:
+        paac_loss_backward_ppo).  ppo_stats_out: float32[2] = {clip_fraction, approx_kl}."""
+        B = self._check_states(states)
+        _lib.check(self.lib.paac_loss_backward_ppo(
+            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
+            _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"),
+            _ptr(y, torch.float32, B, "y"), _ptr(adv, torch.float32, B, "adv"), _ptr(p_old, torch.float32, B, "p_old"),
+            float(clip_eps), B, float(entropy_beta), _ptr(grad, torch.float32, self.layout["total"], "grad"),
+            _ptr(loss_out, torch.float32, 4, "loss_out", True), _ptr(ppo_stats_out, torch.float32, 2, "ppo_stats_out", True),
+            1 if forward_done else 0, int(phase), _stream()), "paac_loss_backward_ppo")
 
     def clip_rmsprop(self, params, grad, ms, mom, lr_dev, decay, momentum, eps, clip_norm, clip_mode, grad_scale=1.0,
                      gnorm_out=None):
@@ -355,7 +390,7 @@ class Context(object):
 
     def debug_activation(self, what, batch):
         convs, fc = arch_geometry(self.arch)
-        cap = activation_size(convs, fc, what, batch)
+        cap = int(batch) * self.num_actions if int(what) == 26 else activation_size(convs, fc, what, batch)
         if cap is None:
             raise ValueError("debug_activation: what=%d is not an activation of this geometry" % what)
         out = torch.empty(cap, dtype=torch.float32, device=self.device)

@@ -92,6 +92,12 @@ class DeviceRollout(object):
         # the replayed collective against the eager one
         self.exchange_mode = "none" if not self.phased else ("split" if not self.single_exchange else "single")
         self.exchange_fallback = None
+        # --ppo_epochs K: epochs 2..K ride behind the cycle's update, each with its own exchange (one all-reduce per epoch)
+        self.K = L.ppo_epochs
+        if self.K > 1 and self.phased and not self.single_exchange:
+            raise ValueError("--ppo_epochs above 1 is not built for PAAC_ALLREDUCE=split (the two-piece exchange): use graph "
+                             "or single")
+        self.graph_epoch = [[], []]                    # eager exchange: [parity][k - 1] = update + epoch k + 1's backward
         self.short_first = os.environ.get("PAAC_SHORT_GRAPH_FIRST", "1") != "0"
         self.spin_sync = os.environ.get("PAAC_SPIN_SYNC", "1") != "0"
         self.verify_exchange = os.environ.get("PAAC_VERIFY_EXCHANGE", "1") != "0"
@@ -189,7 +195,23 @@ class DeviceRollout(object):
                                     phase=(0 if self.single_exchange else 1) if self.phased else 3,
                                     global_step_dev=self.global_step_dev, increment=self.total_envs * T,
                                     initial_lr=L.initial_lr, lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev,
-                                    tick_dev=self.tick, tick_inc=T, gae_lambda=L.gae_lambda)
+                                    tick_dev=self.tick, tick_inc=T, gae_lambda=L.gae_lambda,
+                                    p_old_out=L.p_old if self.K > 1 else None)
+
+    def _epoch_backward(self, parity, k):
+        """Epoch k + 1 of the cycle up to its gradient (the update of epoch k has run)."""
+        self.L.ppo_epoch_backward(k, self.rollout_states(parity), self.actions.view(-1), self.y, self.adv,
+                                  phase=0 if self.phased else 3)
+
+    def _later_epochs(self, parity, exchange, before_last_update=None):
+        """Behind the cycle's first update: epochs 2..K, each backward -> [exchange] -> update."""
+        for k in range(1, self.K):
+            self._epoch_backward(parity, k)
+            if exchange:
+                self._exchange(None)
+            if before_last_update is not None and k == self.K - 1:
+                before_last_update()
+            self._update()
 
     def _backward_conv(self, parity):
         L = self.L
@@ -219,6 +241,7 @@ class DeviceRollout(object):
                 if self.graph_exchange:
                     self._exchange(None)          # recorded into the graph like the kernels around it
                 self._update()
+                self._later_epochs(parity, self.graph_exchange)
 
         if self.graph_exchange:
             # the communicator must exist before a capture can record its collective: one eager all-reduce of a scratch
@@ -263,6 +286,8 @@ class DeviceRollout(object):
                     # the optimizer step of cycle k rides in front of cycle k+1's graph: two graph launches per
                     # cycle around the exchange instead of three (synchronize() flushes a pending step)
                     self.graph_ua[parity] = captured(lambda: (self._update(), cycle(parity, False)))
+                    self.graph_epoch[parity] = [captured(lambda: (self._update(), self._epoch_backward(parity, k)))
+                                                for k in range(1, self.K)]
             if self.phased:
                 self.graph_b = captured(self._update)
             else:
@@ -278,7 +303,7 @@ class DeviceRollout(object):
         L = self.L
         ts = [self.states, self.actions, self.values, self.rewards, self.masks, self.probs, self.y, self.adv, self.ep_reward,
               self.ep_len, self.finished, self.tick, self.global_step_dev] + [t for _, t in L.update_state] + \
-             [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev]
+             [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev] + [t for t in (L.p_old, L.ppo_loss, L.ppo_stats) if t is not None]
         for name in ("raw", "walk_scratch", "mt_state"):
             t = getattr(self, name, None)
             if t is not None:
@@ -300,8 +325,11 @@ class DeviceRollout(object):
 
         self._rollout_and_backward(0)
         self._exchange(None)
-        eager = L.grad.clone()
+        eager = [L.grad.clone()]
         self._update()                                    # (consumes what the backward left pending in the ctx)
+        # (--ppo_epochs: the LAST epoch's exchanged gradient is compared -- it depends on every exchange before it)
+        self._later_epochs(0, True, before_last_update=lambda: eager.__setitem__(0, L.grad.clone()))
+        eager = eager[0]
         restore()
         self.graph_a[0].launch()                          # backward -> captured all-reduce -> update; grad stays as exchanged
         replayed = L.grad.clone()
@@ -362,6 +390,9 @@ class DeviceRollout(object):
                 if self.phased and not self.graph_exchange:
                     (self.graph_ua if self.pending_update else self.graph_a)[self.parity].launch()
                     self._exchange(None if self.single_exchange else self.graph_conv[self.parity].launch)
+                    for g in self.graph_epoch[self.parity]:      # update of the epoch before + this epoch's backward
+                        g.launch()
+                        self._exchange(None)
                     self.pending_update = True
                 else:
                     self.graph_a[self.parity].launch()
@@ -370,6 +401,7 @@ class DeviceRollout(object):
                 if self.phased:
                     self._exchange(None if self.single_exchange else (lambda: self._backward_conv(self.parity)))
                 self._update()
+                self._later_epochs(self.parity, self.phased)
         self.parity ^= 1
 
     def _exchange(self, conv_backward):
@@ -419,7 +451,7 @@ class DeviceRollout(object):
     def close(self):
         for g in (self.graph_a[0], self.graph_a[1], self.graph_conv[0], self.graph_conv[1], self.graph_b, self.graph_multi[0],
                   self.graph_multi[1], self.graph_multi_long[0], self.graph_multi_long[1],
-                  self.graph_ua[0], self.graph_ua[1]):
+                  self.graph_ua[0], self.graph_ua[1]) + tuple(self.graph_epoch[0]) + tuple(self.graph_epoch[1]):
             if g is not None:
                 g.close()
         self.graph_a = [None, None]
@@ -428,6 +460,7 @@ class DeviceRollout(object):
         self.graph_multi = [None, None]
         self.graph_multi_long = [None, None]
         self.graph_ua = [None, None]
+        self.graph_epoch = [[], []]
 
 
 class DeviceObservations(object):
@@ -483,6 +516,14 @@ class PAACLearner(ActorLearner):
                            steps_per_s_avg=float(steps_per_s_avg), last_10_rewards_avg=float(last_ten),
                            lr=float(self.lr_dev.item()), grad_norm=float(self.gnorm_dev.item()), loss=float(loss[0]),
                            actor_loss=float(loss[1]), critic_loss=float(loss[2]), entropy=float(loss[3]))
+        if self.ppo_epochs > 1:          # one record per epoch of the last cycle (epoch 1: the update above, ratio == 1)
+            losses, stats = self.ppo_loss.cpu().numpy(), self.ppo_stats.cpu().numpy()
+            losses[0] = loss
+            for k in range(self.ppo_epochs):
+                self.metrics.write("ppo_epoch", global_step=int(self.global_step), epoch=k + 1, loss=float(losses[k, 0]),
+                                   actor_loss=float(losses[k, 1]), critic_loss=float(losses[k, 2]),
+                                   entropy=float(losses[k, 3]), clip_fraction=float(stats[k, 0]),
+                                   approx_kl=float(stats[k, 1]))
         self.metrics.flush()
 
     @staticmethod
@@ -751,10 +792,18 @@ class PAACLearner(ActorLearner):
             hip_ops.returns(d_vboot, d_rewards, d_masks, d_values, self.gamma, d_y, d_adv, self.gae_lambda)
             lr = self.get_lr()
             self.lr_dev.fill_(float(np.float32(lr)))
-            self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv,
-                                   self.entropy_beta, self.grad, self.loss_dev)
+            if self.ppo_epochs > 1:
+                self.ctx.loss_backward_record(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv,
+                                              self.p_old, self.entropy_beta, self.grad, self.loss_dev)
+            else:
+                self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv,
+                                       self.entropy_beta, self.grad, self.loss_dev)
             self._allreduce_grad()
             self.apply_gradients()
+            for k in range(1, self.ppo_epochs):      # epochs 2..K on the frozen y / adv / p_old, the same lr
+                self.ppo_epoch_backward(k, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv, phase=0)
+                self._allreduce_grad()
+                self.apply_gradients()
             if getattr(self.args, "record_feeds", False):
                 self.last_feed = dict(states=d_states.view(T * N, 84, 84, 4).cpu().numpy(), y=d_y.cpu().numpy(),
                                       adv=d_adv.cpu().numpy(), actions=d_actions.view(-1).cpu().numpy(), lr=lr,

@@ -79,6 +79,12 @@ BUILD_FLAGS = (
     (("--gae_lambda",), "gae_lambda", 1.0, float,
      "advantage estimator: 1.0 = the reference's n-step return (bit for bit); a value in [0, 1) = generalized advantage "
      "estimation GAE(lambda) on the same rollout records, 0 being the one-step TD error"),
+    (("--ppo_epochs",), "ppo_epochs", 1, int,
+     "optimizer steps per rollout: 1 = the reference's single update (bit for bit, whatever --ppo_clip says); K in [2, 16] = "
+     "PPO: epoch 1 is that update, epochs 2..K re-run the training forward on the same rollout under the clipped "
+     "probability-ratio objective"),
+    (("--ppo_clip",), "ppo_clip", 0.2, float, "PPO clip range EPS in (0, 1): the ratio is clipped to [1 - EPS, 1 + EPS]; read "
+                                              "only when --ppo_epochs is above 1"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),

@@ -252,6 +252,26 @@ int paac_loss_backward_ppo(paac_ctx* ctx, const float* params, const uint8_t* st
                            float entropy_beta, float* grad, float* loss_out, float* ppo_stats_out, int forward_done,
                            int phase, paac_stream_t stream);
 
+/* --ppo_vclip EPSV: the PPO2 critic term (value clipping) for epochs 2..K of a --ppo_epochs cycle.  The reference has no
+ * counterpart; this is the contract.  EPSV = 0 (the default) is off: paac_loss_backward_ppo, unchanged.  Read only when K > 1.
+ *   Epoch 1 is the update above; it also records v_old[i], the fp32 value its own training-side heads computed: a copy out of
+ *   the ctx's value buffer right behind epoch 1's backward (paac_debug_activation(25) into the caller's array: one captured
+ *   device-to-device copy; a record instantiation per estimator, action bucket and heads kernel would store the same bits at the
+ *   price of sixteen more kernels).  In epoch 1 v == v_old, the term is inert and needs no arithmetic.
+ *   Epochs 2..K: paac_loss_backward_ppo_vclip in place of paac_loss_backward_ppo.  Per row, fp32, no contraction:
+ *     vc = v_old + fminf(fmaxf(v - v_old, -EPSV), EPSV)
+ *     l1 = (y - v)^2;  l2 = (y - vc)^2;  vclipped = l2 > l1
+ *     critic term = 0.25 * fmaxf(l1, l2)
+ *     dv = vclipped ? 0 : s*0.5*(v - y)
+ *   The actor and entropy parts are paac_loss_backward_ppo's exactly; with v_old = v the row is its row bit for bit.
+ * ppo_stats_out (nullable): device float[3] = {clip_fraction, approx_kl, value_clip_fraction = mean of vclipped}, through the
+ * same fixed-order reduction launch.  vclip_eps <= 0 (NaN included) and a NULL v_old are refused; everything else as
+ * paac_loss_backward_ppo. */
+int paac_loss_backward_ppo_vclip(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                                 const float* y, const float* adv, const float* p_old, const float* v_old, float clip_eps,
+                                 float vclip_eps, int batch, float entropy_beta, float* grad, float* loss_out,
+                                 float* ppo_stats_out, int forward_done, int phase, paac_stream_t stream);
+
 /* Gradient clipping + RMSPropOptimizer.apply_gradients (actor_learner.py:31-34,51-64,70):
  *   g <- grad * grad_scale           (grad_scale = 1/world_size after the sum all-reduce)
  *   mode IGNORE: f = 1
@@ -334,6 +354,30 @@ int paac_gae_returns_tick(const float* v_boot, const float* rewards, const float
                           int T, int N, double gamma, double gae_lambda, float* y, float* adv, int64_t* global_step_dev,
                           int64_t increment, double initial_lr, int64_t lr_annealing_steps, float* lr_out_dev,
                           uint64_t* tick_dev, uint64_t tick_inc, paac_stream_t stream);
+
+/* --adv_norm: advantage normalisation.  The reference has no counterpart; this is the contract.
+ *   The statistics are taken per rank and per rollout, over the B = T*N advantages the estimator (n-step or GAE) produced:
+ *     mean = sum(adv) / B;  std = sqrt(sum((adv - mean)^2) / B)      (fp32 adv promoted to fp64; population form, two passes)
+ *     adv_n[i] = f32((adv[i] - mean) / (std + 1e-8))
+ *   One workgroup, a fixed summation order, no float atomics: the same inputs give the same bits on every launch, replayed
+ *   from a graph or not.  std == 0 (B = 1, a rollout of identical advantages) gives all zeros; non-finite inputs propagate.
+ *   Only the actor term reads adv_n (pass it as `adv` of paac_loss_backward* / paac_loss_backward_ppo*), in every epoch; y, the
+ *   critic term and the recorded adv array are unchanged.  Under data parallelism every rank normalises its own shard: no
+ *   collective is added, and G ranks x N environments is not the same update as one rank with G*N environments.
+ * paac_adv_normalize: standalone.  adv / adv_n_out: device float[B] (may be the same array); stats_out (nullable): device
+ * double[2] = {mean, std}.
+ * paac_returns_norm_tick: paac_nstep_returns_tick or paac_gae_returns_tick (by ret->estimator; y_out / adv_out equal theirs bit
+ * for bit, and so does the global_step / lr / frame-counter bookkeeping, which is optional here as in paac_returns) + the
+ * normalisation of adv_out into adv_n_out (== paac_adv_normalize's bits), in ONE launch.  The returns cannot ride inside the
+ * backward's first launch when the flag is on -- a row's workgroup cannot know the batch-wide mean -- so the cycle becomes:
+ * training forward (trunk), this call, paac_loss_backward[_record](y_out, adv_n_out, forward_done = 1).
+ * ret->v_boot == NULL: the bootstrap values are rows [T*N, T*N + N) of the training forward that has already run on `ctx`
+ * (paac_train_forward[_trunk] over T*N + N rows, or kept acting rows + paac_bootstrap_forward_trunk): a pending trunk-only
+ * forward gets the heads of those N rows finished here (one launch; the rollout rows stay pending, kept rows stay kept, and
+ * the backward's first launch finishes them as usual).  With ret->v_boot set, ctx and params may be NULL. */
+int paac_adv_normalize(const float* adv, int B, float* adv_n_out, double* stats_out, paac_stream_t stream);
+int paac_returns_norm_tick(paac_ctx* ctx, const float* params, const paac_returns* ret, float* adv_n_out, double* stats_out,
+                           paac_stream_t stream);
 
 /* paac.py:34-45 bit-exact: probs - float32.epsneg, then numpy legacy multinomial(1, p) per env in
  * index order on ONE MT19937 stream.  mt_state: device uint32[625] = numpy key[624] + pos, advanced

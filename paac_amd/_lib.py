@@ -71,6 +71,11 @@ _SIGNATURES = {
                                           c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "paac_loss_backward_ppo": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                        c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "paac_loss_backward_ppo_vclip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                             c_void_p]),
+    "paac_adv_normalize": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "paac_returns_norm_tick": (c_int, [c_void_p, c_void_p, POINTER(Returns), c_void_p, c_void_p, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_clip_rmsprop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,

@@ -6,6 +6,7 @@ with the TensorFlow optimizer graph (compute_gradients / clip_by_global_norm / a
 paac_loss_backward + paac_clip_rmsprop (paac_clip_adam) on a flat parameter buffer.
 """
 import logging
+import math
 import os
 
 import numpy as np
@@ -64,6 +65,17 @@ class ActorLearner(object):
         self.ppo_clip = float(getattr(args, "ppo_clip", 0.2))
         if not 0.0 < self.ppo_clip < 1.0:               # (NaN fails both comparisons)
             raise ValueError("ppo_clip %r: expected a value in (0, 1)" % (self.ppo_clip,))
+        # --adv_norm / --ppo_vclip EPSV (include/paac_hip.h has the contracts): Namespaces / args.json files without the fields
+        # mean off.  adv_norm: the actor term reads the rollout's advantages normalised by their own mean and std (every
+        # epoch); EPSV > 0: epochs 2..K use the value-clipped critic term, read only when K > 1
+        self.adv_norm = getattr(args, "adv_norm", False)
+        if not isinstance(self.adv_norm, (bool, np.bool_)):
+            raise ValueError("adv_norm %r: expected True or False" % (self.adv_norm,))
+        self.adv_norm = bool(self.adv_norm)
+        self.ppo_vclip = float(getattr(args, "ppo_vclip", 0.0))
+        if not (0.0 <= self.ppo_vclip and math.isfinite(self.ppo_vclip)):          # (NaN fails the comparison)
+            raise ValueError("ppo_vclip %r: expected a finite value >= 0 (0 = off)" % (self.ppo_vclip,))
+        self.vclip_on = self.ppo_epochs > 1 and self.ppo_vclip > 0.0
         self.clip_norm = args.clip_norm
         self.clip_norm_type = args.clip_norm_type
         if self.clip_norm_type == 'ignore':
@@ -115,7 +127,15 @@ class ActorLearner(object):
         if self.ppo_epochs > 1:
             self.p_old = torch.zeros(self.emulator_counts * self.max_local_steps, dtype=torch.float32, device=dev)
             self.ppo_loss = torch.zeros((self.ppo_epochs, 4), dtype=torch.float32, device=dev)
-            self.ppo_stats = torch.zeros((self.ppo_epochs, 2), dtype=torch.float32, device=dev)
+            self.ppo_stats = torch.zeros((self.ppo_epochs, 3 if self.vclip_on else 2), dtype=torch.float32, device=dev)
+        # --adv_norm: adv_n [T*N] is what the actor term reads, adv_stats = {mean, std} of the last rollout (fp64);
+        # --ppo_vclip: v_old [T*N], epoch 1's values.  Per-cycle scratch like p_old
+        self.adv_n = self.adv_stats = self.v_old = None
+        if self.adv_norm:
+            self.adv_n = torch.zeros(self.emulator_counts * self.max_local_steps, dtype=torch.float32, device=dev)
+            self.adv_stats = torch.zeros(2, dtype=torch.float64, device=dev)
+        if self.vclip_on:
+            self.v_old = torch.zeros(self.emulator_counts * self.max_local_steps, dtype=torch.float32, device=dev)
         self.train_step = Placeholder('train_step')
 
         self.ctx = hip_ops.Context(self.network.arch_id, self.num_actions,
@@ -202,9 +222,15 @@ class ActorLearner(object):
 
     def ppo_epoch_backward(self, k, states, actions, y, adv, phase):
         """Epoch k + 1 (k = 1 .. ppo_epochs - 1) up to its gradient: training forward (trunk) over the rollout rows on the
-        current weights, then the clipped-surrogate backward on the frozen y / adv / p_old."""
+        current weights, then the clipped-surrogate backward on the frozen y / adv / p_old (adv: what the actor term reads,
+        adv_n under --adv_norm; with --ppo_vclip the critic term is clipped around the frozen v_old)."""
         params = self.network.params
         self.ctx.train_forward_trunk(params, states)
+        if self.vclip_on:
+            self.ctx.loss_backward_ppo_vclip(params, states, actions, y, adv, self.p_old, self.v_old, self.ppo_clip,
+                                             self.ppo_vclip, self.entropy_beta, self.grad, self.ppo_loss[k], self.ppo_stats[k],
+                                             forward_done=True, phase=phase)
+            return
         self.ctx.loss_backward_ppo(params, states, actions, y, adv, self.p_old, self.ppo_clip, self.entropy_beta, self.grad,
                                    self.ppo_loss[k], self.ppo_stats[k], forward_done=True, phase=phase)
 

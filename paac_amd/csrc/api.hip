@@ -195,6 +195,7 @@ int paac_create(const paac_cfg* cfg, paac_ctx** out) {
   PAAC_CHECK_HIP(hipMalloc(&c->dh, (size_t)B * c->spec.fc * sizeof(float)));
   PAAC_CHECK_HIP(hipMalloc(&c->dl_buf, (size_t)B * paac::kDlStride * sizeof(float)));
   PAAC_CHECK_HIP(hipMalloc(&c->ppo_rows, (size_t)B * 2 * sizeof(float)));
+  PAAC_CHECK_HIP(hipMalloc(&c->vclip_rows, (size_t)B * sizeof(float)));
   c->wslab_floats = wslab_floats_needed(cfg->arch);
   PAAC_CHECK_HIP(hipMalloc(&c->wslab, (size_t)c->wslab_floats * sizeof(float)));
   PAAC_CHECK_HIP(hipMalloc(&c->partials, 8192 * sizeof(float)));
@@ -245,7 +246,7 @@ int paac_destroy(paac_ctx* c) {
   }
   for (int i = 0; i < 3; ++i)
     if (c->dact[i]) (void)hipFree(c->dact[i]);
-  float* bufs[] = {c->dh, c->wslab, c->partials, c->dl_buf, c->zeros, c->ppo_rows};
+  float* bufs[] = {c->dh, c->wslab, c->partials, c->dl_buf, c->zeros, c->ppo_rows, c->vclip_rows};
   for (float* b : bufs)
     if (b) (void)hipFree(b);
   if (c->mt_ahead) (void)hipFree(c->mt_ahead);
@@ -600,6 +601,60 @@ static int64_t debug_activation_elems(const ArchSpec& spec, int what, int batch)
   }
   if (what == 4 || what == 14) return (int64_t)batch * spec.fc;
   return -1;
+}
+
+int paac_returns_norm_tick(paac_ctx* ctx, const float* params, const paac_returns* ret, float* adv_n_out, double* stats_out,
+                           paac_stream_t stream) {
+  PAAC_REQUIRE(ret && adv_n_out, "paac_returns_norm_tick: null argument");
+  PAAC_REQUIRE(ret->T > 0 && ret->N > 0, "paac_returns_norm_tick: T=%d N=%d", ret->T, ret->N);
+  PAAC_REQUIRE(ret->rewards && ret->masks && ret->values && ret->y_out && ret->adv_out,
+               "paac_returns_norm_tick: null rollout record");
+  PAAC_REQUIRE(ret->estimator == PAAC_RETURNS_NSTEP || ret->estimator == PAAC_RETURNS_GAE,
+               "paac_returns_norm_tick: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", ret->estimator);
+  PAAC_REQUIRE(ret->gae_lambda >= 0.0 && ret->gae_lambda <= 1.0, "paac_returns_norm_tick: gae_lambda %g outside [0, 1]",
+               ret->gae_lambda);
+  PAAC_REQUIRE(!ret->global_step_dev || (ret->lr_out_dev && ret->lr_annealing_steps > 0),
+               "paac_returns_norm_tick: schedule bookkeeping needs lr_out_dev and lr_annealing_steps");
+  const float* v_boot = ret->v_boot;
+  if (!v_boot) {
+    const int64_t batch = (int64_t)ret->T * ret->N;
+    PAAC_REQUIRE(ctx && params && batch + ret->N <= ctx->max_batch,
+                 "paac_returns_norm_tick: v_boot == NULL takes the bootstrap values from rows [T*N, T*N + N) of a training "
+                 "forward that has already run over T*N + N rows of this ctx");
+    const int rc = launch_bootstrap_heads(ctx, params, (int)batch, ret->N, (hipStream_t)stream);
+    if (rc) return rc;
+    v_boot = ctx->ws[1].values + batch;
+  }
+  const int rc = launch_returns_norm(ret, v_boot, adv_n_out, stats_out, (hipStream_t)stream);
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_loss_backward_ppo_vclip(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                                 const float* y, const float* adv, const float* p_old, const float* v_old, float clip_eps,
+                                 float vclip_eps, int batch, float entropy_beta, float* grad, float* loss_out,
+                                 float* ppo_stats_out, int forward_done, int phase, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && states && actions && y && adv && grad, "paac_loss_backward_ppo_vclip: null argument");
+  PAAC_REQUIRE(p_old, "paac_loss_backward_ppo_vclip: null p_old");
+  PAAC_REQUIRE(v_old, "paac_loss_backward_ppo_vclip: null v_old");
+  PAAC_REQUIRE(clip_eps > 0.f && clip_eps < 1.f, "paac_loss_backward_ppo_vclip: clip_eps %g outside (0, 1)", (double)clip_eps);   // (NaN fails)
+  PAAC_REQUIRE(vclip_eps > 0.f, "paac_loss_backward_ppo_vclip: vclip_eps %g is not positive (0 = off: paac_loss_backward_ppo)",
+               (double)vclip_eps);                                                                                                // (NaN fails)
+  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_ppo_vclip: batch %d outside (0, max_batch=%d]", batch,
+               ctx->max_batch);
+  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward_ppo_vclip: phase %d", phase);
+  int rc = 0;
+  if (!forward_done && phase != 2) {
+    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  ctx->last_ws = 1;
+  rc = launch_backward(ctx, params, states, actions, y, adv, batch, entropy_beta, grad, loss_out, phase, (hipStream_t)stream,
+                       nullptr, 3, const_cast<float*>(p_old), clip_eps, ppo_stats_out, v_old, vclip_eps);
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 int64_t paac_debug_activation_size(int arch, int what, int batch) {

@@ -136,6 +136,7 @@ struct paac_ctx {
   int ahead_D;                     // doubles the step can consume at most: N * (A - 1)
   float* dl_buf;                   // [max_batch][kDlStride] per-row head gradients + loss terms (heads.h)
   float* ppo_rows;                 // [max_batch][2] per-row clip / KL terms of paac_loss_backward_ppo (heads.h: ppo_stats_kernel)
+  float* vclip_rows;               // [max_batch] per-row vclipped of paac_loss_backward_ppo_vclip
   int fc_splits_max;
   // conv tower (csrc/tower.h, Nature only): conv weights pre-split into bf16 planes in MFMA operand order
   void* tower_pack;      // kTowerPackVecs x 16 bytes, nullptr when the tower is off
@@ -212,6 +213,10 @@ inline void launch_k(K kernel, dim3 grid, dim3 block, hipStream_t s, int part, A
 // launchers implemented in the kernel translation units
 int launch_forward_trunk_train(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, hipStream_t s);
 int launch_deferred_heads(paac_ctx* ctx, const float* params, hipStream_t s);
+// --adv_norm: the heads of the N bootstrap rows [batch, batch + N) of a pending trunk-only training forward alone (the
+// rollout rows stay pending for the backward's first launch); the returns + normalisation launch (csrc/misc.hip)
+int launch_bootstrap_heads(paac_ctx* ctx, const float* params, int batch, int N, hipStream_t s);
+int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv_n, double* stats, hipStream_t s);
 int launch_forward(paac_ctx* ctx, int ws, const float* params, const uint8_t* states, int batch, float* logits,
                    float* probs, float* values, hipStream_t s);
 struct SynthStepArgs;
@@ -269,6 +274,7 @@ int launch_sample_env_step_heads(const float* partial, int ntiles, const float* 
 int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
                     const float* adv, int batch, float beta, float* grad, float* loss_out, int phase, hipStream_t s,
                     const paac_returns* ret = nullptr, int loss = 0, float* p_old = nullptr, float clip_eps = 0.f,
-                    float* ppo_stats_out = nullptr);   // loss: heads.h kLossA3c / kLossA3cRecord / kLossPpo
+                    float* ppo_stats_out = nullptr,    // loss: heads.h kLossA3c / kLossA3cRecord / kLossPpo / kLossPpoVclip
+                    const float* v_old = nullptr, float vclip_eps = 0.f);
 
 }  // namespace paac

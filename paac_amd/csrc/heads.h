@@ -223,17 +223,23 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
 //                   g_a = -(adv*active*1[a=act]*invq - beta*(...));  actor term = -(min(r adv, clamp(r, 1-EPS, 1+EPS) adv) + beta H)
 //                   pstats: {1 - active, log(p_old+eps) - log(pi[act]+eps)} (clip fraction and approximate KL of the row).
 //                   With p_old = pi[act] the row is active, invq is the plain loss's 1/(pi_a+eps), and every gradient bit is its.
-constexpr int kLossA3c = 0, kLossA3cRecord = 1, kLossPpo = 2;
+//   kLossPpoVclip   kLossPpo with the PPO2 critic term (--ppo_vclip EPSV) on the frozen v_old:
+//                   vc = v_old + clamp(v - v_old, -EPSV, EPSV); l1 = (y-v)^2; l2 = (y-vc)^2; vclipped = l2 > l1
+//                   critic term = 0.25*max(l1, l2); dv = vclipped ? 0 : s*0.5*(v - y); pstats[2] = vclipped.
+//                   With v_old = v: vc = v, l2 = l1, and the row is the kLossPpo row bit for bit.
+constexpr int kLossA3c = 0, kLossA3cRecord = 1, kLossPpo = 2, kLossPpoVclip = 3;
+constexpr bool loss_is_ppo(int loss) { return loss == kLossPpo || loss == kLossPpoVclip; }
 template <int AP, int LOSS = kLossA3c>
 __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, int act, float y, float adv, float beta,
                                               float s, int A, float (&out)[AP + 1], float* stats, float p_old = 0.f,
-                                              float clip_eps = 0.f, float* pstats = nullptr) {
+                                              float clip_eps = 0.f, float* pstats = nullptr, float v_old = 0.f,
+                                              float vclip_eps = 0.f) {
 #pragma clang fp contract(off)   // inlined into several kernels that must produce the same bits: no context-dependent fma
   const float eps = 1e-30f;
   float g[AP];
   float dot = 0.f, ent = 0.f, logp = 0.f;
   float invq = 0.f, ratio = 0.f, af = 1.f;
-  if constexpr (LOSS == kLossPpo) {
+  if constexpr (loss_is_ppo(LOSS)) {
     float pact = 0.f;
 #pragma unroll
     for (int a = 0; a < AP; ++a) pact = (a == act) ? pi[a] : pact;
@@ -249,7 +255,7 @@ __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, in
     const float lp = logf(p + eps);
     const float inv = 1.0f / (p + eps);
     const float oh = (a == act) ? 1.f : 0.f;
-    if constexpr (LOSS == kLossPpo)
+    if constexpr (loss_is_ppo(LOSS))
       g[a] = on ? -(adv * af * oh * invq - beta * (lp + p * inv)) : 0.f;
     else
       g[a] = on ? -(adv * oh * inv - beta * (lp + p * inv)) : 0.f;
@@ -260,20 +266,33 @@ __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, in
 #pragma unroll
   for (int a = 0; a < AP; ++a) out[a] = (a < A) ? s * pi[a] * (g[a] - dot) : 0.f;
   out[AP] = s * 0.5f * (v - y);
+  float l12 = 0.f;
+  bool vclipped = false;
+  if constexpr (LOSS == kLossPpoVclip) {
+    const float vc = v_old + fminf(fmaxf(v - v_old, -vclip_eps), vclip_eps);
+    const float l1 = (y - v) * (y - v), l2 = (y - vc) * (y - vc);
+    vclipped = l2 > l1;
+    l12 = fmaxf(l1, l2);
+    out[AP] = vclipped ? 0.f : out[AP];
+  }
   if (stats) {
-    if constexpr (LOSS == kLossPpo) {
+    if constexpr (loss_is_ppo(LOSS)) {
       const float rc = fminf(fmaxf(ratio, 1.0f - clip_eps), 1.0f + clip_eps);
       stats[0] = -(fminf(ratio * adv, rc * adv) + beta * ent);   // clipped surrogate + entropy bonus
     } else {
       stats[0] = -(logp * adv + beta * ent);   // actor objective term
     }
-    stats[1] = 0.25f * (y - v) * (y - v);    // critic term
+    if constexpr (LOSS == kLossPpoVclip)
+      stats[1] = 0.25f * l12;                  // clipped critic term
+    else
+      stats[1] = 0.25f * (y - v) * (y - v);    // critic term
     stats[2] = ent;
   }
-  if constexpr (LOSS == kLossPpo) {
+  if constexpr (loss_is_ppo(LOSS)) {
     if (pstats) {
       pstats[0] = 1.f - af;
       pstats[1] = logf(p_old + eps) - logp;
+      if constexpr (LOSS == kLossPpoVclip) pstats[2] = vclipped ? 1.f : 0.f;
     }
   }
 }
@@ -450,7 +469,15 @@ struct PpoArgs {
   float* stat_rows;     // kLossPpo: [B][2] per-row {clipped, log(p_old+eps) - log(p+eps)}, summed by ppo_stats_kernel
 };
 template <class Base> struct WithPpo : Base { PpoArgs ppo; };
+// ... and kLossPpoVclip three more behind the PPO block.
+struct VclipArgs {
+  const float* v_old;   // [B]: the values epoch 1's training-side heads computed
+  float vclip_eps;
+  float* stat_rows;     // [B] per-row vclipped (0 / 1), summed by ppo_vclip_stats_kernel
+};
+template <class Base> struct WithVclip : WithPpo<Base> { VclipArgs vc; };
 template <int EST, int LOSS> struct ArgsOf { using type = WithPpo<typename ReturnsOf<EST>::type>; };
+template <int EST> struct ArgsOf<EST, kLossPpoVclip> { using type = WithVclip<typename ReturnsOf<EST>::type>; };
 template <int EST> struct ArgsOf<EST, kLossA3c> { using type = typename ReturnsOf<EST>::type; };
 
 template <int AP, int LOSS = kLossA3c, class RT>
@@ -463,10 +490,14 @@ __device__ __forceinline__ void load_row_and_grad(const float* __restrict__ prob
   float pi[AP];
 #pragma unroll
   for (int a = 0; a < AP; ++a) pi[a] = probs[(long)i * A + (a < A ? a : 0)];
-  float yv, av, pold = 0.f, ceps = 0.f;
-  if constexpr (LOSS == kLossPpo) {
+  float yv, av, pold = 0.f, ceps = 0.f, vold = 0.f, veps = 0.f;
+  if constexpr (loss_is_ppo(LOSS)) {
     pold = rt.ppo.p_old[i];
     ceps = rt.ppo.clip_eps;
+  }
+  if constexpr (LOSS == kLossPpoVclip) {
+    vold = rt.vc.v_old[i];
+    veps = rt.vc.vclip_eps;
   }
   if (rt.v_boot) {
     returns_row(rt, i, yv, av);
@@ -478,7 +509,9 @@ __device__ __forceinline__ void load_row_and_grad(const float* __restrict__ prob
     *yv_out = yv;
     *av_out = av;
   }
-  if constexpr (LOSS == kLossPpo)
+  if constexpr (LOSS == kLossPpoVclip)
+    head_grad_row<AP, kLossPpoVclip>(pi, values[i], actions[i], yv, av, beta, s, A, out, stats, pold, ceps, pstats, vold, veps);
+  else if constexpr (LOSS == kLossPpo)
     head_grad_row<AP, kLossPpo>(pi, values[i], actions[i], yv, av, beta, s, A, out, stats, pold, ceps, pstats);
   else
     head_grad_row<AP>(pi, values[i], actions[i], yv, av, beta, s, A, out, stats);
@@ -592,7 +625,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
   for (int i = tid; i < B; i += 256) {
     float dl[NV], stats[3];
     float yv, av;
-    float pst[2];
+    float pst[3];
     load_row_and_grad<AP, LOSS>(probs, values, actions, y, adv, i, A, beta, s, dl, stats, rt, &yv, &av, pst);
     if (rt.v_boot) {          // the learner's records of the returns (paac.py:151-154 feed layout)
       rt.y_out[i] = yv;
@@ -602,10 +635,11 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
       const int ai = actions[i];
       rt.ppo.p_old[i] = probs[(long)i * A + (ai >= 0 && ai < A ? ai : 0)];   // (an action outside [0, A) reads no other row)
     }
-    if constexpr (LOSS == kLossPpo) {
+    if constexpr (loss_is_ppo(LOSS)) {
       rt.ppo.stat_rows[2 * i] = pst[0];
       rt.ppo.stat_rows[2 * i + 1] = pst[1];
     }
+    if constexpr (LOSS == kLossPpoVclip) rt.vc.stat_rows[i] = pst[2];
 #pragma unroll
     for (int a = 0; a < NV; ++a) accv[a] += dl[a];
     accv[NV] += stats[0]; accv[NV + 1] += stats[1]; accv[NV + 2] += stats[2];
@@ -688,11 +722,13 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
   }
   const int act = actions[i];
   float pold = 0.f, ypre = 0.f, apre = 0.f;     // kLossPpo: the row's frozen p_old / y / adv, wave-uniform like act
-  if constexpr (LOSS == kLossPpo) {
+  if constexpr (loss_is_ppo(LOSS)) {
     pold = rt.ppo.p_old[i];
     ypre = y[i];
     apre = adv[i];
   }
+  float vold = 0.f;                             // kLossPpoVclip: the row's frozen v_old
+  if constexpr (LOSS == kLossPpoVclip) vold = rt.vc.v_old[i];
   // (the row's returns scan runs on thread 0 further down: its inputs are wave-uniform addresses, requested here)
   typename PreOf<EST>::type npre;
   if (rt.rewards) npre = returns_preload(rt, i);
@@ -748,7 +784,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
     }
     values_ws[i] = lg[AP];
     float yv, av;
-    if constexpr (LOSS == kLossPpo) {
+    if constexpr (loss_is_ppo(LOSS)) {
       yv = ypre;
       av = apre;
     } else if (rt.rewards) {
@@ -777,7 +813,16 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
   float pi[AP], dl[NV], stats[3];
 #pragma unroll
   for (int a = 0; a < AP; ++a) pi[a] = row_s[a];
-  if constexpr (LOSS == kLossPpo) {
+  if constexpr (LOSS == kLossPpoVclip) {
+    float pst[3];
+    head_grad_row<AP, kLossPpoVclip>(pi, lg[AP], act, row_s[AP], row_s[AP + 1], beta, 5.0f / (float)B, A, dl, stats, pold,
+                                     rt.ppo.clip_eps, pst, vold, rt.vc.vclip_eps);
+    if (tid == 0) {
+      rt.ppo.stat_rows[2 * i] = pst[0];
+      rt.ppo.stat_rows[2 * i + 1] = pst[1];
+      rt.vc.stat_rows[i] = pst[2];
+    }
+  } else if constexpr (LOSS == kLossPpo) {
     float pst[2];
     head_grad_row<AP, kLossPpo>(pi, lg[AP], act, row_s[AP], row_s[AP + 1], beta, 5.0f / (float)B, A, dl, stats, pold,
                                 rt.ppo.clip_eps, pst);

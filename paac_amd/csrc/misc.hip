@@ -3,6 +3,7 @@
 #include "common.h"
 #include "synth_dev.h"
 #include "fc_heads.h"
+#include "heads.h"
 #include "tower.h"
 
 namespace paac {
@@ -130,6 +131,78 @@ __global__ void gae_returns_kernel(const float* __restrict__ v_boot, const float
       }
     }
   }
+}
+
+// --adv_norm (include/paac_hip.h has the contract): the B = T*N advantages of one rollout, normalised by their own mean and
+// population standard deviation.  ONE workgroup of kNormThreads threads does everything, so the statistics need no second
+// launch and no atomics: thread t owns rows t, t + kNormThreads, ... in every pass, a block sum is 32 column sums of 32
+// per-thread values and then the sum of those 32, every step a separate round-to-nearest fp64 operation -- the same inputs
+// give the same bits wherever the launch sits.  Two passes (the mean first, then the squared deviations from it).
+constexpr int kNormThreads = 1024;
+__device__ __forceinline__ double norm_block_sum(const double v, double* lds /* kNormThreads + 32 */) {
+  const int tid = threadIdx.x;
+  lds[tid] = v;
+  __syncthreads();
+  if (tid < 32) {
+    double t = 0.0;
+    for (int i = 0; i < kNormThreads / 32; ++i) t = __dadd_rn(t, lds[i * 32 + tid]);
+    lds[kNormThreads + tid] = t;
+  }
+  __syncthreads();
+  double r = 0.0;
+  for (int c = 0; c < 32; ++c) r = __dadd_rn(r, lds[kNormThreads + c]);   // (every thread: the same order, the same value)
+  __syncthreads();
+  return r;
+}
+// adv / adv_n may be the same array; stats (nullable) = {mean, std}.  std == 0 (B = 1, identical advantages) gives zeros;
+// a non-finite input makes mean and std non-finite and with them every output.
+__device__ __forceinline__ void adv_normalize_block(const float* adv, const int B, float* adv_n, double* stats, double* lds) {
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int i = tid; i < B; i += kNormThreads) acc = __dadd_rn(acc, (double)adv[i]);
+  const double mean = norm_block_sum(acc, lds) / (double)B;
+  acc = 0.0;
+  for (int i = tid; i < B; i += kNormThreads) {
+    const double d = __dsub_rn((double)adv[i], mean);
+    acc = __dadd_rn(acc, __dmul_rn(d, d));
+  }
+  const double sd = sqrt(norm_block_sum(acc, lds) / (double)B);
+  const double den = __dadd_rn(sd, 1e-8);
+  for (int i = tid; i < B; i += kNormThreads)
+    adv_n[i] = (sd == 0.0) ? 0.f : (float)(__dsub_rn((double)adv[i], mean) / den);
+  if (tid == 0 && stats) {
+    stats[0] = mean;
+    stats[1] = sd;
+  }
+}
+__global__ __launch_bounds__(kNormThreads) void adv_normalize_kernel(const float* adv, int B, float* adv_n, double* stats) {
+  __shared__ double lds[kNormThreads + 32];
+  adv_normalize_block(adv, B, adv_n, stats, lds);
+}
+// The returns of either estimator (heads.h: nstep_row_from / gae_row_from, the scans the backward's first launch runs -- every
+// row rescans its own return, so y / adv equal nstep_returns_kernel's / gae_returns_kernel's bit for bit), the cycle
+// bookkeeping of those kernels, and the normalisation above, in one launch.
+template <class RT>
+__global__ __launch_bounds__(kNormThreads) void returns_norm_kernel(const RT r, float* adv_n, double* stats) {
+  __shared__ double lds[kNormThreads + 32];
+  const int tid = threadIdx.x, B = r.T * r.N;
+  for (int i = tid; i < B; i += kNormThreads) {
+    float yv, av;
+    returns_row(r, i, yv, av);
+    r.y_out[i] = yv;
+    r.adv_out[i] = av;        // (read back below by the thread that wrote it)
+  }
+  if (tid == 0) {
+    if (r.global_step) {
+      const int64_t step = *r.global_step + r.step_inc;
+      *r.global_step = step;
+      double lr = 0.0;
+      if (step <= r.anneal) lr = r.lr0 - ((double)step * r.lr0 / (double)r.anneal);
+      *r.lr_out = (float)lr;
+    }
+    if (r.tick) *r.tick += r.tick_inc;
+  }
+  adv_normalize_block(r.adv_out, B, adv_n, stats, lds);
 }
 
 // actor_learner.py:119-123 evaluated after the cycle's increments (paac.py:127,156).
@@ -1990,6 +2063,24 @@ int launch_sample_env_step_heads(const float* partial, int ntiles, const float* 
   return 0;
 }
 
+// (arguments validated by paac_returns_norm_tick, csrc/api.hip)
+int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv_n, double* stats, hipStream_t s) {
+  GaeArgs rt;
+  memset(&rt, 0, sizeof(rt));
+  rt.v_boot = v_boot; rt.rewards = ret->rewards; rt.masks = ret->masks; rt.values_act = ret->values;
+  rt.T = ret->T; rt.N = ret->N; rt.gamma = ret->gamma; rt.y_out = ret->y_out; rt.adv_out = ret->adv_out;
+  rt.global_step = ret->global_step_dev; rt.step_inc = ret->increment; rt.lr0 = ret->initial_lr;
+  rt.anneal = ret->lr_annealing_steps; rt.lr_out = ret->lr_out_dev; rt.tick = ret->tick_dev; rt.tick_inc = ret->tick_inc;
+  if (ret->estimator == PAAC_RETURNS_GAE) {
+    rt.gl = ret->gamma * ret->gae_lambda;
+    launch_k(returns_norm_kernel<GaeArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rt, adv_n, stats);
+  } else {
+    const ReturnsArgs& rn = rt;
+    launch_k(returns_norm_kernel<ReturnsArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rn, adv_n, stats);
+  }
+  return 0;
+}
+
 }  // namespace paac
 
 using namespace paac;
@@ -2056,6 +2147,14 @@ int paac_gae_returns_tick(const float* v_boot, const float* rewards, const float
   ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
   launch_k(gae_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
            values, T, N, gamma, gamma * gae_lambda, y, adv, ct);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_adv_normalize(const float* adv, int B, float* adv_n_out, double* stats_out, paac_stream_t stream) {
+  PAAC_REQUIRE(adv && adv_n_out, "paac_adv_normalize: null argument");
+  PAAC_REQUIRE(B > 0, "paac_adv_normalize: B=%d", B);
+  launch_k(adv_normalize_kernel, dim3(1), dim3(kNormThreads), (hipStream_t)stream, PROF_WHOLE, adv, B, adv_n_out, stats_out);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

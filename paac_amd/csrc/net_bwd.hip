@@ -234,11 +234,35 @@ __global__ __launch_bounds__(256) void ppo_stats_kernel(const float* __restrict_
   if (threadIdx.x < 2) out2[threadIdx.x] = red[threadIdx.x] / (float)B;
 }
 
+// kLossPpoVclip: the same two means plus value_clip_fraction = the mean of vclip_rows, in the same launch and order.
+__global__ __launch_bounds__(256) void ppo_vclip_stats_kernel(const float* __restrict__ stat_rows,
+                                                              const float* __restrict__ vclip_rows, int B,
+                                                              float* __restrict__ out3) {
+  __shared__ float smem[3 * 256 + 3 * 8];
+  __shared__ float red[3];
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < B; i += 256) {
+    acc[0] += stat_rows[2 * i];
+    acc[1] += stat_rows[2 * i + 1];
+    acc[2] += vclip_rows[i];
+  }
+  block_sums_256<3>(acc, smem, red);
+  if (threadIdx.x < 3) out3[threadIdx.x] = red[threadIdx.x] / (float)B;
+}
+
 // The heads launch of a LOSS != kLossA3c instantiation: its estimator's argument block with the PPO fields behind it.
 // (kLossPpo reads y / adv from the arrays whatever estimator made them: one instantiation, under the n-step block.)
 template <class Go>
-static void launch_ppo_heads(Go&& go, int loss, int estimator, const GaeArgs& rt, const PpoArgs& ppo) {
+static void launch_ppo_heads(Go&& go, int loss, int estimator, const GaeArgs& rt, const PpoArgs& ppo, const VclipArgs& vc) {
   using std::integral_constant;
+  if (loss == kLossPpoVclip) {                 // (like kLossPpo: one instantiation, under the n-step block)
+    WithVclip<ReturnsArgs> ra;
+    static_cast<ReturnsArgs&>(ra) = rt;
+    ra.ppo = ppo;
+    ra.vc = vc;
+    go(integral_constant<int, kEstNstep>{}, integral_constant<int, kLossPpoVclip>{}, ra);
+    return;
+  }
   if (loss == kLossA3cRecord && estimator == kEstGae) {
     WithPpo<GaeArgs> ra;
     static_cast<GaeArgs&>(ra) = rt;
@@ -256,8 +280,8 @@ static void launch_ppo_heads(Go&& go, int loss, int estimator, const GaeArgs& rt
 template <class NT>
 static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                          const float* y, const float* adv, int batch, float beta, float* grad, float* loss_out,
-                         int phase, const GaeArgs& rt, int estimator, int loss, const PpoArgs& ppo, float* ppo_stats_out,
-                         hipStream_t s) {
+                         int phase, const GaeArgs& rt, int estimator, int loss, const PpoArgs& ppo, const VclipArgs& vc,
+                         float* ppo_stats_out, hipStream_t s) {
   const paac_layout& L = ctx->layout;
   Workspace& W = ctx->ws[1];
   const int cls = batch_class(batch);
@@ -305,7 +329,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
             params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A, batch, W.h, W.logits, W.probs, W.values, actions, y,
             adv, beta, ctx->dh, ctx->dl_buf, ra);
       };
-      launch_ppo_heads(go, loss, estimator, rtl, ppo);
+      launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
     } else if (estimator == kEstGae)
       launch_heads_train<NT::H, kEstGae>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
                                          fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
@@ -325,7 +349,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
             wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa], grad + L.offset[i_wa + 1], grad + L.offset[i_wc],
             grad + L.offset[i_wc + 1], loss_out, ra);
       };
-      launch_ppo_heads(go, loss, estimator, rtl, ppo);
+      launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
     } else if (estimator == kEstGae)
       launch_heads_bwd<NT::H, kEstGae>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
                                        adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
@@ -337,6 +361,9 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
   }
   if (do_fc && loss == kLossPpo && ppo_stats_out)
     launch_k(ppo_stats_kernel, dim3(1), dim3(256), s, PROF_NONE, (const float*)ppo.stat_rows, batch, ppo_stats_out);
+  if (do_fc && loss == kLossPpoVclip && ppo_stats_out)
+    launch_k(ppo_vclip_stats_kernel, dim3(1), dim3(256), s, PROF_NONE, (const float*)ppo.stat_rows,
+             (const float*)vc.stat_rows, batch, ppo_stats_out);
   const float* xf = (NT::NCONV == 3) ? W.act[2] : W.act[1];   // flattened last conv output
   float* dxf = (NT::NCONV == 3) ? ctx->dact[2] : ctx->dact[1];
   FinalizeArgs fin;
@@ -579,7 +606,12 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
 
 int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
                     const float* adv, int batch, float beta, float* grad, float* loss_out, int phase, hipStream_t s,
-                    const paac_returns* ret, int loss, float* p_old, float clip_eps, float* ppo_stats_out) {
+                    const paac_returns* ret, int loss, float* p_old, float clip_eps, float* ppo_stats_out,
+                    const float* v_old, float vclip_eps) {
+  VclipArgs vc;
+  vc.v_old = v_old;
+  vc.vclip_eps = vclip_eps;
+  vc.stat_rows = ctx->vclip_rows;
   PpoArgs ppo;
   ppo.p_old = p_old;
   ppo.clip_eps = clip_eps;
@@ -596,8 +628,8 @@ int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, c
     rt.anneal = ret->lr_annealing_steps; rt.lr_out = ret->lr_out_dev; rt.tick = ret->tick_dev; rt.tick_inc = ret->tick_inc;
   }
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, ppo_stats_out, s);
-  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, ppo_stats_out, s);
+    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, vc, ppo_stats_out, s);
+  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, vc, ppo_stats_out, s);
 }
 
 int64_t wslab_floats_needed(int arch) {

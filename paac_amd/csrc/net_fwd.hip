@@ -485,6 +485,39 @@ int launch_deferred_heads(paac_ctx* ctx, const float* params, hipStream_t s) {
   return 0;
 }
 
+// The heads of rows [batch, batch + N) of the pending forward only: the bootstrap values a returns launch in front of the
+// backward needs (paac_returns_norm_tick).  The pending state stays: the backward's first launch still finishes the rollout
+// rows' heads itself (or launch_deferred_heads runs over all rows, these included, with the same results).
+int launch_bootstrap_heads(paac_ctx* ctx, const float* params, int batch, int N, hipStream_t s) {
+  const int rows = ctx->heads_pending_rows;
+  if (rows <= 0) return 0;             // a whole training forward has run: its value head holds the bootstrap rows already
+  if (rows < batch + N) {
+    set_error("paac_returns_norm_tick: the pending training forward covers %d rows, the bootstrap rows end at %d", rows, batch + N);
+    return -1;
+  }
+  const paac_layout& L = ctx->layout;
+  const int nt = L.num_tensors;
+  Workspace& W = ctx->ws[1];
+  PhiloxArgs ph;
+  memset(&ph, 0, sizeof(ph));
+  SynthStepArgs st;
+  memset(&st, 0, sizeof(st));
+  const int A = ctx->cfg.num_actions, H = ctx->spec.fc;
+  const float *bf = ctx->heads_pending_h ? ctx->zeros : params + L.offset[nt - 5], *wa = params + L.offset[nt - 4],
+              *ba = params + L.offset[nt - 3], *wc = params + L.offset[nt - 2], *bc = params + L.offset[nt - 1];
+  const size_t r0 = (size_t)batch;
+  ProfScope ps(ctx, F_HEADS_FWD, N, s);
+  if (ctx->cfg.arch == PAAC_ARCH_NATURE)
+    launch_heads_fwd<NatureNet::H>(A, dim3(N), s, (const float*)W.fc_slab + r0 * H, ctx->heads_pending_splits, (long)rows * H, bf,
+                                   wa, ba, wc, bc, A, W.h + r0 * H, W.logits + r0 * A, W.probs + r0 * A, W.values + r0,
+                                   (float*)nullptr, (float*)nullptr, (float*)nullptr, ph, N, st);
+  else
+    launch_heads_fwd<OtherNet::H>(A, dim3(N), s, (const float*)W.fc_slab + r0 * H, ctx->heads_pending_splits, (long)rows * H, bf,
+                                  wa, ba, wc, bc, A, W.h + r0 * H, W.logits + r0 * A, W.probs + r0 * A, W.values + r0,
+                                  (float*)nullptr, (float*)nullptr, (float*)nullptr, ph, N, st);
+  return 0;
+}
+
 bool forward_has_fc_heads(const paac_ctx* ctx) {
   return fc_heads_waves(ctx->cfg.arch == PAAC_ARCH_NATURE ? NatureNet::FLAT : OtherNet::FLAT) > 0;
 }

@@ -258,6 +258,41 @@ class Context(object):
             _ptr(loss_out, torch.float32, 4, "loss_out", True), _ptr(ppo_stats_out, torch.float32, 2, "ppo_stats_out", True),
             1 if forward_done else 0, int(phase), _stream()), "paac_loss_backward_ppo")
 
+    def loss_backward_ppo_vclip(self, params, states, actions, y, adv, p_old, v_old, clip_eps, vclip_eps, entropy_beta, grad,
+                                loss_out=None, ppo_stats_out=None, forward_done=False, phase=0):
+        """loss_backward_ppo with the value-clipped critic term of --ppo_vclip on the frozen v_old (include/paac_hip.h:
+        paac_loss_backward_ppo_vclip).  ppo_stats_out: float32[3] = {clip_fraction, approx_kl, value_clip_fraction}."""
+        B = self._check_states(states)
+        _lib.check(self.lib.paac_loss_backward_ppo_vclip(
+            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
+            _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"),
+            _ptr(y, torch.float32, B, "y"), _ptr(adv, torch.float32, B, "adv"), _ptr(p_old, torch.float32, B, "p_old", True),
+            _ptr(v_old, torch.float32, B, "v_old", True), float(clip_eps), float(vclip_eps), B, float(entropy_beta),
+            _ptr(grad, torch.float32, self.layout["total"], "grad"), _ptr(loss_out, torch.float32, 4, "loss_out", True),
+            _ptr(ppo_stats_out, torch.float32, 3, "ppo_stats_out", True), 1 if forward_done else 0, int(phase), _stream()),
+            "paac_loss_backward_ppo_vclip")
+
+    def train_values_into(self, out, batch):
+        """out[:batch] = the values the training-side heads computed last (paac_debug_activation(25) into the caller's
+        array: one device-to-device copy on the stream, capturable): v_old of a --ppo_vclip cycle, right behind epoch 1."""
+        _lib.check(self.lib.paac_debug_activation(self.handle, 25, int(batch), _ptr(out, torch.float32, int(batch), "out"),
+                                                  int(batch), _stream()), "paac_debug_activation")
+
+    def returns_norm_tick(self, params, v_boot, rewards, masks, values, gamma, y_out, adv_out, adv_n_out, stats_out=None,
+                          global_step_dev=None, increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None,
+                          tick_dev=None, tick_inc=0, gae_lambda=None):
+        """Returns of either estimator + the cycle's schedule bookkeeping + --adv_norm's normalisation in one launch
+        (include/paac_hip.h: paac_returns_norm_tick).  v_boot=None: the bootstrap values are rows [T*N, T*N + N) of the
+        training forward that has already run on this ctx (the heads of those rows are finished here when they are pending).
+        stats_out: float64[2] = {mean, std}."""
+        T, N = rewards.shape
+        ret = _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
+                              lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda)
+        _lib.check(self.lib.paac_returns_norm_tick(
+            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"), ctypes.byref(ret),
+            _ptr(adv_n_out, torch.float32, T * N, "adv_n_out"), _ptr(stats_out, torch.float64, 2, "stats_out", True), _stream()),
+            "paac_returns_norm_tick")
+
     def clip_rmsprop(self, params, grad, ms, mom, lr_dev, decay, momentum, eps, clip_norm, clip_mode, grad_scale=1.0,
                      gnorm_out=None):
         n = self.layout["total"]
@@ -427,6 +462,47 @@ def lr_step(global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_d
     _lib.check(lib.paac_lr_step(_ptr(global_step_dev, torch.int64, 1, "global_step"), int(increment), float(initial_lr),
                                 int(lr_annealing_steps), _ptr(lr_out_dev, torch.float32, 1, "lr_out"), _stream()),
                "paac_lr_step")
+
+
+def _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
+                    lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda):
+    T, N = rewards.shape
+    return _lib.Returns(
+        v_boot=_ptr(v_boot, torch.float32, N, "v_boot", True), rewards=_ptr(rewards, torch.float32, T * N, "rewards"),
+        masks=_ptr(masks, torch.float32, T * N, "masks"), values=_ptr(values, torch.float32, T * N, "values"), T=T, N=N,
+        gamma=float(gamma), y_out=_ptr(y_out, torch.float32, T * N, "y_out"), adv_out=_ptr(adv_out, torch.float32, T * N, "adv_out"),
+        global_step_dev=_ptr(global_step_dev, torch.int64, 1, "global_step", True), increment=int(increment),
+        initial_lr=float(initial_lr), lr_annealing_steps=int(lr_annealing_steps),
+        lr_out_dev=_ptr(lr_out_dev, torch.float32, 1, "lr_out", True),
+        tick_dev=_ptr(tick_dev, torch.int64, 1, "tick", True), tick_inc=int(tick_inc),
+        estimator=_lib.RETURNS_GAE if uses_gae(gae_lambda) else _lib.RETURNS_NSTEP,
+        gae_lambda=float(gae_lambda) if uses_gae(gae_lambda) else 0.0)
+
+
+def adv_normalize(adv, adv_n_out, stats_out=None):
+    """--adv_norm's normalisation on its own (include/paac_hip.h: paac_adv_normalize): adv_n_out = (adv - mean) / (std + 1e-8)
+    over all of adv, fp64 statistics in a fixed order.  stats_out: float64[2] = {mean, std}."""
+    B = adv.numel()
+    lib = _lib.load()
+    _lib.check(lib.paac_adv_normalize(_ptr(adv, torch.float32, B, "adv"), B, _ptr(adv_n_out, torch.float32, B, "adv_n_out"),
+                                      _ptr(stats_out, torch.float64, 2, "stats_out", True), _stream()), "paac_adv_normalize")
+
+
+def returns_norm_tick(v_boot, rewards, masks, values, gamma, y_out, adv_out, adv_n_out, stats_out=None, global_step_dev=None,
+                      increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None, tick_dev=None, tick_inc=0,
+                      gae_lambda=None):
+    """paac_returns_norm_tick with the bootstrap values given (no ctx): == nstep_returns_tick / gae_returns_tick followed by
+    adv_normalize, in one launch."""
+    T, N = rewards.shape
+    ret = _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
+                          lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda)
+    if not ret.v_boot:
+        raise ValueError("returns_norm_tick: v_boot is required without a ctx (Context.returns_norm_tick takes it from the "
+                         "training forward)")
+    lib = _lib.load()
+    _lib.check(lib.paac_returns_norm_tick(None, None, ctypes.byref(ret), _ptr(adv_n_out, torch.float32, T * N, "adv_n_out"),
+                                          _ptr(stats_out, torch.float64, 2, "stats_out", True), _stream()),
+               "paac_returns_norm_tick")
 
 
 def uses_gae(gae_lambda):

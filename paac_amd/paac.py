@@ -98,6 +98,8 @@ class DeviceRollout(object):
             raise ValueError("--ppo_epochs above 1 is not built for PAAC_ALLREDUCE=split (the two-piece exchange): use graph "
                              "or single")
         self.graph_epoch = [[], []]                    # eager exchange: [parity][k - 1] = update + epoch k + 1's backward
+        # --adv_norm: the actor term of every epoch reads the normalised advantages; self.adv stays the recorded raw array
+        self.actor_adv = L.adv_n if L.adv_norm else self.adv
         self.short_first = os.environ.get("PAAC_SHORT_GRAPH_FIRST", "1") != "0"
         self.spin_sync = os.environ.get("PAAC_SPIN_SYNC", "1") != "0"
         self.verify_exchange = os.environ.get("PAAC_VERIFY_EXCHANGE", "1") != "0"
@@ -184,6 +186,24 @@ class DeviceRollout(object):
             L.ctx.bootstrap_forward_trunk(params, st[T], T * N)
         else:
             L.ctx.train_forward_trunk(params, self.states[parity * T:(parity + 1) * T + 1].view((T + 1) * N, 84, 84, 4))
+        phase = ((0 if self.single_exchange else 1) if self.phased else 3)
+        if L.adv_norm:
+            # --adv_norm: a row's workgroup cannot know the rollout's mean, so the returns leave the backward's first launch:
+            # heads of the bootstrap rows, then returns + statistics + normalisation + the cycle's bookkeeping in one launch,
+            # then the backward on (y, adv_n); the rollout rows' heads still ride in the backward's first launch
+            L.ctx.returns_norm_tick(params, None, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
+                                    L.adv_stats, global_step_dev=self.global_step_dev, increment=self.total_envs * T,
+                                    initial_lr=L.initial_lr, lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev,
+                                    tick_dev=self.tick, tick_inc=T, gae_lambda=L.gae_lambda)
+            if self.K > 1:
+                L.ctx.loss_backward_record(params, self.rollout_states(parity), self.actions.view(-1), self.y, L.adv_n, L.p_old,
+                                           L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=phase)
+            else:
+                L.ctx.loss_backward(params, self.rollout_states(parity), self.actions.view(-1), self.y, L.adv_n,
+                                    L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=phase)
+            if L.vclip_on:
+                L.ctx.train_values_into(L.v_old, T * N)
+            return
         # n-step returns + global_step/lr schedule + frame counter (paac.py:127,144-156) ride in the backward's first
         # launch.  One process: whole backward here, with the slab reduction of the conv weight gradients left to the norm
         # pass of the optimizer step that follows (phase 3: one launch less); data parallel: the complete gradient
@@ -191,16 +211,17 @@ class DeviceRollout(object):
         # the fc/heads gradient tail overlaps the conv backward (phase 2, _backward_conv)
         L.ctx.loss_backward_returns(params, self.rollout_states(parity), self.actions.view(-1), None, self.rewards,
                                     self.masks, self.values, L.gamma, self.y, self.adv, L.entropy_beta, L.grad,
-                                    L.loss_dev, forward_done=True,
-                                    phase=(0 if self.single_exchange else 1) if self.phased else 3,
+                                    L.loss_dev, forward_done=True, phase=phase,
                                     global_step_dev=self.global_step_dev, increment=self.total_envs * T,
                                     initial_lr=L.initial_lr, lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev,
                                     tick_dev=self.tick, tick_inc=T, gae_lambda=L.gae_lambda,
                                     p_old_out=L.p_old if self.K > 1 else None)
+        if L.vclip_on:         # --ppo_vclip: v_old = the values epoch 1's heads just computed (one captured copy)
+            L.ctx.train_values_into(L.v_old, T * N)
 
     def _epoch_backward(self, parity, k):
         """Epoch k + 1 of the cycle up to its gradient (the update of epoch k has run)."""
-        self.L.ppo_epoch_backward(k, self.rollout_states(parity), self.actions.view(-1), self.y, self.adv,
+        self.L.ppo_epoch_backward(k, self.rollout_states(parity), self.actions.view(-1), self.y, self.actor_adv,
                                   phase=0 if self.phased else 3)
 
     def _later_epochs(self, parity, exchange, before_last_update=None):
@@ -303,7 +324,7 @@ class DeviceRollout(object):
         L = self.L
         ts = [self.states, self.actions, self.values, self.rewards, self.masks, self.probs, self.y, self.adv, self.ep_reward,
               self.ep_len, self.finished, self.tick, self.global_step_dev] + [t for _, t in L.update_state] + \
-             [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev] + [t for t in (L.p_old, L.ppo_loss, L.ppo_stats) if t is not None]
+             [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev] + [t for t in (L.p_old, L.ppo_loss, L.ppo_stats, L.adv_n, L.adv_stats, L.v_old) if t is not None]
         for name in ("raw", "walk_scratch", "mt_state"):
             t = getattr(self, name, None)
             if t is not None:
@@ -523,7 +544,11 @@ class PAACLearner(ActorLearner):
                 self.metrics.write("ppo_epoch", global_step=int(self.global_step), epoch=k + 1, loss=float(losses[k, 0]),
                                    actor_loss=float(losses[k, 1]), critic_loss=float(losses[k, 2]),
                                    entropy=float(losses[k, 3]), clip_fraction=float(stats[k, 0]),
-                                   approx_kl=float(stats[k, 1]))
+                                   approx_kl=float(stats[k, 1]),
+                                   **(dict(value_clip_fraction=float(stats[k, 2])) if self.vclip_on else {}))
+        if self.adv_norm:                # the statistics the last rollout's advantages were normalised by (this rank's)
+            mean, std = self.adv_stats.cpu().numpy()
+            self.metrics.write("adv_norm", global_step=int(self.global_step), mean=float(mean), std=float(std))
         self.metrics.flush()
 
     @staticmethod
@@ -790,18 +815,24 @@ class PAACLearner(ActorLearner):
             d_rewards.copy_(torch.from_numpy(rewards))
             d_masks.copy_(torch.from_numpy(masks))
             hip_ops.returns(d_vboot, d_rewards, d_masks, d_values, self.gamma, d_y, d_adv, self.gae_lambda)
+            d_actor_adv = d_adv
+            if self.adv_norm:         # the actor term reads the normalised advantages; d_adv stays the recorded raw array
+                hip_ops.adv_normalize(d_adv, self.adv_n, self.adv_stats)
+                d_actor_adv = self.adv_n
             lr = self.get_lr()
             self.lr_dev.fill_(float(np.float32(lr)))
             if self.ppo_epochs > 1:
-                self.ctx.loss_backward_record(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv,
+                self.ctx.loss_backward_record(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
                                               self.p_old, self.entropy_beta, self.grad, self.loss_dev)
             else:
-                self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv,
+                self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
                                        self.entropy_beta, self.grad, self.loss_dev)
+            if self.vclip_on:         # v_old = the values epoch 1's heads just computed
+                self.ctx.train_values_into(self.v_old, T * N)
             self._allreduce_grad()
             self.apply_gradients()
-            for k in range(1, self.ppo_epochs):      # epochs 2..K on the frozen y / adv / p_old, the same lr
-                self.ppo_epoch_backward(k, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_adv, phase=0)
+            for k in range(1, self.ppo_epochs):      # epochs 2..K on the frozen y / adv / p_old (/ v_old), the same lr
+                self.ppo_epoch_backward(k, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv, phase=0)
                 self._allreduce_grad()
                 self.apply_gradients()
             if getattr(self.args, "record_feeds", False):

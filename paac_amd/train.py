@@ -85,6 +85,12 @@ BUILD_FLAGS = (
      "probability-ratio objective"),
     (("--ppo_clip",), "ppo_clip", 0.2, float, "PPO clip range EPS in (0, 1): the ratio is clipped to [1 - EPS, 1 + EPS]; read "
                                               "only when --ppo_epochs is above 1"),
+    (("--ppo_vclip",), "ppo_vclip", 0.0, float,
+     "PPO value clipping range EPSV: 0 = off; above 0, epochs 2..K use the critic term max((y - v)^2, (y - vc)^2) with vc = v "
+     "clipped to within EPSV of the value epoch 1 computed; read only when --ppo_epochs is above 1"),
+    (("--adv_norm",), "adv_norm", False, bool_arg,
+     "normalise each rollout's advantages by their own mean and standard deviation before the actor term reads them (per "
+     "rank under data parallelism); the critic target and the recorded advantages are unchanged"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),

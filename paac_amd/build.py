@@ -144,8 +144,11 @@ if __name__ == "__main__":
     if "--user-arch" in sys.argv:        # e.g. --user-arch 32,64,64,1024 (filter counts, then the fc width), or
         spec = sys.argv[sys.argv.index("--user-arch") + 1]          # 32:8:4,64:5:2,64:3:1,512 (filters:size:stride per layer)
         print(build_user_arch(*parse_user_arch(spec), verbose=True))
-    elif "--stamps" in sys.argv:
-        print(build(extra_flags=["-DPAAC_DMM_STAMPS"], lib_path=os.path.join(HERE, "libpaac_hip_stamps.so"),
-                    obj_suffix="_stamps"))
+    elif "--stamps" in sys.argv or "--ksplit" in sys.argv:
+        # --stamps: cycle stamps inside the kernels (tools/probe_*stamps.py); --ksplit: the conv tower's small regions on the K
+        # split over wave pairs instead of GEMM / helper wave roles (csrc/tower.h: PAAC_T_ROLES), for A/B runs.  They combine.
+        tag = ("_stamps" if "--stamps" in sys.argv else "") + ("_ksplit" if "--ksplit" in sys.argv else "")
+        flags = (["-DPAAC_DMM_STAMPS"] if "--stamps" in sys.argv else []) + (["-DPAAC_T_ROLES=0"] if "--ksplit" in sys.argv else [])
+        print(build(extra_flags=flags, lib_path=os.path.join(HERE, "libpaac_hip%s.so" % tag), obj_suffix=tag))
     else:
         print(build(force="--force" in sys.argv))

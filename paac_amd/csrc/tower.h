@@ -17,7 +17,8 @@
 //     lane -- one 8-byte LDS store per plane (one 16-byte global store when the fp32 activation is kept for backward).
 //   * 8 waves per workgroup.  A wave owns one 16-channel tile (weights are streamed from L2 exactly once per workgroup)
 //     and either all pixel tiles over half of K (the two halves summed through LDS) or half of the pixel tiles over all
-//     of K, whichever divides evenly.
+//     of K, whichever divides evenly.  The small regions (TowerGeom::ROLES) instead run conv2 / conv3 on waves 0-3 alone,
+//     all pixel tiles over all of K, and use waves 4-7 as helpers that write the kept fp32 rows meanwhile.
 //   * Regions: with 32 acting rows, one workgroup per sample would light 32 of 256 CUs.  A sample is cut into 2x2
 //     overlapping regions of 4x4 conv3 outputs (origins 0 / 3; conv2 6x6, conv1 14x14, input 60x60 each): 128 workgroups,
 //     about 2x redundant conv1 / conv2 arithmetic, no exchange between workgroups (up to 16 rows: 2x4 regions of 4x2, the
@@ -69,6 +70,11 @@ struct TowerArgs {
 #endif
 #ifndef PAAC_T_KS3
 #define PAAC_T_KS3 2
+#endif
+// 1: the small regions (PT2 <= PAAC_T_KS2 and PT3 <= PAAC_T_KS3) run conv2 / conv3 on four GEMM waves, one per channel tile
+// over all of K, with waves 4-7 as helpers (TowerGeom::ROLES); 0: the K split over the wave pair everywhere it was chosen
+#ifndef PAAC_T_ROLES
+#define PAAC_T_ROLES 1
 #endif
 constexpr int kTowerW1Vecs = 8 * 2 * 3 * 64, kTowerW2Vecs = 16 * 4 * 3 * 64, kTowerW3Vecs = 18 * 4 * 3 * 64;   // bf16x8 each
 constexpr int kTowerPackVecs = kTowerW1Vecs + kTowerW2Vecs + kTowerW3Vecs;
@@ -128,11 +134,18 @@ struct TowerGeom {
   // K split over the two waves of a channel tile (else the pixel tiles are): forced when the tiles do not halve -- and for
   // the small regions, where a weight fragment fetched by BOTH waves for one or two pixel tiles each makes the layer wait
   // for the CU's L1 (stamped at 32 rows: conv2 6.4 k cycles for 3.1 k of MFMA issue, 392 KB of fragments through the L1)
-  static constexpr bool KSPLIT2 = (PT2 % 2) != 0 || PT2 <= PAAC_T_KS2, KSPLIT3 = (PT3 % 2) != 0 || PT3 <= PAAC_T_KS3;
+  // Wave roles (the small regions): the K split buys "every weight fragment through the L1 once" with an exchange of partial
+  // sums through LDS and a barrier per layer.  One wave per channel tile over ALL of K fetches every fragment once just the
+  // same: waves 0-3 (one per SIMD) run conv2 / conv3 with the MFMA count per SIMD unchanged, nothing is exchanged, and
+  // waves 4-7 are free to write the kept fp32 rows (WRITE_ALL) from the LDS planes while the GEMMs run.
+  static constexpr bool ROLES = PAAC_T_ROLES != 0 && PT2 <= PAAC_T_KS2 && PT3 <= PAAC_T_KS3;
+  static constexpr bool KSPLIT2 = !ROLES && ((PT2 % 2) != 0 || PT2 <= PAAC_T_KS2);
+  static constexpr bool KSPLIT3 = !ROLES && ((PT3 % 2) != 0 || PT3 <= PAAC_T_KS3);
   static constexpr int NT1 = (PT1 + 3) / 4;                            // conv1: pixel tiles per wave (4 pixel groups x 2 channel tiles)
-  static constexpr int NT2 = KSPLIT2 ? PT2 : PT2 / 2, NT3 = KSPLIT3 ? PT3 : PT3 / 2;
-  // weight prefetch depth per layer (k-steps ahead); a depth >= the k-step count loads every fragment up front
-  static constexpr int PF1 = 8, PF2 = KSPLIT2 ? 8 : 6, PF3 = KSPLIT3 ? 9 : 6;
+  static constexpr int NT2 = (KSPLIT2 || ROLES) ? PT2 : PT2 / 2, NT3 = (KSPLIT3 || ROLES) ? PT3 : PT3 / 2;
+  // weight prefetch depth per layer (k-steps ahead); a depth >= the k-step count loads every fragment up front.  ROLES: one
+  // window of 8 k-steps slides over conv2's 16 and on into conv3's 18 (the register footprint of the K split's 8 + 9)
+  static constexpr int PF1 = 8, PF2 = (KSPLIT2 || ROLES) ? 8 : 6, PF3 = ROLES ? 8 : KSPLIT3 ? 9 : 6;
   static constexpr int IN_BYTES = RIH * RIW * 8;
   static constexpr int SCR2 = KSPLIT2 ? 4 * NT2 * 1024 : 0;            // K-split partials of 4 waves, f32x4 per lane and tile
   static constexpr int FRONT = (IN_BYTES > 3 * PL2 + SCR2) ? IN_BYTES : 3 * PL2 + SCR2;   // input image, later conv2 planes (+ partials)
@@ -164,7 +177,10 @@ struct NoHook {
   __device__ __forceinline__ void operator()(int) const {}
 };
 
-template <int NS, int NT, int CT, int BP, int BPL, int PF_, class KOFF, bool DB = true>
+//   KSETS  : (BP = 3, TowerGeom::ROLES) > 0: k-step i accumulates into set (i / KSETS) & 1 of two accumulators per tile, added
+//            at the end -- the sums the K split over a wave pair forms (conv2: k-steps 0-7 | 8-15, KSETS = 8; conv3: channel
+//            half = even | odd k-steps, KSETS = 1), product for product, so one wave over all of K leaves the same bits
+template <int NS, int NT, int CT, int BP, int BPL, int PF_, class KOFF, bool DB = true, int KSETS = 0>
 struct WaveGemm {
   static constexpr int PF = PF_ < NS ? PF_ : NS;
   static constexpr int RING = PF < NS ? PF + 1 : NS;
@@ -205,6 +221,11 @@ struct WaveGemm {
     // DB: the patch fragments of step i + 1 are read while step i computes (two register sets); !DB (many tiles per
     // wave): one set, read at the top of the step
     bf16x8 b[DB ? 2 : 1][NT][BP];
+    f32x4 acc2[KSETS > 0 ? NT : 1];      // the second accumulator set (KSETS > 0 only)
+    if constexpr (KSETS > 0) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc2[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
     if constexpr (DB) read_b(b[0], lds_b, bb, 0);
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
@@ -225,12 +246,25 @@ struct WaveGemm {
         for (int pl = 2; pl >= 0; --pl)
 #pragma unroll
           for (int t = 0; t < NT; ++t) acc[t] = mfma_bf16(a[slot][pl], b[i % NB][t][0], acc[t]);
-      }
+      } else if constexpr (KSETS > 0) {   // the order of the products of the plain case below, the tiles interleaved
+        const bf16x8(&bs)[NT][BP] = b[i % NB];
+        f32x4(&as)[NT] = ((i / KSETS) & 1) ? acc2 : acc;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const bf16x8(&bt)[BP] = b[i % NB][t];
-        if constexpr (BP == 1) {
-        } else {
+        for (int t = 0; t < NT; ++t) as[t] = mfma_bf16(a[slot][2], bs[t][0], as[t]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) as[t] = mfma_bf16(a[slot][1], bs[t][1], as[t]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) as[t] = mfma_bf16(a[slot][0], bs[t][2], as[t]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) as[t] = mfma_bf16(a[slot][1], bs[t][0], as[t]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) as[t] = mfma_bf16(a[slot][0], bs[t][1], as[t]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) as[t] = mfma_bf16(a[slot][0], bs[t][0], as[t]);
+      } else {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const bf16x8(&bt)[BP] = b[i % NB][t];
           acc[t] = mfma_bf16(a[slot][2], bt[0], acc[t]);
           acc[t] = mfma_bf16(a[slot][1], bt[1], acc[t]);
           acc[t] = mfma_bf16(a[slot][0], bt[2], acc[t]);
@@ -240,6 +274,10 @@ struct WaveGemm {
         }
       }
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (KSETS > 0) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[t] += acc2[t];
     }
   }
 };
@@ -260,6 +298,35 @@ __device__ __forceinline__ void store_split4(char* dst, const f32x4 v) {
   *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_hi16(xb[0], xb[1]), pack_hi16(xb[2], xb[3])};
   *reinterpret_cast<u32x2*>(dst + PLANE_STRIDE) = (u32x2){pack_hi16(r1b[0], r1b[1]), pack_hi16(r1b[2], r1b[3])};
   *reinterpret_cast<u32x2*>(dst + 2 * PLANE_STRIDE) = (u32x2){pack_hi16(r2b[0], r2b[1]), pack_hi16(r2b[2], r2b[3])};
+}
+
+// Helper waves (TowerGeom::ROLES, WRITE_ALL): the fp32 activations of a layer, rebuilt from its three bf16 planes in LDS --
+// x = hi + mid + lo holds exactly (split3_bf16; for x = 0 and x >= 2^-103 -- below that the remainders are subnormal and
+// their truncation drops bits: a conv output that small and not 0 does not come out of a sum of fp32 terms), and
+// (lo + mid) + hi rounds nowhere: lo + mid is the 16-bit remainder r1, r1 + hi is x -- and stored as the region's rows of
+// the [B, H, W, C] image.  htid = 0 .. 255 over the four helper waves.
+template <int P, int RW, int S, int PL, int C>
+__device__ __forceinline__ void store_kept_rows(const char* __restrict__ planes, float* __restrict__ img /* region origin */,
+                                                const int img_w, const int htid) {
+  constexpr int V = C / 4, N = P * V;     // f32x4 per pixel, per region
+#pragma unroll
+  for (int i0 = 0; i0 < N; i0 += 256) {
+    const int i = i0 + htid;
+    if (i0 + 256 > N && i >= N) break;
+    const int pi = i / V, c4 = i - pi * V;
+    const char* src = planes + pi * S + c4 * 8;
+    const u32x2 h = *reinterpret_cast<const u32x2*>(src), m = *reinterpret_cast<const u32x2*>(src + PL),
+                l = *reinterpret_cast<const u32x2*>(src + 2 * PL);
+    f32x4 v;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      v[2 * q] = (__builtin_bit_cast(float, l[q] << 16) + __builtin_bit_cast(float, m[q] << 16)) + __builtin_bit_cast(float, h[q] << 16);
+      v[2 * q + 1] = (__builtin_bit_cast(float, l[q] & 0xFFFF0000u) + __builtin_bit_cast(float, m[q] & 0xFFFF0000u)) +
+                     __builtin_bit_cast(float, h[q] & 0xFFFF0000u);
+    }
+    const int y = pi / RW, x = pi - y * RW;
+    *reinterpret_cast<f32x4*>(img + ((size_t)y * img_w + x) * C + 4 * c4) = v;
+  }
 }
 
 template <class G>
@@ -304,7 +371,9 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
   TOWER_STAMP(1);
   // conv1's weights: from LDS (staged below) with a short read-ahead, or straight from global, all 8 k-steps requested now
   WaveGemm<8, G::NT1, 2, 1, 0, G::W1_LDS ? 2 : G::PF1, Koff1<G>> g1;
-  WaveGemm<G::KSPLIT2 ? 8 : 16, G::NT2, 4, 3, G::PL1, G::PF2, Koff2<G>> g2;
+  WaveGemm<G::KSPLIT2 ? 8 : 16, G::NT2, 4, 3, G::PL1, G::PF2, Koff2<G>, true, G::ROLES ? 8 : 0> g2;
+  // ROLES: waves 0-3 are the GEMM waves of conv2 / conv3 (channel tile = wave), waves 4-7 the helpers
+  const bool gemm_wave = !G::ROLES || wave < 4;
 
   // ---- phase 0: input region -> LDS as bf16 (a byte is exact in bf16) ---------------------------------------------
   {
@@ -383,23 +452,25 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
       // waves of 4-5 pixel tiles instead of eight of 2-3 (less LDS traffic for the weight fragments) measured equal.
       g2.set(p.w2p + lane, wave & 3, 1, G::KSPLIT2 ? 8 * (wave >> 2) : 0);
       g1.prologue(reinterpret_cast<const bf16x8*>(lds_w1) + lane, ct, 1, 0);
-      g1.run(lds_in, bb, acc, [&](const int i) { g2.prologue_step(i); });
+      g1.run(lds_in, bb, acc, [&](const int i) { if (gemm_wave) g2.prologue_step(i); });
 #pragma unroll
-      for (int j = 8; j < decltype(g2)::PF; ++j) g2.prologue_step(j);
+      for (int j = 8; j < decltype(g2)::PF; ++j)
+        if (gemm_wave) g2.prologue_step(j);
       __builtin_amdgcn_sched_barrier(0);
     } else {
       g1.run(lds_in, bb, acc);
     }
     TOWER_STAMP(4);
-    if constexpr (!G::W1_LDS)   // conv2's first weights: ahead of the epilogue + barrier (W1_LDS: requested before conv1's GEMM)
-      g2.prologue(p.w2p + lane, wave & 3, 1, G::KSPLIT2 ? 8 * (wave >> 2) : 0);
+    if constexpr (!G::W1_LDS) {   // conv2's first weights: ahead of the epilogue + barrier (W1_LDS: requested before conv1's GEMM)
+      if (gemm_wave) g2.prologue(p.w2p + lane, wave & 3, 1, G::KSPLIT2 ? 8 * (wave >> 2) : 0);
+    }
 #pragma unroll
     for (int j = 0; j < G::NT1; ++j) {
       if (pix[j] < 0) continue;
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[j][e] * kInputScale + bias[e], 0.f);   // networks.py:115 scale, bias, ReLU
-      if constexpr (WRITE_ALL) {
+      if constexpr (WRITE_ALL && !G::ROLES) {      // ROLES: the helper waves store act1 while conv2's GEMM runs
         const int y1 = pix[j] / G::R1W, x1 = pix[j] - y1 * G::R1W;
         *reinterpret_cast<f32x4*>(p.act1 + ((size_t)(b * 20 + y1a + y1) * 20 + x1a + x1) * 32 + 16 * ct + 4 * kq) = v;
       }
@@ -411,10 +482,10 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
   TOWER_STAMP(6);
 
   WaveGemm<9, G::NT3, 4, 3, G::PL2, G::PF3, Koff3Half<G>> g3h;     // only the one matching KSPLIT3 is used
-  WaveGemm<18, G::NT3, 4, 3, G::PL2, G::PF3, Koff3Full<G>> g3f;
+  WaveGemm<18, G::NT3, 4, 3, G::PL2, G::PF3, Koff3Full<G>, true, G::ROLES ? 1 : 0> g3f;
   // ---- phase 2: conv2 (K = 512 = 16 taps x 32 channels) ---------------------------------------------------------------
-  {
-    const int ct = wave & 3, half = wave >> 2;
+  if (gemm_wave) {
+    const int ct = wave & 3, half = wave >> 2;      // ROLES: half == 0, every pixel tile over all of K
     unsigned bb[G::NT2];
     int pix[G::NT2];
 #pragma unroll
@@ -470,18 +541,22 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[j][e] + bias[e], 0.f);
-      if constexpr (WRITE_ALL) {
+      if constexpr (WRITE_ALL && !G::ROLES) {      // ROLES: the helper waves store act2 while conv3's GEMM runs
         const int y2 = pix[j] / G::R2W, x2 = pix[j] - y2 * G::R2W;
         *reinterpret_cast<f32x4*>(p.act2 + ((size_t)(b * 9 + y3a + y2) * 9 + x3a + x2) * 64 + 16 * ct + 4 * kq) = v;
       }
       store_split4<G::PL2>(lds_a2 + pix[j] * G::S2 + (16 * ct + 4 * kq) * 2, v);
     }
+  } else {
+    if constexpr (WRITE_ALL)      // helper waves: the kept conv1 rows, from the planes conv2's GEMM is reading
+      store_kept_rows<G::P1, G::R1W, G::S1, G::PL1, 32>(lds_a1, p.act1 + ((size_t)(b * 20 + y1a) * 20 + x1a) * 32, 20, tid - 256);
+    TOWER_STAMP(7);
   }
   __syncthreads();
   TOWER_STAMP(8);
 
   // ---- phase 3: conv3 (K = 576 = 9 taps x 64 channels) ----------------------------------------------------------------
-  {
+  if (gemm_wave) {
     const int ct = wave & 3, half = wave >> 2;
     unsigned bb[G::NT3];
     int pix[G::NT3];
@@ -534,6 +609,10 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
         if (p.act3_rows) *reinterpret_cast<f32x4*>(p.act3_rows + (size_t)b * 3136 + k0) = v;
       }
     }
+  } else {
+    if constexpr (WRITE_ALL)      // helper waves: the kept conv2 rows
+      store_kept_rows<G::P2, G::R2W, G::S2, G::PL2, 64>(lds_a2, p.act2 + ((size_t)(b * 9 + y3a) * 9 + x3a) * 64, 9, tid - 256);
+    TOWER_STAMP(9);
   }
   TOWER_STAMP(10);
   TOWER_STAMP(11);

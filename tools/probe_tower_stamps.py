@@ -34,6 +34,8 @@ for rep in range(3):
     ctx.forward(P, S, probs=probs)
     torch.cuda.synchronize()
     st = stamps.cpu().numpy()[:-1024].reshape(-1, 12)
+    wave_id = np.arange(len(st)) % 8                      # stamps are [workgroup][wave][12]
+    wave_id = wave_id[st[:, 0] != 0]
     st = st[st[:, 0] != 0].astype(np.float64)
     w0, w1 = st[:, 0], st[:, 11]
     print("waves %d | start spread %.2f us | lifetime med %.2f max %.2f us | first start -> last end %.2f us" % (
@@ -43,4 +45,8 @@ for rep in range(3):
     seg = np.diff(st[:, 1:11], axis=1)
     print("    " + " | ".join("%s %d" % (n, np.median(seg[:, i])) for i, n in enumerate(names)) + "  (median cycles; max: " +
           " ".join("%d" % seg[:, i].max() for i in range(seg.shape[1])) + ")")
+    # wave roles (csrc/tower.h, TowerGeom::ROLES): waves 0-3 run conv2 / conv3 (no reduce in their epilogue segments), waves
+    # 4-7 store the kept rows in the "gemm" segments and wait in the others
+    for label, sel in (("waves 0-3", wave_id < 4), ("waves 4-7", wave_id >= 4)):
+        print("    %s: " % label + " | ".join("%s %d" % (n, np.median(seg[sel, i])) for i, n in enumerate(names)))
 lib.paac_debug_set_tower_stamps(None)

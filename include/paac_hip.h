@@ -272,6 +272,59 @@ int paac_loss_backward_ppo_vclip(paac_ctx* ctx, const float* params, const uint8
                                  float vclip_eps, int batch, float entropy_beta, float* grad, float* loss_out,
                                  float* ppo_stats_out, int forward_done, int phase, paac_stream_t stream);
 
+/* --ppo_minibatches M: K epochs of M shuffled minibatches (arXiv 1707.06347, Algorithm 1; the PPO2 loop) in place of K full-batch
+ * steps.  The reference has no counterpart; this is the contract.  M = 1 (the default) is the --ppo_epochs cycle above through
+ * the same launches, bit for bit.  M is read only when K > 1.  With K > 1 and M > 1, B = T*N rows and b = B/M, one cycle is:
+ *   1. Rollout and bootstrap forward, as always.
+ *   2. Record pass (nothing is recorded after a weight update): paac_record_policy finishes the training-side heads of the
+ *      rollout rows on the pre-update weights and writes p_old[i] = pi(a_i | s_i) (and v_old[i] under --ppo_vclip); y and adv
+ *      come from the returns launches above (paac_nstep_returns_tick / paac_gae_returns_tick / paac_returns_norm_tick: the same
+ *      bits as the M = 1 cycle's for the same rollout and weights; the schedule bookkeeping happens here, once per cycle); adv_n
+ *      is normalised over the whole rollout, not per minibatch.  y, adv, adv_n, p_old, v_old are frozen from here on.
+ *   3. Permutations, ONE launch for all K epochs (paac_minibatch_perms): for epoch e and row i, key_i = word 0 of
+ *      philox4x32-10(ctr = {i, step lo, step hi, 0x504D0000 + e}; key = seed), step = *step_base_dev + step_offset (base in
+ *      memory + immediate offset like paac_sample_philox: a replayed graph draws a fresh shuffle every cycle; the learner passes
+ *      --sampler_seed and the cycle's frame counter).  perm_e = the row indices in ascending (key_i, i) order
+ *      (np.argsort(keys, kind="stable")).  Minibatch j of epoch e is perm_e[j*b : (j+1)*b].  Nothing rank-specific enters the
+ *      counter: every data-parallel rank applies the same permutation to its own shard.
+ *   4. Per epoch ONE gather launch (paac_gather_minibatch): states_p[r] = states[perm_e[r]] into a staging block allocated once
+ *      (fixed addresses under replay), the same index map on actions, y, the array the actor term reads (adv or adv_n), p_old
+ *      and v_old.
+ *   5. Per minibatch j: paac_train_forward_trunk on rows [j*b, (j+1)*b) of the staging block, paac_loss_backward_ppo[_vclip]
+ *      with batch = b (every mean is over the minibatch), the exchange under data parallelism (one all-reduce per step), the
+ *      same clip and optimizer step with the cycle's one lr (Adam's powers advance per step).  All K epochs run this way, the
+ *      first included: an M > 1 cycle has no full-batch update, K*M optimizer steps.  (The first step runs on the weights
+ *      p_old was recorded on: nothing is clipped there, and its ratio is 1 -- exactly when the record pass and the step's
+ *      forward run the same kernels, up to the summation order of kept acting rows against a recomputed trunk otherwise.)
+ *   Refused: M outside [1, PAAC_PPO_MINIBATCHES_MAX], M that does not divide T*N, K*M > PAAC_PPO_STEPS_MAX (a captured cycle
+ *   grows by about ten launches per step), T*N > PAAC_MINIBATCH_MAX_ROWS with M > 1.
+ * paac_minibatch_perms: perms_out = device int32[epochs][B], epoch e's permutation of 0..B-1 at row e.  One workgroup per epoch
+ * sorts 64-bit (key << 32 | row) composites in LDS (64 KB at PAAC_MINIBATCH_MAX_ROWS rows); a B that is no power of two is padded
+ * with composites (0xFFFFFFFF << 32 | row >= B), larger than every real pair even when a real key is 0xFFFFFFFF.
+ * step_base_dev may be NULL (base 0).
+ * paac_gather_minibatch: out[r] = in[perm[r]] for r < B.  states / states_out: u8 [B,84,84,4], 16-byte aligned, moved as 16-byte
+ * vectors (1764 per row); actions (int32), y, adv, p_old, v_old (float), each [B].  Every array comes with its output or both
+ * are NULL (any of them, the states included); an output that overlaps its input is refused.  perm entries outside [0, B) are
+ * skipped (nothing is read through them).
+ * paac_record_policy: the heads of a pending trunk-only training forward (paac_train_forward_trunk, or kept acting rows +
+ * paac_bootstrap_forward_trunk) are finished by the launch a backward that cannot fuse them would run (all pending rows, on
+ * `params`); after a whole training forward nothing is pending and nothing is recomputed.  Then one small launch writes
+ * p_old_out[i] = probabilities[i, actions[i]] for i < batch and v_out[i] = value[i] for i < value_rows, straight out of the ctx's
+ * training-side head outputs (what paac_debug_activation(26) / (25) copy).  value_rows may exceed batch: with the bootstrap
+ * observations appended as rows [batch, batch + N), v_out[batch ...] are the bootstrap values the returns launch needs.
+ * p_old_out or v_out may be NULL (not both).  No gradient; a following paac_loss_backward*(forward_done = 1) finds the heads
+ * finished and computes the gradient it computes without this call, bit for bit. */
+#define PAAC_PPO_MINIBATCHES_MAX 16
+#define PAAC_PPO_STEPS_MAX 64
+#define PAAC_MINIBATCH_MAX_ROWS 8192
+int paac_minibatch_perms(int B, int epochs, uint64_t seed, const uint64_t* step_base_dev, uint64_t step_offset,
+                         int32_t* perms_out, paac_stream_t stream);
+int paac_gather_minibatch(const int32_t* perm, int B, const uint8_t* states, uint8_t* states_out, const int32_t* actions,
+                          int32_t* actions_out, const float* y, float* y_out, const float* adv, float* adv_out,
+                          const float* p_old, float* p_old_out, const float* v_old, float* v_old_out, paac_stream_t stream);
+int paac_record_policy(paac_ctx* ctx, const float* params, const int32_t* actions, int batch, float* p_old_out, float* v_out,
+                       int value_rows, paac_stream_t stream);
+
 /* Gradient clipping + RMSPropOptimizer.apply_gradients (actor_learner.py:31-34,51-64,70):
  *   g <- grad * grad_scale           (grad_scale = 1/world_size after the sum all-reduce)
  *   mode IGNORE: f = 1

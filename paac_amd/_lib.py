@@ -16,6 +16,9 @@ ARCH_NIPS, ARCH_NATURE, ARCH_USER = 0, 1, 2
 CLIP_IGNORE, CLIP_GLOBAL, CLIP_LOCAL = 0, 1, 2
 RETURNS_NSTEP, RETURNS_GAE = 0, 1
 PPO_EPOCHS_MAX = 16            # PAAC_PPO_EPOCHS_MAX
+PPO_MINIBATCHES_MAX = 16       # PAAC_PPO_MINIBATCHES_MAX
+PPO_STEPS_MAX = 64             # PAAC_PPO_STEPS_MAX: optimizer steps (epochs x minibatches) of one cycle
+MINIBATCH_MAX_ROWS = 8192      # PAAC_MINIBATCH_MAX_ROWS
 
 
 class Layout(ctypes.Structure):
@@ -74,6 +77,10 @@ _SIGNATURES = {
     "paac_loss_backward_ppo_vclip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                              c_void_p]),
+    "paac_minibatch_perms": (c_int, [c_int, c_int, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "paac_gather_minibatch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "paac_record_policy": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "paac_adv_normalize": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "paac_returns_norm_tick": (c_int, [c_void_p, c_void_p, POINTER(Returns), c_void_p, c_void_p, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -76,6 +76,29 @@ class ActorLearner(object):
         if not (0.0 <= self.ppo_vclip and math.isfinite(self.ppo_vclip)):          # (NaN fails the comparison)
             raise ValueError("ppo_vclip %r: expected a finite value >= 0 (0 = off)" % (self.ppo_vclip,))
         self.vclip_on = self.ppo_epochs > 1 and self.ppo_vclip > 0.0
+        # --ppo_minibatches M (include/paac_hip.h has the contract): Namespaces / args.json files without the field, and M = 1,
+        # mean full-batch epochs through today's calls; M > 1 is read only when K > 1 and turns the cycle into K epochs of M
+        # shuffled minibatches (K * M optimizer steps, none of them full-batch)
+        M = getattr(args, "ppo_minibatches", 1)
+        if isinstance(M, (bool, np.bool_)) or not isinstance(M, (int, float, np.integer, np.floating)) or M != M or \
+                M != int(M) or not 1 <= int(M) <= _lib.PPO_MINIBATCHES_MAX:
+            raise ValueError("ppo_minibatches %r: expected an integer in [1, %d]" % (M, _lib.PPO_MINIBATCHES_MAX))
+        self.ppo_minibatches = int(M)
+        self.minibatch_on = self.ppo_epochs > 1 and self.ppo_minibatches > 1
+        if self.minibatch_on:
+            rows = args.emulator_counts * args.max_local_steps
+            if rows % self.ppo_minibatches:
+                raise ValueError("ppo_minibatches %d does not divide the rollout's %d rows (emulator_counts x max_local_steps)"
+                                 % (self.ppo_minibatches, rows))
+            if self.ppo_epochs * self.ppo_minibatches > _lib.PPO_STEPS_MAX:
+                raise ValueError("ppo_minibatches %d x ppo_epochs %d: more than %d optimizer steps per rollout (a captured cycle "
+                                 "grows by about ten launches per step)" % (self.ppo_minibatches, self.ppo_epochs,
+                                                                            _lib.PPO_STEPS_MAX))
+            if rows > _lib.MINIBATCH_MAX_ROWS:
+                raise ValueError("ppo_minibatches above 1 needs a rollout of at most %d rows (the shuffle is one workgroup's LDS "
+                                 "sort), got %d" % (_lib.MINIBATCH_MAX_ROWS, rows))
+        # optimizer steps of one cycle = rows of ppo_loss / ppo_stats
+        self.ppo_steps = self.ppo_epochs * (self.ppo_minibatches if self.minibatch_on else 1)
         self.clip_norm = args.clip_norm
         self.clip_norm_type = args.clip_norm_type
         if self.clip_norm_type == 'ignore':
@@ -126,8 +149,8 @@ class ActorLearner(object):
         self.p_old = self.ppo_loss = self.ppo_stats = None
         if self.ppo_epochs > 1:
             self.p_old = torch.zeros(self.emulator_counts * self.max_local_steps, dtype=torch.float32, device=dev)
-            self.ppo_loss = torch.zeros((self.ppo_epochs, 4), dtype=torch.float32, device=dev)
-            self.ppo_stats = torch.zeros((self.ppo_epochs, 3 if self.vclip_on else 2), dtype=torch.float32, device=dev)
+            self.ppo_loss = torch.zeros((self.ppo_steps, 4), dtype=torch.float32, device=dev)
+            self.ppo_stats = torch.zeros((self.ppo_steps, 3 if self.vclip_on else 2), dtype=torch.float32, device=dev)
         # --adv_norm: adv_n [T*N] is what the actor term reads, adv_stats = {mean, std} of the last rollout (fp64);
         # --ppo_vclip: v_old [T*N], epoch 1's values.  Per-cycle scratch like p_old
         self.adv_n = self.adv_stats = self.v_old = None
@@ -136,6 +159,21 @@ class ActorLearner(object):
             self.adv_stats = torch.zeros(2, dtype=torch.float64, device=dev)
         if self.vclip_on:
             self.v_old = torch.zeros(self.emulator_counts * self.max_local_steps, dtype=torch.float32, device=dev)
+        # --ppo_minibatches: the K shuffles of the cycle and the staging block one gather per epoch fills (allocated once: a
+        # replayed graph sees fixed addresses); row s = e * M + j of ppo_loss / ppo_stats = minibatch j + 1 of epoch e + 1.
+        # v_rec = the values the record pass reads out of the training-side heads: the rollout rows' (v_old is its head under
+        # --ppo_vclip) and, in the device loop, the bootstrap rows' behind them
+        self.mb = None
+        if self.minibatch_on:
+            rows = self.emulator_counts * self.max_local_steps
+            f32 = lambda: torch.zeros(rows, dtype=torch.float32, device=dev)
+            self.v_rec = torch.zeros(rows + self.emulator_counts, dtype=torch.float32, device=dev)
+            if self.vclip_on:
+                self.v_old = self.v_rec[:rows]
+            self.mb = dict(perms=torch.zeros((self.ppo_epochs, rows), dtype=torch.int32, device=dev),
+                           states=torch.zeros((rows, 84, 84, 4), dtype=torch.uint8, device=dev),
+                           actions=torch.zeros(rows, dtype=torch.int32, device=dev), y=f32(), adv=f32(), p_old=f32(),
+                           v_old=f32() if self.vclip_on else None)
         self.train_step = Placeholder('train_step')
 
         self.ctx = hip_ops.Context(self.network.arch_id, self.num_actions,
@@ -233,6 +271,37 @@ class ActorLearner(object):
             return
         self.ctx.loss_backward_ppo(params, states, actions, y, adv, self.p_old, self.ppo_clip, self.entropy_beta, self.grad,
                                    self.ppo_loss[k], self.ppo_stats[k], forward_done=True, phase=phase)
+
+    def minibatch_record(self, actions, value_rows):
+        """The record pass of an M > 1 cycle on the pending training forward (pre-update weights): p_old, and the values of
+        the training set's first value_rows rows into v_rec (v_old; rows past T*N are the appended bootstrap rows')."""
+        self.ctx.record_policy(self.network.params, actions, actions.numel(), self.p_old, self.v_rec, value_rows)
+
+    def minibatch_perms(self, seed, step_base_dev, step_offset=0):
+        """The cycle's K shuffles in one launch."""
+        hip_ops.minibatch_perms(self.mb["perms"].shape[1], seed, step_base_dev, step_offset, self.mb["perms"])
+
+    def minibatch_step_backward(self, s, states, actions, y, adv, phase):
+        """Optimizer step s = e * M + j of an M > 1 cycle up to its gradient: at j == 0 epoch e's gather of the frozen rollout
+        (states, actions, y, adv = what the actor term reads, p_old, v_old) into the staging block, then the training forward
+        (trunk) over minibatch j's rows of it and the clipped-surrogate backward with batch = T*N / M."""
+        mb, M = self.mb, self.ppo_minibatches
+        e, j = divmod(s, M)
+        if j == 0:
+            hip_ops.gather_minibatch(mb["perms"][e], states, mb["states"], actions, mb["actions"], y, mb["y"], adv, mb["adv"],
+                                     self.p_old, mb["p_old"], self.v_old if self.vclip_on else None, mb["v_old"])
+        b = mb["perms"].shape[1] // M
+        r = slice(j * b, (j + 1) * b)
+        params = self.network.params
+        self.ctx.train_forward_trunk(params, mb["states"][r])
+        if self.vclip_on:
+            self.ctx.loss_backward_ppo_vclip(params, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
+                                             mb["v_old"][r], self.ppo_clip, self.ppo_vclip, self.entropy_beta, self.grad,
+                                             self.ppo_loss[s], self.ppo_stats[s], forward_done=True, phase=phase)
+            return
+        self.ctx.loss_backward_ppo(params, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
+                                   self.ppo_clip, self.entropy_beta, self.grad, self.ppo_loss[s], self.ppo_stats[s],
+                                   forward_done=True, phase=phase)
 
     # -- one optimizer step from a reference-style feed dict (Session.run([train_step, ...], feed)) ----
     def _train_step_from_feed(self, feed_dict):

@@ -631,6 +631,29 @@ int paac_returns_norm_tick(paac_ctx* ctx, const float* params, const paac_return
   return 0;
 }
 
+int paac_record_policy(paac_ctx* ctx, const float* params, const int32_t* actions, int batch, float* p_old_out, float* v_out,
+                       int value_rows, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params, "paac_record_policy: null argument");
+  PAAC_REQUIRE(p_old_out || v_out, "paac_record_policy: nothing to record (p_old_out and v_out are both NULL)");
+  PAAC_REQUIRE(!p_old_out || actions, "paac_record_policy: p_old_out needs the actions");
+  if (!p_old_out) batch = 0;
+  if (!v_out) value_rows = 0;
+  const int rows = batch > value_rows ? batch : value_rows;
+  PAAC_REQUIRE(batch >= 0 && value_rows >= 0 && rows > 0 && rows <= ctx->max_batch,
+               "paac_record_policy: batch %d / value_rows %d outside (0, max_batch=%d]", batch, value_rows, ctx->max_batch);
+  // a trunk-only forward (or kept acting rows) is waiting for its heads: the launch a backward that cannot fuse them runs
+  if (ctx->heads_pending_rows > 0) {
+    PAAC_REQUIRE(rows <= ctx->heads_pending_rows, "paac_record_policy: the pending training forward covers %d rows, %d are asked "
+                 "for", ctx->heads_pending_rows, rows);
+    const int rc = launch_deferred_heads(ctx, params, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  const int rc = launch_record_policy(ctx, actions, batch, value_rows, p_old_out, v_out, (hipStream_t)stream);
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int paac_loss_backward_ppo_vclip(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                                  const float* y, const float* adv, const float* p_old, const float* v_old, float clip_eps,
                                  float vclip_eps, int batch, float entropy_beta, float* grad, float* loss_out,

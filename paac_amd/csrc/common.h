@@ -217,6 +217,8 @@ int launch_deferred_heads(paac_ctx* ctx, const float* params, hipStream_t s);
 // rollout rows stay pending for the backward's first launch); the returns + normalisation launch (csrc/misc.hip)
 int launch_bootstrap_heads(paac_ctx* ctx, const float* params, int batch, int N, hipStream_t s);
 int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv_n, double* stats, hipStream_t s);
+// --ppo_minibatches' record pass: p_old / values out of the finished training-side heads (csrc/misc.hip)
+int launch_record_policy(paac_ctx* ctx, const int32_t* actions, int batch, int vrows, float* p_old, float* v_out, hipStream_t s);
 int launch_forward(paac_ctx* ctx, int ws, const float* params, const uint8_t* states, int batch, float* logits,
                    float* probs, float* values, hipStream_t s);
 struct SynthStepArgs;

@@ -262,6 +262,112 @@ __global__ void sample_philox_kernel(const float* __restrict__ probs, int N, int
 }
 
 // =============================================================================================
+// --ppo_minibatches (include/paac_hip.h has the contract): the shuffles of one cycle, the gather that makes a shuffled
+// epoch's rows contiguous, and the record pass's pick of p_old / v_old out of the finished training-side heads.
+
+// Workgroup e = epoch e: B Philox keys, then a bitonic sort of 64-bit composites (key << 32 | row) in LDS.  The row index in
+// the low half makes every composite distinct, so ascending composites ARE ascending (key, row) -- the stable argsort --
+// whatever network sorts them.  Rows [B, P) of the power-of-two network hold (0xFFFFFFFF << 32 | row): a real key can be
+// 0xFFFFFFFF too, and then the padding still compares larger on its row index (>= B).
+constexpr int kPermMaxRows = 8192;        // 64 KB of LDS
+constexpr int kPermThreads = 1024;
+constexpr uint32_t kPermDomain = 0x504D0000u;      // counter word 3 of epoch e = kPermDomain + e (the sampler's is 0)
+
+__global__ __launch_bounds__(kPermThreads) void minibatch_perms_kernel(int B, int P, uint64_t seed,
+                                                                       const uint64_t* __restrict__ step_base,
+                                                                       uint64_t step_off, int32_t* __restrict__ perms) {
+  __shared__ uint64_t s[kPermMaxRows];
+  const int e = blockIdx.x;
+  const uint64_t step = (step_base ? *step_base : 0ull) + step_off;
+  for (int i = threadIdx.x; i < P; i += kPermThreads) {
+    uint32_t key = 0xFFFFFFFFu;
+    if (i < B) {
+      uint32_t c[4] = {(uint32_t)i, (uint32_t)step, (uint32_t)(step >> 32), kPermDomain + (uint32_t)e};
+      philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+      key = c[0];
+    }
+    s[i] = ((uint64_t)key << 32) | (uint32_t)i;
+  }
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += kPermThreads) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));      // pair (lo, lo + j): bit j of lo is clear
+        const int hi = lo | j;
+        const uint64_t a = s[lo], b = s[hi];
+        if ((a > b) == ((lo & k) == 0)) {
+          s[lo] = b;
+          s[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < B; i += kPermThreads) perms[(long)e * B + i] = (int32_t)(uint32_t)s[i];
+}
+
+// states_out[r] = states[perm[r]] in 16-byte vectors (a row is 1764 of them; kGatherParts workgroups per row), and the same
+// index map on the small arrays (any pair of them absent) in the launch's last workgroups, one row per lane.
+constexpr int kRowVecs = PAAC_OBS_BYTES / 16;      // 1764
+constexpr int kGatherParts = 4;                    // 441 vectors each
+static_assert(kRowVecs % kGatherParts == 0 && kRowVecs * 16 == PAAC_OBS_BYTES, "row split");
+
+struct GatherSmall {
+  const int32_t* actions; int32_t* actions_out;
+  const float* y; float* y_out;
+  const float* adv; float* adv_out;
+  const float* p_old; float* p_old_out;
+  const float* v_old; float* v_old_out;
+};
+
+__global__ __launch_bounds__(256) void gather_minibatch_kernel(const int32_t* __restrict__ perm, int B,
+                                                               const uint4* __restrict__ states, uint4* __restrict__ states_out,
+                                                               const GatherSmall g) {
+  const int state_groups = states ? B * kGatherParts : 0;
+  if ((int)blockIdx.x < state_groups) {
+    const int r = blockIdx.x / kGatherParts, part = blockIdx.x % kGatherParts;
+    const int src = perm[r];
+    if ((unsigned)src >= (unsigned)B) return;          // not a row index: nothing is read through it
+    constexpr int V = kRowVecs / kGatherParts;
+    const uint4* in = states + (long)src * kRowVecs + part * V;
+    uint4* out = states_out + (long)r * kRowVecs + part * V;
+    for (int v = threadIdx.x; v < V; v += 256) out[v] = in[v];
+    return;
+  }
+  const int r = ((int)blockIdx.x - state_groups) * 256 + threadIdx.x;
+  if (r >= B) return;
+  const int src = perm[r];
+  if ((unsigned)src >= (unsigned)B) return;
+  if (g.actions) g.actions_out[r] = g.actions[src];
+  if (g.y) g.y_out[r] = g.y[src];
+  if (g.adv) g.adv_out[r] = g.adv[src];
+  if (g.p_old) g.p_old_out[r] = g.p_old[src];
+  if (g.v_old) g.v_old_out[r] = g.v_old[src];
+}
+
+// p_old[i] = probs[i, a_i] of the first `batch` rows, v_out[i] = values[i] of the first `vrows` rows of the training set.
+__global__ __launch_bounds__(256) void record_policy_kernel(const float* __restrict__ probs, const float* __restrict__ values,
+                                                            const int32_t* __restrict__ actions, int A, int batch, int vrows,
+                                                            float* __restrict__ p_old, float* __restrict__ v_out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (p_old && i < batch) {
+    const int a = actions[i];
+    if ((unsigned)a < (unsigned)A) p_old[i] = probs[(long)i * A + a];
+  }
+  if (v_out && i < vrows) v_out[i] = values[i];
+}
+
+int launch_record_policy(paac_ctx* ctx, const int32_t* actions, int batch, int vrows, float* p_old, float* v_out,
+                         hipStream_t s) {
+  const Workspace& W = ctx->ws[1];
+  const int rows = batch > vrows ? batch : vrows;
+  ProfScope ps(ctx, F_MISC, rows, s);
+  launch_k(record_policy_kernel, dim3((rows + 255) / 256), dim3(256), s, PROF_WHOLE, (const float*)W.probs,
+           (const float*)W.values, actions, ctx->cfg.num_actions, batch, vrows, p_old, v_out);
+  return 0;
+}
+
+// =============================================================================================
 // numpy-parity sampler: legacy MT19937 multinomial(1, p - epsneg) per env, ONE serial stream
 // (paac.py:34-45; restated in oracle/sampler.py:sample_mt_restated).
 // (mt_temper / mt_mix: csrc/mt_ahead.h)
@@ -2186,6 +2292,58 @@ int paac_sample_philox(const float* probs, int N, int A, uint64_t seed, const ui
   ProfScope ps(g_prof_ctx, F_SAMPLE_PHILOX, N, (hipStream_t)stream);
   launch_k(sample_philox_kernel, dim3((N + 63) / 64), dim3(64), (hipStream_t)stream, PROF_WHOLE, probs, N, A, seed,
            step_base_dev, step_offset, env_offset, actions);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_minibatch_perms(int B, int epochs, uint64_t seed, const uint64_t* step_base_dev, uint64_t step_offset,
+                         int32_t* perms_out, paac_stream_t stream) {
+  PAAC_REQUIRE(perms_out, "paac_minibatch_perms: null perms_out");
+  PAAC_REQUIRE(B > 0 && B <= PAAC_MINIBATCH_MAX_ROWS, "paac_minibatch_perms: B=%d outside [1, %d] (one workgroup's LDS sort)", B,
+               PAAC_MINIBATCH_MAX_ROWS);
+  PAAC_REQUIRE(epochs > 0 && epochs <= PAAC_PPO_EPOCHS_MAX, "paac_minibatch_perms: epochs=%d outside [1, %d]", epochs,
+               PAAC_PPO_EPOCHS_MAX);
+  static_assert(PAAC_MINIBATCH_MAX_ROWS == kPermMaxRows, "the sort's LDS array");
+  int P = 1;
+  while (P < B) P <<= 1;
+  ProfScope ps(g_prof_ctx, F_MISC, B, (hipStream_t)stream);
+  launch_k(minibatch_perms_kernel, dim3(epochs), dim3(kPermThreads), (hipStream_t)stream, PROF_WHOLE, B, P, seed, step_base_dev,
+           step_offset, perms_out);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_gather_minibatch(const int32_t* perm, int B, const uint8_t* states, uint8_t* states_out, const int32_t* actions,
+                          int32_t* actions_out, const float* y, float* y_out, const float* adv, float* adv_out,
+                          const float* p_old, float* p_old_out, const float* v_old, float* v_old_out, paac_stream_t stream) {
+  PAAC_REQUIRE(perm, "paac_gather_minibatch: null perm");
+  PAAC_REQUIRE(B > 0 && B <= PAAC_MINIBATCH_MAX_ROWS, "paac_gather_minibatch: B=%d outside [1, %d]", B, PAAC_MINIBATCH_MAX_ROWS);
+  // every array comes with its output; an output that overlaps its input would be read after it was written
+  auto pair_ok = [&](const void* in, const void* out, size_t bytes, const char* name) {
+    if ((in == nullptr) != (out == nullptr)) {
+      set_error("paac_gather_minibatch: %s and %s_out must both be given or both be NULL", name, name);
+      return false;
+    }
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    if (in && a < b + bytes && b < a + bytes) {
+      set_error("paac_gather_minibatch: %s_out overlaps %s (the gather cannot run in place)", name, name);
+      return false;
+    }
+    return true;
+  };
+  if (!pair_ok(states, states_out, (size_t)B * PAAC_OBS_BYTES, "states") || !pair_ok(actions, actions_out, (size_t)B * 4, "actions") ||
+      !pair_ok(y, y_out, (size_t)B * 4, "y") || !pair_ok(adv, adv_out, (size_t)B * 4, "adv") ||
+      !pair_ok(p_old, p_old_out, (size_t)B * 4, "p_old") || !pair_ok(v_old, v_old_out, (size_t)B * 4, "v_old"))
+    return -1;
+  PAAC_REQUIRE(((uintptr_t)states | (uintptr_t)states_out) % 16 == 0, "paac_gather_minibatch: states / states_out must be "
+               "16-byte aligned");
+  const bool small = actions || y || adv || p_old || v_old;
+  PAAC_REQUIRE(states || small, "paac_gather_minibatch: nothing to gather");
+  const GatherSmall g{actions, actions_out, y, y_out, adv, adv_out, p_old, p_old_out, v_old, v_old_out};
+  const unsigned grid = (states ? (unsigned)B * kGatherParts : 0u) + (small ? (unsigned)(B + 255) / 256 : 0u);
+  ProfScope ps(g_prof_ctx, F_MISC, B, (hipStream_t)stream);
+  launch_k(gather_minibatch_kernel, dim3(grid), dim3(256), (hipStream_t)stream, PROF_WHOLE, perm, B,
+           reinterpret_cast<const uint4*>(states), reinterpret_cast<uint4*>(states_out), g);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -278,6 +278,20 @@ class Context(object):
         _lib.check(self.lib.paac_debug_activation(self.handle, 25, int(batch), _ptr(out, torch.float32, int(batch), "out"),
                                                   int(batch), _stream()), "paac_debug_activation")
 
+    def record_policy(self, params, actions, batch, p_old_out=None, v_out=None, value_rows=None):
+        """--ppo_minibatches' record pass (include/paac_hip.h: paac_record_policy): finishes the heads a trunk-only training
+        forward (or kept acting rows) left pending, then p_old_out[:batch] = pi(a_i | s_i) and v_out[:value_rows] = the values
+        of the training set's first value_rows rows (default batch; more reaches the appended bootstrap rows).  No gradient."""
+        batch = int(batch)
+        value_rows = batch if value_rows is None else int(value_rows)
+        if not 0 < max(batch, value_rows) <= self.max_batch or batch < 0 or value_rows < 0:
+            raise ValueError("record_policy: batch %d / value_rows %d outside (0, %d]" % (batch, value_rows, self.max_batch))
+        _lib.check(self.lib.paac_record_policy(
+            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
+            _ptr(actions, torch.int32, batch, "actions", p_old_out is None), batch,
+            _ptr(p_old_out, torch.float32, batch, "p_old_out", True), _ptr(v_out, torch.float32, value_rows, "v_out", True),
+            value_rows, _stream()), "paac_record_policy")
+
     def returns_norm_tick(self, params, v_boot, rewards, masks, values, gamma, y_out, adv_out, adv_n_out, stats_out=None,
                           global_step_dev=None, increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None,
                           tick_dev=None, tick_inc=0, gae_lambda=None):
@@ -603,6 +617,46 @@ def sample_philox(probs, seed, step_base_dev, step_offset, env_offset, actions):
                                       _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
                                       int(env_offset), _ptr(actions, torch.int32, N, "actions"), _stream()),
                "paac_sample_philox")
+
+
+def minibatch_perms(B, seed, step_base_dev, step_offset, perms_out):
+    """perms_out int32 [K, B]: row e = epoch e's shuffle of 0..B-1 (include/paac_hip.h: paac_minibatch_perms), the stable argsort
+    of philox4x32-10 keys on counter (row, step lo, step hi, 0x504D0000 + e), step = *step_base_dev + step_offset."""
+    B = int(B)
+    if perms_out.dim() != 2 or perms_out.shape[1] != B:
+        raise ValueError("perms_out must be int32 [epochs, %d], got %s" % (B, tuple(perms_out.shape)))
+    K = int(perms_out.shape[0])
+    if not 1 <= B <= _lib.MINIBATCH_MAX_ROWS or not 1 <= K <= _lib.PPO_EPOCHS_MAX:
+        raise ValueError("minibatch_perms: B=%d (1..%d), epochs=%d (1..%d)" % (B, _lib.MINIBATCH_MAX_ROWS, K, _lib.PPO_EPOCHS_MAX))
+    _lib.check(_lib.load().paac_minibatch_perms(B, K, int(seed), _ptr(step_base_dev, torch.int64, 1, "step_base", True),
+                                                int(step_offset), _ptr(perms_out, torch.int32, K * B, "perms_out"), _stream()),
+               "paac_minibatch_perms")
+
+
+def gather_minibatch(perm, states=None, states_out=None, actions=None, actions_out=None, y=None, y_out=None, adv=None,
+                     adv_out=None, p_old=None, p_old_out=None, v_old=None, v_old_out=None):
+    """out[r] = in[perm[r]] for the states ([B,84,84,4] u8, 16-byte vectors) and the small [B] arrays in one launch
+    (include/paac_hip.h: paac_gather_minibatch).  Every array comes with its output or not at all; an output that overlaps its
+    input is refused."""
+    B = int(perm.numel())
+    if not 1 <= B <= _lib.MINIBATCH_MAX_ROWS:
+        raise ValueError("gather_minibatch: %d rows outside [1, %d]" % (B, _lib.MINIBATCH_MAX_ROWS))
+    pairs = (("states", states, states_out, torch.uint8, B * 28224), ("actions", actions, actions_out, torch.int32, B),
+             ("y", y, y_out, torch.float32, B), ("adv", adv, adv_out, torch.float32, B),
+             ("p_old", p_old, p_old_out, torch.float32, B), ("v_old", v_old, v_old_out, torch.float32, B))
+    ptrs = []
+    for name, src, dst, dtype, numel in pairs:
+        if (src is None) != (dst is None):
+            raise ValueError("gather_minibatch: %s and %s_out must both be given or both be None" % (name, name))
+        if src is not None:
+            a, b, nbytes = src.data_ptr(), dst.data_ptr(), numel * src.element_size()
+            if a < b + nbytes and b < a + nbytes:
+                raise ValueError("gather_minibatch: %s_out overlaps %s (the gather cannot run in place)" % (name, name))
+        ptrs += [_ptr(src, dtype, numel, name, True), _ptr(dst, dtype, numel, name + "_out", True)]
+    if states is not None and tuple(states.shape[1:]) != OBS_SHAPE:
+        raise ValueError("states must be [B,84,84,4] uint8, got %s" % (tuple(states.shape),))
+    _lib.check(_lib.load().paac_gather_minibatch(_ptr(perm, torch.int32, B, "perm"), B, *(ptrs + [_stream()])),
+               "paac_gather_minibatch")
 
 
 def debug_clock(out2_dev):

@@ -93,10 +93,11 @@ class DeviceRollout(object):
         self.exchange_mode = "none" if not self.phased else ("split" if not self.single_exchange else "single")
         self.exchange_fallback = None
         # --ppo_epochs K: epochs 2..K ride behind the cycle's update, each with its own exchange (one all-reduce per epoch)
-        self.K = L.ppo_epochs
+        # --ppo_minibatches M: K * M optimizer steps per cycle instead, the first of them behind the record pass
+        self.K = L.ppo_steps
         if self.K > 1 and self.phased and not self.single_exchange:
-            raise ValueError("--ppo_epochs above 1 is not built for PAAC_ALLREDUCE=split (the two-piece exchange): use graph "
-                             "or single")
+            raise ValueError("--ppo_epochs above 1%s is not built for PAAC_ALLREDUCE=split (the two-piece exchange): use graph "
+                             "or single" % (" with --ppo_minibatches above 1" if L.minibatch_on else ""))
         self.graph_epoch = [[], []]                    # eager exchange: [parity][k - 1] = update + epoch k + 1's backward
         # --adv_norm: the actor term of every epoch reads the normalised advantages; self.adv stays the recorded raw array
         self.actor_adv = L.adv_n if L.adv_norm else self.adv
@@ -187,6 +188,9 @@ class DeviceRollout(object):
         else:
             L.ctx.train_forward_trunk(params, self.states[parity * T:(parity + 1) * T + 1].view((T + 1) * N, 84, 84, 4))
         phase = ((0 if self.single_exchange else 1) if self.phased else 3)
+        if L.minibatch_on:
+            self._record_and_first_minibatch(parity, phase)
+            return
         if L.adv_norm:
             # --adv_norm: a row's workgroup cannot know the rollout's mean, so the returns leave the backward's first launch:
             # heads of the bootstrap rows, then returns + statistics + normalisation + the cycle's bookkeeping in one launch,
@@ -219,8 +223,34 @@ class DeviceRollout(object):
         if L.vclip_on:         # --ppo_vclip: v_old = the values epoch 1's heads just computed (one captured copy)
             L.ctx.train_values_into(L.v_old, T * N)
 
+    def _record_and_first_minibatch(self, parity, phase):
+        """--ppo_minibatches: what follows the rollout and the bootstrap forward in an M > 1 cycle up to the first gradient --
+        the record pass on the pre-update weights (p_old, v_old and the bootstrap values out of the finished heads; y / adv /
+        adv_n and the cycle's bookkeeping from the standalone returns launches), the cycle's K shuffles on the frame counter
+        the returns launch has just advanced, then optimizer step 0 (epoch 1's gather, minibatch 1)."""
+        L, T, N = self.L, self.T, self.N
+        B = T * N
+        L.minibatch_record(self.actions.view(-1), B + N)
+        v_boot = L.v_rec[B:]
+        tick = dict(global_step_dev=self.global_step_dev, increment=self.total_envs * T, initial_lr=L.initial_lr,
+                    lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev, tick_dev=self.tick, tick_inc=T)
+        if L.adv_norm:
+            hip_ops.returns_norm_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
+                                      L.adv_stats, gae_lambda=L.gae_lambda, **tick)
+        elif hip_ops.uses_gae(L.gae_lambda):
+            hip_ops.gae_returns_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, L.gae_lambda, self.y, self.adv,
+                                     **tick)
+        else:
+            hip_ops.nstep_returns_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, **tick)
+        L.minibatch_perms(self.sampler_seed, self.tick)
+        L.minibatch_step_backward(0, self.rollout_states(parity), self.actions.view(-1), self.y, self.actor_adv, phase)
+
     def _epoch_backward(self, parity, k):
-        """Epoch k + 1 of the cycle up to its gradient (the update of epoch k has run)."""
+        """Epoch k + 1 of the cycle up to its gradient (the update of epoch k has run); --ppo_minibatches: optimizer step k."""
+        if self.L.minibatch_on:
+            self.L.minibatch_step_backward(k, self.rollout_states(parity), self.actions.view(-1), self.y, self.actor_adv,
+                                           phase=0 if self.phased else 3)
+            return
         self.L.ppo_epoch_backward(k, self.rollout_states(parity), self.actions.view(-1), self.y, self.actor_adv,
                                   phase=0 if self.phased else 3)
 
@@ -325,6 +355,8 @@ class DeviceRollout(object):
         ts = [self.states, self.actions, self.values, self.rewards, self.masks, self.probs, self.y, self.adv, self.ep_reward,
               self.ep_len, self.finished, self.tick, self.global_step_dev] + [t for _, t in L.update_state] + \
              [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev] + [t for t in (L.p_old, L.ppo_loss, L.ppo_stats, L.adv_n, L.adv_stats, L.v_old) if t is not None]
+        if L.minibatch_on:      # (the staging block of states is rewritten by every epoch's gather before anything reads it)
+            ts += [L.v_rec] + [t for k, t in L.mb.items() if t is not None and k != "states"]
         for name in ("raw", "walk_scratch", "mt_state"):
             t = getattr(self, name, None)
             if t is not None:
@@ -530,7 +562,8 @@ class PAACLearner(ActorLearner):
     def _progress_record(self, steps_per_s, steps_per_s_avg, last_ten):
         if self.metrics is None:
             return
-        loss = self.loss_dev.cpu().numpy()
+        # (an M > 1 --ppo_minibatches cycle has no full-batch update: its summary line carries the last optimizer step's loss)
+        loss = (self.ppo_loss[-1] if self.minibatch_on else self.loss_dev).cpu().numpy()
         stats = self.ctx.grad_stats(self.clip_norm, self.clip_mode)      # actor_learner.py:85-87 summaries
         self.metrics.write("gradients", global_step=int(self.global_step), **stats)
         self.metrics.write("progress", global_step=int(self.global_step), steps_per_s=float(steps_per_s),
@@ -539,9 +572,13 @@ class PAACLearner(ActorLearner):
                            actor_loss=float(loss[1]), critic_loss=float(loss[2]), entropy=float(loss[3]))
         if self.ppo_epochs > 1:          # one record per epoch of the last cycle (epoch 1: the update above, ratio == 1)
             losses, stats = self.ppo_loss.cpu().numpy(), self.ppo_stats.cpu().numpy()
-            losses[0] = loss
-            for k in range(self.ppo_epochs):
-                self.metrics.write("ppo_epoch", global_step=int(self.global_step), epoch=k + 1, loss=float(losses[k, 0]),
+            if not self.minibatch_on:
+                losses[0] = loss
+            for k in range(self.ppo_steps):
+                # --ppo_minibatches above 1: one record per optimizer step, `minibatch` = 1..M inside its epoch
+                where = dict(minibatch=k % self.ppo_minibatches + 1) if self.minibatch_on else {}
+                epoch = k // self.ppo_minibatches + 1 if self.minibatch_on else k + 1
+                self.metrics.write("ppo_epoch", global_step=int(self.global_step), epoch=epoch, **where, loss=float(losses[k, 0]),
                                    actor_loss=float(losses[k, 1]), critic_loss=float(losses[k, 2]),
                                    entropy=float(losses[k, 3]), clip_fraction=float(stats[k, 0]),
                                    approx_kl=float(stats[k, 1]),
@@ -712,6 +749,7 @@ class PAACLearner(ActorLearner):
         d_adv = torch.zeros((T * N,), dtype=torch.float32, device=dev)
         mt_state = hip_ops.mt_state_from_numpy(np.random.get_state(), dev)
         mt_scratch = hip_ops.sample_mt_scratch(N, A, dev)
+        mb_step = torch.zeros((1,), dtype=torch.int64, device=dev)      # --ppo_minibatches: the shuffles' step counter
         rewards = np.zeros((T, N), dtype=np.float32)
         masks = np.zeros((T, N), dtype=np.float32)
         # the sampled action indices come back through a page-locked buffer: an asynchronous copy + an event instead of a
@@ -821,20 +859,33 @@ class PAACLearner(ActorLearner):
                 d_actor_adv = self.adv_n
             lr = self.get_lr()
             self.lr_dev.fill_(float(np.float32(lr)))
-            if self.ppo_epochs > 1:
-                self.ctx.loss_backward_record(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
-                                              self.p_old, self.entropy_beta, self.grad, self.loss_dev)
+            if self.minibatch_on:
+                # --ppo_minibatches: record pass on the pre-update weights, the cycle's shuffles (on the frames each environment
+                # has taken so far, the device loop's counter), then K x M optimizer steps on the staged minibatches
+                rows, acts = d_states.view(T * N, 84, 84, 4), d_actions.view(-1)
+                self.ctx.train_forward_trunk(params, rows)
+                self.minibatch_record(acts, T * N)
+                mb_step.fill_((counter + 1) * T)
+                self.minibatch_perms(getattr(self.args, "sampler_seed", 42), mb_step)
+                for k in range(self.ppo_steps):
+                    self.minibatch_step_backward(k, rows, acts, d_y, d_actor_adv, phase=0)
+                    self._allreduce_grad()
+                    self.apply_gradients()
             else:
-                self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
-                                       self.entropy_beta, self.grad, self.loss_dev)
-            if self.vclip_on:         # v_old = the values epoch 1's heads just computed
-                self.ctx.train_values_into(self.v_old, T * N)
-            self._allreduce_grad()
-            self.apply_gradients()
-            for k in range(1, self.ppo_epochs):      # epochs 2..K on the frozen y / adv / p_old (/ v_old), the same lr
-                self.ppo_epoch_backward(k, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv, phase=0)
+                if self.ppo_epochs > 1:
+                    self.ctx.loss_backward_record(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
+                                                  self.p_old, self.entropy_beta, self.grad, self.loss_dev)
+                else:
+                    self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
+                                           self.entropy_beta, self.grad, self.loss_dev)
+                if self.vclip_on:         # v_old = the values epoch 1's heads just computed
+                    self.ctx.train_values_into(self.v_old, T * N)
                 self._allreduce_grad()
                 self.apply_gradients()
+                for k in range(1, self.ppo_epochs):      # epochs 2..K on the frozen y / adv / p_old (/ v_old), the same lr
+                    self.ppo_epoch_backward(k, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv, phase=0)
+                    self._allreduce_grad()
+                    self.apply_gradients()
             if getattr(self.args, "record_feeds", False):
                 self.last_feed = dict(states=d_states.view(T * N, 84, 84, 4).cpu().numpy(), y=d_y.cpu().numpy(),
                                       adv=d_adv.cpu().numpy(), actions=d_actions.view(-1).cpu().numpy(), lr=lr,

@@ -88,6 +88,10 @@ BUILD_FLAGS = (
     (("--ppo_vclip",), "ppo_vclip", 0.0, float,
      "PPO value clipping range EPSV: 0 = off; above 0, epochs 2..K use the critic term max((y - v)^2, (y - vc)^2) with vc = v "
      "clipped to within EPSV of the value epoch 1 computed; read only when --ppo_epochs is above 1"),
+    (("--ppo_minibatches",), "ppo_minibatches", 1, int,
+     "minibatches per PPO epoch: 1 = full-batch epochs; M in [2, 16] (a divisor of emulator_counts x max_local_steps, with "
+     "ppo_epochs x M <= 64) = every epoch is M optimizer steps on a fresh shuffle of the rollout, drawn on the GPU from "
+     "--sampler_seed; read only when --ppo_epochs is above 1"),
     (("--adv_norm",), "adv_norm", False, bool_arg,
      "normalise each rollout's advantages by their own mean and standard deviation before the actor term reads them (per "
      "rank under data parallelism); the critic target and the recorded advantages are unchanged"),

@@ -475,6 +475,24 @@ int paac_synth_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     uint8_t* stack_out2, float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len,
                     void* finished, uint8_t* raw_scratch, paac_stream_t stream);
 
+/* Device-resident catch environments: a learnable game (a ball falls, a paddle moves, +1 for a catch, -1 for a miss) on a
+ * 14 x 14 board of 6 x 6 pixel cells, rendered into the same [N,84,84,4] u8 observations; spec in paac_amd/catch.py, a
+ * BaseEnvironment plugin producing the same numbers on the host.  3 actions: 0 stay, 1 left, 2 right.
+ *   state: i32 [N,8] per environment {bx, by, dx, px, k, 0, 0, 0}; the episode-start hashes are keyed by (seed,
+ *          env_offset + e, k).
+ * paac_catch_reset: episode 0's start states into state_out, their observations ([0, 0, 0, plane]) into stack_out.
+ * paac_catch_step: one step of N environments on actions [N] -- state_in -> state_out, stack_in -> stack_out (history shifted,
+ *   the new state's plane pushed; after a terminal step the next episode's start state and an empty history), the records of
+ *   paac_synth_step (rewards_out / masks_out [N], ep_reward / ep_len [N] in place, the finished ring, nullable).  One launch.
+ *   The step does not run in place: state_in / stack_in must not be state_out / stack_out (refused).  state_out2 / stack_out2
+ *   (nullable): second copies of the outputs, like paac_synth_step's stack_out2 (a ring's wrap-around slot). */
+int paac_catch_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                     paac_stream_t stream);
+int paac_catch_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                    int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                    float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
+                    paac_stream_t stream);
+
 /* paac_sample_mt + paac_synth_step (path A) in ONE launch: workgroup 0 samples (numpy-parity MT19937 stream) and does
  * the per-env bookkeeping while the other workgroups shift the observation stacks (stack_out2, nullable: a second copy
  * of the new stacks, like paac_synth_step's).  Limit: N*(A-1) <= 2304 (covers 256 environments x 4 actions and

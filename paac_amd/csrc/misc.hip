@@ -2,6 +2,7 @@
 // frame preprocessing / stacking, device-resident synthetic environments, clip + RMSProp.
 #include "common.h"
 #include "synth_dev.h"
+#include "catch_dev.h"
 #include "fc_heads.h"
 #include "heads.h"
 #include "tower.h"
@@ -1343,6 +1344,50 @@ __global__ __launch_bounds__(256) void synth_step_a_kernel(uint64_t seed, uint32
   synth_shift_band(seed, env_offset, id, thresh, e * PRE_BANDS + band, stack_in, stack_out, stack_out2, force_reset != 0);
 }
 
+// Catch environments (spec: paac_amd/catch.py); device helpers in catch_dev.h.  The shape of synth_step_a_kernel: grid (N, 7),
+// 256 threads, 252 of them own one quad of four pixels -- one 16-byte load of the old stack and one 16-byte store of the new
+// one per thread, no LDS.  The new state is a pure function of (state_in[e], actions[e]): every band workgroup of an
+// environment recomputes it in registers, one thread of band 0 writes it out and does the bookkeeping.  Nothing in the launch
+// writes what the launch reads: state_in / state_out and stack_in / stack_out are different buffers.
+// state_in == nullptr: reset -- episode 0's start state, an empty history; actions / stack_in / the records are not touched.
+__global__ __launch_bounds__(256) void catch_step_kernel(uint64_t seed, uint32_t env_offset, int N,
+                                                         const int32_t* __restrict__ actions,
+                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
+                                                         int32_t* __restrict__ state_out2,
+                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                         uint32_t* __restrict__ stack_out2, float* rewards_out,
+                                                         float* masks_out, float* ep_reward, int32_t* ep_len,
+                                                         FinishedRing* fin) {
+  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
+  const int e = blockIdx.x;
+  const int band = blockIdx.y;
+  const int i = threadIdx.x;
+  const bool owner = i < QUADS_PER_BAND;
+  const int q = band * QUADS_PER_BAND + i;
+  const long quad = (long)e * (OBS_PIX / 4) + q;
+  uint4 old = make_uint4(0u, 0u, 0u, 0u);
+  CatchState s;
+  float r = 0.f;
+  bool term = false;
+  if (state_in) {
+    // the old stack is requested before the state arrives (whether or not the step ends the episode): one round trip, not two
+    if (owner) old = reinterpret_cast<const uint4*>(stack_in)[quad];
+    s = catch_advance(seed, env_offset + (uint32_t)e, catch_load(state_in, e), actions[e], &r, &term);
+    if (term) old = make_uint4(0u, 0u, 0u, 0u);
+  } else {
+    s = catch_start(seed, env_offset + (uint32_t)e, 0);
+  }
+  if (band == 0 && i == 0) {
+    catch_store(state_out, e, s);
+    if (state_out2) catch_store(state_out2, e, s);
+    if (state_in) env_bookkeep(r, term, e, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
+  }
+  if (!owner) return;
+  const uint4 outv = catch_shift_quad(s, q, old);
+  reinterpret_cast<uint4*>(stack_out)[quad] = outv;
+  if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
+}
+
 // Path A with the numpy-parity sampler folded in: workgroup 0 runs the (inherently serial) MT19937 sampler and then
 // the per-env bookkeeping, the other N*7 workgroups shift the observation stacks meanwhile -- the new frame and the
 // terminal flag of the synthetic environments do not depend on the action, only reward bookkeeping does.  One launch
@@ -2441,6 +2486,34 @@ int paac_synth_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
              (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, (const uint8_t*)nullptr,
              (const uint8_t*)nullptr, (const float*)masks_out);
   }
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_catch_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                     paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && state_out && stack_out, "paac_catch_reset: bad arguments");
+  hipLaunchKernelGGL(catch_step_kernel, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
+                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                     (int32_t*)nullptr, (FinishedRing*)nullptr);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_catch_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                    int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                    float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
+                    paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
+               ep_len, "paac_catch_step: bad arguments");
+  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
+               "paac_catch_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+  launch_k(catch_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
+           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
+           ep_reward, ep_len, (FinishedRing*)finished);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -31,11 +31,9 @@ struct FinishedRing {
 // a caller that waits for the action computes them first (synth_reward_slot / synth_terminal).
 __device__ __forceinline__ uint32_t synth_reward_slot(uint32_t key) { return lowbias32(key ^ 0xA511E9B3u) % 5u; }
 __device__ __forceinline__ bool synth_terminal(uint32_t key, uint32_t thresh) { return lowbias32(key ^ 0x3C6EF372u) < thresh; }
-__device__ __forceinline__ bool synth_bookkeep_hashed(uint32_t hr5, bool term, int e, int act, float ep_reward0,
-                                                      int32_t ep_len0, float* rewards_out, float* masks_out,
-                                                      float* ep_reward, int32_t* ep_len, FinishedRing* fin) {
-  const float table[5] = {-2.f, 0.f, 0.f, 1.f, 3.f};
-  const float r = table[(hr5 + (uint32_t)act) % 5u];
+// env_bookkeep: the same records for a step whose unclipped reward r and terminal flag are already known (csrc/catch_dev.h).
+__device__ __forceinline__ bool env_bookkeep(float r, bool term, int e, float ep_reward0, int32_t ep_len0, float* rewards_out,
+                                             float* masks_out, float* ep_reward, int32_t* ep_len, FinishedRing* fin) {
   rewards_out[e] = fminf(fmaxf(r, -1.f), 1.f);   // actor_learner.py:95-101
   masks_out[e] = term ? 0.f : 1.f;               // paac.py:119
   const float tot = ep_reward0 + r;
@@ -53,6 +51,13 @@ __device__ __forceinline__ bool synth_bookkeep_hashed(uint32_t hr5, bool term, i
     ep_len[e] = len;
   }
   return term;
+}
+__device__ __forceinline__ bool synth_bookkeep_hashed(uint32_t hr5, bool term, int e, int act, float ep_reward0,
+                                                      int32_t ep_len0, float* rewards_out, float* masks_out,
+                                                      float* ep_reward, int32_t* ep_len, FinishedRing* fin) {
+  const float table[5] = {-2.f, 0.f, 0.f, 1.f, 3.f};
+  return env_bookkeep(table[(hr5 + (uint32_t)act) % 5u], term, e, ep_reward0, ep_len0, rewards_out, masks_out, ep_reward, ep_len,
+                      fin);
 }
 __device__ __forceinline__ bool synth_bookkeep_with(uint32_t key, int e, int act, uint32_t thresh, float ep_reward0,
                                                     int32_t ep_len0, float* rewards_out, float* masks_out,

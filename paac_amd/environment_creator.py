@@ -4,9 +4,11 @@ The reference probes an ALE ROM for `num_actions` and builds AtariEmulator insta
 emulator that is out of this build's scope, so the factory creates the synthetic
 environments of paac_amd/synthetic.py; `num_actions` per game is ALE's minimal action-set size (pinned for
 breakout/qbert/seaquest by the reference's pretrained/*/checkpoints/*.index actor_output_biases shapes).
+`--emulator catch` creates the catch game of paac_amd/catch.py instead (3 actions, whatever `-g` says).
 A user environment plugs in exactly as in the reference: subclass BaseEnvironment and return it from
 create_environment(i).
 """
+from . import catch
 from .synthetic import SyntheticEnvironment, terminal_threshold
 
 # ALE minimal action set sizes.
@@ -31,6 +33,15 @@ class EnvironmentCreator(object):
             self._device_twin = False
             return
         self._device_twin = True
+        self._catch = getattr(args, "emulator", "synthetic") == "catch"
+        if self._catch:
+            # paac_amd/catch.py: its own game (-g is ignored), 3 actions; no raw-screen form
+            if self._raw():
+                raise ValueError("--emulator catch has no raw 210x160 frames: --synthetic_raw_frames applies to --emulator "
+                                 "synthetic only")
+            self.num_actions = catch.NUM_ACTIONS
+            self.create_environment = lambda i: catch.CatchEnvironment(i, seed=self._seed())
+            return
         self.num_actions = int(getattr(args, "num_actions_override", 0) or GAME_NUM_ACTIONS.get(game, 6))
         # args.random_seed is set by train.get_network_and_environment_creator AFTER this constructor runs
         # (train.py:52-56), so it is read when an environment is created, like atari_emulator.py:18 does.
@@ -51,5 +62,7 @@ class EnvironmentCreator(object):
         """Device-batched twin of the same environments (PAACLearner uses it when present)."""
         if not self._device_twin:
             return None
+        if self._catch:
+            return dict(kind="catch", seed=self._seed())
         return dict(kind="synthetic", seed=self._seed(), terminal_threshold=terminal_threshold(self._terminal_p()),
                     raw_frames=self._raw())

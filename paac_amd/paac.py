@@ -58,6 +58,11 @@ class DeviceRollout(object):
         self.tick = torch.zeros((1,), dtype=torch.int64, device=dev)          # env steps taken (per env)
         self.global_step_dev = torch.full((1,), int(L.global_step), dtype=torch.int64, device=dev)
         self.raw = None
+        # kind "catch" (paac_amd/catch.py): the environments carry state from step to step -- a ring of state records beside
+        # the observation ring, slot for slot (a step reads slot t and writes slot t + 1: nothing is updated in place, and the
+        # wrap-around second output goes to slot 0 of both)
+        self.catch = env_spec.get("kind", "synthetic") == "catch"
+        self.env_state = torch.zeros((2 * T + 1, N, hip_ops.CATCH_STATE_WORDS), dtype=torch.int32, device=dev) if self.catch else None
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
         if env_spec.get("raw_frames"):
@@ -117,7 +122,10 @@ class DeviceRollout(object):
         towered = getattr(L.network, "ARCH", None) in ("NATURE", "NIPS") and os.environ.get("PAAC_TOWER", "1") != "0"
         self.act_step_large = os.environ.get("PAAC_MT_AHEAD", "1") != "0" and N <= hip_ops.ACT_STEP_MAX_ENVS_LARGE and towered
         self.reuse_acting = os.environ.get("PAAC_REUSE_ACTING", "1") != "0" and towered and N <= hip_ops.KEEP_FORWARD_MAX_ROWS
-        hip_ops.synth_reset(env_spec["seed"], self.env_offset, self.states[0], self.raw)
+        if self.catch:
+            hip_ops.catch_reset(env_spec["seed"], self.env_offset, self.env_state[0], self.states[0])
+        else:
+            hip_ops.synth_reset(env_spec["seed"], self.env_offset, self.states[0], self.raw)
         torch.cuda.synchronize(dev)
 
     # -- stages --------------------------------------------------------------------------------------
@@ -140,6 +148,20 @@ class DeviceRollout(object):
                 L.ctx.keep_next_forward(t * N)
             # the ring wraps after an odd cycle: its last step also writes slot 0 (the next even cycle's first slot)
             wrap = self.states[0] if (parity == 1 and t == T - 1) else None
+            if self.catch:
+                # the generic route only: forward (+ sampler), then the environment step on the sampled actions
+                if self.sampler == "numpy":
+                    L.ctx.forward(params, st[t], probs=self.probs, values=self.values[t])
+                    hip_ops.sample_mt(self.probs, self.mt_state, self.mt_scratch, self.actions[t])
+                else:
+                    L.ctx.forward_sample(params, st[t], self.sampler_seed, self.tick, t, self.env_offset,
+                                         self.actions[t], probs=self.probs, values=self.values[t])
+                slot = self._slot(parity, t)
+                hip_ops.catch_step(self.env_spec["seed"], self.env_offset, self.actions[t], self.env_state[slot],
+                                   self.env_state[slot + 1], st[t], st[t + 1], self.rewards[t], self.masks[t], self.ep_reward,
+                                   self.ep_len, self.finished, stack_out2=wrap,
+                                   state_out2=self.env_state[0] if wrap is not None else None)
+                continue
             # (path B -- self.raw -- rides the same fused launches: they write the raw screen pairs instead of shifting the
             # stacks and the preprocess launch follows)
             fused = self.sampler == "numpy" and N * (self.A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS
@@ -357,7 +379,7 @@ class DeviceRollout(object):
              [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev] + [t for t in (L.p_old, L.ppo_loss, L.ppo_stats, L.adv_n, L.adv_stats, L.v_old) if t is not None]
         if L.minibatch_on:      # (the staging block of states is rewritten by every epoch's gather before anything reads it)
             ts += [L.v_rec] + [t for k, t in L.mb.items() if t is not None and k != "states"]
-        for name in ("raw", "walk_scratch", "mt_state"):
+        for name in ("raw", "walk_scratch", "mt_state", "env_state"):
             t = getattr(self, name, None)
             if t is not None:
                 ts.append(t)

@@ -64,7 +64,9 @@ BUILD_FLAGS = (
     (("--synthetic_raw_frames",), "synthetic_raw_frames", False, bool_arg,
      "synthetic environments emit two raw 210x160 screens per step (GPU max + resize + history)"),
     (("--emulator",), "emulator", "synthetic", None,
-     "'synthetic' (paac_amd/synthetic.py) or 'ale' (Atari through an installed Arcade Learning Environment)"),
+     "'synthetic' (paac_amd/synthetic.py), 'catch' (paac_amd/catch.py: a learnable game on the GPU, 3 actions; -g, "
+     "--synthetic_terminal_p and --synthetic_raw_frames do not apply) or 'ale' (Atari through an installed Arcade Learning "
+     "Environment)"),
     (("--device_preprocess",), "device_preprocess", False, bool_arg,
      "host environments hand out raw screen pairs; max + resize + frame history run on the GPU"),
     (("--user_arch",), "user_arch", "", None,
@@ -108,7 +110,7 @@ def get_arg_parser():
         if kind is not None:
             kwargs["type"] = kind
         if dest in ("sampler", "emulator", "checkpoint_format", "optimizer"):
-            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "ale"],
+            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "ale"],
                                  "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"]}[dest]
         parser.add_argument(*options, **kwargs)
     return parser

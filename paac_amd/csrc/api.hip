@@ -193,6 +193,11 @@ int paac_create(const paac_cfg* cfg, paac_ctx** out) {
     PAAC_CHECK_HIP(hipMalloc(&c->dact[i], (size_t)B * cs.oh * cs.ow * cs.cout * sizeof(float)));
   }
   PAAC_CHECK_HIP(hipMalloc(&c->dh, (size_t)B * c->spec.fc * sizeof(float)));
+  if (paac::dh_planes_supported(c->spec.fc)) {
+    PAAC_CHECK_HIP(hipMalloc(&c->dh_planes, paac::dh_planes_bytes((int)B, c->spec.fc)));
+    PAAC_CHECK_HIP(hipMemset(c->dh_planes, 0, paac::dh_planes_bytes((int)B, c->spec.fc)));
+  }
+  { const char* v = getenv("PAAC_FC_DGRAD_ONCE"); c->fc_dgrad_once = !(v && *v && atoi(v) == 0); }
   PAAC_CHECK_HIP(hipMalloc(&c->dl_buf, (size_t)B * paac::kDlStride * sizeof(float)));
   PAAC_CHECK_HIP(hipMalloc(&c->ppo_rows, (size_t)B * 2 * sizeof(float)));
   PAAC_CHECK_HIP(hipMalloc(&c->vclip_rows, (size_t)B * sizeof(float)));
@@ -250,6 +255,7 @@ int paac_destroy(paac_ctx* c) {
   for (float* b : bufs)
     if (b) (void)hipFree(b);
   if (c->mt_ahead) (void)hipFree(c->mt_ahead);
+  if (c->dh_planes) (void)hipFree(c->dh_planes);
   if (c->tower_pack) (void)hipFree(c->tower_pack);
   if (c->fc_pack) (void)hipFree(c->fc_pack);
   for (int i = 0; i < paac_ctx::PROF_MAX_EVENTS; ++i) {

@@ -85,6 +85,11 @@ inline int batch_class(int batch) { return batch > 512 ? 2 : batch > 64 ? 1 : 0;
 
 constexpr int kDlStride = 36;   // floats per row of paac_ctx::dl_buf (heads.h)
 
+// dH as bf16 planes (csrc/fc_dgrad_once.h): the fc widths whose producers can stage a dH row in the LDS they already own
+// (>= 1536 floats in either heads kernel), and the bytes of the plane buffer (rows padded to a multiple of 16, 3 x 2 B)
+constexpr bool dh_planes_supported(int H) { return (H % 32) == 0 && H <= 1024; }
+inline size_t dh_planes_bytes(int max_batch, int H) { return (size_t)((max_batch + 15) / 16 * 16) * H * 6; }
+
 // Split-K slab reduction of the conv weight gradients into the flat gradient (net_bwd.hip): segments of one backward.
 struct FinalizeSeg {
   const float* src;  // first slab
@@ -110,6 +115,11 @@ struct paac_ctx {
   int last_ws;
   float* dact[3];  // gradients wrt conv outputs (post ReLU mask)
   float* dh;       // [max_batch][H]
+  // dH once more as three bf16 planes (hi, mid, lo of the exact split) in the fragment order of fc_dgrad_once_kernel
+  // (csrc/fc_dgrad_once.h), rows padded to a multiple of 16; written by the heads-gradient kernels next to dh
+  void* dh_planes;         // nullptr: the fc width has no plane form
+  int dh_planes_rows;      // rows of the update whose planes are current (0: none -- the generic fc data gradient runs)
+  int fc_dgrad_once;       // PAAC_FC_DGRAD_ONCE (default 1; read at paac_create): 0 = always the generic fc data gradient
   float* wslab;    // wgrad split-K slabs (all layers)
   int64_t wslab_floats;
   float* partials; // norm / gradient-summary partials of the last paac_clip_rmsprop / paac_clip_adam (5 x kNormPartialsMax

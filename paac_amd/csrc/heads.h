@@ -5,6 +5,7 @@
 // in registers, and block-wide sums go through LDS in two short stages instead of long ds_bpermute chains.
 #pragma once
 #include "common.h"
+#include "fc_dgrad_once.h"
 #include "synth_dev.h"
 
 namespace paac {
@@ -531,7 +532,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
                                                         int A, int B, float beta, float* __restrict__ dH,
                                                         float* __restrict__ gWa, float* __restrict__ gba,
                                                         float* __restrict__ gWc, float* __restrict__ gbc,
-                                                        float* __restrict__ loss_out,
+                                                        float* __restrict__ loss_out, bf16x8* __restrict__ dh_planes,
                                                         const typename ArgsOf<EST, LOSS>::type rt) {
   constexpr int NV = AP + 1;
   constexpr int NS = NV + 3;                       // + 3 loss statistics (role 3)
@@ -539,7 +540,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
   const float s = 5.0f / (float)B;
   HEADS_STAMP_INIT();
   HEADS_STAMP(0);
-  __shared__ float smem[NS * 256 + NS * 8 > HB_CHUNK * NV ? NS * 256 + NS * 8 : HB_CHUNK * NV];
+  __shared__ __attribute__((aligned(16))) float smem[NS * 256 + NS * 8 > HB_CHUNK * NV ? NS * 256 + NS * 8 : HB_CHUNK * NV];
   __shared__ float red[NS];
   if ((int)blockIdx.x < B) {
     // ---- role 1 ----
@@ -562,8 +563,11 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
       float acc = dl[AP] * wcj[jj];
 #pragma unroll
       for (int a = 0; a < AP; ++a) acc = fmaf(dl[a], waj[jj][a], acc);   // explicit: the two kernels with this line must round alike
-      dH[(long)i * H + j] = hv[jj] > 0.f ? acc : 0.f;
+      const float d = hv[jj] > 0.f ? acc : 0.f;
+      dH[(long)i * H + j] = d;
+      if constexpr (dh_planes_supported(H)) smem[j] = d;
     }
+    store_dh_planes<H>(smem, i, B, dh_planes);     // the row's three bf16 planes for fc_dgrad_once_kernel (nullptr: none)
     HEADS_STAMP(1);
     return;
   }
@@ -688,7 +692,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
                                                           float* __restrict__ probs_ws, float* __restrict__ values_ws,
                                                           const int32_t* __restrict__ actions, const float* __restrict__ y,
                                                           const float* __restrict__ adv, float beta, float* __restrict__ dH,
-                                                          float* __restrict__ dl_buf,
+                                                          float* __restrict__ dl_buf, bf16x8* __restrict__ dh_planes,
                                                           const typename ArgsOf<EST, LOSS>::type rt) {
   constexpr int JPT = H / 256;
   constexpr int NV = AP + 1;                 // A logits (padded) + value
@@ -753,7 +757,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
     part[AP] = fmaf(s, wcj[jj], part[AP]);
     part[NV] = fmaf(sbt, wcj[jj], part[NV]);
   }
-  __shared__ float scratch[NB * 256 + NB * 8];
+  __shared__ __attribute__((aligned(16))) float scratch[NB * 256 + NB * 8];
   __shared__ float lg[NB];
   __shared__ float row_s[AP + 3];            // probabilities, then y, adv
   block_sums_256<NB>(part, scratch, lg);
@@ -845,8 +849,11 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
     float acc = dl[AP] * wcj[jj];
 #pragma unroll
     for (int a = 0; a < AP; ++a) acc = fmaf(dl[a], waj[jj][a], acc);   // explicit: the two kernels with this line must round alike
-    dH[(long)i * H + j] = hv[jj] > 0.f ? acc : 0.f;
+    const float d = hv[jj] > 0.f ? acc : 0.f;
+    dH[(long)i * H + j] = d;
+    if constexpr (dh_planes_supported(H)) scratch[j] = d;      // (the block sums are long done with it)
   }
+  store_dh_planes<H>(scratch, i, B, dh_planes);     // the row's three bf16 planes for fc_dgrad_once_kernel (nullptr: none)
 }
 
 // Roles 2 and 3 of heads_bwd_kernel with the per-row head gradients read from dl_buf (written by heads_train_kernel in an

@@ -3,6 +3,7 @@
 
 #include "net_common.h"
 #include "dgrad_tower.h"
+#include "fc_dgrad_once.h"
 #include "gemm3.h"
 
 namespace paac {
@@ -315,6 +316,14 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     rtl.v_boot = W.values + batch;
     rtl.boot_in_fwd = 0;
   }
+  // The heads-gradient launch also leaves dH as bf16 planes when this update's fc data gradient takes the split-once kernel
+  // (fc_dgrad_once.h): decided here from the shapes and the switch alone, so that every route to the same update -- whole or
+  // phased backward, either heads kernel, PPO epochs and minibatches -- runs the same arithmetic.
+  static const int gemm3_rows_once = env_int("PAAC_GEMM3_MIN_ROWS", 513);
+  const bool once_shape = ctx->fc_dgrad_once && ctx->dh_planes && dh_planes_supported(NT::H) && batch <= kFcOnceMaxRows &&
+                          batch < gemm3_rows_once && (NT::FLAT % 16) == 0;
+  bf16x8* dhp = once_shape ? reinterpret_cast<bf16x8*>(ctx->dh_planes) : nullptr;
+  if (do_fc) ctx->dh_planes_rows = dhp ? batch : 0;      // (every heads launch below writes the planes it is handed)
   // (1) heads: dH, head weight/bias grads, loss scalars
   if (do_fc && fused_heads) {
     ProfScope ps(ctx, F_HEADS_BWD, batch, s);
@@ -327,17 +336,17 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
         launch_heads_train<NT::H, decltype(est)::value, decltype(lossc)::value>(
             A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H, fc_b, wa,
             params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A, batch, W.h, W.logits, W.probs, W.values, actions, y,
-            adv, beta, ctx->dh, ctx->dl_buf, ra);
+            adv, beta, ctx->dh, ctx->dl_buf, dhp, ra);
       };
       launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
     } else if (estimator == kEstGae)
       launch_heads_train<NT::H, kEstGae>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
                                          fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
-                                         batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, rtl);
+                                         batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, dhp, rtl);
     else
       launch_heads_train<NT::H, kEstNstep>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
                                            fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
-                                           batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, rtn);
+                                           batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, dhp, rtn);
     ctx->heads_pending_rows = 0;
     ctx->heads_pending_h = 0;
   } else if (do_fc) {
@@ -347,17 +356,17 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
         launch_heads_bwd<NT::H, decltype(est)::value, decltype(lossc)::value>(
             A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y, adv, (const float*)W.h,
             wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa], grad + L.offset[i_wa + 1], grad + L.offset[i_wc],
-            grad + L.offset[i_wc + 1], loss_out, ra);
+            grad + L.offset[i_wc + 1], loss_out, dhp, ra);
       };
       launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
     } else if (estimator == kEstGae)
       launch_heads_bwd<NT::H, kEstGae>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
                                        adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
-                                       grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, rtl);
+                                       grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, dhp, rtl);
     else
       launch_heads_bwd<NT::H, kEstNstep>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
                                          adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
-                                         grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, rtn);
+                                         grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, dhp, rtn);
   }
   if (do_fc && loss == kLossPpo && ppo_stats_out)
     launch_k(ppo_stats_kernel, dim3(1), dim3(256), s, PROF_NONE, (const float*)ppo.stat_rows, batch, ppo_stats_out);
@@ -442,6 +451,24 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       a.stages_per_split = NT::H / 32;
       prof_mix(6);
       launch_k(gemm3_kernel<D>, dim3((unsigned)(a.MB * a.NB)), dim3(D::THREADS), s, PROF_WHOLE, a);
+    } else if (once_shape && ctx->dh_planes_rows == batch) {
+      // update batches that fit one workgroup's rows: operands split once (fc_dgrad_once.h), 16 columns per workgroup
+      if constexpr (dh_planes_supported(NT::H) && (NT::FLAT % 16) == 0) {
+        using D = FcOnce<NT::H, 1, kFcOnceWaves, kFcOnceTilesPerWave, 3>;
+        FcOnceArgs a;
+        a.planes = ctx->dh_planes;
+        a.planes_bytes = (unsigned)dh_planes_bytes(batch, NT::H);
+        a.wf = wf;
+        a.xf = xf;
+        a.dx = dxf;
+        a.M = batch;
+        a.FLAT = NT::FLAT;
+#ifdef PAAC_DMM_STAMPS
+        a.stamps = gd.stamps;
+#endif
+        prof_mix(6);
+        launch_k(fc_dgrad_once_kernel<D>, dim3(NT::FLAT / 16), dim3(D::THREADS), s, PROF_WHOLE, a);
+      }
     } else {
       launch_dgrad<typename NT::GFCH, NT::FLAT, NT::H, EPI_MASK>(gd, 1, ctx->tune[OP_FC_DGRAD][cls], s);
     }

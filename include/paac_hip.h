@@ -493,6 +493,22 @@ int paac_catch_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                     paac_stream_t stream);
 
+/* Device-resident bricks environments: a brick-wall game with lives (a ball bounces between a two-cell paddle and three rows
+ * of 14 bricks, +1 per brick struck, three lives, at most 500 steps per episode) on the same 14 x 14 board, rendered into the
+ * same [N,84,84,4] u8 observations; spec in paac_amd/bricks.py, a BaseEnvironment plugin producing the same numbers on the
+ * host.  3 actions: 0 stay, 1 left, 2 right.
+ *   state: i32 [N,12] per environment {bx, by, dx, dy, px, lives, steps, k, rows0, rows1, rows2, 0}; the episode-start and
+ *          serve hashes are keyed by (seed, env_offset + e, k).  The step trusts its records: they come from
+ *          paac_bricks_reset, from an earlier step, or from a caller that writes valid states.
+ * paac_bricks_reset / paac_bricks_step: the argument lists, outputs, records and refusals of paac_catch_reset /
+ *   paac_catch_step; single_life != 0 makes every lost life end the episode (--single_life_episodes).  One launch. */
+int paac_bricks_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                      paac_stream_t stream);
+int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                     int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, int single_life,
+                     paac_stream_t stream);
+
 /* paac_sample_mt + paac_synth_step (path A) in ONE launch: workgroup 0 samples (numpy-parity MT19937 stream) and does
  * the per-env bookkeeping while the other workgroups shift the observation stacks (stack_out2, nullable: a second copy
  * of the new stacks, like paac_synth_step's).  Limit: N*(A-1) <= 2304 (covers 256 environments x 4 actions and

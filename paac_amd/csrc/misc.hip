@@ -3,6 +3,7 @@
 #include "common.h"
 #include "synth_dev.h"
 #include "catch_dev.h"
+#include "bricks_dev.h"
 #include "fc_heads.h"
 #include "heads.h"
 #include "tower.h"
@@ -1388,6 +1389,49 @@ __global__ __launch_bounds__(256) void catch_step_kernel(uint64_t seed, uint32_t
   if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
 }
 
+// Bricks environments (spec: paac_amd/bricks.py); device helpers in bricks_dev.h.  The shape of catch_step_kernel: grid (N, 7),
+// 256 threads, 252 of them own one quad -- one 16-byte load of the old stack, requested before the state record is looked at,
+// one 16-byte store (and the optional second one), no LDS.  The new state is a pure function of (state_in[e], actions[e],
+// single_life): every band workgroup of an environment recomputes it in registers, one thread of band 0 writes it out and
+// does the bookkeeping.  Nothing is updated in place.  state_in == nullptr: reset.
+__global__ __launch_bounds__(256) void bricks_step_kernel(uint64_t seed, uint32_t env_offset, int N,
+                                                          const int32_t* __restrict__ actions,
+                                                          const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
+                                                          int32_t* __restrict__ state_out2,
+                                                          const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                          uint32_t* __restrict__ stack_out2, float* rewards_out,
+                                                          float* masks_out, float* ep_reward, int32_t* ep_len,
+                                                          FinishedRing* fin, int single_life) {
+  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
+  const int e = blockIdx.x;
+  const int band = blockIdx.y;
+  const int i = threadIdx.x;
+  const bool owner = i < QUADS_PER_BAND;
+  const int q = band * QUADS_PER_BAND + i;
+  const long quad = (long)e * (OBS_PIX / 4) + q;
+  uint4 old = make_uint4(0u, 0u, 0u, 0u);
+  BricksState s;
+  float r = 0.f;
+  bool term = false;
+  if (state_in) {
+    // every thread loads (the four that own no quad read the band's first one): with the load under a condition the compiler
+    // pulls the history's shift up behind it, and with the shift the wait -- the state record would be asked for only then
+    old = reinterpret_cast<const uint4*>(stack_in)[owner ? quad : quad - i];
+    s = bricks_advance(seed, env_offset + (uint32_t)e, bricks_load(state_in, e), actions[e], single_life != 0, &r, &term);
+  } else {
+    s = bricks_start(seed, env_offset + (uint32_t)e, 0);
+  }
+  if (band == 0 && i == 0) {
+    bricks_store(state_out, e, s);
+    if (state_out2) bricks_store(state_out2, e, s);
+    if (state_in) env_bookkeep(r, term, e, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
+  }
+  if (!owner) return;
+  const uint4 outv = bricks_shift_quad(s, q, old, term);   // a terminal step drops the history it loaded
+  reinterpret_cast<uint4*>(stack_out)[quad] = outv;
+  if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
+}
+
 // Path A with the numpy-parity sampler folded in: workgroup 0 runs the (inherently serial) MT19937 sampler and then
 // the per-env bookkeeping, the other N*7 workgroups shift the observation stacks meanwhile -- the new frame and the
 // terminal flag of the synthetic environments do not depend on the action, only reward bookkeeping does.  One launch
@@ -2514,6 +2558,34 @@ int paac_catch_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
   launch_k(catch_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
            state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
            ep_reward, ep_len, (FinishedRing*)finished);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_bricks_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                      paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && state_out && stack_out, "paac_bricks_reset: bad arguments");
+  hipLaunchKernelGGL(bricks_step_kernel, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
+                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                     (int32_t*)nullptr, (FinishedRing*)nullptr, 0);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                     int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, int single_life,
+                     paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
+               ep_len, "paac_bricks_step: bad arguments");
+  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
+               "paac_bricks_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+  launch_k(bricks_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
+           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
+           ep_reward, ep_len, (FinishedRing*)finished, single_life);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

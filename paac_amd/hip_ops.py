@@ -719,44 +719,62 @@ def synth_step(seed, env_offset, actions, terminal_threshold, step_base_dev, ste
 
 
 CATCH_STATE_WORDS = 8            # int32 words of a catch environment's state record (paac_amd/catch.py)
+BRICKS_STATE_WORDS = 12          # ... of a bricks environment's (paac_amd/bricks.py)
 
 
-def catch_reset(seed, env_offset, state_out, stack_out):
+def _stateful_reset(entry, words, seed, env_offset, state_out, stack_out):
+    """paac_<game>_reset of a game whose environments carry a state record of `words` int32."""
     N = stack_out.shape[0]
     if tuple(stack_out.shape) != (N,) + OBS_SHAPE:
         raise ValueError("stack_out must be [N,84,84,4]")
-    if tuple(state_out.shape) != (N, CATCH_STATE_WORDS):
-        raise ValueError("state_out must be [%d,%d], got %s" % (N, CATCH_STATE_WORDS, tuple(state_out.shape)))
-    _lib.check(_lib.load().paac_catch_reset(int(seed), int(env_offset), N,
-                                            _ptr(state_out, torch.int32, N * CATCH_STATE_WORDS, "state_out"),
-                                            _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _stream()),
-               "paac_catch_reset")
+    if tuple(state_out.shape) != (N, words):
+        raise ValueError("state_out must be [%d,%d], got %s" % (N, words, tuple(state_out.shape)))
+    _lib.check(getattr(_lib.load(), entry)(int(seed), int(env_offset), N, _ptr(state_out, torch.int32, N * words, "state_out"),
+                                           _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _stream()), entry)
 
 
-def catch_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
-               finished=None, stack_out2=None, state_out2=None):
+def _stateful_step(entry, words, seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out,
+                   ep_reward, ep_len, finished, stack_out2, state_out2, extra=()):
+    """paac_<game>_step: the shape checks and the argument list the stateful games share; `extra` = the game's own integer
+    arguments, which follow `finished`."""
     N = actions.shape[0]
     for nm, t in (("stack_in", stack_in), ("stack_out", stack_out), ("stack_out2", stack_out2)):
         if t is not None and tuple(t.shape) != (N,) + OBS_SHAPE:
             raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
     for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
-        if t is not None and tuple(t.shape) != (N, CATCH_STATE_WORDS):
-            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, CATCH_STATE_WORDS, tuple(t.shape)))
+        if t is not None and tuple(t.shape) != (N, words):
+            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
     if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
         raise ValueError("finished ring too small")
-    _lib.check(_lib.load().paac_catch_step(int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
-                                           _ptr(state_in, torch.int32, N * CATCH_STATE_WORDS, "state_in"),
-                                           _ptr(state_out, torch.int32, N * CATCH_STATE_WORDS, "state_out"),
-                                           _ptr(state_out2, torch.int32, N * CATCH_STATE_WORDS, "state_out2", True),
-                                           _ptr(stack_in, torch.uint8, N * 28224, "stack_in"),
-                                           _ptr(stack_out, torch.uint8, N * 28224, "stack_out"),
-                                           _ptr(stack_out2, torch.uint8, N * 28224, "stack_out2", True),
-                                           _ptr(rewards_out, torch.float32, N, "rewards_out"),
-                                           _ptr(masks_out, torch.float32, N, "masks_out"),
-                                           _ptr(ep_reward, torch.float32, N, "ep_reward"),
-                                           _ptr(ep_len, torch.int32, N, "ep_len"),
-                                           ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0),
-                                           _stream()), "paac_catch_step")
+    args = [int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
+            _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
+            _ptr(state_out2, torch.int32, N * words, "state_out2", True),
+            _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), _ptr(stack_out, torch.uint8, N * 28224, "stack_out"),
+            _ptr(stack_out2, torch.uint8, N * 28224, "stack_out2", True),
+            _ptr(rewards_out, torch.float32, N, "rewards_out"), _ptr(masks_out, torch.float32, N, "masks_out"),
+            _ptr(ep_reward, torch.float32, N, "ep_reward"), _ptr(ep_len, torch.int32, N, "ep_len"),
+            ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0)]
+    _lib.check(getattr(_lib.load(), entry)(*(args + [int(x) for x in extra] + [_stream()])), entry)
+
+
+def catch_reset(seed, env_offset, state_out, stack_out):
+    _stateful_reset("paac_catch_reset", CATCH_STATE_WORDS, seed, env_offset, state_out, stack_out)
+
+
+def catch_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
+               finished=None, stack_out2=None, state_out2=None):
+    _stateful_step("paac_catch_step", CATCH_STATE_WORDS, seed, env_offset, actions, state_in, state_out, stack_in, stack_out,
+                   rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2)
+
+
+def bricks_reset(seed, env_offset, state_out, stack_out):
+    _stateful_reset("paac_bricks_reset", BRICKS_STATE_WORDS, seed, env_offset, state_out, stack_out)
+
+
+def bricks_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
+                finished=None, stack_out2=None, state_out2=None, single_life=False):
+    _stateful_step("paac_bricks_step", BRICKS_STATE_WORDS, seed, env_offset, actions, state_in, state_out, stack_in, stack_out,
+                   rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2, extra=(bool(single_life),))
 
 
 FUSED_SAMPLE_MAX_DRAWS = 2304

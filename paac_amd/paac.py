@@ -23,6 +23,15 @@ from .actor_learner import ActorLearner
 from .runners import EmulatorRunner, RawEmulatorRunner, Runners
 
 
+# Device environments that carry a state record from step to step, by env_spec["kind"]: int32 words of a record, the reset and
+# step wrappers (one argument list, catch's), and the keys of the spec the step wrapper takes as keyword arguments.
+STATEFUL_KINDS = {
+    "catch": dict(words=hip_ops.CATCH_STATE_WORDS, reset=hip_ops.catch_reset, step=hip_ops.catch_step, spec_kwargs=()),
+    "bricks": dict(words=hip_ops.BRICKS_STATE_WORDS, reset=hip_ops.bricks_reset, step=hip_ops.bricks_step,
+                   spec_kwargs=("single_life",)),
+}
+
+
 class DeviceRollout(object):
     """Device-resident rollout/update cycle for N local environments x T steps."""
 
@@ -58,11 +67,15 @@ class DeviceRollout(object):
         self.tick = torch.zeros((1,), dtype=torch.int64, device=dev)          # env steps taken (per env)
         self.global_step_dev = torch.full((1,), int(L.global_step), dtype=torch.int64, device=dev)
         self.raw = None
-        # kind "catch" (paac_amd/catch.py): the environments carry state from step to step -- a ring of state records beside
-        # the observation ring, slot for slot (a step reads slot t and writes slot t + 1: nothing is updated in place, and the
-        # wrap-around second output goes to slot 0 of both)
+        # a stateful kind (STATEFUL_KINDS: catch, bricks): the environments carry state from step to step -- a ring of state
+        # records beside the observation ring, slot for slot (a step reads slot t and writes slot t + 1: nothing is updated in
+        # place, and the wrap-around second output goes to slot 0 of both)
+        self.stateful = STATEFUL_KINDS.get(env_spec.get("kind", "synthetic"))
         self.catch = env_spec.get("kind", "synthetic") == "catch"
-        self.env_state = torch.zeros((2 * T + 1, N, hip_ops.CATCH_STATE_WORDS), dtype=torch.int32, device=dev) if self.catch else None
+        self.env_state = None
+        if self.stateful:
+            self.env_state = torch.zeros((2 * T + 1, N, self.stateful["words"]), dtype=torch.int32, device=dev)
+            self.env_step_kwargs = {k: env_spec[k] for k in self.stateful["spec_kwargs"]}
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
         if env_spec.get("raw_frames"):
@@ -122,8 +135,8 @@ class DeviceRollout(object):
         towered = getattr(L.network, "ARCH", None) in ("NATURE", "NIPS") and os.environ.get("PAAC_TOWER", "1") != "0"
         self.act_step_large = os.environ.get("PAAC_MT_AHEAD", "1") != "0" and N <= hip_ops.ACT_STEP_MAX_ENVS_LARGE and towered
         self.reuse_acting = os.environ.get("PAAC_REUSE_ACTING", "1") != "0" and towered and N <= hip_ops.KEEP_FORWARD_MAX_ROWS
-        if self.catch:
-            hip_ops.catch_reset(env_spec["seed"], self.env_offset, self.env_state[0], self.states[0])
+        if self.stateful:
+            self.stateful["reset"](env_spec["seed"], self.env_offset, self.env_state[0], self.states[0])
         else:
             hip_ops.synth_reset(env_spec["seed"], self.env_offset, self.states[0], self.raw)
         torch.cuda.synchronize(dev)
@@ -148,7 +161,7 @@ class DeviceRollout(object):
                 L.ctx.keep_next_forward(t * N)
             # the ring wraps after an odd cycle: its last step also writes slot 0 (the next even cycle's first slot)
             wrap = self.states[0] if (parity == 1 and t == T - 1) else None
-            if self.catch:
+            if self.stateful:
                 # the generic route only: forward (+ sampler), then the environment step on the sampled actions
                 if self.sampler == "numpy":
                     L.ctx.forward(params, st[t], probs=self.probs, values=self.values[t])
@@ -157,10 +170,10 @@ class DeviceRollout(object):
                     L.ctx.forward_sample(params, st[t], self.sampler_seed, self.tick, t, self.env_offset,
                                          self.actions[t], probs=self.probs, values=self.values[t])
                 slot = self._slot(parity, t)
-                hip_ops.catch_step(self.env_spec["seed"], self.env_offset, self.actions[t], self.env_state[slot],
-                                   self.env_state[slot + 1], st[t], st[t + 1], self.rewards[t], self.masks[t], self.ep_reward,
-                                   self.ep_len, self.finished, stack_out2=wrap,
-                                   state_out2=self.env_state[0] if wrap is not None else None)
+                self.stateful["step"](self.env_spec["seed"], self.env_offset, self.actions[t], self.env_state[slot],
+                                      self.env_state[slot + 1], st[t], st[t + 1], self.rewards[t], self.masks[t],
+                                      self.ep_reward, self.ep_len, self.finished, stack_out2=wrap,
+                                      state_out2=self.env_state[0] if wrap is not None else None, **self.env_step_kwargs)
                 continue
             # (path B -- self.raw -- rides the same fused launches: they write the raw screen pairs instead of shifting the
             # stacks and the preprocess launch follows)

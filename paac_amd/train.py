@@ -65,8 +65,10 @@ BUILD_FLAGS = (
      "synthetic environments emit two raw 210x160 screens per step (GPU max + resize + history)"),
     (("--emulator",), "emulator", "synthetic", None,
      "'synthetic' (paac_amd/synthetic.py), 'catch' (paac_amd/catch.py: a learnable game on the GPU, 3 actions; -g, "
-     "--synthetic_terminal_p and --synthetic_raw_frames do not apply) or 'ale' (Atari through an installed Arcade Learning "
-     "Environment)"),
+     "--synthetic_terminal_p and --synthetic_raw_frames do not apply), 'bricks' (paac_amd/bricks.py: a brick-wall game with "
+     "three lives on the GPU, 3 actions, episodes of up to 500 steps; --single_life_episodes applies, -g, "
+     "--synthetic_terminal_p, --synthetic_raw_frames and --random_start do not) or 'ale' (Atari through an installed Arcade "
+     "Learning Environment)"),
     (("--device_preprocess",), "device_preprocess", False, bool_arg,
      "host environments hand out raw screen pairs; max + resize + frame history run on the GPU"),
     (("--user_arch",), "user_arch", "", None,
@@ -110,7 +112,7 @@ def get_arg_parser():
         if kind is not None:
             kwargs["type"] = kind
         if dest in ("sampler", "emulator", "checkpoint_format", "optimizer"):
-            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "ale"],
+            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "ale"],
                                  "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"]}[dest]
         parser.add_argument(*options, **kwargs)
     return parser

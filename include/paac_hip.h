@@ -509,6 +509,29 @@ int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* a
                      float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, int single_life,
                      paac_stream_t stream);
 
+/* GPU-resident evaluation of the stateful games (spec: paac_amd/evaluation.py): one evaluation step of N environments in one
+ * launch, behind the acting forward that wrote probs [N, A].  With t = *step_base_dev + step_offset (base NULL = 0; a captured
+ * block of steps replays with a fresh base, paac_counter_add) and g = env_offset + e:
+ *   no-ops   noops_e = word 0 of philox4x32-10(ctr = {g, 0, 0, 0x45560002}; key = eval_seed) % (noops + 1); noops = 0: none
+ *   action   t < noops_e: 0 (both games' no-op); else greedy != 0: argmax of probs[e] (lowest index on ties; NaN rows are not
+ *            supported), greedy == 0: paac_sample_philox's inverse CDF on u = philox(ctr = {g, t lo, t hi, 0x45560001};
+ *            key = eval_seed) -- streams of their own (the rollout sampler's is 0, the minibatch shuffles' 0x504D0000 + epoch);
+ *            written to actions_out[e]
+ *   game     state_in -> state_out, stack_in -> stack_out exactly as the game's step entry does on that action (seed
+ *            env_seed, single_life off); not in place: state_in == state_out or stack_in == stack_out is refused
+ *   accounts from t = noops_e on and while done[e] == 0: score[e] += reward, length[e] += 1, and on a terminal step (its
+ *            reward included) done[e] = 1 and *alive -= 1 (one atomic per finishing environment).  Rewards and terminals of
+ *            the no-op steps are ignored; after done nothing of e changes again (the game itself keeps being stepped).
+ *            The caller zeroes score / length / done and sets *alive = N before step 0.
+ * The rollout bookkeeping (ep_reward / ep_len / finished ring) is not touched.  Refused with a message, without a launch:
+ * the in-place buffers above, N <= 0, A outside [2, 32], noops < 0, a game id that is neither of the two. */
+#define PAAC_EVAL_CATCH 0
+#define PAAC_EVAL_BRICKS 1
+int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
+                   const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
+                   const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out,
+                   float* score, int32_t* length, int32_t* done, int32_t* alive, paac_stream_t stream);
+
 /* paac_sample_mt + paac_synth_step (path A) in ONE launch: workgroup 0 samples (numpy-parity MT19937 stream) and does
  * the per-env bookkeeping while the other workgroups shift the observation stacks (stack_out2, nullable: a second copy
  * of the new stacks, like paac_synth_step's).  Limit: N*(A-1) <= 2304 (covers 256 environments x 4 actions and

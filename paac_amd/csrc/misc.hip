@@ -1432,6 +1432,116 @@ __global__ __launch_bounds__(256) void bricks_step_kernel(uint64_t seed, uint32_
   if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
 }
 
+// =============================================================================================
+// GPU-resident evaluation (spec: paac_amd/evaluation.py): one evaluation step of N environments of a stateful game per launch
+// -- the action is chosen from the acting forward's probs, the game advances, the first scored episode is accounted.  The
+// shape of the step kernels above: grid (N, 7), 256 threads, 252 of them own one quad; the stack load is requested first (by
+// every thread, the bricks kernel's reason), then the action and the new state are worked out in registers by every band
+// workgroup of the environment -- both are pure functions of (probs[e], state_in[e], t) -- and thread 0 of band 0 writes the
+// record, the action and the accounts.  state_in / stack_in are never state_out / stack_out; score / length / done of
+// environment e are read and written by that one thread only.  A finished environment keeps being stepped (parking it would
+// make every band read `done`, which band 0 writes): nothing of that shows in score / length / done.
+// The two Philox streams of an evaluation (counter word 3); the rollout sampler's is 0, the minibatch shuffles' are
+// 0x504D0000 + epoch.  paac_amd/evaluation.py: EVAL_STREAM_ACTION / EVAL_STREAM_NOOP are the same numbers.
+constexpr uint32_t kEvalStreamAction = 0x45560001u;
+constexpr uint32_t kEvalStreamNoop = 0x45560002u;
+
+struct EvalCatch {
+  typedef CatchState State;
+  static __device__ __forceinline__ State load(const int32_t* __restrict__ st, int e) { return catch_load(st, e); }
+  static __device__ __forceinline__ void store(int32_t* __restrict__ st, int e, const State& s) { catch_store(st, e, s); }
+  static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, float* r, bool* term) {
+    return catch_advance(seed, env, s, a, r, term);
+  }
+  static __device__ __forceinline__ uint4 shift_quad(const State& s, int q, uint4 old, bool fresh) {
+    return catch_shift_quad(s, q, fresh ? make_uint4(0u, 0u, 0u, 0u) : old);
+  }
+};
+
+struct EvalBricks {
+  typedef BricksState State;
+  static __device__ __forceinline__ State load(const int32_t* __restrict__ st, int e) { return bricks_load(st, e); }
+  static __device__ __forceinline__ void store(int32_t* __restrict__ st, int e, const State& s) { bricks_store(st, e, s); }
+  static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, float* r, bool* term) {
+    return bricks_advance(seed, env, s, a, false, r, term);      // evaluation plays whole episodes: single_life is off
+  }
+  static __device__ __forceinline__ uint4 shift_quad(const State& s, int q, uint4 old, bool fresh) {
+    return bricks_shift_quad(s, q, old, fresh);
+  }
+};
+
+template <class G>
+__global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict__ probs, int A, int greedy, uint64_t eval_seed,
+                                                        int noops, const uint64_t* __restrict__ step_base, uint64_t step_off,
+                                                        uint64_t env_seed, uint32_t env_offset, int N,
+                                                        const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
+                                                        const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                        int32_t* __restrict__ actions_out, float* score, int32_t* length,
+                                                        int32_t* done, int32_t* alive) {
+  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
+  const int e = blockIdx.x;
+  const int band = blockIdx.y;
+  const int i = threadIdx.x;
+  const bool owner = i < QUADS_PER_BAND;
+  const int q = band * QUADS_PER_BAND + i;
+  const long quad = (long)e * (OBS_PIX / 4) + q;
+  // every thread loads (the four that own no quad read the band's first one): see bricks_step_kernel
+  const uint4 old = reinterpret_cast<const uint4*>(stack_in)[owner ? quad : quad - i];
+  const uint32_t g = env_offset + (uint32_t)e;
+  const uint64_t t = (step_base ? *step_base : 0ull) + step_off;
+  uint32_t noops_e = 0u;
+  if (noops > 0) {
+    uint32_t c[4] = {g, 0u, 0u, kEvalStreamNoop};
+    philox4x32_10(c, (uint32_t)eval_seed, (uint32_t)(eval_seed >> 32));
+    noops_e = c[0] % ((uint32_t)noops + 1u);
+  }
+  const bool playing = t >= (uint64_t)noops_e;
+  int act = 0;                                             // the no-op of both games
+  if (playing) {
+    const float* __restrict__ p = probs + (long)e * A;
+    if (greedy) {
+      float best = p[0];
+      for (int j = 1; j < A; ++j) {
+        const float v = p[j];
+        if (v > best) {                                    // strictly: the lowest index wins a tie
+          best = v;
+          act = j;
+        }
+      }
+    } else {
+      uint32_t c[4] = {g, (uint32_t)t, (uint32_t)(t >> 32), kEvalStreamAction};
+      philox4x32_10(c, (uint32_t)eval_seed, (uint32_t)(eval_seed >> 32));
+      const float u = (float)(c[0] >> 8) * (1.0f / 16777216.0f);
+      act = A - 1;
+      float cum = 0.f;
+      for (int j = 0; j < A - 1; ++j) {
+        cum += p[j];
+        if (u < cum) {
+          act = j;
+          break;
+        }
+      }
+    }
+  }
+  float r = 0.f;
+  bool term = false;
+  const typename G::State s = G::advance(env_seed, g, G::load(state_in, e), act, &r, &term);
+  if (band == 0 && i == 0) {
+    G::store(state_out, e, s);
+    actions_out[e] = act;
+    if (playing && done[e] == 0) {                         // the first episode that starts after the no-ops, its last step included
+      score[e] += r;
+      length[e] += 1;
+      if (term) {
+        done[e] = 1;
+        atomicSub(alive, 1);
+      }
+    }
+  }
+  if (!owner) return;
+  reinterpret_cast<uint4*>(stack_out)[quad] = G::shift_quad(s, q, old, term);
+}
+
 // Path A with the numpy-parity sampler folded in: workgroup 0 runs the (inherently serial) MT19937 sampler and then
 // the per-env bookkeeping, the other N*7 workgroups shift the observation stacks meanwhile -- the new frame and the
 // terminal flag of the synthetic environments do not depend on the action, only reward bookkeeping does.  One launch
@@ -2586,6 +2696,33 @@ int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* a
   launch_k(bricks_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
            state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
            ep_reward, ep_len, (FinishedRing*)finished, single_life);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
+                   const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
+                   const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out,
+                   float* score, int32_t* length, int32_t* done, int32_t* alive, paac_stream_t stream) {
+  PAAC_REQUIRE(game == PAAC_EVAL_CATCH || game == PAAC_EVAL_BRICKS, "paac_eval_step: game %d is neither catch (%d) nor bricks (%d)",
+               game, PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS);
+  PAAC_REQUIRE(N > 0, "paac_eval_step: N=%d", N);
+  PAAC_REQUIRE(A >= 2 && A <= 32, "paac_eval_step: A=%d outside [2, 32]", A);
+  PAAC_REQUIRE(noops >= 0, "paac_eval_step: noops=%d is negative", noops);
+  PAAC_REQUIRE(probs && state_in && state_out && stack_in && stack_out && actions_out && score && length && done && alive,
+               "paac_eval_step: bad arguments");
+  PAAC_REQUIRE(state_in != state_out && stack_in != stack_out,
+               "paac_eval_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+  if (game == PAAC_EVAL_CATCH)
+    launch_k(eval_step_kernel<EvalCatch>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
+             step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
+             (uint32_t*)stack_out, actions_out, score, length, done, alive);
+  else
+    launch_k(eval_step_kernel<EvalBricks>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
+             step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
+             (uint32_t*)stack_out, actions_out, score, length, done, alive);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -777,6 +777,40 @@ def bricks_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_
                    rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2, extra=(bool(single_life),))
 
 
+EVAL_GAMES = {"catch": (_lib.EVAL_CATCH, CATCH_STATE_WORDS), "bricks": (_lib.EVAL_BRICKS, BRICKS_STATE_WORDS)}
+
+
+def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
+              stack_in, stack_out, actions_out, score, length, done, alive):
+    """One evaluation step of N environments of `game` ('catch' / 'bricks') on probs [N, A] (include/paac_hip.h:
+    paac_eval_step; spec in paac_amd/evaluation.py): the action (no-op, argmax or the evaluation's own Philox stream) into
+    actions_out, the game stepped from state_in / stack_in into state_out / stack_out, the first scored episode accounted in
+    score / length / done [N] and alive [1].  Shapes are checked here; the library refuses in-place buffers, A outside [2, 32]
+    and negative noops with a PaacHipError, before any launch."""
+    if game not in EVAL_GAMES:
+        raise ValueError("eval_step: game %r has no device evaluation (--emulator catch|bricks)" % (game,))
+    game_id, words = EVAL_GAMES[game]
+    if probs.dim() != 2:
+        raise ValueError("probs must be [N, A], got %s" % (tuple(probs.shape),))
+    N, A = probs.shape
+    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out)):
+        if tuple(t.shape) != (N,) + OBS_SHAPE:
+            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
+    for nm, t in (("state_in", state_in), ("state_out", state_out)):
+        if tuple(t.shape) != (N, words):
+            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
+    if not 0 <= int(env_offset) <= 0xFFFFFFFF - N:
+        raise ValueError("eval_step: env_offset %r" % (env_offset,))
+    _lib.check(_lib.load().paac_eval_step(
+        game_id, _ptr(probs, torch.float32, N * A, "probs"), N, A, 1 if greedy else 0, int(eval_seed) & 0xFFFFFFFFFFFFFFFF,
+        int(noops), _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
+        int(env_seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), _ptr(state_in, torch.int32, N * words, "state_in"),
+        _ptr(state_out, torch.int32, N * words, "state_out"), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"),
+        _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(actions_out, torch.int32, N, "actions_out"),
+        _ptr(score, torch.float32, N, "score"), _ptr(length, torch.int32, N, "length"), _ptr(done, torch.int32, N, "done"),
+        _ptr(alive, torch.int32, 1, "alive"), _stream()), "paac_eval_step")
+
+
 FUSED_SAMPLE_MAX_DRAWS = 2304
 ACT_STEP_MAX_DRAWS = 1024
 ACT_STEP_MAX_ENVS = 64

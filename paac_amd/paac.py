@@ -24,11 +24,13 @@ from .runners import EmulatorRunner, RawEmulatorRunner, Runners
 
 
 # Device environments that carry a state record from step to step, by env_spec["kind"]: int32 words of a record, the reset and
-# step wrappers (one argument list, catch's), and the keys of the spec the step wrapper takes as keyword arguments.
+# step wrappers (one argument list, catch's), the keys of the spec the step wrapper takes as keyword arguments, and the longest
+# episode of the game in steps (what bounds an evaluation: paac_amd/evaluation.py).
 STATEFUL_KINDS = {
-    "catch": dict(words=hip_ops.CATCH_STATE_WORDS, reset=hip_ops.catch_reset, step=hip_ops.catch_step, spec_kwargs=()),
+    "catch": dict(words=hip_ops.CATCH_STATE_WORDS, reset=hip_ops.catch_reset, step=hip_ops.catch_step, spec_kwargs=(),
+                  max_episode_steps=13),
     "bricks": dict(words=hip_ops.BRICKS_STATE_WORDS, reset=hip_ops.bricks_reset, step=hip_ops.bricks_step,
-                   spec_kwargs=("single_life",)),
+                   spec_kwargs=("single_life",), max_episode_steps=500),
 }
 
 
@@ -687,6 +689,23 @@ class PAACLearner(ActorLearner):
         # mismatch ends the run on every rank (parallel.ReplicaMismatch -> non-zero exit)
         check_every = max(1, int(os.environ.get("PAAC_REPLICA_CHECK_CYCLES", "1024")))
         next_check = 1 if parallel.collectives_active() else None
+        # --eval_every: a DeviceEvaluator (paac_amd/evaluation.py) on a context of its own -- unmanaged: its forwards repack the
+        # weights they are given -- scores the live weights at the first chunk boundary at or after every multiple of
+        # eval_every global steps.  It draws from its own Philox streams and writes only its own buffers: the training
+        # context, its kept-forward state, its graphs, tick, the finished ring and the MT19937 state are never touched
+        from . import evaluation
+        evaluator = eval_ctx = None
+        eval_every = int(getattr(args, "eval_every", 0)) if evaluation.check_train_flags(args, world) else 0
+        if eval_every:
+            count = int(getattr(args, "eval_count", 64))
+            seed = int(getattr(args, "random_seed", 3)) + 1
+            eval_ctx = hip_ops.Context(self.network.arch_id, self.num_actions, max_batch=min(count, evaluation.MAX_CHUNK),
+                                       device_index=self.torch_device.index or 0)
+            spec = dict(self.environment_creator.device_env_spec, seed=seed, single_life=False)
+            evaluator = evaluation.DeviceEvaluator(self.network, eval_ctx, spec, count, noops=30,
+                                                   greedy=bool(getattr(args, "eval_greedy", True)), seed=seed,
+                                                   use_graph=getattr(args, "use_graph", True), stream=self.rollout.stream)
+            next_eval = (self.global_step // eval_every + 1) * eval_every
         while self.global_step < self.max_global_steps:
             if next_check is not None and counter >= next_check:
                 if next_check == 1:
@@ -709,6 +728,9 @@ class PAACLearner(ActorLearner):
                 until_log = int(log_every) - counter % int(log_every)
                 until_save = -(-(self.last_saving_step + CHECKPOINT_INTERVAL - self.global_step) // steps_per_cycle)
                 chunk = max(1, min(until_end, until_log, until_save))
+                if evaluator is not None:
+                    until_eval = -(-(next_eval - self.global_step) // steps_per_cycle)
+                    chunk = max(1, min(chunk, until_eval))
             if next_check is not None:
                 chunk = max(1, min(chunk, next_check - counter))
             self.rollout.run_cycles(chunk)
@@ -729,8 +751,24 @@ class PAACLearner(ActorLearner):
                     episodes_seen = count
                     self._progress_record(chunk * steps_per_cycle / (curr_time - loop_start_time),
                                           (self.global_step - global_step_start) / (curr_time - start_time), last_ten)
+            if evaluator is not None and self.global_step >= next_eval:
+                self.rollout.synchronize()
+                scores, lengths, seconds = evaluator.timed_run()
+                record = evaluator.summary(scores, lengths, seconds)
+                next_eval = (self.global_step // eval_every + 1) * eval_every
+                logging.info("Evaluation at {} steps: {} episodes ({}), mean {:.3f}, min {:.3f}, max {:.3f}, std {:.3f}, mean "
+                             "length {:.1f}, {:.3f} s".format(self.global_step, record["count"],
+                                                              "greedy" if record["greedy"] else "sampled", record["mean"],
+                                                              record["min"], record["max"], record["std"],
+                                                              record["mean_length"], seconds))
+                if metrics is not None:
+                    metrics.write("eval", global_step=int(self.global_step), **record)
+                    metrics.flush()
             self.save_vars()          # _sync_device() flushes the rollout first when a checkpoint is due
         self.rollout.synchronize()
+        if evaluator is not None:
+            evaluator.close()
+            eval_ctx.close()
         if next_check is not None:
             self.rollout.check_replicas("weights")
 

@@ -8,6 +8,10 @@ Flags as upstream (-f, -tc, -np, -gn, -gf, -d).  One deliberate difference: the 
 (`while not all(episodes_over)`, test.py:77-83) overwrites every environment's flag each step, so with test_count > 1
 it only stops when all environments happen to finish on the same step and keeps adding post-episode rewards; here an
 environment's score is frozen when its first episode ends.
+
+--device_environments true (runs of --emulator catch|bricks) plays the games on the GPU instead (paac_amd/evaluation.py:
+DeviceEvaluator): -tc up to 4096, --greedy true for the argmax action, --eval_seed for the game instances, the no-op counts
+and the sampled actions; the summary gains a 'Mean length' line.  --gif_name is refused there.
 """
 import argparse
 import os
@@ -19,7 +23,7 @@ import numpy as np
 from . import hip_ops, logger_utils
 from .paac import PAACLearner
 from .session import Session
-from .train import get_network_and_environment_creator
+from .train import bool_arg, get_network_and_environment_creator
 
 # (option strings, dest, default, type, required, help) -- names and defaults are upstream's (test.py:22-30)
 FLAGS = (
@@ -29,6 +33,13 @@ FLAGS = (
     (("-gn", "--gif_name"), "gif_name", None, str, False, "record every screen of environment i into <name><i>.gif"),
     (("-gf", "--gif_folder"), "gif_folder", "", str, False, "directory the gifs are written to"),
     (("-d", "--device"), "device", "/gpu:0", str, False, "'/gpu:N': which MI355X evaluates the policy"),
+    (("--device_environments",), "device_environments", False, bool_arg, False,
+     "play the games on the GPU (paac_amd/evaluation.py; --emulator catch|bricks runs only): -tc up to 4096, no gifs"),
+    (("--greedy",), "greedy", False, bool_arg, False,
+     "with --device_environments true: the argmax action instead of a sampled one"),
+    (("--eval_seed",), "eval_seed", None, int, False,
+     "with --device_environments true: seed of the game instances, the no-op counts and the sampled actions (default: the "
+     "training run's random_seed)"),
 )
 
 
@@ -98,8 +109,55 @@ def restore_settings(cli):
     return settings
 
 
+def check_device_flags(cli):
+    """Start-up refusals of --device_environments true (before anything touches the GPU)."""
+    from . import evaluation
+    if cli.gif_name:
+        raise ValueError("--gif_name cannot be combined with --device_environments true: the games run on the GPU and there "
+                         "are no host screens to record")
+    evaluation.check_count(cli.test_count, "test_count")
+    if cli.noops < 0:
+        raise ValueError("noops %d is negative" % cli.noops)
+
+
+def evaluate_on_device(cli, args):
+    """--device_environments true: the DeviceEvaluator (paac_amd/evaluation.py) in the place of evaluate() ->
+    (scores float32 [test_count], lengths int32 [test_count])."""
+    from . import evaluation
+    seed = cli.eval_seed if cli.eval_seed is not None else int(getattr(args, "random_seed", 3))
+    network_creator, env_creator = get_network_and_environment_creator(args, random_seed=seed)
+    spec = getattr(env_creator, "device_env_spec", None)
+    evaluation.check_env_spec(spec)
+    network = network_creator()
+    ctx = hip_ops.Context(network.arch_id, env_creator.num_actions, max_batch=min(cli.test_count, evaluation.MAX_CHUNK),
+                          device_index=network.torch_device.index or 0)
+    session = Session(network, ctx)
+    network.init(os.path.join(cli.folder, 'checkpoints'), network.make_saver(), session)
+    evaluator = evaluation.DeviceEvaluator(network, ctx, spec, cli.test_count, noops=cli.noops, greedy=cli.greedy, seed=seed)
+    try:
+        return evaluator.run()
+    finally:
+        evaluator.close()
+        session.close()
+        ctx.close()
+
+
+def print_summary(args, rewards, lengths=None):
+    print('Performed {} tests for {}.'.format(args.test_count, args.game))
+    for label, stat in (('Mean', np.mean), ('Min', np.min), ('Max', np.max), ('Std', np.std)):
+        print('{0}: {1:.2f}'.format(label, stat(rewards)))
+    if lengths is not None:
+        print('Mean length: {0:.2f}'.format(np.mean(lengths)))
+
+
 def main(argv=None):
     cli = get_arg_parser().parse_args(argv)
+    if cli.device_environments:
+        check_device_flags(cli)
+        args = restore_settings(cli)
+        rewards, lengths = evaluate_on_device(cli, args)
+        print_summary(args, rewards, lengths)
+        return rewards
     args = restore_settings(cli)
     seed = int(np.random.RandomState(int(time.time())).randint(1000))
     network_creator, env_creator = get_network_and_environment_creator(args, random_seed=seed)
@@ -116,9 +174,7 @@ def main(argv=None):
     finally:
         session.close()
         ctx.close()
-    print('Performed {} tests for {}.'.format(args.test_count, args.game))
-    for label, stat in (('Mean', np.mean), ('Min', np.min), ('Max', np.max), ('Std', np.std)):
-        print('{0}: {1:.2f}'.format(label, stat(rewards)))
+    print_summary(args, rewards)
     return rewards
 
 

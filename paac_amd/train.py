@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import environment_creator, logger_utils, parallel
+from . import environment_creator, evaluation, logger_utils, parallel
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -99,6 +99,13 @@ BUILD_FLAGS = (
     (("--adv_norm",), "adv_norm", False, bool_arg,
      "normalise each rollout's advantages by their own mean and standard deviation before the actor term reads them (per "
      "rank under data parallelism); the critic target and the recorded advantages are unchanged"),
+    (("--eval_every",), "eval_every", 0, int,
+     "device loop, --emulator catch|bricks: score the current policy on --eval_count held-out game instances (seed random_seed "
+     "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "
+     "steps, on the GPU, and write an 'eval' record to metrics.jsonl; 0 = off.  Training is bit-identical with it on or off"),
+    (("--eval_count",), "eval_count", 64, int, "environments (one episode each) of an --eval_every evaluation, 1 to 4096"),
+    (("--eval_greedy",), "eval_greedy", True, bool_arg,
+     "--eval_every evaluations take the argmax action (true) or sample from the policy on a Philox stream of their own (false)"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),
@@ -142,6 +149,9 @@ def get_network_and_environment_creator(args, random_seed=3):
     return network_creator, env_creator
 
 
+check_eval_flags = evaluation.check_train_flags      # (args, world_size) -> on?; raises ValueError with the refusal
+
+
 def _stop(learner, owner_pid, signum, frame):
     """First signal: ask the training loop to stop at the next cycle boundary (it then runs cleanup() itself, with
     nothing in flight on the GPU and, data parallel, every rank leaving at the same cycle).  Second signal: clean up
@@ -176,6 +186,7 @@ def main(args):
     G * ec per step), gradients are summed over RCCL once per update, rank 0 writes checkpoints / args / metrics."""
     world = parallel.init_from_env(args)          # before anything touches a GPU
     logging.debug('Configuration: %s', args)
+    check_eval_flags(args, world)                 # --eval_every's refusals, before a learner exists
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)
     setup_kill_signal_handler(learner)

@@ -581,6 +581,15 @@ int paac_debug_report_zero(int sampler_workgroup);
  * (-1 = size heuristic), ksplit = blockIdx.z K split (0 = heuristic), xcd_dim = grid dimension tied to the XCD. */
 int paac_debug_set_tuning(paac_ctx* ctx, int op, int batch_class, int cfg, int ksplit, int xcd_dim);
 int paac_debug_get_tuning(paac_ctx* ctx, int op, int batch_class, int* cfg, int* ksplit, int* xcd_dim);
+/* Which configuration ids the launchers have (no ctx, no device).  paac_debug_cfg_known: 1 when `cfg` is an id op `op` runs --
+ * an entry of its family's table on the plain path, + 100 on the exact-bf16 path (conv1 only), + 200 on the split-bf16
+ * path, + 300 with narrow tiles (forward), an id whose path does not instantiate the entry counting as its plain form; any
+ * cfg < 0 (the size heuristic); for op 11 any value (region counts the tower does not have mean "by batch") -- else 0.
+ * paac_debug_set_tuning and PAAC_TUNE_OVERRIDE refuse an id that is not known, and a launcher handed one fails its call.
+ * paac_debug_cfg_body: the id of the table entry that runs for `cfg` (cfg itself where its path instantiates it, its plain
+ * form where the launchers fall back), -1 for the heuristic / automatic choice, -2 for an id that is not known. */
+int paac_debug_cfg_known(int op, int cfg);
+int paac_debug_cfg_body(int op, int cfg);
 
 /* The user architecture compiled into this library: returns 1 and fills nconv (2 or 3), filters3[3] (0 for an absent third
  * layer) and fc_width; returns 0 (and zeros) for the stock library. */

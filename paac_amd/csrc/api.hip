@@ -71,6 +71,7 @@ bool arch_supported(int arch) {
 int64_t wslab_floats_needed(int arch);
 size_t tower_pack_bytes();
 void default_tuning(paac_ctx* c);
+int cfg_body(int op, int cfg);      // net_bwd.hip: -2 = an id the launchers refuse
 int fc_splits_max();
 
 static const char* kFamilyNames[PAAC_PROF_FAMILIES] = {
@@ -165,11 +166,28 @@ int paac_create(const paac_cfg* cfg, paac_ctx** out) {
   // paac_debug_set_tuning), so that a whole bench.py run can be taken with another launch configuration
   if (const char* ov = getenv("PAAC_TUNE_OVERRIDE")) {
     int op, cls, cf, ks, xc, used = 0;
-    while (sscanf(ov, "%d:%d:%d:%d:%d%n", &op, &cls, &cf, &ks, &xc, &used) == 5) {
-      if (op >= 0 && op < OP_COUNT && cls >= 0 && cls < 3) c->tune[op][cls] = Tune{cf, ks, xc};
+    // every entry is applied or refused: an unreadable entry, an op / class outside the table or a configuration id the
+    // launchers do not have fails the creation (a typo must not time a run with another configuration -- or none)
+    while (*ov) {
+      const bool read = sscanf(ov, "%d:%d:%d:%d:%d%n", &op, &cls, &cf, &ks, &xc, &used) == 5;
+      const bool ends = read && (ov[used] == ',' || ov[used] == 0);
+      if (!ends || op < 0 || op >= OP_COUNT || cls < 0 || cls > 2 || cfg_body(op, cf) < -1) {
+        char entry[48];
+        size_t n = strcspn(ov, ",");
+        if (n >= sizeof(entry)) n = sizeof(entry) - 1;
+        memcpy(entry, ov, n);
+        entry[n] = 0;
+        if (!ends) set_error("paac_create: PAAC_TUNE_OVERRIDE entry \"%s\" is not op:class:cfg:ksplit:xcd", entry);
+        else if (op < 0 || op >= OP_COUNT || cls < 0 || cls > 2)
+          set_error("paac_create: PAAC_TUNE_OVERRIDE entry \"%s\": op %d / class %d outside the table (ops 0..%d, classes 0..2)",
+                    entry, op, cls, OP_COUNT - 1);
+        else set_error("paac_create: PAAC_TUNE_OVERRIDE entry \"%s\": op %d has no configuration id %d", entry, op, cf);
+        delete c;
+        return -1;
+      }
+      c->tune[op][cls] = Tune{cf, ks, xc};
       ov += used;
-      if (*ov != ',') break;
-      ++ov;
+      if (*ov == ',') ++ov;
     }
   }
   const int64_t B = cfg->max_batch;
@@ -733,9 +751,13 @@ int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, in
 
 int paac_debug_set_tuning(paac_ctx* ctx, int op, int batch_class, int cfg, int ksplit, int xcd_dim) {
   PAAC_REQUIRE(ctx && op >= 0 && op < OP_COUNT && batch_class >= 0 && batch_class <= 2, "paac_debug_set_tuning: bad op/class");
+  PAAC_REQUIRE(cfg_body(op, cfg) >= -1, "paac_debug_set_tuning: op %d has no configuration id %d (paac_debug_cfg_known)", op, cfg);
   ctx->tune[op][batch_class] = Tune{cfg, ksplit, xcd_dim};
   return 0;
 }
+
+int paac_debug_cfg_known(int op, int cfg) { return cfg_body(op, cfg) >= -1 ? 1 : 0; }
+int paac_debug_cfg_body(int op, int cfg) { return cfg_body(op, cfg); }
 
 int paac_debug_get_tuning(paac_ctx* ctx, int op, int batch_class, int* cfg, int* ksplit, int* xcd_dim) {
   PAAC_REQUIRE(ctx && op >= 0 && op < OP_COUNT && batch_class >= 0 && batch_class <= 2 && cfg && ksplit && xcd_dim,

@@ -28,26 +28,37 @@ static void resolve_dgrad(const GemmArgs& g, int zdim, Tune t, int& cfg, int& xc
   }
 }
 
+// Returns 0, or -1 (error set) for a configuration id outside the tables.
 template <class G, int NDIM, int BCO, int EPI>
-static void launch_dgrad(const GemmArgs& g, int zdim, Tune t, hipStream_t s) {
+static int launch_dgrad(const GemmArgs& g, int zdim, Tune t, hipStream_t s) {
   int cfg, xcd;
   resolve_dgrad<NDIM, EPI>(g, zdim, t, cfg, xcd);
+  const int body = canon_dgrad(cfg);      // the id of the body that runs (net_common.h); run or refused, never skipped
+  if (body < 0) {
+    set_error("launch_dgrad: configuration id %d is not in the data-gradient tables", cfg);
+    return -1;
+  }
+  cfg = body;
   if (cfg >= kSplitBf16) {
     switch (cfg - kSplitBf16) {
 #define X(id, TM, NWM, WK, PF) \
-  case id: launch_dmm<DgradBody<G, NDIM, BCO, EPI, TM, NWM, WK, split_pf(PF), 2>>(g, zdim, 1, xcd, s); return;
+  case id: launch_dmm<DgradBody<G, NDIM, BCO, EPI, TM, NWM, WK, split_pf(PF), 2>>(g, zdim, 1, xcd, s); return 0;
       PAAC_DGRAD_SPLIT_CFGS(X)
 #undef X
-      default: cfg -= kSplitBf16; break;
+      default: break;
     }
+    set_error("launch_dgrad: split-bf16 id %d has no case", cfg);
+    return -1;
   }
   switch (cfg) {
 #define X(id, TM, NWM, WK, PF) \
-  case id: launch_dmm<DgradBody<G, NDIM, BCO, EPI, TM, NWM, WK, PF>>(g, zdim, 1, xcd, s); break;
+  case id: launch_dmm<DgradBody<G, NDIM, BCO, EPI, TM, NWM, WK, PF>>(g, zdim, 1, xcd, s); return 0;
     PAAC_DGRAD_CFGS(X)
 #undef X
     default: break;
   }
+  set_error("launch_dgrad: id %d has no case", cfg);
+  return -1;
 }
 
 // wgrad: A = FRAG_MN patches^T (16*TM features per wave), B = FRAG_MN dY; split-K slabs + bias-gradient row.
@@ -80,28 +91,31 @@ static void resolve_wgrad(const GemmArgs& g, int max_split, Tune t, int& cfg, in
   }
   if (ks < 1) ks = 1;
   if (ks > max_split) ks = max_split;
-  const int plain = cfg % kExactBf16;
-  if (U8 && (plain == 4 || plain == 5)) cfg -= plain;   // u8 patches are loaded as uchar4: 64 features per wave only
-  if (U8 && cfg >= kSplitBf16) cfg = kExactBf16 + plain;              // u8 operand: exact path, not the split one
-  if (!U8 && cfg >= kExactBf16 && cfg < kSplitBf16) cfg = plain;
+  cfg = canon_wgrad(cfg, U8);      // the id of the body that runs (net_common.h), kCfgUnknown for an id outside the tables
 }
 
+// Returns the K split, -1 (error set) for a configuration id outside the tables.
 template <class G, bool U8, int NDIM>
 static int launch_wgrad(const GemmArgs& g, int max_split, Tune t, hipStream_t s) {
   int cfg, ks, xcd;
   resolve_wgrad<U8, NDIM>(g, max_split, t, cfg, ks, xcd);
+  if (cfg < 0) {
+    set_error("launch_wgrad: configuration id %d is not in the weight-gradient tables", t.cfg);
+    return -1;
+  }
   if constexpr (U8) {
     if (cfg >= kExactBf16) {
       switch (cfg - kExactBf16) {
-#define X(id, TM, WK, PF)                                                                         \
-  case id:                                                                                        \
-    if constexpr (TM == 4) launch_dmm<WgradBody<G, U8, NDIM, TM, WK, PF, 1>>(g, ks, ks, xcd, s); \
+#define X(id, TM, WK, PF)                                                                                       \
+  case id:                                                                                                      \
+    if constexpr (TM == 4) { launch_dmm<WgradBody<G, U8, NDIM, TM, WK, PF, 1>>(g, ks, ks, xcd, s); return ks; } \
     break;
         PAAC_WGRAD_CFGS(X)
 #undef X
         default: break;
       }
-      return ks;
+      set_error("launch_wgrad: exact-bf16 id %d has no case", cfg);
+      return -1;
     }
   }
   if constexpr (!U8) {
@@ -111,20 +125,23 @@ static int launch_wgrad(const GemmArgs& g, int max_split, Tune t, hipStream_t s)
   case id: launch_dmm<WgradBody<G, U8, NDIM, TM, WK, split_pf(PF), 2>>(g, ks, ks, xcd, s); return ks;
         PAAC_WGRAD_SPLIT_CFGS(X)
 #undef X
-        default: cfg -= kSplitBf16; break;
+        default: break;
       }
+      set_error("launch_wgrad: split-bf16 id %d has no case", cfg);
+      return -1;
     }
   }
   switch (cfg) {
-#define X(id, TM, WK, PF)                                                                   \
-  case id:                                                                                  \
-    if constexpr (!U8 || TM == 4) launch_dmm<WgradBody<G, U8, NDIM, TM, WK, PF>>(g, ks, ks, xcd, s); \
+#define X(id, TM, WK, PF)                                                                                            \
+  case id:                                                                                                           \
+    if constexpr (!U8 || TM == 4) { launch_dmm<WgradBody<G, U8, NDIM, TM, WK, PF>>(g, ks, ks, xcd, s); return ks; } \
     break;
     PAAC_WGRAD_CFGS(X)
 #undef X
     default: break;
   }
-  return ks;
+  set_error("launch_wgrad: id %d has no case", cfg);
+  return -1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -432,7 +449,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       launch_k(gemm3_kernel<D>, dim3((unsigned)(a.MB * a.NB)), dim3(D::THREADS), s, PROF_WHOLE, a);
     } else if (!fc_wgrad_held) {
       ProfScope ps(ctx, F_FC_WGRAD, batch, s);
-      launch_wgrad<typename NT::GFC, false, NT::H>(gw, 1, ctx->tune[OP_FC_WGRAD][cls], s);
+      if (launch_wgrad<typename NT::GFC, false, NT::H>(gw, 1, ctx->tune[OP_FC_WGRAD][cls], s) < 0) return -1;
     }
     ProfScope ps(ctx, F_FC_DGRAD, batch, s);
     if (batch >= gemm3_min_rows && (NT::H % 32) == 0) {
@@ -470,7 +487,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
         launch_k(fc_dgrad_once_kernel<D>, dim3(NT::FLAT / 16), dim3(D::THREADS), s, PROF_WHOLE, a);
       }
     } else {
-      launch_dgrad<typename NT::GFCH, NT::FLAT, NT::H, EPI_MASK>(gd, 1, ctx->tune[OP_FC_DGRAD][cls], s);
+      if (launch_dgrad<typename NT::GFCH, NT::FLAT, NT::H, EPI_MASK>(gd, 1, ctx->tune[OP_FC_DGRAD][cls], s) < 0) return -1;
     }
   }
   if (!do_conv) return 0;
@@ -490,7 +507,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     resolve_wgrad<false, NT::C3>(gw, W_SPLITS_MAX, ctx->tune[OP_CONV3_WGRAD][cls], c3, k3, x3);
     if (fc_wgrad_held && c3 != 1) {        // not the pair's configuration: the held-back launch goes out on its own
       ProfScope ps(ctx, F_FC_WGRAD, batch, s);
-      launch_wgrad<typename NT::GFC, false, NT::H>(held_gw, 1, ctx->tune[OP_FC_WGRAD][cls], s);
+      if (launch_wgrad<typename NT::GFC, false, NT::H>(held_gw, 1, ctx->tune[OP_FC_WGRAD][cls], s) < 0) return -1;
       fc_wgrad_held = false;
     }
     if (fc_wgrad_held) {
@@ -508,6 +525,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     } else {
       ProfScope ps(ctx, F_CONV3_WGRAD, batch, s);
       splits = launch_wgrad<typename NT::G3, false, NT::C3>(gw, W_SPLITS_MAX, ctx->tune[OP_CONV3_WGRAD][cls], s);
+      if (splits < 0) return -1;
     }
     if (ctx->tower_on) {
       // conv3 AND conv2 data gradients in one launch (dgrad_tower.h): da2 -> dact[1], da1 -> dact[0]
@@ -540,7 +558,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       launch_k(dgrad_tower_kernel, dim3((unsigned)(batch + hg.blocks)), dim3(512), s, PROF_WHOLE, da, hg);
     } else if constexpr (NT::FAMILY) {
       ProfScope ps(ctx, F_CONV3_DGRAD, batch, s);
-      launch_dgrad<typename NT::G3D, NT::C2, NT::C3, EPI_MASK>(gd, 1, ctx->tune[OP_CONV3_DGRAD][cls], s);
+      if (launch_dgrad<typename NT::G3D, NT::C2, NT::C3, EPI_MASK>(gd, 1, ctx->tune[OP_CONV3_DGRAD][cls], s) < 0) return -1;
     } else {
       ProfScope ps(ctx, F_CONV3_DGRAD, batch, s);
       launch_dgrad_direct<typename NT::G3, NT::C3>(ctx->dact[2], w3, W.act[1], ctx->dact[1], batch, s);
@@ -566,7 +584,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       launch_dgrad_direct<typename NT::G2, NT::C2>(ctx->dact[1], w2, W.act[0], ctx->dact[0], batch, s);
     } else if (!(NT::NCONV == 3 && ctx->tower_on)) {     // Nature with the tower: done by dgrad_tower_kernel above
       ProfScope ps(ctx, F_CONV2_DGRAD, batch, s);
-      launch_dgrad<typename NT::G2D, NT::C1, NT::C2, EPI_MASK_PARITY>(gd, 4, ctx->tune[OP_CONV2_DGRAD][cls], s);
+      if (launch_dgrad<typename NT::G2D, NT::C1, NT::C2, EPI_MASK_PARITY>(gd, 4, ctx->tune[OP_CONV2_DGRAD][cls], s) < 0) return -1;
     }
     int splits = 0;
     // The conv2 and conv1 weight gradients wait on the data-gradient tower only, and a workgroup of each fits a CU
@@ -601,6 +619,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     if (splits == 0) {
       ProfScope ps(ctx, F_CONV2_WGRAD, batch, s);
       splits = launch_wgrad<typename NT::G2, false, NT::C2>(gw, W_SPLITS_MAX, ctx->tune[OP_CONV2_WGRAD][cls], s);
+      if (splits < 0) return -1;
     }
     wgrad_out(i_w2, feats, NT::C2, slab, splits);
     slab += (long)W_SPLITS_MAX * (feats + 1) * NT::C2;
@@ -615,6 +634,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       GemmArgs g = make_args(states, (size_t)batch * 28224, ctx->dact[0], (size_t)batch * P1 * NT::C1 * 4, slab, nullptr, feats, NT::C1, batch * P1, NT::C1, NT::C1);
       g.slab_rows = feats + 1;
       splits = launch_wgrad<typename NT::G1, true, NT::C1>(g, W_SPLITS_MAX, ctx->tune[OP_CONV1_WGRAD][cls], s);
+      if (splits < 0) return -1;
     }
     wgrad_out(i_w1, feats, NT::C1, slab, splits);
   }
@@ -672,6 +692,28 @@ int64_t wslab_floats_needed(int arch) {
 }  // namespace paac
 
 namespace paac {
+// The body configuration id `cfg` of op `op` names, by the launchers' own rules (net_common.h: canon_*): the id of the table
+// entry that runs, -1 for the size heuristic / the tower's automatic region count, kCfgUnknown for an id the launchers
+// refuse.  Context-free: the narrow forward bodies are counted where a 64-column layer has them (conv2 / conv3 of the
+// three-conv trunk); a narrower layer runs the same ids in their plain form.
+int cfg_body(int op, int cfg) {
+  if (op < 0 || op >= OP_COUNT) return kCfgUnknown;
+  if (op == OP_CONV_TOWER)      // regions per sample the tower launchers accept (net_fwd.hip); anything else = automatic
+    return (cfg == 1 || cfg == 2 || cfg == 4 || cfg == 8 || cfg == 9) ? cfg : -1;
+  if (cfg < 0) return -1;
+  switch (op) {
+    case OP_CONV1_FWD: return canon_fwd(cfg, true, false);
+    case OP_CONV2_FWD:
+    case OP_CONV3_FWD: return canon_fwd(cfg, false, true);
+    case OP_FC_FWD: return canon_fwd(cfg, false, false);
+    case OP_FC_DGRAD:
+    case OP_CONV3_DGRAD:
+    case OP_CONV2_DGRAD: return canon_dgrad(cfg);
+    case OP_CONV1_WGRAD: return canon_wgrad(cfg, true);
+    default: return canon_wgrad(cfg, false);      // OP_FC_WGRAD, OP_CONV3_WGRAD, OP_CONV2_WGRAD
+  }
+}
+
 // Launch tuning measured on MI355X with tools/tune_gemm.py on the benchmark shapes (Nature, 32 envs x t_max 5:
 // batch 32 acting, 160 training; profiles/r01_tune_gemm.txt).  The sweep is flat -- the size heuristics are within
 // 1 us of the best everywhere except the entries below; anything else (other archs, larger batches) keeps the

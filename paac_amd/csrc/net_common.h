@@ -143,5 +143,68 @@ constexpr int kNarrow = 300;       // ... with half-width N tiles (32 columns pe
 constexpr int kSplitBf16 = 200;   // ... on the six-product split-bf16 path (fp32 operands; dmm.h: XB = 2)
 constexpr int split_pf(int pf) { return pf > 2 ? 2 : pf; }   // a stage is two K groups there: shallower ring
 
+// ---------------------------------------------------------------------------------------------
+// Which body a configuration id names.  One set of rules, generated from the tables above, for the launchers
+// (net_fwd.hip: launch_fwd; net_bwd.hip: launch_dgrad, launch_wgrad) and for the context-free query
+// paac_debug_cfg_known / paac_debug_cfg_body (api.hip): canon_*() turns an id >= 0 into the id of the body that runs --
+// the id itself where it is instantiated on the path it names, its plain form where the launchers fall back to it -- or
+// kCfgUnknown.  The launchers switch on the canonical id and fail on anything their tables do not hold, so an id is
+// either run or refused, never skipped.
+constexpr int kCfgUnknown = -2;
+#define PAAC_CFG_IS4(id, a, b, c, d) || x == id
+#define PAAC_CFG_IS3(id, a, b, c) || x == id
+#define PAAC_CFG_ONE4(id, a, b, c, d) +1
+#define PAAC_CFG_ONE3(id, a, b, c) +1
+constexpr bool fwd_cfg(int x) { return false PAAC_FWD_CFGS(PAAC_CFG_IS4); }
+constexpr bool fwd_split_cfg(int x) { return false PAAC_FWD_SPLIT_CFGS(PAAC_CFG_IS4); }
+constexpr bool fwd_narrow_cfg(int x) { return false PAAC_FWD_NARROW_CFGS(PAAC_CFG_IS4); }
+constexpr bool dgrad_cfg(int x) { return false PAAC_DGRAD_CFGS(PAAC_CFG_IS4); }
+constexpr bool dgrad_split_cfg(int x) { return false PAAC_DGRAD_SPLIT_CFGS(PAAC_CFG_IS4); }
+constexpr bool wgrad_cfg(int x) { return false PAAC_WGRAD_CFGS(PAAC_CFG_IS3); }
+constexpr bool wgrad_split_cfg(int x) { return false PAAC_WGRAD_SPLIT_CFGS(PAAC_CFG_IS3); }
+static_assert(0 PAAC_FWD_CFGS(PAAC_CFG_ONE4) == kFwdCfgs && 0 PAAC_DGRAD_CFGS(PAAC_CFG_ONE4) == kDgradCfgs &&
+              0 PAAC_WGRAD_CFGS(PAAC_CFG_ONE3) == kWgradCfgs, "table sizes");
+
+// u8: the layer reads the u8 frames (conv1).  narrow_bodies: the half-width bodies exist for this layer (64-column tiles
+// with the bias + ReLU epilogue); elsewhere a narrow id is its plain form.
+constexpr int canon_fwd(int cfg, bool u8, bool narrow_bodies) {
+  if (u8) return fwd_cfg(cfg >= kExactBf16 ? cfg - kExactBf16 : cfg) ? cfg : kCfgUnknown;   // plain or exact-bf16, nothing else
+  if (cfg >= kNarrow) {
+    if (narrow_bodies && fwd_narrow_cfg(cfg - kNarrow)) return cfg;
+    cfg -= kNarrow;
+  }
+  if (cfg >= kSplitBf16) {
+    if (fwd_split_cfg(cfg - kSplitBf16)) return cfg;
+    cfg -= kSplitBf16;                      // not instantiated on the split path: its fp32 form
+  }
+  return fwd_cfg(cfg) ? cfg : kCfgUnknown;
+}
+constexpr int canon_dgrad(int cfg) {
+  if (cfg >= kSplitBf16) {
+    if (dgrad_split_cfg(cfg - kSplitBf16)) return cfg;
+    cfg -= kSplitBf16;
+  }
+  return dgrad_cfg(cfg) ? cfg : kCfgUnknown;
+}
+constexpr int canon_wgrad(int cfg, bool u8) {
+  int plain = cfg % kExactBf16;
+  if (u8) {
+    // u8 patches are loaded as uchar4: 64 features per wave only (entries 4 and 5 run as entry 0); the u8 operand has the
+    // plain and the exact-bf16 path, and an id of a later path is the exact one
+    if (plain == 4 || plain == 5) {
+      cfg -= plain;
+      plain = 0;
+    }
+    if (cfg >= kSplitBf16) cfg = kExactBf16 + plain;
+    return wgrad_cfg(plain) ? cfg : kCfgUnknown;
+  }
+  if (cfg >= kExactBf16 && cfg < kSplitBf16) cfg = plain;     // fp32 operands have no exact path
+  if (cfg >= kSplitBf16) {
+    if (wgrad_split_cfg(cfg - kSplitBf16)) return cfg;
+    cfg -= kSplitBf16;
+  }
+  return wgrad_cfg(cfg) ? cfg : kCfgUnknown;
+}
+
 
 }  // namespace paac

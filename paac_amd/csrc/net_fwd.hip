@@ -23,7 +23,8 @@ extern "C" void paac_debug_set_stamps(unsigned long long* p, int which) {
 }
 #endif
 
-// Forward conv/fc: A = FRAG_K patches, B = FRAG_MN weights [K,N].  N per wave = 16*VN.
+// Forward conv/fc: A = FRAG_K patches, B = FRAG_MN weights [K,N].  N per wave = 16*VN.  Returns the K split, -1 (error set)
+// for a configuration id outside the tables.
 template <class G, bool U8, int NDIM, int EPI>
 static int launch_fwd(const GemmArgs& g, Tune t, hipStream_t s) {
   constexpr int VN = (NDIM % 64 == 0) ? 4 : (NDIM % 32 == 0) ? 2 : 1;
@@ -42,30 +43,41 @@ static int launch_fwd(const GemmArgs& g, Tune t, hipStream_t s) {
     if (U8) cfg += kExactBf16;   // the u8 operand always takes the exact-bf16 path (faster at every size measured)
     xcd = -1;
   }
+  // the id of the body that runs (net_common.h: canon_fwd); every switch below ends in a failure, so that an id is run
+  // or refused -- a table row without a case cannot leave the layer's output as it was
+  constexpr bool kNarrowBodies = !U8 && VN == 4 && EPI == EPI_BIAS_RELU;
+  const int body = canon_fwd(cfg, U8, kNarrowBodies);
+  if (body < 0) {
+    set_error("launch_fwd: configuration id %d is not in the forward tables", cfg);
+    return -1;
+  }
+  cfg = body;
   if constexpr (U8) {
     if (cfg >= kExactBf16) {   // conv1 on the bf16 MFMA with exactly split weights (dmm.h: XB), same tile table
       switch (cfg - kExactBf16) {
 #define X(id, TM, NWM, WK, PF) \
-  case id: launch_dmm<Dmm<G, U8, FRAG_K, FRAG_MN, TM, VN, NWM, 1, WK, 1, EPI, false, PF, 1>>(g, ksplit, ksplit, xcd, s); break;
+  case id: launch_dmm<Dmm<G, U8, FRAG_K, FRAG_MN, TM, VN, NWM, 1, WK, 1, EPI, false, PF, 1>>(g, ksplit, ksplit, xcd, s); return ksplit;
         PAAC_FWD_CFGS(X)
 #undef X
         default: break;
       }
-      return ksplit;
+      set_error("launch_fwd: exact-bf16 id %d has no case", cfg);
+      return -1;
     }
   }
-  if constexpr (!U8 && VN == 4 && EPI == EPI_BIAS_RELU) {
+  if constexpr (kNarrowBodies) {
     if (cfg >= kNarrow) {
       switch (cfg - kNarrow) {
 #define X(id, TM, NWM, WK, PF) \
   case id: launch_dmm<Dmm<G, U8, FRAG_K, FRAG_MN, TM, 2, NWM, 1, WK, 1, EPI, false, PF>>(g, ksplit, ksplit, xcd, s); return ksplit;
         PAAC_FWD_NARROW_CFGS(X)
 #undef X
-        default: cfg -= kNarrow; break;
+        default: break;
       }
+      set_error("launch_fwd: narrow id %d has no case", cfg);
+      return -1;
     }
   }
-  if (cfg >= kNarrow) cfg -= kNarrow;
   if constexpr (!U8) {
     if (cfg >= kSplitBf16) {
       switch (cfg - kSplitBf16) {
@@ -73,18 +85,21 @@ static int launch_fwd(const GemmArgs& g, Tune t, hipStream_t s) {
   case id: launch_dmm<Dmm<G, U8, FRAG_K, FRAG_MN, TM, VN, NWM, 1, WK, 1, EPI, false, split_pf(PF), 2>>(g, ksplit, ksplit, xcd, s); return ksplit;
         PAAC_FWD_SPLIT_CFGS(X)
 #undef X
-        default: cfg -= kSplitBf16; break;   // not instantiated on the split path: its fp32 form
+        default: break;
       }
+      set_error("launch_fwd: split-bf16 id %d has no case", cfg);
+      return -1;
     }
   }
   switch (cfg) {
 #define X(id, TM, NWM, WK, PF) \
-  case id: launch_dmm<Dmm<G, U8, FRAG_K, FRAG_MN, TM, VN, NWM, 1, WK, 1, EPI, false, PF>>(g, ksplit, ksplit, xcd, s); break;
+  case id: launch_dmm<Dmm<G, U8, FRAG_K, FRAG_MN, TM, VN, NWM, 1, WK, 1, EPI, false, PF>>(g, ksplit, ksplit, xcd, s); return ksplit;
     PAAC_FWD_CFGS(X)
 #undef X
     default: break;
   }
-  return ksplit;
+  set_error("launch_fwd: id %d has no case", cfg);
+  return -1;
 }
 
 // fc forward at large training batches on the LDS-tiled split-bf16 GEMM (gemm3.h): split-K slabs like launch_fwd's
@@ -331,13 +346,13 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
     ProfScope ps(ctx, F_CONV1_FWD, batch, s);
     constexpr int P1 = NT::G1::OPIX, F1 = NT::G1::FEATS;
     GemmArgs g = make_args(states, (size_t)batch * 28224, w1, (size_t)F1 * NT::C1 * 4, W.act[0], b1, batch * P1, NT::C1, F1, NT::C1, NT::C1);
-    launch_fwd<typename NT::G1, true, NT::C1, EPI_BIAS_RELU>(g, ctx->tune[OP_CONV1_FWD][cls], s);
+    if (launch_fwd<typename NT::G1, true, NT::C1, EPI_BIAS_RELU>(g, ctx->tune[OP_CONV1_FWD][cls], s) < 0) return -1;
   }
   if (!tower && !tower2) {
     ProfScope ps(ctx, F_CONV2_FWD, batch, s);
     constexpr int P1 = NT::G1::OPIX, P2 = NT::G2::OPIX, F2 = NT::G2::FEATS;
     GemmArgs g = make_args(W.act[0], (size_t)batch * P1 * NT::C1 * 4, w2, (size_t)F2 * NT::C2 * 4, W.act[1], b2, batch * P2, NT::C2, F2, NT::C2, NT::C2);
-    launch_fwd<typename NT::G2, false, NT::C2, EPI_BIAS_RELU>(g, ctx->tune[OP_CONV2_FWD][cls], s);
+    if (launch_fwd<typename NT::G2, false, NT::C2, EPI_BIAS_RELU>(g, ctx->tune[OP_CONV2_FWD][cls], s) < 0) return -1;
   }
   const float* last = W.act[1];
   if constexpr (NT::NCONV == 3) {
@@ -349,7 +364,7 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
     ProfScope ps(ctx, F_CONV3_FWD, batch, s);
     constexpr int P2 = NT::G2::OPIX, P3 = NT::G3::OPIX, F3 = NT::G3::FEATS;
     GemmArgs g = make_args(W.act[1], (size_t)batch * P2 * NT::C2 * 4, w3, (size_t)F3 * NT::C3 * 4, W.act[2], b3, batch * P3, NT::C3, F3, NT::C3, NT::C3);
-    launch_fwd<typename NT::G3, false, NT::C3, EPI_BIAS_RELU>(g, ctx->tune[OP_CONV3_FWD][cls], s);
+    if (launch_fwd<typename NT::G3, false, NT::C3, EPI_BIAS_RELU>(g, ctx->tune[OP_CONV3_FWD][cls], s) < 0) return -1;
     last = W.act[2];
   }
   // Small acting / evaluation batches: fc with the head contractions folded into its epilogue (fc_heads.h), then the
@@ -414,6 +429,7 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
     g.slab_rows = batch;
     splits = launch_fc_gemm3(last, wf, W.fc_slab, batch, NT::FLAT, NT::H, s);
     if (splits == 0) splits = launch_fwd<typename NT::GFC, false, NT::H, EPI_SLAB>(g, ctx->tune[OP_FC_FWD][cls], s);
+    if (splits < 0) return -1;
   }
   if (wsi == 1) ctx->heads_pending_rows = 0;
   if (trunk_only && wsi == 1) {      // the backward's first launch finishes the heads (heads.h: heads_train_kernel)

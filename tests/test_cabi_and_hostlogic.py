@@ -26,6 +26,23 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().paac_version() >= 100
 
 
+def test_cfg_query_needs_no_device_and_follows_the_table_sizes():
+    """paac_debug_cfg_known / paac_debug_cfg_body (what paac_debug_set_tuning and PAAC_TUNE_OVERRIDE validate with): the
+    plain band of every op has the number of entries csrc/net_common.h states; the exhaustive walk is tests/test_tuning_table_gpu.py."""
+    from paac_amd import _lib
+    lib = _lib.load()
+    src = open(os.path.join(ROOT, "paac_amd", "csrc", "net_common.h")).read()
+    n_fwd, n_dgrad, n_wgrad = map(int, re.search(r"kFwdCfgs = (\d+), kDgradCfgs = (\d+), kWgradCfgs = (\d+);", src).groups())
+    want = {0: n_fwd, 1: n_fwd, 2: n_fwd, 3: n_fwd, 4: n_wgrad, 5: n_dgrad, 6: n_wgrad, 7: n_dgrad, 8: n_wgrad, 9: n_dgrad,
+            10: n_wgrad}
+    for op, n in want.items():
+        assert [c for c in range(100) if lib.paac_debug_cfg_known(op, c)] == list(range(n)), op
+        assert lib.paac_debug_cfg_known(op, -1) == 1 and lib.paac_debug_cfg_body(op, n) == -2
+    assert lib.paac_debug_cfg_known(1, 113) == 0 and lib.paac_debug_cfg_known(0, 112) == 1       # exact-bf16: conv1 only
+    assert lib.paac_debug_cfg_body(1, 205) == 5 and lib.paac_debug_cfg_body(1, 204) == 204          # split path or its plain form
+    assert lib.paac_debug_cfg_known(11, 3) == 1 and lib.paac_debug_cfg_known(12, 0) == 0           # tower: any; no such op
+
+
 def test_param_layout_matches_oracle_order():
     from oracle import network as onet
     from paac_amd import _lib

@@ -87,10 +87,16 @@ def test_forward_parity_at_trained_magnitudes(arch, A, B, scale):
         assert ref["pi"].min() < 5.9604645e-08          # rows the sampler sees as p - epsneg < 0
 
 
-def _forward_parity(arch, A, B, weight_scale):
+def _forward_parity(arch, A, B, weight_scale, prepare=None, records=None):
+    """prepare(ctx): called on the fresh context (e.g. to force launch configurations); records: a list that receives the
+    profiler's (family, batch, ms, mix) records of the forward (tests that assert which route ran)."""
     from paac_amd import hip_ops
     params, states, idx, y, adv = make_case(arch, A, B, seed=1, weight_scale=weight_scale)
     ctx = hip_ops.Context(ARCH_ID[arch], A, max_batch=max(B, 8))
+    if prepare is not None:
+        prepare(ctx)
+    if records is not None:
+        ctx.prof_enable(True)
     p = upload_params(ctx, params)
     s = torch.from_numpy(states).cuda()
     logits = torch.zeros((B, A), device="cuda")
@@ -98,6 +104,9 @@ def _forward_parity(arch, A, B, weight_scale):
     values = torch.zeros((B,), device="cuda")
     ctx.forward(p, s, logits, probs, values)
     torch.cuda.synchronize()
+    if records is not None:
+        records.extend(ctx.prof_read(with_mix=True))
+        ctx.prof_enable(False)
     ref = onet.forward(params, states, arch, dtype=np.float64, keep=True)
     check_activations(ctx, ref["cache"], arch, B, weight_scale)
     # north_star tolerance: logits / values within 1e-4 of the reference-equivalent CPU path
@@ -115,9 +124,16 @@ def test_managed_acting_forward_parity(A, B, scale):
     """The acting forward of the learner (managed weights: conv tower -> fc with the head contractions in its epilogue ->
     heads finish by one workgroup up to 64 rows, by a few -- heads_finish_rows_kernel -- up to 256) against the oracle: the
     128- and 256-environment shards' policy step."""
+    _managed_forward_parity(A, B, scale)
+
+
+def _managed_forward_parity(A, B, scale, prepare=None, records=None):
+    """(prepare / records: as in _forward_parity)"""
     from paac_amd import hip_ops
     params, states, idx, y, adv = make_case("NATURE", A, B, seed=5, weight_scale=scale)
     ctx = hip_ops.Context(ARCH_ID["NATURE"], A, max_batch=B)
+    if prepare is not None:
+        prepare(ctx)
     p = upload_params(ctx, params)
     ctx.set_managed_weights(True)
     ctx.pack_weights(p)
@@ -125,8 +141,13 @@ def test_managed_acting_forward_parity(A, B, scale):
     logits = torch.zeros((B, A), device="cuda")
     probs = torch.zeros((B, A), device="cuda")
     values = torch.zeros((B,), device="cuda")
+    if records is not None:
+        ctx.prof_enable(True)
     ctx.forward(p, s, logits, probs, values)
     torch.cuda.synchronize()
+    if records is not None:
+        records.extend(ctx.prof_read(with_mix=True))
+        ctx.prof_enable(False)
     ref = onet.forward(params, states, "NATURE", dtype=np.float64)
     if scale != 1.0:
         assert np.abs(ref["logits"]).max() > 4.0 and np.abs(ref["v"]).max() > 2.0
@@ -195,17 +216,25 @@ def test_backward_parity_at_trained_magnitudes(arch, A, B, scale):
     _backward_parity(arch, A, B, scale)
 
 
-def _backward_parity(arch, A, B, weight_scale):
+def _backward_parity(arch, A, B, weight_scale, prepare=None, records=None):
+    """(prepare / records: as in _forward_parity; the records cover the training forward and the backward)"""
     from paac_amd import hip_ops
     params, states, idx, y, adv = make_case(arch, A, B, seed=2, weight_scale=weight_scale)
     ctx = hip_ops.Context(ARCH_ID[arch], A, max_batch=B)
+    if prepare is not None:
+        prepare(ctx)
     p = upload_params(ctx, params)
     s = torch.from_numpy(states).cuda()
     grad = torch.zeros(ctx.layout["total"], device="cuda")
     loss = torch.zeros(4, device="cuda")
+    if records is not None:
+        ctx.prof_enable(True)
     ctx.loss_backward(p, s, torch.from_numpy(idx).cuda(), torch.from_numpy(y).cuda(), torch.from_numpy(adv).cuda(),
                       0.02, grad, loss)
     torch.cuda.synchronize()
+    if records is not None:
+        records.extend(ctx.prof_read(with_mix=True))
+        ctx.prof_enable(False)
     # ReLU masks are taken from the device activations: a pre-activation within rounding of 0 may legitimately
     # land on either side under a different summation order; the forward test bounds the activations themselves.
     nconv = 3 if arch == "NATURE" else 2
@@ -584,6 +613,10 @@ def test_trunk_forward_with_heads_in_the_backward_is_bit_identical(arch, A, T, N
     value head of the bootstrap rows ride in the backward's first launch (three-conv network, whole backward), or run as
     the launch that was left out (other networks / phases / small batches).  Gradient, returns, loss terms, schedule and
     the update equal paac_train_forward + paac_loss_backward_returns(v_boot=values[B:]) bit for bit."""
+    _trunk_forward_fused_heads_bit_identity(arch, A, T, N, phase)
+
+
+def _trunk_forward_fused_heads_bit_identity(arch, A, T, N, phase):
     from paac_amd import hip_ops, _lib
     B = T * N
     params, states, idx, _, _ = make_case(arch, A, B + N, seed=31)

@@ -509,11 +509,27 @@ int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* a
                      float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, int single_life,
                      paac_stream_t stream);
 
+/* Device-resident rally environments: a two-paddle game with an opponent (a ball flies between the agent's two-cell paddle in
+ * the bottom row and a scripted opponent's in the top row; +1 when the opponent misses, -1 when the agent does, first to five
+ * points, at most 1000 steps per episode) on the same 14 x 14 board, rendered into the same [N,84,84,4] u8 observations; spec
+ * in paac_amd/rally.py, a BaseEnvironment plugin producing the same numbers on the host.  6 actions, ALE Pong's minimal set:
+ * 0 noop, 1 fire (= noop), 2 right, 3 left, 4 rightfire (= right), 5 leftfire (= left).
+ *   state: i32 [N,12] per environment {bx, by, dx, dy, px, ox, mine, theirs, steps, k, 0, 0}; the episode-start, serve and
+ *          opponent-laziness hashes are keyed by (seed, env_offset + e, k).  The step trusts its records, as bricks' does.
+ * paac_rally_reset / paac_rally_step: the argument lists, outputs, records and refusals of paac_catch_reset /
+ *   paac_catch_step.  One launch. */
+int paac_rally_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                     paac_stream_t stream);
+int paac_rally_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                    int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                    float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
+                    paac_stream_t stream);
+
 /* GPU-resident evaluation of the stateful games (spec: paac_amd/evaluation.py): one evaluation step of N environments in one
  * launch, behind the acting forward that wrote probs [N, A].  With t = *step_base_dev + step_offset (base NULL = 0; a captured
  * block of steps replays with a fresh base, paac_counter_add) and g = env_offset + e:
  *   no-ops   noops_e = word 0 of philox4x32-10(ctr = {g, 0, 0, 0x45560002}; key = eval_seed) % (noops + 1); noops = 0: none
- *   action   t < noops_e: 0 (both games' no-op); else greedy != 0: argmax of probs[e] (lowest index on ties; NaN rows are not
+ *   action   t < noops_e: 0 (every game's no-op); else greedy != 0: argmax of probs[e] (lowest index on ties; NaN rows are not
  *            supported), greedy == 0: paac_sample_philox's inverse CDF on u = philox(ctr = {g, t lo, t hi, 0x45560001};
  *            key = eval_seed) -- streams of their own (the rollout sampler's is 0, the minibatch shuffles' 0x504D0000 + epoch);
  *            written to actions_out[e]
@@ -524,9 +540,10 @@ int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* a
  *            the no-op steps are ignored; after done nothing of e changes again (the game itself keeps being stepped).
  *            The caller zeroes score / length / done and sets *alive = N before step 0.
  * The rollout bookkeeping (ep_reward / ep_len / finished ring) is not touched.  Refused with a message, without a launch:
- * the in-place buffers above, N <= 0, A outside [2, 32], noops < 0, a game id that is neither of the two. */
+ * the in-place buffers above, N <= 0, A outside [2, 32], noops < 0, a game id that is none of the three. */
 #define PAAC_EVAL_CATCH 0
 #define PAAC_EVAL_BRICKS 1
+#define PAAC_EVAL_RALLY 2
 int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
                    const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
                    const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out,

@@ -19,7 +19,7 @@ PPO_EPOCHS_MAX = 16            # PAAC_PPO_EPOCHS_MAX
 PPO_MINIBATCHES_MAX = 16       # PAAC_PPO_MINIBATCHES_MAX
 PPO_STEPS_MAX = 64             # PAAC_PPO_STEPS_MAX: optimizer steps (epochs x minibatches) of one cycle
 MINIBATCH_MAX_ROWS = 8192      # PAAC_MINIBATCH_MAX_ROWS
-EVAL_CATCH, EVAL_BRICKS = 0, 1 # PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS
+EVAL_CATCH, EVAL_BRICKS, EVAL_RALLY = 0, 1, 2          # PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS, PAAC_EVAL_RALLY
 
 
 class Layout(ctypes.Structure):
@@ -116,6 +116,9 @@ _SIGNATURES = {
     "paac_bricks_reset": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
     "paac_bricks_step": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "paac_rally_reset": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
+    "paac_rally_step": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "paac_eval_step": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_void_p, c_uint64, c_uint64, c_uint32,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),

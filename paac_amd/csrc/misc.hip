@@ -4,6 +4,7 @@
 #include "synth_dev.h"
 #include "catch_dev.h"
 #include "bricks_dev.h"
+#include "rally_dev.h"
 #include "fc_heads.h"
 #include "heads.h"
 #include "tower.h"
@@ -1432,6 +1433,49 @@ __global__ __launch_bounds__(256) void bricks_step_kernel(uint64_t seed, uint32_
   if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
 }
 
+// Rally environments (spec: paac_amd/rally.py); device helpers in rally_dev.h.  The shape of bricks_step_kernel: grid (N, 7),
+// 256 threads, 252 of them own one quad -- one 16-byte load of the old stack, requested before the state record is looked at,
+// one 16-byte store (and the optional second one), no LDS.  The new state is a pure function of (state_in[e], actions[e]):
+// every band workgroup of an environment recomputes it in registers (the opponent's look-ahead included: at most five
+// iterations, the same in every thread of the workgroup), one thread of band 0 writes it out and does the bookkeeping.
+// Nothing is updated in place.  state_in == nullptr: reset.
+__global__ __launch_bounds__(256) void rally_step_kernel(uint64_t seed, uint32_t env_offset, int N,
+                                                         const int32_t* __restrict__ actions,
+                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
+                                                         int32_t* __restrict__ state_out2,
+                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                         uint32_t* __restrict__ stack_out2, float* rewards_out,
+                                                         float* masks_out, float* ep_reward, int32_t* ep_len,
+                                                         FinishedRing* fin) {
+  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
+  const int e = blockIdx.x;
+  const int band = blockIdx.y;
+  const int i = threadIdx.x;
+  const bool owner = i < QUADS_PER_BAND;
+  const int q = band * QUADS_PER_BAND + i;
+  const long quad = (long)e * (OBS_PIX / 4) + q;
+  uint4 old = make_uint4(0u, 0u, 0u, 0u);
+  RallyState s;
+  float r = 0.f;
+  bool term = false;
+  if (state_in) {
+    // every thread loads (the four that own no quad read the band's first one): see bricks_step_kernel
+    old = reinterpret_cast<const uint4*>(stack_in)[owner ? quad : quad - i];
+    s = rally_advance(seed, env_offset + (uint32_t)e, rally_load(state_in, e), actions[e], &r, &term);
+  } else {
+    s = rally_start(seed, env_offset + (uint32_t)e, 0);
+  }
+  if (band == 0 && i == 0) {
+    rally_store(state_out, e, s);
+    if (state_out2) rally_store(state_out2, e, s);
+    if (state_in) env_bookkeep(r, term, e, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
+  }
+  if (!owner) return;
+  const uint4 outv = rally_shift_quad(s, q, old, term);    // a terminal step drops the history it loaded
+  reinterpret_cast<uint4*>(stack_out)[quad] = outv;
+  if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
+}
+
 // =============================================================================================
 // GPU-resident evaluation (spec: paac_amd/evaluation.py): one evaluation step of N environments of a stateful game per launch
 // -- the action is chosen from the acting forward's probs, the game advances, the first scored episode is accounted.  The
@@ -1470,6 +1514,18 @@ struct EvalBricks {
   }
 };
 
+struct EvalRally {
+  typedef RallyState State;
+  static __device__ __forceinline__ State load(const int32_t* __restrict__ st, int e) { return rally_load(st, e); }
+  static __device__ __forceinline__ void store(int32_t* __restrict__ st, int e, const State& s) { rally_store(st, e, s); }
+  static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, float* r, bool* term) {
+    return rally_advance(seed, env, s, a, r, term);
+  }
+  static __device__ __forceinline__ uint4 shift_quad(const State& s, int q, uint4 old, bool fresh) {
+    return rally_shift_quad(s, q, old, fresh);
+  }
+};
+
 template <class G>
 __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict__ probs, int A, int greedy, uint64_t eval_seed,
                                                         int noops, const uint64_t* __restrict__ step_base, uint64_t step_off,
@@ -1496,7 +1552,7 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
     noops_e = c[0] % ((uint32_t)noops + 1u);
   }
   const bool playing = t >= (uint64_t)noops_e;
-  int act = 0;                                             // the no-op of both games
+  int act = 0;                                             // the no-op of every game
   if (playing) {
     const float* __restrict__ p = probs + (long)e * A;
     if (greedy) {
@@ -2700,12 +2756,41 @@ int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* a
   return 0;
 }
 
+int paac_rally_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                     paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && state_out && stack_out, "paac_rally_reset: bad arguments");
+  hipLaunchKernelGGL(rally_step_kernel, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
+                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                     (int32_t*)nullptr, (FinishedRing*)nullptr);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_rally_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                    int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                    float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
+                    paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
+               ep_len, "paac_rally_step: bad arguments");
+  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
+               "paac_rally_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+  launch_k(rally_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
+           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
+           ep_reward, ep_len, (FinishedRing*)finished);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
                    const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
                    const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out,
                    float* score, int32_t* length, int32_t* done, int32_t* alive, paac_stream_t stream) {
-  PAAC_REQUIRE(game == PAAC_EVAL_CATCH || game == PAAC_EVAL_BRICKS, "paac_eval_step: game %d is neither catch (%d) nor bricks (%d)",
-               game, PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS);
+  PAAC_REQUIRE(game == PAAC_EVAL_CATCH || game == PAAC_EVAL_BRICKS || game == PAAC_EVAL_RALLY,
+               "paac_eval_step: game %d is none of catch (%d), bricks (%d), rally (%d)", game, PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS,
+               PAAC_EVAL_RALLY);
   PAAC_REQUIRE(N > 0, "paac_eval_step: N=%d", N);
   PAAC_REQUIRE(A >= 2 && A <= 32, "paac_eval_step: A=%d outside [2, 32]", A);
   PAAC_REQUIRE(noops >= 0, "paac_eval_step: noops=%d is negative", noops);
@@ -2719,8 +2804,12 @@ int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint6
     launch_k(eval_step_kernel<EvalCatch>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
              step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
              (uint32_t*)stack_out, actions_out, score, length, done, alive);
-  else
+  else if (game == PAAC_EVAL_BRICKS)
     launch_k(eval_step_kernel<EvalBricks>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
+             step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
+             (uint32_t*)stack_out, actions_out, score, length, done, alive);
+  else
+    launch_k(eval_step_kernel<EvalRally>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
              step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
              (uint32_t*)stack_out, actions_out, score, length, done, alive);
   PAAC_CHECK_HIP(hipGetLastError());

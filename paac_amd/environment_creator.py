@@ -5,11 +5,12 @@ emulator that is out of this build's scope, so the 
 environments of paac_amd/synthetic.py; `num_actions` per game is ALE's minimal action-set size (pinned for
 breakout/qbert/seaquest by the reference's pretrained/*/checkpoints/*.index actor_output_biases shapes).
 `--emulator catch` creates the catch game of paac_amd/catch.py instead (3 actions, whatever `-g` says), `--emulator bricks`
-the brick-wall game of paac_amd/bricks.py (3 actions, lives: `--single_life_episodes` applies).
+the brick-wall game of paac_amd/bricks.py (3 actions, lives: `--single_life_episodes` applies), `--emulator rally` the
+two-paddle game of paac_amd/rally.py (6 actions, ALE Pong's minimal set; no lives).
 A user environment plugs in exactly as in the reference: subclass BaseEnvironment and return it from
 create_environment(i).
 """
-from . import bricks, catch
+from . import bricks, catch, rally
 from .synthetic import SyntheticEnvironment, terminal_threshold
 
 # ALE minimal action set sizes.
@@ -35,14 +36,18 @@ class EnvironmentCreator(object):
             return
         self._device_twin = True
         self._game = getattr(args, "emulator", "synthetic")
-        if self._game in ("catch", "bricks"):
-            # paac_amd/catch.py, paac_amd/bricks.py: games of their own (-g is ignored), 3 actions; no raw-screen form
+        if self._game in ("catch", "bricks", "rally"):
+            # paac_amd/catch.py, paac_amd/bricks.py, paac_amd/rally.py: games of their own (-g is ignored), 3 actions (rally: 6);
+            # no raw-screen form
             if self._raw():
                 raise ValueError("--emulator %s has no raw 210x160 frames: --synthetic_raw_frames applies to --emulator "
                                  "synthetic only" % self._game)
             if self._game == "catch":
                 self.num_actions = catch.NUM_ACTIONS
                 self.create_environment = lambda i: catch.CatchEnvironment(i, seed=self._seed())
+            elif self._game == "rally":
+                self.num_actions = rally.NUM_ACTIONS
+                self.create_environment = lambda i: rally.RallyEnvironment(i, seed=self._seed())
             else:
                 self.num_actions = bricks.NUM_ACTIONS
                 self.create_environment = lambda i: bricks.BricksEnvironment(i, seed=self._seed(),
@@ -73,6 +78,8 @@ class EnvironmentCreator(object):
             return None
         if self._game == "catch":
             return dict(kind="catch", seed=self._seed())
+        if self._game == "rally":
+            return dict(kind="rally", seed=self._seed())
         if self._game == "bricks":
             return dict(kind="bricks", seed=self._seed(), single_life=self._single_life())
         return dict(kind="synthetic", seed=self._seed(), terminal_threshold=terminal_threshold(self._terminal_p()),

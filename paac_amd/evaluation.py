@@ -1,6 +1,6 @@
-"""GPU-resident evaluation of the device games: many episodes of `--emulator catch|bricks` scored without the host.
+"""GPU-resident evaluation of the device games: many episodes of `--emulator catch|bricks|rally` scored without the host.
 
-This is the SPEC of an evaluation, as catch.py and bricks.py are the specs of the games; the same numbers are produced
+This is the SPEC of an evaluation, as catch.py, bricks.py and rally.py are the specs of the games; the same numbers are produced
   * on the host by the plain-numpy functions below (`eval_noops`, `eval_action`, `account`, `replay_on_twins`), and
   * on the device by paac_eval_step (csrc/misc.hip; include/paac_hip.h has the contract), one evaluation step of N
     environments per launch, driven by `DeviceEvaluator`.
@@ -12,14 +12,14 @@ Spec
                0x504D0000 + epoch, so an evaluation never shares random words with training, whatever the seeds.
   no-ops       environment g starts with noops_g = word 0 of philox(g, 0, 0, EVAL_STREAM_NOOP) % (noops + 1) no-op steps
                (noops = 0: none) -- the reproducible stand-in for random.randint(0, noops) of the host loop (test.py)
-  action       step t < noops_g: the game's no-op, action 0 in both games.  Otherwise, greedy: argmax of the probabilities, the
+  action       step t < noops_g: the game's no-op, action 0 in every game.  Otherwise, greedy: argmax of the probabilities, the
                lowest index on ties (a NaN row is not a supported input); sampled: the throughput sampler's rule, the first j
                with u < p_0 + .. + p_j on float32 running sums, else A - 1, with u = the 24 high bits of word 0 of
                philox(g, t lo, t hi, EVAL_STREAM_ACTION) * 2^-24
   accounting   the host loop's rule, per environment: rewards and terminals of the no-op steps are ignored (the game resets
                itself there); from t = noops_g on the reward is added to score_g and length_g grows by one, until the first
                terminal step at t >= noops_g, whose reward is included; then done_g = 1 and nothing of g changes again
-  bound        max_steps = noops + the game's longest episode (paac.STATEFUL_KINDS: 13 for catch, 500 for bricks): every
+  bound        max_steps = noops + the game's longest episode (paac.STATEFUL_KINDS: 13 for catch, 500 for bricks, 1000 for rally): every
                environment is done by then; a smaller max_steps given by hand leaves done_g = 0
   game         the games' own specs, single_life off (test.py's restore_settings forces it off too); environment g of an
                evaluation is game environment g of the game seed, whatever the chunking
@@ -141,7 +141,7 @@ def check_env_spec(env_spec):
     from .paac import STATEFUL_KINDS
     kind = None if env_spec is None else env_spec.get("kind", "synthetic")
     if kind not in STATEFUL_KINDS:
-        raise ValueError("device evaluation plays the games resident on the GPU only: --emulator catch|bricks (got %s; the "
+        raise ValueError("device evaluation plays the games resident on the GPU only: --emulator catch|bricks|rally (got %s; the "
                          "synthetic reward is a hash, and ALE or user plugins are stepped on the host)"
                          % ("a host-only environment" if kind is None else "'%s'" % kind))
     return kind
@@ -157,8 +157,8 @@ def check_train_flags(args, world_size=1):
     check_count(getattr(args, "eval_count", 64), "eval_count")
     if getattr(args, "host_environments", False):
         raise ValueError("--eval_every evaluates on the device games: it cannot be combined with --host_environments true")
-    if getattr(args, "emulator", "synthetic") not in ("catch", "bricks"):
-        raise ValueError("--eval_every needs a game resident on the GPU: --emulator catch|bricks (got '%s')"
+    if getattr(args, "emulator", "synthetic") not in ("catch", "bricks", "rally"):
+        raise ValueError("--eval_every needs a game resident on the GPU: --emulator catch|bricks|rally (got '%s')"
                          % getattr(args, "emulator", "synthetic"))
     if int(world_size) > 1:
         raise ValueError("--eval_every is not built for data-parallel runs (world size %d): evaluate the checkpoints with "

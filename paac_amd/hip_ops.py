@@ -720,6 +720,7 @@ def synth_step(seed, env_offset, actions, terminal_threshold, step_base_dev, ste
 
 CATCH_STATE_WORDS = 8            # int32 words of a catch environment's state record (paac_amd/catch.py)
 BRICKS_STATE_WORDS = 12          # ... of a bricks environment's (paac_amd/bricks.py)
+RALLY_STATE_WORDS = 12           # ... of a rally environment's (paac_amd/rally.py)
 
 
 def _stateful_reset(entry, words, seed, env_offset, state_out, stack_out):
@@ -777,18 +778,29 @@ def bricks_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_
                    rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2, extra=(bool(single_life),))
 
 
-EVAL_GAMES = {"catch": (_lib.EVAL_CATCH, CATCH_STATE_WORDS), "bricks": (_lib.EVAL_BRICKS, BRICKS_STATE_WORDS)}
+def rally_reset(seed, env_offset, state_out, stack_out):
+    _stateful_reset("paac_rally_reset", RALLY_STATE_WORDS, seed, env_offset, state_out, stack_out)
+
+
+def rally_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
+               finished=None, stack_out2=None, state_out2=None):
+    _stateful_step("paac_rally_step", RALLY_STATE_WORDS, seed, env_offset, actions, state_in, state_out, stack_in, stack_out,
+                   rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2)
+
+
+EVAL_GAMES = {"catch": (_lib.EVAL_CATCH, CATCH_STATE_WORDS), "bricks": (_lib.EVAL_BRICKS, BRICKS_STATE_WORDS),
+              "rally": (_lib.EVAL_RALLY, RALLY_STATE_WORDS)}
 
 
 def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
               stack_in, stack_out, actions_out, score, length, done, alive):
-    """One evaluation step of N environments of `game` ('catch' / 'bricks') on probs [N, A] (include/paac_hip.h:
+    """One evaluation step of N environments of `game` ('catch' / 'bricks' / 'rally') on probs [N, A] (include/paac_hip.h:
     paac_eval_step; spec in paac_amd/evaluation.py): the action (no-op, argmax or the evaluation's own Philox stream) into
     actions_out, the game stepped from state_in / stack_in into state_out / stack_out, the first scored episode accounted in
     score / length / done [N] and alive [1].  Shapes are checked here; the library refuses in-place buffers, A outside [2, 32]
     and negative noops with a PaacHipError, before any launch."""
     if game not in EVAL_GAMES:
-        raise ValueError("eval_step: game %r has no device evaluation (--emulator catch|bricks)" % (game,))
+        raise ValueError("eval_step: game %r has no device evaluation (--emulator catch|bricks|rally)" % (game,))
     game_id, words = EVAL_GAMES[game]
     if probs.dim() != 2:
         raise ValueError("probs must be [N, A], got %s" % (tuple(probs.shape),))

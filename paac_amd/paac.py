@@ -31,6 +31,8 @@ STATEFUL_KINDS = {
                   max_episode_steps=13),
     "bricks": dict(words=hip_ops.BRICKS_STATE_WORDS, reset=hip_ops.bricks_reset, step=hip_ops.bricks_step,
                    spec_kwargs=("single_life",), max_episode_steps=500),
+    "rally": dict(words=hip_ops.RALLY_STATE_WORDS, reset=hip_ops.rally_reset, step=hip_ops.rally_step, spec_kwargs=(),
+                  max_episode_steps=1000),
 }
 
 
@@ -69,7 +71,7 @@ class DeviceRollout(object):
         self.tick = torch.zeros((1,), dtype=torch.int64, device=dev)          # env steps taken (per env)
         self.global_step_dev = torch.full((1,), int(L.global_step), dtype=torch.int64, device=dev)
         self.raw = None
-        # a stateful kind (STATEFUL_KINDS: catch, bricks): the environments carry state from step to step -- a ring of state
+        # a stateful kind (STATEFUL_KINDS: catch, bricks, rally): the environments carry state from step to step -- a ring of state
         # records beside the observation ring, slot for slot (a step reads slot t and writes slot t + 1: nothing is updated in
         # place, and the wrap-around second output goes to slot 0 of both)
         self.stateful = STATEFUL_KINDS.get(env_spec.get("kind", "synthetic"))

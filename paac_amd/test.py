@@ -9,7 +9,7 @@ Flags as upstream (-f, -tc, -np, -gn, -gf, -d).  One deliberate difference: the 
 it only stops when all environments happen to finish on the same step and keeps adding post-episode rewards; here an
 environment's score is frozen when its first episode ends.
 
---device_environments true (runs of --emulator catch|bricks) plays the games on the GPU instead (paac_amd/evaluation.py:
+--device_environments true (runs of --emulator catch|bricks|rally) plays the games on the GPU instead (paac_amd/evaluation.py:
 DeviceEvaluator): -tc up to 4096, --greedy true for the argmax action, --eval_seed for the game instances, the no-op counts
 and the sampled actions; the summary gains a 'Mean length' line.  --gif_name is refused there.
 """
@@ -34,7 +34,7 @@ FLAGS = (
     (("-gf", "--gif_folder"), "gif_folder", "", str, False, "directory the gifs are written to"),
     (("-d", "--device"), "device", "/gpu:0", str, False, "'/gpu:N': which MI355X evaluates the policy"),
     (("--device_environments",), "device_environments", False, bool_arg, False,
-     "play the games on the GPU (paac_amd/evaluation.py; --emulator catch|bricks runs only): -tc up to 4096, no gifs"),
+     "play the games on the GPU (paac_amd/evaluation.py; --emulator catch|bricks|rally runs only): -tc up to 4096, no gifs"),
     (("--greedy",), "greedy", False, bool_arg, False,
      "with --device_environments true: the argmax action instead of a sampled one"),
     (("--eval_seed",), "eval_seed", None, int, False,

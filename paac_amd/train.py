@@ -67,7 +67,10 @@ BUILD_FLAGS = (
      "'synthetic' (paac_amd/synthetic.py), 'catch' (paac_amd/catch.py: a learnable game on the GPU, 3 actions; -g, "
      "--synthetic_terminal_p and --synthetic_raw_frames do not apply), 'bricks' (paac_amd/bricks.py: a brick-wall game with "
      "three lives on the GPU, 3 actions, episodes of up to 500 steps; --single_life_episodes applies, -g, "
-     "--synthetic_terminal_p, --synthetic_raw_frames and --random_start do not) or 'ale' (Atari through an installed Arcade "
+     "--synthetic_terminal_p, --synthetic_raw_frames and --random_start do not), 'rally' (paac_amd/rally.py: a two-paddle game "
+     "against a scripted opponent on the GPU, the 6 actions of ALE Pong, rewards of both signs, first to five points, episodes "
+     "of up to 1000 steps; --single_life_episodes, -g, --synthetic_terminal_p, --synthetic_raw_frames and --random_start do not "
+     "apply) or 'ale' (Atari through an installed Arcade "
      "Learning Environment)"),
     (("--device_preprocess",), "device_preprocess", False, bool_arg,
      "host environments hand out raw screen pairs; max + resize + frame history run on the GPU"),
@@ -100,7 +103,7 @@ BUILD_FLAGS = (
      "normalise each rollout's advantages by their own mean and standard deviation before the actor term reads them (per "
      "rank under data parallelism); the critic target and the recorded advantages are unchanged"),
     (("--eval_every",), "eval_every", 0, int,
-     "device loop, --emulator catch|bricks: score the current policy on --eval_count held-out game instances (seed random_seed "
+     "device loop, --emulator catch|bricks|rally: score the current policy on --eval_count held-out game instances (seed random_seed "
      "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "
      "steps, on the GPU, and write an 'eval' record to metrics.jsonl; 0 = off.  Training is bit-identical with it on or off"),
     (("--eval_count",), "eval_count", 64, int, "environments (one episode each) of an --eval_every evaluation, 1 to 4096"),
@@ -119,7 +122,7 @@ def get_arg_parser():
         if kind is not None:
             kwargs["type"] = kind
         if dest in ("sampler", "emulator", "checkpoint_format", "optimizer"):
-            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "ale"],
+            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "rally", "ale"],
                                  "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"]}[dest]
         parser.add_argument(*options, **kwargs)
     return parser

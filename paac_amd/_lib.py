@@ -110,15 +110,6 @@ _SIGNATURES = {
     "paac_synth_step": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
-    "paac_catch_reset": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
-    "paac_catch_step": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "paac_bricks_reset": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
-    "paac_bricks_step": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "paac_rally_reset": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
-    "paac_rally_step": (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "paac_eval_step": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_void_p, c_uint64, c_uint64, c_uint32,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
@@ -151,6 +142,13 @@ _SIGNATURES = {
     "paac_user_arch": (c_int, [POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "paac_user_arch_layers": (c_int, [POINTER(c_int32), POINTER(c_int32)]),
 }
+
+# the device games (hip_ops.DEVICE_GAMES): one reset / step pair each, catch's argument list; bricks' step takes one more integer
+# (single_life) before the stream
+for _game in ("catch", "bricks", "rally"):
+    _SIGNATURES["paac_%s_reset" % _game] = (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p])
+    _SIGNATURES["paac_%s_step" % _game] = (c_int, [c_uint64, c_uint32, c_int] + [c_void_p] * 12 +
+                                           ([c_int] if _game == "bricks" else []) + [c_void_p])
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -1346,141 +1346,53 @@ __global__ __launch_bounds__(256) void synth_step_a_kernel(uint64_t seed, uint32
   synth_shift_band(seed, env_offset, id, thresh, e * PRE_BANDS + band, stack_in, stack_out, stack_out2, force_reset != 0);
 }
 
-// Catch environments (spec: paac_amd/catch.py); device helpers in catch_dev.h.  The shape of synth_step_a_kernel: grid (N, 7),
-// 256 threads, 252 of them own one quad of four pixels -- one 16-byte load of the old stack and one 16-byte store of the new
-// one per thread, no LDS.  The new state is a pure function of (state_in[e], actions[e]): every band workgroup of an
-// environment recomputes it in registers, one thread of band 0 writes it out and does the bookkeeping.  Nothing in the launch
-// writes what the launch reads: state_in / state_out and stack_in / stack_out are different buffers.
-// state_in == nullptr: reset -- episode 0's start state, an empty history; actions / stack_in / the records are not touched.
-__global__ __launch_bounds__(256) void catch_step_kernel(uint64_t seed, uint32_t env_offset, int N,
-                                                         const int32_t* __restrict__ actions,
-                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
-                                                         int32_t* __restrict__ state_out2,
-                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
-                                                         uint32_t* __restrict__ stack_out2, float* rewards_out,
-                                                         float* masks_out, float* ep_reward, int32_t* ep_len,
-                                                         FinishedRing* fin) {
-  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
-  const int e = blockIdx.x;
-  const int band = blockIdx.y;
-  const int i = threadIdx.x;
-  const bool owner = i < QUADS_PER_BAND;
-  const int q = band * QUADS_PER_BAND + i;
-  const long quad = (long)e * (OBS_PIX / 4) + q;
+// The device games (catch, bricks, rally: one trait G each, csrc/game_dev.h and the game's header).  The shape of
+// synth_step_a_kernel: grid (N, 7), 256 threads, 252 of them own one quad of four pixels -- one 16-byte load of the old stack,
+// requested before the state record is looked at (whether or not the step ends the episode: one round trip, not two), one
+// 16-byte store (and the optional second one), no LDS.  The new state is a pure function of (state_in[e], actions[e], opt):
+// every band workgroup of an environment recomputes it in registers, one thread of band 0 writes it out and does the
+// bookkeeping.  Nothing in the launch writes what the launch reads: state_in / state_out and stack_in / stack_out are different
+// buffers.  state_in == nullptr: reset -- episode 0's start state, an empty history; actions / stack_in / the records are not
+// touched.
+template <class G>
+__global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t env_offset, int N,
+                                                        const int32_t* __restrict__ actions,
+                                                        const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
+                                                        int32_t* __restrict__ state_out2,
+                                                        const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                        uint32_t* __restrict__ stack_out2, float* rewards_out,
+                                                        float* masks_out, float* ep_reward, int32_t* ep_len,
+                                                        FinishedRing* fin, int opt) {
+  const QuadThread t = quad_thread();
+  const int e = t.e;
   uint4 old = make_uint4(0u, 0u, 0u, 0u);
-  CatchState s;
-  float r = 0.f;
-  bool term = false;
-  if (state_in) {
-    // the old stack is requested before the state arrives (whether or not the step ends the episode): one round trip, not two
-    if (owner) old = reinterpret_cast<const uint4*>(stack_in)[quad];
-    s = catch_advance(seed, env_offset + (uint32_t)e, catch_load(state_in, e), actions[e], &r, &term);
-    if (term) old = make_uint4(0u, 0u, 0u, 0u);
-  } else {
-    s = catch_start(seed, env_offset + (uint32_t)e, 0);
-  }
-  if (band == 0 && i == 0) {
-    catch_store(state_out, e, s);
-    if (state_out2) catch_store(state_out2, e, s);
-    if (state_in) env_bookkeep(r, term, e, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
-  }
-  if (!owner) return;
-  const uint4 outv = catch_shift_quad(s, q, old);
-  reinterpret_cast<uint4*>(stack_out)[quad] = outv;
-  if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
-}
-
-// Bricks environments (spec: paac_amd/bricks.py); device helpers in bricks_dev.h.  The shape of catch_step_kernel: grid (N, 7),
-// 256 threads, 252 of them own one quad -- one 16-byte load of the old stack, requested before the state record is looked at,
-// one 16-byte store (and the optional second one), no LDS.  The new state is a pure function of (state_in[e], actions[e],
-// single_life): every band workgroup of an environment recomputes it in registers, one thread of band 0 writes it out and
-// does the bookkeeping.  Nothing is updated in place.  state_in == nullptr: reset.
-__global__ __launch_bounds__(256) void bricks_step_kernel(uint64_t seed, uint32_t env_offset, int N,
-                                                          const int32_t* __restrict__ actions,
-                                                          const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
-                                                          int32_t* __restrict__ state_out2,
-                                                          const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
-                                                          uint32_t* __restrict__ stack_out2, float* rewards_out,
-                                                          float* masks_out, float* ep_reward, int32_t* ep_len,
-                                                          FinishedRing* fin, int single_life) {
-  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
-  const int e = blockIdx.x;
-  const int band = blockIdx.y;
-  const int i = threadIdx.x;
-  const bool owner = i < QUADS_PER_BAND;
-  const int q = band * QUADS_PER_BAND + i;
-  const long quad = (long)e * (OBS_PIX / 4) + q;
-  uint4 old = make_uint4(0u, 0u, 0u, 0u);
-  BricksState s;
+  typename G::State s;
   float r = 0.f;
   bool term = false;
   if (state_in) {
     // every thread loads (the four that own no quad read the band's first one): with the load under a condition the compiler
     // pulls the history's shift up behind it, and with the shift the wait -- the state record would be asked for only then
-    old = reinterpret_cast<const uint4*>(stack_in)[owner ? quad : quad - i];
-    s = bricks_advance(seed, env_offset + (uint32_t)e, bricks_load(state_in, e), actions[e], single_life != 0, &r, &term);
+    old = reinterpret_cast<const uint4*>(stack_in)[t.load_quad];
+    s = G::advance(seed, env_offset + (uint32_t)e, G::load(state_in, e), actions[e], opt, &r, &term);
   } else {
-    s = bricks_start(seed, env_offset + (uint32_t)e, 0);
+    s = G::start(seed, env_offset + (uint32_t)e);
   }
-  if (band == 0 && i == 0) {
-    bricks_store(state_out, e, s);
-    if (state_out2) bricks_store(state_out2, e, s);
+  if (t.band == 0 && t.i == 0) {
+    G::store(state_out, e, s);
+    if (state_out2) G::store(state_out2, e, s);
     if (state_in) env_bookkeep(r, term, e, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
   }
-  if (!owner) return;
-  const uint4 outv = bricks_shift_quad(s, q, old, term);   // a terminal step drops the history it loaded
-  reinterpret_cast<uint4*>(stack_out)[quad] = outv;
-  if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
-}
-
-// Rally environments (spec: paac_amd/rally.py); device helpers in rally_dev.h.  The shape of bricks_step_kernel: grid (N, 7),
-// 256 threads, 252 of them own one quad -- one 16-byte load of the old stack, requested before the state record is looked at,
-// one 16-byte store (and the optional second one), no LDS.  The new state is a pure function of (state_in[e], actions[e]):
-// every band workgroup of an environment recomputes it in registers (the opponent's look-ahead included: at most five
-// iterations, the same in every thread of the workgroup), one thread of band 0 writes it out and does the bookkeeping.
-// Nothing is updated in place.  state_in == nullptr: reset.
-__global__ __launch_bounds__(256) void rally_step_kernel(uint64_t seed, uint32_t env_offset, int N,
-                                                         const int32_t* __restrict__ actions,
-                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
-                                                         int32_t* __restrict__ state_out2,
-                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
-                                                         uint32_t* __restrict__ stack_out2, float* rewards_out,
-                                                         float* masks_out, float* ep_reward, int32_t* ep_len,
-                                                         FinishedRing* fin) {
-  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
-  const int e = blockIdx.x;
-  const int band = blockIdx.y;
-  const int i = threadIdx.x;
-  const bool owner = i < QUADS_PER_BAND;
-  const int q = band * QUADS_PER_BAND + i;
-  const long quad = (long)e * (OBS_PIX / 4) + q;
-  uint4 old = make_uint4(0u, 0u, 0u, 0u);
-  RallyState s;
-  float r = 0.f;
-  bool term = false;
-  if (state_in) {
-    // every thread loads (the four that own no quad read the band's first one): see bricks_step_kernel
-    old = reinterpret_cast<const uint4*>(stack_in)[owner ? quad : quad - i];
-    s = rally_advance(seed, env_offset + (uint32_t)e, rally_load(state_in, e), actions[e], &r, &term);
-  } else {
-    s = rally_start(seed, env_offset + (uint32_t)e, 0);
-  }
-  if (band == 0 && i == 0) {
-    rally_store(state_out, e, s);
-    if (state_out2) rally_store(state_out2, e, s);
-    if (state_in) env_bookkeep(r, term, e, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
-  }
-  if (!owner) return;
-  const uint4 outv = rally_shift_quad(s, q, old, term);    // a terminal step drops the history it loaded
-  reinterpret_cast<uint4*>(stack_out)[quad] = outv;
-  if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
+  if (!t.owner) return;
+  const uint4 outv = G::shift_quad(s, t.q, old, term);     // a terminal step drops the history it loaded
+  reinterpret_cast<uint4*>(stack_out)[t.quad] = outv;
+  if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[t.quad] = outv;   // second copy (the observation ring's wrap-around slot)
 }
 
 // =============================================================================================
 // GPU-resident evaluation (spec: paac_amd/evaluation.py): one evaluation step of N environments of a stateful game per launch
 // -- the action is chosen from the acting forward's probs, the game advances, the first scored episode is accounted.  The
-// shape of the step kernels above: grid (N, 7), 256 threads, 252 of them own one quad; the stack load is requested first (by
-// every thread, the bricks kernel's reason), then the action and the new state are worked out in registers by every band
+// shape of game_step_kernel above: grid (N, 7), 256 threads, 252 of them own one quad; the stack load is requested first (by
+// every thread, game_step_kernel's reason), then the action and the new state are worked out in registers by every band
 // workgroup of the environment -- both are pure functions of (probs[e], state_in[e], t) -- and thread 0 of band 0 writes the
 // record, the action and the accounts.  state_in / stack_in are never state_out / stack_out; score / length / done of
 // environment e are read and written by that one thread only.  A finished environment keeps being stepped (parking it would
@@ -1490,42 +1402,6 @@ __global__ __launch_bounds__(256) void rally_step_kernel(uint64_t seed, uint32_t
 constexpr uint32_t kEvalStreamAction = 0x45560001u;
 constexpr uint32_t kEvalStreamNoop = 0x45560002u;
 
-struct EvalCatch {
-  typedef CatchState State;
-  static __device__ __forceinline__ State load(const int32_t* __restrict__ st, int e) { return catch_load(st, e); }
-  static __device__ __forceinline__ void store(int32_t* __restrict__ st, int e, const State& s) { catch_store(st, e, s); }
-  static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, float* r, bool* term) {
-    return catch_advance(seed, env, s, a, r, term);
-  }
-  static __device__ __forceinline__ uint4 shift_quad(const State& s, int q, uint4 old, bool fresh) {
-    return catch_shift_quad(s, q, fresh ? make_uint4(0u, 0u, 0u, 0u) : old);
-  }
-};
-
-struct EvalBricks {
-  typedef BricksState State;
-  static __device__ __forceinline__ State load(const int32_t* __restrict__ st, int e) { return bricks_load(st, e); }
-  static __device__ __forceinline__ void store(int32_t* __restrict__ st, int e, const State& s) { bricks_store(st, e, s); }
-  static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, float* r, bool* term) {
-    return bricks_advance(seed, env, s, a, false, r, term);      // evaluation plays whole episodes: single_life is off
-  }
-  static __device__ __forceinline__ uint4 shift_quad(const State& s, int q, uint4 old, bool fresh) {
-    return bricks_shift_quad(s, q, old, fresh);
-  }
-};
-
-struct EvalRally {
-  typedef RallyState State;
-  static __device__ __forceinline__ State load(const int32_t* __restrict__ st, int e) { return rally_load(st, e); }
-  static __device__ __forceinline__ void store(int32_t* __restrict__ st, int e, const State& s) { rally_store(st, e, s); }
-  static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, float* r, bool* term) {
-    return rally_advance(seed, env, s, a, r, term);
-  }
-  static __device__ __forceinline__ uint4 shift_quad(const State& s, int q, uint4 old, bool fresh) {
-    return rally_shift_quad(s, q, old, fresh);
-  }
-};
-
 template <class G>
 __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict__ probs, int A, int greedy, uint64_t eval_seed,
                                                         int noops, const uint64_t* __restrict__ step_base, uint64_t step_off,
@@ -1534,15 +1410,10 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
                                                         int32_t* __restrict__ actions_out, float* score, int32_t* length,
                                                         int32_t* done, int32_t* alive) {
-  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
-  const int e = blockIdx.x;
-  const int band = blockIdx.y;
-  const int i = threadIdx.x;
-  const bool owner = i < QUADS_PER_BAND;
-  const int q = band * QUADS_PER_BAND + i;
-  const long quad = (long)e * (OBS_PIX / 4) + q;
-  // every thread loads (the four that own no quad read the band's first one): see bricks_step_kernel
-  const uint4 old = reinterpret_cast<const uint4*>(stack_in)[owner ? quad : quad - i];
+  const QuadThread th = quad_thread();
+  const int e = th.e;
+  // every thread loads (the four that own no quad read the band's first one): see game_step_kernel
+  const uint4 old = reinterpret_cast<const uint4*>(stack_in)[th.load_quad];
   const uint32_t g = env_offset + (uint32_t)e;
   const uint64_t t = (step_base ? *step_base : 0ull) + step_off;
   uint32_t noops_e = 0u;
@@ -1581,8 +1452,9 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
   }
   float r = 0.f;
   bool term = false;
-  const typename G::State s = G::advance(env_seed, g, G::load(state_in, e), act, &r, &term);
-  if (band == 0 && i == 0) {
+  // evaluation plays whole episodes: opt = 0 (bricks' single_life is off)
+  const typename G::State s = G::advance(env_seed, g, G::load(state_in, e), act, 0, &r, &term);
+  if (th.band == 0 && th.i == 0) {
     G::store(state_out, e, s);
     actions_out[e] = act;
     if (playing && done[e] == 0) {                         // the first episode that starts after the no-ops, its last step included
@@ -1594,8 +1466,8 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
       }
     }
   }
-  if (!owner) return;
-  reinterpret_cast<uint4*>(stack_out)[quad] = G::shift_quad(s, q, old, term);
+  if (!th.owner) return;
+  reinterpret_cast<uint4*>(stack_out)[th.quad] = G::shift_quad(s, th.q, old, term);
 }
 
 // Path A with the numpy-parity sampler folded in: workgroup 0 runs the (inherently serial) MT19937 sampler and then
@@ -2442,6 +2314,48 @@ int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv
   return 0;
 }
 
+// paac_<game>_reset / paac_<game>_step of the device games: `name` is the entry point's, for the messages.
+template <class G>
+static int game_reset(const char* name, uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                      paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && state_out && stack_out, "%s: bad arguments", name);
+  hipLaunchKernelGGL(game_step_kernel<G>, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
+                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                     (int32_t*)nullptr, (FinishedRing*)nullptr, 0);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+template <class G>
+static int game_step(const char* name, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions,
+                     const int32_t* state_in, int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in,
+                     uint8_t* stack_out, uint8_t* stack_out2, float* rewards_out, float* masks_out, float* ep_reward,
+                     int32_t* ep_len, void* finished, int opt, paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
+               ep_len, "%s: bad arguments", name);
+  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
+               "%s: the step cannot run in place (every band workgroup of an environment reads state_in)", name);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+  launch_k(game_step_kernel<G>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
+           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
+           ep_reward, ep_len, (FinishedRing*)finished, opt);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// One evaluation step of game G (paac_eval_step, which has validated the arguments).
+template <class G>
+static void launch_eval_step(hipStream_t s, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
+                             const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
+                             const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out,
+                             int32_t* actions_out, float* score, int32_t* length, int32_t* done, int32_t* alive) {
+  launch_k(eval_step_kernel<G>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops, step_base_dev,
+           step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in, (uint32_t*)stack_out,
+           actions_out, score, length, done, alive);
+}
+
 }  // namespace paac
 
 using namespace paac;
@@ -2702,86 +2616,41 @@ int paac_synth_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
 
 int paac_catch_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
                      paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && state_out && stack_out, "paac_catch_reset: bad arguments");
-  hipLaunchKernelGGL(catch_step_kernel, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
-                     (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
-                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                     (int32_t*)nullptr, (FinishedRing*)nullptr);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return game_reset<CatchGame>("paac_catch_reset", seed, env_offset, N, state_out, stack_out, stream);
 }
 
 int paac_catch_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
                     int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                     paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
-               ep_len, "paac_catch_step: bad arguments");
-  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
-               "paac_catch_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
-  launch_k(catch_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
-           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
-           ep_reward, ep_len, (FinishedRing*)finished);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return game_step<CatchGame>("paac_catch_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
+                              stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, 0, stream);
 }
 
 int paac_bricks_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
                       paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && state_out && stack_out, "paac_bricks_reset: bad arguments");
-  hipLaunchKernelGGL(bricks_step_kernel, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
-                     (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
-                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                     (int32_t*)nullptr, (FinishedRing*)nullptr, 0);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return game_reset<BricksGame>("paac_bricks_reset", seed, env_offset, N, state_out, stack_out, stream);
 }
 
 int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
                      int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                      float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, int single_life,
                      paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
-               ep_len, "paac_bricks_step: bad arguments");
-  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
-               "paac_bricks_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
-  launch_k(bricks_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
-           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
-           ep_reward, ep_len, (FinishedRing*)finished, single_life);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return game_step<BricksGame>("paac_bricks_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
+                               stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, single_life, stream);
 }
 
 int paac_rally_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
                      paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && state_out && stack_out, "paac_rally_reset: bad arguments");
-  hipLaunchKernelGGL(rally_step_kernel, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
-                     (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
-                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                     (int32_t*)nullptr, (FinishedRing*)nullptr);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return game_reset<RallyGame>("paac_rally_reset", seed, env_offset, N, state_out, stack_out, stream);
 }
 
 int paac_rally_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
                     int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                     paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
-               ep_len, "paac_rally_step: bad arguments");
-  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
-               "paac_rally_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
-  launch_k(rally_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
-           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
-           ep_reward, ep_len, (FinishedRing*)finished);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return game_step<RallyGame>("paac_rally_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
+                              stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, 0, stream);
 }
 
 int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
@@ -2800,18 +2669,10 @@ int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint6
                "paac_eval_step: the step cannot run in place (every band workgroup of an environment reads state_in)");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
-  if (game == PAAC_EVAL_CATCH)
-    launch_k(eval_step_kernel<EvalCatch>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
-             step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
-             (uint32_t*)stack_out, actions_out, score, length, done, alive);
-  else if (game == PAAC_EVAL_BRICKS)
-    launch_k(eval_step_kernel<EvalBricks>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
-             step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
-             (uint32_t*)stack_out, actions_out, score, length, done, alive);
-  else
-    launch_k(eval_step_kernel<EvalRally>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed, noops,
-             step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
-             (uint32_t*)stack_out, actions_out, score, length, done, alive);
+  const auto launch = game == PAAC_EVAL_CATCH ? launch_eval_step<CatchGame>
+                                              : (game == PAAC_EVAL_BRICKS ? launch_eval_step<BricksGame> : launch_eval_step<RallyGame>);
+  launch(s, probs, N, A, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out, stack_in,
+         stack_out, actions_out, score, length, done, alive);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -20,6 +20,15 @@ GAME_NUM_ACTIONS = {
 }
 
 
+# --emulator catch | bricks | rally: the spec module, its host environment, and the options both that environment's constructor
+# and the device spec take (each read by the creator's method _<option>).
+DEVICE_GAMES = {
+    "catch": (catch, catch.CatchEnvironment, ()),
+    "bricks": (bricks, bricks.BricksEnvironment, ("single_life",)),
+    "rally": (rally, rally.RallyEnvironment, ()),
+}
+
+
 class EnvironmentCreator(object):
     def __init__(self, args):
         game = getattr(args, "game", "pong")
@@ -36,22 +45,14 @@ class EnvironmentCreator(object):
             return
         self._device_twin = True
         self._game = getattr(args, "emulator", "synthetic")
-        if self._game in ("catch", "bricks", "rally"):
-            # paac_amd/catch.py, paac_amd/bricks.py, paac_amd/rally.py: games of their own (-g is ignored), 3 actions (rally: 6);
-            # no raw-screen form
+        if self._game in DEVICE_GAMES:
+            # games of their own (-g is ignored), with their own action counts; no raw-screen form
             if self._raw():
                 raise ValueError("--emulator %s has no raw 210x160 frames: --synthetic_raw_frames applies to --emulator "
                                  "synthetic only" % self._game)
-            if self._game == "catch":
-                self.num_actions = catch.NUM_ACTIONS
-                self.create_environment = lambda i: catch.CatchEnvironment(i, seed=self._seed())
-            elif self._game == "rally":
-                self.num_actions = rally.NUM_ACTIONS
-                self.create_environment = lambda i: rally.RallyEnvironment(i, seed=self._seed())
-            else:
-                self.num_actions = bricks.NUM_ACTIONS
-                self.create_environment = lambda i: bricks.BricksEnvironment(i, seed=self._seed(),
-                                                                             single_life=self._single_life())
+            module, env_class, _ = DEVICE_GAMES[self._game]
+            self.num_actions = module.NUM_ACTIONS
+            self.create_environment = lambda i: env_class(i, seed=self._seed(), **self._game_options())
             return
         self.num_actions = int(getattr(args, "num_actions_override", 0) or GAME_NUM_ACTIONS.get(game, 6))
         # args.random_seed is set by train.get_network_and_environment_creator AFTER this constructor runs
@@ -68,6 +69,10 @@ class EnvironmentCreator(object):
     def _single_life(self):
         return bool(getattr(self.args, "single_life_episodes", False))
 
+    def _game_options(self):
+        """The options of the game (DEVICE_GAMES): keywords of the host environment and keys of the device spec alike."""
+        return {key: getattr(self, "_" + key)() for key in DEVICE_GAMES[self._game][2]}
+
     def _raw(self):
         return bool(getattr(self.args, "synthetic_raw_frames", False))
 
@@ -76,11 +81,7 @@ class EnvironmentCreator(object):
         """Device-batched twin of the same environments (PAACLearner uses it when present)."""
         if not self._device_twin:
             return None
-        if self._game == "catch":
-            return dict(kind="catch", seed=self._seed())
-        if self._game == "rally":
-            return dict(kind="rally", seed=self._seed())
-        if self._game == "bricks":
-            return dict(kind="bricks", seed=self._seed(), single_life=self._single_life())
+        if self._game in DEVICE_GAMES:
+            return dict(kind=self._game, seed=self._seed(), **self._game_options())
         return dict(kind="synthetic", seed=self._seed(), terminal_threshold=terminal_threshold(self._terminal_p()),
                     raw_frames=self._raw())

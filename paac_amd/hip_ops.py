@@ -5,6 +5,7 @@ extent on the host BEFORE the launch (a kernel that faults can take the whole no
 device pointers to libpaac_hip.so on torch's current HIP stream.
 """
 import ctypes
+import functools
 import gc
 
 import numpy as np
@@ -718,9 +719,14 @@ def synth_step(seed, env_offset, actions, terminal_threshold, step_base_dev, ste
                                            _stream()), "paac_synth_step")
 
 
-CATCH_STATE_WORDS = 8            # int32 words of a catch environment's state record (paac_amd/catch.py)
-BRICKS_STATE_WORDS = 12          # ... of a bricks environment's (paac_amd/bricks.py)
-RALLY_STATE_WORDS = 12           # ... of a rally environment's (paac_amd/rally.py)
+# The device games that carry a state record (csrc/<game>_dev.h): int32 words of a record (paac_amd/<game>.py: STATE_WORDS),
+# the id paac_eval_step knows the game by, and the keyword of the step's one integer option, which follows `finished` in
+# paac_<game>_step (None: the game has none).  The entry points are paac_<game>_reset / paac_<game>_step.
+DEVICE_GAMES = {
+    "catch": dict(words=8, eval_id=_lib.EVAL_CATCH, step_option=None),
+    "bricks": dict(words=12, eval_id=_lib.EVAL_BRICKS, step_option="single_life"),
+    "rally": dict(words=12, eval_id=_lib.EVAL_RALLY, step_option=None),
+}
 
 
 def _stateful_reset(entry, words, seed, env_offset, state_out, stack_out):
@@ -758,38 +764,27 @@ def _stateful_step(entry, words, seed, env_offset, actions, state_in, state_out,
     _lib.check(getattr(_lib.load(), entry)(*(args + [int(x) for x in extra] + [_stream()])), entry)
 
 
-def catch_reset(seed, env_offset, state_out, stack_out):
-    _stateful_reset("paac_catch_reset", CATCH_STATE_WORDS, seed, env_offset, state_out, stack_out)
+def game_reset(kind, seed, env_offset, state_out, stack_out):
+    _stateful_reset("paac_%s_reset" % kind, DEVICE_GAMES[kind]["words"], seed, env_offset, state_out, stack_out)
 
 
-def catch_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
-               finished=None, stack_out2=None, state_out2=None):
-    _stateful_step("paac_catch_step", CATCH_STATE_WORDS, seed, env_offset, actions, state_in, state_out, stack_in, stack_out,
-                   rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2)
+def game_step(kind, seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
+              finished=None, stack_out2=None, state_out2=None, **option):
+    """`option`: the game's step option by its keyword (DEVICE_GAMES: bricks' single_life, False if not given)."""
+    game = DEVICE_GAMES[kind]
+    name = game["step_option"]
+    if set(option) - {name}:
+        raise TypeError("%s_step: unexpected keyword arguments %s" % (kind, sorted(set(option) - {name})))
+    extra = (bool(option.get(name, False)),) if name else ()
+    _stateful_step("paac_%s_step" % kind, game["words"], seed, env_offset, actions, state_in, state_out, stack_in, stack_out,
+                   rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2, extra=extra)
 
 
-def bricks_reset(seed, env_offset, state_out, stack_out):
-    _stateful_reset("paac_bricks_reset", BRICKS_STATE_WORDS, seed, env_offset, state_out, stack_out)
-
-
-def bricks_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
-                finished=None, stack_out2=None, state_out2=None, single_life=False):
-    _stateful_step("paac_bricks_step", BRICKS_STATE_WORDS, seed, env_offset, actions, state_in, state_out, stack_in, stack_out,
-                   rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2, extra=(bool(single_life),))
-
-
-def rally_reset(seed, env_offset, state_out, stack_out):
-    _stateful_reset("paac_rally_reset", RALLY_STATE_WORDS, seed, env_offset, state_out, stack_out)
-
-
-def rally_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
-               finished=None, stack_out2=None, state_out2=None):
-    _stateful_step("paac_rally_step", RALLY_STATE_WORDS, seed, env_offset, actions, state_in, state_out, stack_in, stack_out,
-                   rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, state_out2)
-
-
-EVAL_GAMES = {"catch": (_lib.EVAL_CATCH, CATCH_STATE_WORDS), "bricks": (_lib.EVAL_BRICKS, BRICKS_STATE_WORDS),
-              "rally": (_lib.EVAL_RALLY, RALLY_STATE_WORDS)}
+# the games by name: catch_reset / catch_step / CATCH_STATE_WORDS, and the same for bricks and rally
+for _kind, _game in DEVICE_GAMES.items():
+    globals().update({_kind + "_reset": functools.partial(game_reset, _kind), _kind + "_step": functools.partial(game_step, _kind),
+                      _kind.upper() + "_STATE_WORDS": _game["words"]})
+EVAL_GAMES = {kind: (game["eval_id"], game["words"]) for kind, game in DEVICE_GAMES.items()}
 
 
 def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,

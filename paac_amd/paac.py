@@ -11,6 +11,7 @@ train() has two executions of the SAME cycle (paac.py:99-183):
     kernel launches and the numpy sampler/return maths by their HIP twins; actions are bit-identical to
     the reference's numpy sampler on the same np.random seed (paac_sample_mt).
 """
+import functools
 import logging
 import os
 import time
@@ -23,16 +24,18 @@ from .actor_learner import ActorLearner
 from .runners import EmulatorRunner, RawEmulatorRunner, Runners
 
 
-# Device environments that carry a state record from step to step, by env_spec["kind"]: int32 words of a record, the reset and
-# step wrappers (one argument list, catch's), the keys of the spec the step wrapper takes as keyword arguments, and the longest
-# episode of the game in steps (what bounds an evaluation: paac_amd/evaluation.py).
+# Device environments that carry a state record from step to step, by env_spec["kind"]: int32 words of a record and the reset
+# and step wrappers (one argument list, catch's) from hip_ops.DEVICE_GAMES, the keys of the spec the step wrapper takes as
+# keyword arguments, and the longest episode of the game in steps (what bounds an evaluation: paac_amd/evaluation.py).
+def _stateful_kind(kind, spec_kwargs, max_episode_steps):
+    return dict(words=hip_ops.DEVICE_GAMES[kind]["words"], reset=functools.partial(hip_ops.game_reset, kind),
+                step=functools.partial(hip_ops.game_step, kind), spec_kwargs=spec_kwargs, max_episode_steps=max_episode_steps)
+
+
 STATEFUL_KINDS = {
-    "catch": dict(words=hip_ops.CATCH_STATE_WORDS, reset=hip_ops.catch_reset, step=hip_ops.catch_step, spec_kwargs=(),
-                  max_episode_steps=13),
-    "bricks": dict(words=hip_ops.BRICKS_STATE_WORDS, reset=hip_ops.bricks_reset, step=hip_ops.bricks_step,
-                   spec_kwargs=("single_life",), max_episode_steps=500),
-    "rally": dict(words=hip_ops.RALLY_STATE_WORDS, reset=hip_ops.rally_reset, step=hip_ops.rally_step, spec_kwargs=(),
-                  max_episode_steps=1000),
+    "catch": _stateful_kind("catch", (), 13),
+    "bricks": _stateful_kind("bricks", ("single_life",), 500),
+    "rally": _stateful_kind("rally", (), 1000),
 }
 
 

@@ -36,7 +36,7 @@ def drained(fin):
     return count, sorted(zip(host[2:2 + 4096].view(np.float32)[:count].tolist(), host[2 + 4096:2 + 4096 + count].tolist()))
 
 
-@pytest.mark.parametrize("N,env_offset", [(3, 5), (33, 0)])
+@pytest.mark.parametrize("N,env_offset", [(3, 5), (33, 0), (1, 7)])
 def test_kernel_matches_twin_bit_for_bit(N, env_offset):
     from paac_amd import hip_ops
     seed, steps, W = 3, 40, hip_ops.CATCH_STATE_WORDS

@@ -175,6 +175,41 @@ def test_longest_episodes_and_bounds():
     assert evaluation.check_count(4096) == 4096 and evaluation.check_count(1) == 1
 
 
+def test_one_table_of_device_games(monkeypatch):
+    """A game's record width and evaluation id are stated once (hip_ops.DEVICE_GAMES); every other table and the named wrappers
+    follow it, and the device trait and the spec module agree with it."""
+    import re
+    from paac_amd import _lib, hip_ops, rally
+    from paac_amd.paac import STATEFUL_KINDS
+    modules = dict(catch=catch, bricks=bricks, rally=rally)
+    assert set(hip_ops.DEVICE_GAMES) == set(hip_ops.EVAL_GAMES) == set(STATEFUL_KINDS) == set(modules)
+    eval_ids = dict(catch=_lib.EVAL_CATCH, bricks=_lib.EVAL_BRICKS, rally=_lib.EVAL_RALLY)
+    csrc = os.path.join(os.path.dirname(evaluation.__file__), "csrc")
+    for kind, module in modules.items():
+        game = hip_ops.DEVICE_GAMES[kind]
+        words = module.STATE_WORDS
+        assert game["words"] == words == STATEFUL_KINDS[kind]["words"] == getattr(hip_ops, kind.upper() + "_STATE_WORDS")
+        assert hip_ops.EVAL_GAMES[kind] == (eval_ids[kind], words) == (game["eval_id"], words)
+        assert re.search(r"kWords = %d;" % words, open(os.path.join(csrc, kind + "_dev.h")).read())
+        for entry in ("paac_%s_reset" % kind, "paac_%s_step" % kind):
+            assert entry in _lib.EXPORTED_SYMBOLS
+        assert STATEFUL_KINDS[kind]["spec_kwargs"] == ((game["step_option"],) if game["step_option"] else ())
+    # the named step wrappers reach the game's entry point with its option: bricks_step keeps single_life= (default False), the
+    # games without an option refuse one
+    calls = []
+    monkeypatch.setattr(hip_ops, "_stateful_step", lambda entry, words, *args, extra=(): calls.append((entry, words, extra)))
+    hip_ops.bricks_step(*[None] * 11)
+    hip_ops.bricks_step(*[None] * 11, single_life=True)
+    STATEFUL_KINDS["bricks"]["step"](*[None] * 11, finished=None, stack_out2=None, state_out2=None, single_life=1)
+    hip_ops.catch_step(*[None] * 11)
+    hip_ops.rally_step(*[None] * 11, finished=None)
+    assert calls == [("paac_bricks_step", 12, (False,)), ("paac_bricks_step", 12, (True,)), ("paac_bricks_step", 12, (True,)),
+                     ("paac_catch_step", 8, ()), ("paac_rally_step", 12, ())]
+    for step in (hip_ops.catch_step, hip_ops.rally_step):
+        with pytest.raises(TypeError, match="single_life"):
+            step(*[None] * 11, single_life=True)
+
+
 # -- flags ---------------------------------------------------------------------------------------------------------------------
 def test_test_flags_parse_and_refuse():
     from paac_amd import test as harness

@@ -272,6 +272,37 @@ __device__ __forceinline__ void gae_step(const double gamma, const double gl, co
   const double delta = __dsub_rn(__dadd_rn((double)rw, __dmul_rn(__dmul_rn(gamma, Vn), (double)mk)), V);
   A = __dadd_rn(delta, __dmul_rn(__dmul_rn(gl, A), (double)mk));
 }
+// One step of the n-step return (paac.py:146-147) as numpy evaluates it: estimated_return starts as the FLOAT32 network
+// output vb, so the first `gamma * estimated_return` is a float32 product (python float x float32 array -> float32, in
+// numpy 1.x and 2.x alike); it is promoted to float64 by `* masks[t]` and stays float64 afterwards.  Separate
+// round-to-nearest operations (no FMA contraction) keep the scan bit-identical to numpy's.  first: the step at t = T - 1.
+__device__ __forceinline__ void nstep_step(const double gamma, const bool first, const float vb, const float rw, const float mk,
+                                           double& R) {
+  const double prod = first ? (double)__fmul_rn((float)gamma, vb) : __dmul_rn(gamma, R);
+  R = __dadd_rn((double)rw, __dmul_rn(prod, (double)mk));
+}
+
+// The per-cycle bookkeeping (paac.py:127,156; actor_learner.py:119-123), done by one thread of whichever launch computes
+// the cycle's returns -- the standalone scan, the heads gradient kernels, returns_norm_kernel -- or by paac_lr_step alone.
+struct CycleTick {
+  int64_t* global_step;     // += step_inc, then *lr_out = f32(lr0 - step*lr0/anneal), 0 past anneal; nullable: no schedule
+  int64_t step_inc;
+  double lr0;
+  int64_t anneal;
+  float* lr_out;
+  uint64_t* tick;           // += tick_inc (sampler / synthetic-env frame counter); nullable
+  uint64_t tick_inc;
+};
+__device__ __forceinline__ void cycle_tick(const CycleTick& ct) {
+  if (ct.global_step) {
+    const int64_t step = *ct.global_step + ct.step_inc;
+    *ct.global_step = step;
+    double lr = 0.0;
+    if (step <= ct.anneal) lr = ct.lr0 - ((double)step * ct.lr0 / (double)ct.anneal);
+    *ct.lr_out = (float)lr;
+  }
+  if (ct.tick) *ct.tick += ct.tick_inc;
+}
 
 bool norm_head_fits(const paac_ctx* ctx);
 int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row, hipStream_t s);

@@ -301,8 +301,8 @@ __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, in
 // The n-step returns of the rollout (paac.py:140-149) computed where they are consumed: with v_boot set, the heads
 // gradient launch derives y / adv of a row itself from the rollout records (every consumer recomputes the short scan:
 // cheaper than a launch of its own), its last block writes the y / adv arrays for the learner's records and does the
-// per-cycle bookkeeping of paac_nstep_returns_tick (global_step, lr, frame counter).  Arithmetic = nstep_returns_kernel's
-// (csrc/misc.hip), operation for operation.
+// per-cycle bookkeeping of paac_nstep_returns_tick (cycle_tick, common.h).  One step of the scan is nstep_step (common.h),
+// shared with returns_scan_kernel (csrc/misc.hip).
 struct ReturnsArgs {
   const float* v_boot;      // nullptr: y / adv are read from the arrays passed to the kernel (unless boot_in_fwd)
   int boot_in_fwd;          // the training forward covered T*N + N rows: bootstrap value of environment e = value head of
@@ -314,13 +314,7 @@ struct ReturnsArgs {
   double gamma;
   float* y_out;             // [T*N] t-major, written by the last block
   float* adv_out;
-  int64_t* global_step;     // += step_inc, then lr = f32(lr0 - step*lr0/anneal)   (actor_learner.py:119-123); nullable
-  int64_t step_inc;
-  double lr0;
-  int64_t anneal;
-  float* lr_out;
-  uint64_t* tick;           // += tick_inc; nullable
-  uint64_t tick_inc;
+  CycleTick ct;             // done once per launch, by one thread
 };
 
 __device__ __forceinline__ void nstep_row_from(const ReturnsArgs& r, const int i, const float vb, float& y, float& adv) {
@@ -328,8 +322,7 @@ __device__ __forceinline__ void nstep_row_from(const ReturnsArgs& r, const int i
   double R = 0.0;
   for (int tt = r.T - 1; tt >= t; --tt) {
     const long k = (long)tt * r.N + e;
-    const double prod = (tt == r.T - 1) ? (double)__fmul_rn((float)r.gamma, vb) : __dmul_rn(r.gamma, R);
-    R = __dadd_rn((double)r.rewards[k], __dmul_rn(prod, (double)r.masks[k]));
+    nstep_step(r.gamma, tt == r.T - 1, vb, r.rewards[k], r.masks[k], R);
   }
   y = (float)R;
   adv = (float)__dsub_rn(R, (double)r.values_act[(long)t * r.N + e]);
@@ -361,14 +354,11 @@ __device__ __forceinline__ void nstep_row_from(const ReturnsArgs& r, const int i
 #pragma unroll
   for (int k = 0; k < kNstepPre; ++k) {
     const int tt = r.T - 1 - k;
-    if (tt >= t) {
-      const double prod = (k == 0) ? (double)__fmul_rn((float)r.gamma, vb) : __dmul_rn(r.gamma, R);
-      R = __dadd_rn((double)p.rw[k], __dmul_rn(prod, (double)p.mk[k]));
-    }
+    if (tt >= t) nstep_step(r.gamma, k == 0, vb, p.rw[k], p.mk[k], R);
   }
   for (int tt = r.T - 1 - kNstepPre; tt >= t; --tt) {
     const long k = (long)tt * r.N + e;
-    R = __dadd_rn((double)r.rewards[k], __dmul_rn(__dmul_rn(r.gamma, R), (double)r.masks[k]));
+    nstep_step(r.gamma, false, vb, r.rewards[k], r.masks[k], R);
   }
   y = (float)R;
   adv = (float)__dsub_rn(R, (double)p.vact);
@@ -383,11 +373,24 @@ __device__ __forceinline__ void nstep_row(const ReturnsArgs& r, const int i, flo
 // round-to-nearest fp64 operation on the promoted fp32 inputs (no fp32 first product: that is numpy's promotion in the
 // reference's n-step loop, and there is no reference loop here):
 //   delta_t = (r_t + (gamma V_{t+1}) m_t) - V_t;  A_t = delta_t + (gl A_{t+1}) m_t;  adv_t = f32(A_t);  y_t = f32(A_t + V_t)
-// gl = gamma * lambda, formed once on the host.  One step is gae_step (common.h), shared with gae_returns_kernel (csrc/misc.hip).
+// gl = gamma * lambda, formed once on the host.  One step is gae_step (common.h), shared with returns_scan_kernel (csrc/misc.hip).
 constexpr int kEstNstep = 0, kEstGae = 1;      // == PAAC_RETURNS_NSTEP, PAAC_RETURNS_GAE (include/paac_hip.h)
 struct GaeArgs : ReturnsArgs {
   double gl;
 };
+// Host: the argument block from the C struct (ret == nullptr: all zero, the returns are not computed in the launch).  The
+// n-step instantiations take its ReturnsArgs part.  v_boot: what the kernel reads; nullptr = bootstrap rows of the forward.
+inline GaeArgs returns_args(const paac_returns* ret, const float* v_boot) {
+  GaeArgs rt;
+  memset(&rt, 0, sizeof(rt));
+  if (!ret) return rt;
+  rt.v_boot = v_boot; rt.boot_in_fwd = v_boot ? 0 : 1; rt.rewards = ret->rewards; rt.masks = ret->masks; rt.values_act = ret->values;
+  rt.T = ret->T; rt.N = ret->N; rt.gamma = ret->gamma; rt.y_out = ret->y_out; rt.adv_out = ret->adv_out;
+  rt.ct = CycleTick{ret->global_step_dev, ret->increment, ret->initial_lr, ret->lr_annealing_steps, ret->lr_out_dev,
+                    ret->tick_dev, ret->tick_inc};
+  if (ret->estimator == PAAC_RETURNS_GAE) rt.gl = ret->gamma * ret->gae_lambda;
+  return rt;
+}
 template <int EST> struct ReturnsOf { using type = ReturnsArgs; };
 template <> struct ReturnsOf<kEstGae> { using type = GaeArgs; };
 
@@ -648,16 +651,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
     for (int a = 0; a < NV; ++a) accv[a] += dl[a];
     accv[NV] += stats[0]; accv[NV + 1] += stats[1]; accv[NV + 2] += stats[2];
   }
-  if (rt.v_boot && tid == 0) {      // per-cycle bookkeeping (paac.py:127, actor_learner.py:119-123)
-    if (rt.global_step) {
-      const int64_t step = *rt.global_step + rt.step_inc;
-      *rt.global_step = step;
-      double lr = 0.0;
-      if (step <= rt.anneal) lr = rt.lr0 - ((double)step * rt.lr0 / (double)rt.anneal);
-      *rt.lr_out = (float)lr;
-    }
-    if (rt.tick) *rt.tick += rt.tick_inc;
-  }
+  if (rt.v_boot && tid == 0) cycle_tick(rt.ct);      // per-cycle bookkeeping (paac.py:127, actor_learner.py:119-123)
   block_sums_256<NS>(accv, smem, red);
   if (tid < A) gba[tid] = red[tid];
   if (tid == AP) gbc[0] = red[AP];
@@ -802,16 +796,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
     }
     row_s[AP] = yv;
     row_s[AP + 1] = av;
-    if (i == 0 && rt.rewards) {              // per-cycle bookkeeping (paac.py:127, actor_learner.py:119-123)
-      if (rt.global_step) {
-        const int64_t step = *rt.global_step + rt.step_inc;
-        *rt.global_step = step;
-        double lr = 0.0;
-        if (step <= rt.anneal) lr = rt.lr0 - ((double)step * rt.lr0 / (double)rt.anneal);
-        *rt.lr_out = (float)lr;
-      }
-      if (rt.tick) *rt.tick += rt.tick_inc;
-    }
+    if (i == 0 && rt.rewards) cycle_tick(rt.ct);      // per-cycle bookkeeping (paac.py:127, actor_learner.py:119-123)
   }
   __syncthreads();
   float pi[AP], dl[NV], stats[3];

@@ -24,93 +24,27 @@ __device__ unsigned long long* g_misc_stamps = nullptr;   // diagnostic build: p
 #endif
 
 // =============================================================================================
-// n-step returns (paac.py:140-149), fp64 scan like the reference's numpy buffers.
-struct CycleTick {          // optional bookkeeping folded into the returns kernel (one launch instead of three)
-  int64_t* global_step;     // += step_inc, then lr = f32(lr0 - step*lr0/anneal)   (actor_learner.py:119-123)
-  int64_t step_inc;
-  double lr0;
-  int64_t anneal;
-  float* lr_out;
-  uint64_t* tick;           // += tick_inc (sampler / synthetic-env frame counter)
-  uint64_t tick_inc;
-};
-
-__global__ void nstep_returns_kernel(const float* __restrict__ v_boot, const float* __restrict__ rewards,
-                                     const float* __restrict__ masks, const float* __restrict__ values, int T, int N,
-                                     double gamma, float* __restrict__ y, float* __restrict__ adv, const CycleTick ct) {
+// The returns of one rollout, standalone: the n-step return (paac.py:140-149; fp64 scan like the reference's numpy buffers)
+// or generalized advantage estimation, chosen at compile time.  One step is nstep_step / gae_step (common.h: the arithmetic
+// contracts), shared with the scans inside the heads gradient kernels (heads.h).  gl = gamma * lambda, read by GAE alone.
+template <int EST>
+__global__ void returns_scan_kernel(const float* __restrict__ v_boot, const float* __restrict__ rewards,
+                                    const float* __restrict__ masks, const float* __restrict__ values, int T, int N,
+                                    double gamma, double gl, float* __restrict__ y, float* __restrict__ adv,
+                                    const CycleTick ct) {
   // 128 threads: wave 0 scans 64 environments, wave 1 of workgroup 0 does the cycle bookkeeping -- its
   // read-modify-write round trip runs beside the scan's instead of in front of it
   const int e = blockIdx.x * 64 + (threadIdx.x & 63);
   if (threadIdx.x >= 64) {
-    if (blockIdx.x == 0 && threadIdx.x == 64) {
-      if (ct.global_step) {
-        const int64_t step = *ct.global_step + ct.step_inc;
-        *ct.global_step = step;
-        double lr = 0.0;
-        if (step <= ct.anneal) lr = ct.lr0 - ((double)step * ct.lr0 / (double)ct.anneal);
-        *ct.lr_out = (float)lr;
-      }
-      if (ct.tick) *ct.tick += ct.tick_inc;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 64) cycle_tick(ct);
     return;
   }
   if (e >= N) return;
-  // paac.py:146-147 as numpy evaluates it: estimated_return starts as the FLOAT32 network output, so the first
-  // `gamma * estimated_return` is a float32 product (python float x float32 array -> float32, in numpy 1.x
-  // and 2.x alike); it is promoted to float64 by `* masks[t]` and stays float64 afterwards.  Explicit
-  // round-to-nearest mul/add (no FMA contraction) keep the scan bit-identical to numpy's.
   // The scan is serial in t but its inputs are not: each chunk of CH steps is requested at once (one memory round
   // trip per chunk instead of one per step -- at t_max = 5 the whole kernel is a single round trip).
   constexpr int CH = 8;
   const float vb = v_boot[e];
-  double R = 0.0;
-  for (int t0 = T - 1; t0 >= 0; t0 -= CH) {
-    float r[CH], m[CH], v[CH];
-#pragma unroll
-    for (int u = 0; u < CH; ++u) {
-      const int t = t0 - u;
-      const long i = (long)(t >= 0 ? t : 0) * N + e;
-      r[u] = rewards[i];
-      m[u] = masks[i];
-      v[u] = values[i];
-    }
-#pragma unroll
-    for (int u = 0; u < CH; ++u) {
-      const int t = t0 - u;
-      if (t >= 0) {
-        const long i = (long)t * N + e;
-        const double prod = (t == T - 1) ? (double)__fmul_rn((float)gamma, vb) : __dmul_rn(gamma, R);
-        R = __dadd_rn((double)r[u], __dmul_rn(prod, (double)m[u]));
-        y[i] = (float)R;
-        adv[i] = (float)__dsub_rn(R, (double)v[u]);
-      }
-    }
-  }
-}
-
-// The GAE sibling (heads.h: gae_step is the arithmetic contract): same chunked loads, same bookkeeping wave.  gl = gamma *
-// lambda.  V_{t+1} of a chunk's first step is the previous chunk's last value (the bootstrap value at t = T - 1).
-__global__ void gae_returns_kernel(const float* __restrict__ v_boot, const float* __restrict__ rewards,
-                                   const float* __restrict__ masks, const float* __restrict__ values, int T, int N,
-                                   double gamma, double gl, float* __restrict__ y, float* __restrict__ adv,
-                                   const CycleTick ct) {
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (threadIdx.x >= 64) {
-    if (blockIdx.x == 0 && threadIdx.x == 64) {
-      if (ct.global_step) {
-        const int64_t step = *ct.global_step + ct.step_inc;
-        *ct.global_step = step;
-        double lr = 0.0;
-        if (step <= ct.anneal) lr = ct.lr0 - ((double)step * ct.lr0 / (double)ct.anneal);
-        *ct.lr_out = (float)lr;
-      }
-      if (ct.tick) *ct.tick += ct.tick_inc;
-    }
-    return;
-  }
-  if (e >= N) return;
-  constexpr int CH = 8;
-  double A = 0.0, Vn = (double)v_boot[e];
+  double S = 0.0, Vn = (double)vb;      // S: the return R (n-step) / the advantage A (GAE); Vn: GAE's V_{t+1}, v_boot at t = T - 1
   for (int t0 = T - 1; t0 >= 0; t0 -= CH) {
     float r[CH], m[CH], v[CH];
 #pragma unroll
@@ -127,10 +61,16 @@ __global__ void gae_returns_kernel(const float* __restrict__ v_boot, const float
       if (t >= 0) {
         const long i = (long)t * N + e;
         const double V = (double)v[u];
-        gae_step(gamma, gl, r[u], m[u], V, Vn, A);
-        adv[i] = (float)A;
-        y[i] = (float)__dadd_rn(A, V);
-        Vn = V;
+        if constexpr (EST == kEstGae) {
+          gae_step(gamma, gl, r[u], m[u], V, Vn, S);
+          adv[i] = (float)S;
+          y[i] = (float)__dadd_rn(S, V);
+          Vn = V;
+        } else {
+          nstep_step(gamma, t == T - 1, vb, r[u], m[u], S);
+          y[i] = (float)S;
+          adv[i] = (float)__dsub_rn(S, V);
+        }
       }
     }
   }
@@ -183,8 +123,8 @@ __global__ __launch_bounds__(kNormThreads) void adv_normalize_kernel(const float
   adv_normalize_block(adv, B, adv_n, stats, lds);
 }
 // The returns of either estimator (heads.h: nstep_row_from / gae_row_from, the scans the backward's first launch runs -- every
-// row rescans its own return, so y / adv equal nstep_returns_kernel's / gae_returns_kernel's bit for bit), the cycle
-// bookkeeping of those kernels, and the normalisation above, in one launch.
+// row rescans its own return, so y / adv equal returns_scan_kernel's bit for bit), the cycle bookkeeping of that kernel,
+// and the normalisation above, in one launch.
 template <class RT>
 __global__ __launch_bounds__(kNormThreads) void returns_norm_kernel(const RT r, float* adv_n, double* stats) {
   __shared__ double lds[kNormThreads + 32];
@@ -195,26 +135,13 @@ __global__ __launch_bounds__(kNormThreads) void returns_norm_kernel(const RT r, 
     r.y_out[i] = yv;
     r.adv_out[i] = av;        // (read back below by the thread that wrote it)
   }
-  if (tid == 0) {
-    if (r.global_step) {
-      const int64_t step = *r.global_step + r.step_inc;
-      *r.global_step = step;
-      double lr = 0.0;
-      if (step <= r.anneal) lr = r.lr0 - ((double)step * r.lr0 / (double)r.anneal);
-      *r.lr_out = (float)lr;
-    }
-    if (r.tick) *r.tick += r.tick_inc;
-  }
+  if (tid == 0) cycle_tick(r.ct);
   adv_normalize_block(r.adv_out, B, adv_n, stats, lds);
 }
 
 // actor_learner.py:119-123 evaluated after the cycle's increments (paac.py:127,156).
 __global__ void lr_step_kernel(int64_t* global_step, int64_t inc, double lr0, int64_t anneal, float* lr_out) {
-  const int64_t step = *global_step + inc;
-  *global_step = step;
-  double lr = 0.0;
-  if (step <= anneal) lr = lr0 - ((double)step * lr0 / (double)anneal);
-  *lr_out = (float)lr;
+  cycle_tick(CycleTick{global_step, inc, lr0, anneal, lr_out, nullptr, 0});
 }
 
 __global__ void counter_add_kernel(uint64_t* c, uint64_t inc) { *c += inc; }
@@ -2298,19 +2225,28 @@ int launch_sample_env_step_heads(const float* partial, int ntiles, const float* 
 
 // (arguments validated by paac_returns_norm_tick, csrc/api.hip)
 int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv_n, double* stats, hipStream_t s) {
-  GaeArgs rt;
-  memset(&rt, 0, sizeof(rt));
-  rt.v_boot = v_boot; rt.rewards = ret->rewards; rt.masks = ret->masks; rt.values_act = ret->values;
-  rt.T = ret->T; rt.N = ret->N; rt.gamma = ret->gamma; rt.y_out = ret->y_out; rt.adv_out = ret->adv_out;
-  rt.global_step = ret->global_step_dev; rt.step_inc = ret->increment; rt.lr0 = ret->initial_lr;
-  rt.anneal = ret->lr_annealing_steps; rt.lr_out = ret->lr_out_dev; rt.tick = ret->tick_dev; rt.tick_inc = ret->tick_inc;
+  const GaeArgs rt = returns_args(ret, v_boot);
   if (ret->estimator == PAAC_RETURNS_GAE) {
-    rt.gl = ret->gamma * ret->gae_lambda;
     launch_k(returns_norm_kernel<GaeArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rt, adv_n, stats);
   } else {
     const ReturnsArgs& rn = rt;
     launch_k(returns_norm_kernel<ReturnsArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rn, adv_n, stats);
   }
+  return 0;
+}
+
+// The standalone scan behind paac_nstep_returns[_tick] / paac_gae_returns[_tick], which check what is theirs alone (lambda,
+// the bookkeeping pointers): `name` is the entry point's, for the message.
+static int launch_returns_scan(const char* name, int estimator, const float* v_boot, const float* rewards, const float* masks,
+                               const float* values, int T, int N, double gamma, double gae_lambda, float* y, float* adv,
+                               const CycleTick& ct, paac_stream_t stream) {
+  PAAC_REQUIRE(T > 0 && N > 0, "%s: T=%d N=%d", name, T, N);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, s);
+  auto* kernel = estimator == kEstGae ? returns_scan_kernel<kEstGae> : returns_scan_kernel<kEstNstep>;
+  launch_k(kernel, dim3((N + 63) / 64), dim3(128), s, PROF_WHOLE, v_boot, rewards, masks, values, T, N, gamma,
+           gamma * gae_lambda, y, adv, ct);
+  PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
@@ -2370,60 +2306,36 @@ void paac_debug_set_misc_stamps(unsigned long long* p) { (void)hipMemcpyToSymbol
 
 int paac_nstep_returns(const float* v_boot, const float* rewards, const float* masks, const float* values, int T, int N,
                        double gamma, float* y, float* adv, paac_stream_t stream) {
-  PAAC_REQUIRE(T > 0 && N > 0, "paac_nstep_returns: T=%d N=%d", T, N);
-  CycleTick ct;
-  memset(&ct, 0, sizeof(ct));
-  ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
-  launch_k(nstep_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
-           values, T, N, gamma, y, adv, ct);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_returns_scan("paac_nstep_returns", kEstNstep, v_boot, rewards, masks, values, T, N, gamma, 0.0, y, adv,
+                             CycleTick{}, stream);
 }
 
 int paac_nstep_returns_tick(const float* v_boot, const float* rewards, const float* masks, const float* values, int T,
                             int N, double gamma, float* y, float* adv, int64_t* global_step_dev, int64_t increment,
                             double initial_lr, int64_t lr_annealing_steps, float* lr_out_dev, uint64_t* tick_dev,
                             uint64_t tick_inc, paac_stream_t stream) {
-  PAAC_REQUIRE(T > 0 && N > 0, "paac_nstep_returns_tick: T=%d N=%d", T, N);
   PAAC_REQUIRE(global_step_dev && lr_out_dev && lr_annealing_steps > 0, "paac_nstep_returns_tick: bad arguments");
-  CycleTick ct;
-  ct.global_step = global_step_dev; ct.step_inc = increment; ct.lr0 = initial_lr; ct.anneal = lr_annealing_steps;
-  ct.lr_out = lr_out_dev; ct.tick = tick_dev; ct.tick_inc = tick_inc;
-  ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
-  launch_k(nstep_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
-           values, T, N, gamma, y, adv, ct);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_returns_scan("paac_nstep_returns_tick", kEstNstep, v_boot, rewards, masks, values, T, N, gamma, 0.0, y, adv,
+                             CycleTick{global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_dev, tick_dev, tick_inc},
+                             stream);
 }
 
 int paac_gae_returns(const float* v_boot, const float* rewards, const float* masks, const float* values, int T, int N,
                      double gamma, double gae_lambda, float* y, float* adv, paac_stream_t stream) {
-  PAAC_REQUIRE(T > 0 && N > 0, "paac_gae_returns: T=%d N=%d", T, N);
   PAAC_REQUIRE(gae_lambda >= 0.0 && gae_lambda <= 1.0, "paac_gae_returns: gae_lambda %g outside [0, 1]", gae_lambda);
-  CycleTick ct;
-  memset(&ct, 0, sizeof(ct));
-  ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
-  launch_k(gae_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
-           values, T, N, gamma, gamma * gae_lambda, y, adv, ct);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_returns_scan("paac_gae_returns", kEstGae, v_boot, rewards, masks, values, T, N, gamma, gae_lambda, y, adv,
+                             CycleTick{}, stream);
 }
 
 int paac_gae_returns_tick(const float* v_boot, const float* rewards, const float* masks, const float* values, int T,
                           int N, double gamma, double gae_lambda, float* y, float* adv, int64_t* global_step_dev,
                           int64_t increment, double initial_lr, int64_t lr_annealing_steps, float* lr_out_dev,
                           uint64_t* tick_dev, uint64_t tick_inc, paac_stream_t stream) {
-  PAAC_REQUIRE(T > 0 && N > 0, "paac_gae_returns_tick: T=%d N=%d", T, N);
   PAAC_REQUIRE(gae_lambda >= 0.0 && gae_lambda <= 1.0, "paac_gae_returns_tick: gae_lambda %g outside [0, 1]", gae_lambda);
   PAAC_REQUIRE(global_step_dev && lr_out_dev && lr_annealing_steps > 0, "paac_gae_returns_tick: bad arguments");
-  CycleTick ct;
-  ct.global_step = global_step_dev; ct.step_inc = increment; ct.lr0 = initial_lr; ct.anneal = lr_annealing_steps;
-  ct.lr_out = lr_out_dev; ct.tick = tick_dev; ct.tick_inc = tick_inc;
-  ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, (hipStream_t)stream);
-  launch_k(gae_returns_kernel, dim3((N + 63) / 64), dim3(128), (hipStream_t)stream, PROF_WHOLE, v_boot, rewards, masks,
-           values, T, N, gamma, gamma * gae_lambda, y, adv, ct);
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_returns_scan("paac_gae_returns_tick", kEstGae, v_boot, rewards, masks, values, T, N, gamma, gae_lambda, y, adv,
+                             CycleTick{global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_dev, tick_dev, tick_inc},
+                             stream);
 }
 
 int paac_adv_normalize(const float* adv, int B, float* adv_n_out, double* stats_out, paac_stream_t stream) {

@@ -663,17 +663,8 @@ int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, c
   ppo.p_old = p_old;
   ppo.clip_eps = clip_eps;
   ppo.stat_rows = ctx->ppo_rows;
-  GaeArgs rt;
-  memset(&rt, 0, sizeof(rt));
-  int estimator = kEstNstep;
-  if (ret) {
-    estimator = ret->estimator;              // (validated by paac_loss_backward_returns)
-    if (estimator == kEstGae) rt.gl = ret->gamma * ret->gae_lambda;
-    rt.v_boot = ret->v_boot; rt.boot_in_fwd = ret->v_boot ? 0 : 1; rt.rewards = ret->rewards; rt.masks = ret->masks; rt.values_act = ret->values;
-    rt.T = ret->T; rt.N = ret->N; rt.gamma = ret->gamma; rt.y_out = ret->y_out; rt.adv_out = ret->adv_out;
-    rt.global_step = ret->global_step_dev; rt.step_inc = ret->increment; rt.lr0 = ret->initial_lr;
-    rt.anneal = ret->lr_annealing_steps; rt.lr_out = ret->lr_out_dev; rt.tick = ret->tick_dev; rt.tick_inc = ret->tick_inc;
-  }
+  const GaeArgs rt = returns_args(ret, ret ? ret->v_boot : nullptr);
+  const int estimator = ret ? ret->estimator : kEstNstep;      // (validated by paac_loss_backward_returns)
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
     return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, vc, ppo_stats_out, s);
   return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, vc, ppo_stats_out, s);

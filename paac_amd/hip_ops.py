@@ -208,16 +208,8 @@ class Context(object):
         T, N = rewards.shape
         if T * N != B:
             raise ValueError("rollout records are [%d,%d] but the batch has %d rows" % (T, N, B))
-        ret = _lib.Returns(
-            v_boot=_ptr(v_boot, torch.float32, N, "v_boot", True), rewards=_ptr(rewards, torch.float32, B, "rewards"),
-            masks=_ptr(masks, torch.float32, B, "masks"), values=_ptr(values, torch.float32, B, "values"), T=T, N=N,
-            gamma=float(gamma), y_out=_ptr(y_out, torch.float32, B, "y_out"), adv_out=_ptr(adv_out, torch.float32, B, "adv_out"),
-            global_step_dev=_ptr(global_step_dev, torch.int64, 1, "global_step", True), increment=int(increment),
-            initial_lr=float(initial_lr), lr_annealing_steps=int(lr_annealing_steps),
-            lr_out_dev=_ptr(lr_out_dev, torch.float32, 1, "lr_out", True),
-            tick_dev=_ptr(tick_dev, torch.int64, 1, "tick", True), tick_inc=int(tick_inc),
-            estimator=_lib.RETURNS_GAE if uses_gae(gae_lambda) else _lib.RETURNS_NSTEP,
-            gae_lambda=float(gae_lambda) if uses_gae(gae_lambda) else 0.0)
+        ret = _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
+                              lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda)
         if p_old_out is not None:          # include/paac_hip.h: paac_loss_backward_returns_record
             _lib.check(self.lib.paac_loss_backward_returns_record(
                 self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
@@ -534,53 +526,48 @@ def returns(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None):
         nstep_returns(v_boot, rewards, masks, values, gamma, y, adv)
 
 
+def returns_tick(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None, **tick):
+    """nstep_returns_tick or gae_returns_tick by the same rule; tick: their bookkeeping keyword arguments."""
+    if uses_gae(gae_lambda):
+        gae_returns_tick(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv, **tick)
+    else:
+        nstep_returns_tick(v_boot, rewards, masks, values, gamma, y, adv, **tick)
+
+
+def _returns_scan(name, v_boot, rewards, masks, values, gamma, lam, y, adv, tick=None):
+    """The four standalone entries (include/paac_hip.h).  lam: (gae_lambda,) from the GAE pair, () from the n-step pair;
+    tick: (global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_dev, tick_dev, tick_inc) from the _tick pair."""
+    T, N = rewards.shape
+    args = [_ptr(v_boot, torch.float32, N, "v_boot"), _ptr(rewards, torch.float32, T * N, "rewards"),
+            _ptr(masks, torch.float32, T * N, "masks"), _ptr(values, torch.float32, T * N, "values"), T, N, float(gamma),
+            *lam, _ptr(y, torch.float32, T * N, "y"), _ptr(adv, torch.float32, T * N, "adv")]
+    if tick is not None:
+        global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_dev, tick_dev, tick_inc = tick
+        args += [_ptr(global_step_dev, torch.int64, 1, "global_step"), int(increment), float(initial_lr),
+                 int(lr_annealing_steps), _ptr(lr_out_dev, torch.float32, 1, "lr_out"),
+                 _ptr(tick_dev, torch.int64, 1, "tick", True), int(tick_inc)]
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
 def gae_returns(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv):
     """Generalized advantage estimation on the rollout records (include/paac_hip.h: paac_gae_returns)."""
-    T, N = rewards.shape
-    lib = _lib.load()
-    _lib.check(lib.paac_gae_returns(_ptr(v_boot, torch.float32, N, "v_boot"), _ptr(rewards, torch.float32, T * N, "rewards"),
-                                    _ptr(masks, torch.float32, T * N, "masks"), _ptr(values, torch.float32, T * N, "values"),
-                                    T, N, float(gamma), float(gae_lambda), _ptr(y, torch.float32, T * N, "y"),
-                                    _ptr(adv, torch.float32, T * N, "adv"), _stream()), "paac_gae_returns")
+    _returns_scan("paac_gae_returns", v_boot, rewards, masks, values, gamma, (float(gae_lambda),), y, adv)
 
 
 def gae_returns_tick(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv, global_step_dev, increment, initial_lr,
                      lr_annealing_steps, lr_out_dev, tick_dev=None, tick_inc=0):
-    T, N = rewards.shape
-    lib = _lib.load()
-    _lib.check(lib.paac_gae_returns_tick(_ptr(v_boot, torch.float32, N, "v_boot"), _ptr(rewards, torch.float32, T * N, "rewards"),
-                                         _ptr(masks, torch.float32, T * N, "masks"), _ptr(values, torch.float32, T * N, "values"),
-                                         T, N, float(gamma), float(gae_lambda), _ptr(y, torch.float32, T * N, "y"),
-                                         _ptr(adv, torch.float32, T * N, "adv"),
-                                         _ptr(global_step_dev, torch.int64, 1, "global_step"), int(increment),
-                                         float(initial_lr), int(lr_annealing_steps),
-                                         _ptr(lr_out_dev, torch.float32, 1, "lr_out"),
-                                         _ptr(tick_dev, torch.int64, 1, "tick", True), int(tick_inc), _stream()),
-               "paac_gae_returns_tick")
+    _returns_scan("paac_gae_returns_tick", v_boot, rewards, masks, values, gamma, (float(gae_lambda),), y, adv,
+                  (global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_dev, tick_dev, tick_inc))
 
 
 def nstep_returns(v_boot, rewards, masks, values, gamma, y, adv):
-    T, N = rewards.shape
-    lib = _lib.load()
-    _lib.check(lib.paac_nstep_returns(_ptr(v_boot, torch.float32, N, "v_boot"), _ptr(rewards, torch.float32, T * N, "rewards"),
-                                      _ptr(masks, torch.float32, T * N, "masks"), _ptr(values, torch.float32, T * N, "values"),
-                                      T, N, float(gamma), _ptr(y, torch.float32, T * N, "y"),
-                                      _ptr(adv, torch.float32, T * N, "adv"), _stream()), "paac_nstep_returns")
+    _returns_scan("paac_nstep_returns", v_boot, rewards, masks, values, gamma, (), y, adv)
 
 
 def nstep_returns_tick(v_boot, rewards, masks, values, gamma, y, adv, global_step_dev, increment, initial_lr,
                        lr_annealing_steps, lr_out_dev, tick_dev=None, tick_inc=0):
-    T, N = rewards.shape
-    lib = _lib.load()
-    _lib.check(lib.paac_nstep_returns_tick(_ptr(v_boot, torch.float32, N, "v_boot"), _ptr(rewards, torch.float32, T * N, "rewards"),
-                                           _ptr(masks, torch.float32, T * N, "masks"), _ptr(values, torch.float32, T * N, "values"),
-                                           T, N, float(gamma), _ptr(y, torch.float32, T * N, "y"),
-                                           _ptr(adv, torch.float32, T * N, "adv"),
-                                           _ptr(global_step_dev, torch.int64, 1, "global_step"), int(increment),
-                                           float(initial_lr), int(lr_annealing_steps),
-                                           _ptr(lr_out_dev, torch.float32, 1, "lr_out"),
-                                           _ptr(tick_dev, torch.int64, 1, "tick", True), int(tick_inc), _stream()),
-               "paac_nstep_returns_tick")
+    _returns_scan("paac_nstep_returns_tick", v_boot, rewards, masks, values, gamma, (), y, adv,
+                  (global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_dev, tick_dev, tick_inc))
 
 
 def sample_mt_scratch(N, A, device):

@@ -73,6 +73,9 @@ class DeviceRollout(object):
         self.finished = torch.zeros((hip_ops.FINISHED_RING_BYTES // 4,), dtype=torch.int32, device=dev)
         self.tick = torch.zeros((1,), dtype=torch.int64, device=dev)          # env steps taken (per env)
         self.global_step_dev = torch.full((1,), int(L.global_step), dtype=torch.int64, device=dev)
+        # the per-cycle bookkeeping (global_step, lr, frame counter) of whichever launch computes the cycle's returns
+        self.cycle_tick = dict(global_step_dev=self.global_step_dev, increment=self.total_envs * T, initial_lr=L.initial_lr,
+                               lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev, tick_dev=self.tick, tick_inc=T)
         self.raw = None
         # a stateful kind (STATEFUL_KINDS: catch, bricks, rally): the environments carry state from step to step -- a ring of state
         # records beside the observation ring, slot for slot (a step reads slot t and writes slot t + 1: nothing is updated in
@@ -238,9 +241,7 @@ class DeviceRollout(object):
             # heads of the bootstrap rows, then returns + statistics + normalisation + the cycle's bookkeeping in one launch,
             # then the backward on (y, adv_n); the rollout rows' heads still ride in the backward's first launch
             L.ctx.returns_norm_tick(params, None, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
-                                    L.adv_stats, global_step_dev=self.global_step_dev, increment=self.total_envs * T,
-                                    initial_lr=L.initial_lr, lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev,
-                                    tick_dev=self.tick, tick_inc=T, gae_lambda=L.gae_lambda)
+                                    L.adv_stats, gae_lambda=L.gae_lambda, **self.cycle_tick)
             if self.K > 1:
                 L.ctx.loss_backward_record(params, self.rollout_states(parity), self.actions.view(-1), self.y, L.adv_n, L.p_old,
                                            L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=phase)
@@ -257,11 +258,8 @@ class DeviceRollout(object):
         # the fc/heads gradient tail overlaps the conv backward (phase 2, _backward_conv)
         L.ctx.loss_backward_returns(params, self.rollout_states(parity), self.actions.view(-1), None, self.rewards,
                                     self.masks, self.values, L.gamma, self.y, self.adv, L.entropy_beta, L.grad,
-                                    L.loss_dev, forward_done=True, phase=phase,
-                                    global_step_dev=self.global_step_dev, increment=self.total_envs * T,
-                                    initial_lr=L.initial_lr, lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev,
-                                    tick_dev=self.tick, tick_inc=T, gae_lambda=L.gae_lambda,
-                                    p_old_out=L.p_old if self.K > 1 else None)
+                                    L.loss_dev, forward_done=True, phase=phase, gae_lambda=L.gae_lambda,
+                                    p_old_out=L.p_old if self.K > 1 else None, **self.cycle_tick)
         if L.vclip_on:         # --ppo_vclip: v_old = the values epoch 1's heads just computed (one captured copy)
             L.ctx.train_values_into(L.v_old, T * N)
 
@@ -274,16 +272,12 @@ class DeviceRollout(object):
         B = T * N
         L.minibatch_record(self.actions.view(-1), B + N)
         v_boot = L.v_rec[B:]
-        tick = dict(global_step_dev=self.global_step_dev, increment=self.total_envs * T, initial_lr=L.initial_lr,
-                    lr_annealing_steps=L.lr_annealing_steps, lr_out_dev=L.lr_dev, tick_dev=self.tick, tick_inc=T)
         if L.adv_norm:
             hip_ops.returns_norm_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
-                                      L.adv_stats, gae_lambda=L.gae_lambda, **tick)
-        elif hip_ops.uses_gae(L.gae_lambda):
-            hip_ops.gae_returns_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, L.gae_lambda, self.y, self.adv,
-                                     **tick)
+                                      L.adv_stats, gae_lambda=L.gae_lambda, **self.cycle_tick)
         else:
-            hip_ops.nstep_returns_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, **tick)
+            hip_ops.returns_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.gae_lambda,
+                                 **self.cycle_tick)
         L.minibatch_perms(self.sampler_seed, self.tick)
         L.minibatch_step_backward(0, self.rollout_states(parity), self.actions.view(-1), self.y, self.actor_adv, phase)
 

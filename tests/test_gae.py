@@ -90,6 +90,22 @@ def test_routing_rule():
     assert hip_ops.uses_gae(0.0) and hip_ops.uses_gae(0.95) and hip_ops.uses_gae(float(np.nextafter(1.0, 0.0)))
 
 
+def test_returns_tick_follows_the_routing_rule(monkeypatch):
+    """hip_ops.returns_tick: None and 1.0 reach the n-step entry, 0.95 the GAE entry with its lambda; the records and the
+    bookkeeping keyword arguments arrive as given."""
+    from paac_amd import hip_ops
+    calls = []
+    monkeypatch.setattr(hip_ops, "nstep_returns_tick", lambda *a, **k: calls.append(("nstep", a, k)))
+    monkeypatch.setattr(hip_ops, "gae_returns_tick", lambda *a, **k: calls.append(("gae", a, k)))
+    tick = dict(global_step_dev="gs", increment=160, initial_lr=0.0224, lr_annealing_steps=80000000, lr_out_dev="lr",
+                tick_dev="tick", tick_inc=5)
+    hip_ops.returns_tick("vb", "r", "m", "V", 0.99, "y", "adv", **tick)
+    hip_ops.returns_tick("vb", "r", "m", "V", 0.99, "y", "adv", 1.0, **tick)
+    hip_ops.returns_tick("vb", "r", "m", "V", 0.99, "y", "adv", gae_lambda=0.95, **tick)
+    assert calls == [("nstep", ("vb", "r", "m", "V", 0.99, "y", "adv"), tick)] * 2 + \
+        [("gae", ("vb", "r", "m", "V", 0.99, 0.95, "y", "adv"), tick)]
+
+
 def test_header_declares_the_entries_and_the_enum():
     from paac_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "paac_hip.h")).read()
@@ -180,7 +196,8 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-SHAPES = [(1, 1), (5, 8), (5, 32), (5, 65), (9, 32), (20, 128), (20, 256)]    # T = 9, 20: across the 8-step chunk / preload
+# T = 8: the 8-step chunk / preload filled; T = 9, 17, 20: crossed; N = 65, 256: across the scan's 64-environment workgroup
+SHAPES = [(1, 1), (5, 8), (5, 32), (5, 65), (8, 64), (9, 32), (17, 65), (20, 128), (20, 256)]
 
 
 @pytest.mark.gpu
@@ -222,6 +239,34 @@ def test_gae_returns_tick_bit_exact_with_bookkeeping(T, N):
     # without a frame counter
     hip_ops.gae_returns_tick(dev(v_boot), dev(r), dev(m), dev(V), 0.99, 0.5, y, adv, gs, 1, 0.0224, 80000000, lr)
     assert int(gs.item()) == step + 1 and int(tick.item()) == 7 + 4 * T
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T,N", SHAPES)
+def test_nstep_returns_tick_bit_exact_with_bookkeeping(T, N):
+    """The n-step twin: y / adv against oracle.rollout.nstep_returns, the bookkeeping against oracle.rollout.get_lr."""
+    import torch
+    from oracle import rollout as oroll
+    from paac_amd import hip_ops
+    v_boot, r, m, V = records(T, N, T * 1000 + N + 2)
+    gs = torch.tensor([0], dtype=torch.int64, device="cuda")
+    tick = torch.tensor([7], dtype=torch.int64, device="cuda")
+    lr = torch.zeros(1, device="cuda")
+    step = 0
+    for inc, gamma in ((160, 0.99), (160, 1.0), (79999680, 0.99), (5, 1.0)):
+        y, adv = torch.zeros(T * N, device="cuda"), torch.zeros(T * N, device="cuda")
+        hip_ops.nstep_returns_tick(dev(v_boot), dev(r), dev(m), dev(V), gamma, y, adv, gs, inc, 0.0224, 80000000, lr, tick, T)
+        step += inc
+        ye, ae = oroll.nstep_returns(v_boot, r.astype(np.float64), m.astype(np.float64), V.astype(np.float64), gamma)
+        assert np.array_equal(y.cpu().numpy(), ye.reshape(-1).astype(np.float32))
+        assert np.array_equal(adv.cpu().numpy(), ae.reshape(-1).astype(np.float32))
+        assert int(gs.item()) == step
+        assert lr.item() == np.float32(oroll.get_lr(step, 0.0224, 80000000))
+    assert int(tick.item()) == 7 + 4 * T
+    # without a frame counter
+    hip_ops.nstep_returns_tick(dev(v_boot), dev(r), dev(m), dev(V), 0.99, y, adv, gs, 1, 0.0224, 80000000, lr)
+    assert int(gs.item()) == step + 1 and int(tick.item()) == 7 + 4 * T
+    assert lr.item() == np.float32(oroll.get_lr(step + 1, 0.0224, 80000000))
 
 
 @pytest.mark.gpu

@@ -20,7 +20,8 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-@pytest.mark.parametrize("T,N", [(5, 32), (20, 128), (5, 1), (1, 7)])
+# N = 65, 256: across the scan's 64-environment workgroup; T = 8, 9, 17, 20: an 8-step chunk filled, crossed once and twice
+@pytest.mark.parametrize("T,N", [(5, 32), (20, 128), (5, 1), (1, 7), (1, 1), (5, 65), (8, 64), (9, 32), (17, 65), (20, 256)])
 def test_nstep_returns_bit_exact(T, N):
     from paac_amd import hip_ops
     rs = np.random.RandomState(T * 100 + N)

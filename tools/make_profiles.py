@@ -118,7 +118,7 @@ FUSED = [("conv_tower", "tower_kernel<TowerGeom", None), ("fc_fwd", "fc_heads_ke
          ("fc_conv3_wgrad", "dmm_pair_kernel<Dmm<Geom<1, 1, 3136", n_train),
          ("conv2_conv1_wgrad", "dmm_pair_kernel<Dmm<Geom<20, 20, 32", n_train),
          ("grad_finalize", "grad_finalize_kernel", n_train),
-         ("nstep_returns", "nstep_returns_kernel", n_train)]
+         ("nstep_returns", "returns_scan_kernel", n_train)]
 for name, pat, b in FUSED:
     ks = sorted([k for k in fe if pat in k[0]], key=lambda k: traffic["%s|%s" % k])
     if name == "conv_tower":           # acting regions variant (smaller traffic) and whole-sample training variant

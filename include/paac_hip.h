@@ -360,13 +360,60 @@ int paac_clip_adam(paac_ctx* ctx, float* params, const float* grad, float* m, fl
                    const float* lr_dev, float beta1, float beta2, float eps, float clip_norm, int clip_mode,
                    float grad_scale, float* gnorm_out, paac_stream_t stream);
 
+/* --ppo_target_kl D: KL early stopping of a cycle's optimizer steps (Spinning Up's PPO rule, on the approx_kl this library
+ * already computes).  The reference has no counterpart; this is the contract.  D = 0 (the default) is off: every step goes
+ * through the ungated entries above, bit for bit.  D is read only when --ppo_epochs K > 1.  With D > 0:
+ *   Gated steps: the optimizer steps whose backward writes a ppo_stats row.  M = 1: steps s = 1 .. K-1 (step 0 is the plain
+ *     update, its ratio is identically 1, it is never gated).  M > 1: every step s = 0 .. K*M-1.
+ *   The statistic: before a gated step is applied, kl_s = ppo_stats[s][1], the approx_kl of that step's own batch, the mean
+ *     of log(p_old + eps) - log(p + eps).
+ *   The stop rule: if !(kl_s <= thr), thr = float32(1.5 * D), this step and every remaining step of the cycle are skipped.
+ *     A NaN stops too.
+ *   A skipped step writes nothing to the weights, the packed weight copies, the optimizer slots or Adam's beta_powers, and
+ *     leaves gnorm_out (and the local mode's factors) as the last applied step left them.  The norm pass's other work still
+ *     happens -- a pending phase-3 slab reduction of `grad` is completed, the gradient-statistics partials are those of this
+ *     step's gradient -- so the ctx is in the state an applied step leaves.
+ *   The stop flag is sticky: the first gated step of each cycle clears it (first != 0) and nothing else does.
+ *   global_step, the learning rate and the frame counter are per cycle and unaffected.
+ *   No launch is added or removed: a skipped step's forward, backward and both optimizer launches still run (a captured cycle
+ *     keeps its shape); the update launch's workgroups return at once.
+ *   Data parallelism: the value compared is the mean of the ranks' kl_s (equal shards).  It travels inside the step's one
+ *     all-reduce -- the learner keeps the gradient in a store of n + 4 floats, copies ppo_stats[s][1] to element n behind the
+ *     backward, exchanges the whole store and passes kl = store + n, scale = grad_scale -- so every rank takes the same
+ *     decision from the same bits.  One process: kl = ppo_stats[s] + 1, scale = 1.
+ * paac_kl_gate, all pointers in device memory: the norm pass's first thread clears *stop if first, computes k = *kl * scale,
+ * writes *checked = k, sets *stop = 1 if !(k <= thr), writes *applied = !*stop, and under Adam advances the powers (and writes
+ * alpha) only when not stopped; every workgroup of the update launch reads *stop first and returns if it is set.  Plain
+ * stores; the launch boundary orders the decision before its readers.  The gate is an argument of the call: the ctx keeps
+ * nothing of it.
+ * paac_clip_rmsprop_gated / paac_clip_adam_gated: their ungated twin's arguments and contract, plus the gate.  Refused: a NULL
+ * gate, a NULL kl or stop, thr NaN or negative, scale not finite and positive.  applied and checked may be NULL. */
+typedef struct {
+  const float* kl;
+  float scale;
+  float thr;
+  int first;
+  int32_t* stop;
+  int32_t* applied;
+  float* checked;
+} paac_kl_gate;
+int paac_clip_rmsprop_gated(paac_ctx* ctx, float* params, const float* grad, float* ms, float* mom, int64_t n,
+                            const float* lr_dev, float decay, float momentum, float eps, float clip_norm, int clip_mode,
+                            float grad_scale, float* gnorm_out, const paac_kl_gate* gate, paac_stream_t stream);
+int paac_clip_adam_gated(paac_ctx* ctx, float* params, const float* grad, float* m, float* v, float* beta_powers, int64_t n,
+                         const float* lr_dev, float beta1, float beta2, float eps, float clip_norm, int clip_mode,
+                         float grad_scale, float* gnorm_out, const paac_kl_gate* gate, paac_stream_t stream);
+
 /* The reference's gradient summaries (actor_learner.py:85-87 -> logger_utils.py:23-33: mean, stddev, max, min of the
  * flat raw gradient and of the flat clipped gradient, plus global_norm): the reductions ride along the norm pass of
  * the LAST paac_clip_rmsprop / paac_clip_adam on this ctx (no extra pass over the gradient); this call only folds its
  * per-block partials.  stats_out: device float[8] = {sum, sum of squares, max, min, number of exact zeros, 0, 0, 0} of the raw
  * flat gradient (g * grad_scale) over the reference's P elements (alignment pads excluded), in every mode.  In modes
  * IGNORE and GLOBAL the clipped gradient is the raw one times one factor, so its statistics follow; in mode LOCAL they
- * follow from paac_grad_tensor_stats.  Call at the logging cadence. */
+ * follow from paac_grad_tensor_stats.  Call at the logging cadence.
+ * After a gated step that was skipped (--ppo_target_kl) the partials are those of the skipped step's gradient, the last one
+ * computed and not applied, while gnorm_out and the local mode's factors are still the last applied step's: the summaries then
+ * describe a gradient no update used. */
 int paac_grad_stats(paac_ctx* ctx, float* stats_out, paac_stream_t stream);
 
 /* Per-tensor summaries of the last paac_clip_rmsprop / paac_clip_adam, which must have run in mode LOCAL (fails

@@ -46,6 +46,12 @@ class Returns(ctypes.Structure):
                 ("estimator", c_int32), ("gae_lambda", ctypes.c_double)]
 
 
+class KlGate(ctypes.Structure):
+    """paac_kl_gate (include/paac_hip.h): the gate of a --ppo_target_kl optimizer step, every pointer in device memory."""
+    _fields_ = [("kl", c_void_p), ("scale", c_float), ("thr", c_float), ("first", c_int), ("stop", c_void_p),
+                ("applied", c_void_p), ("checked", c_void_p)]
+
+
 class PaacHipError(RuntimeError):
     pass
 
@@ -90,6 +96,10 @@ _SIGNATURES = {
                                   c_float, c_float, c_float, c_int, c_float, c_void_p, c_void_p]),
     "paac_clip_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,
                                c_float, c_float, c_float, c_int, c_float, c_void_p, c_void_p]),
+    "paac_clip_rmsprop_gated": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,
+                                        c_float, c_float, c_float, c_int, c_float, c_void_p, POINTER(KlGate), c_void_p]),
+    "paac_clip_adam_gated": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,
+                                     c_float, c_float, c_float, c_int, c_float, c_void_p, POINTER(KlGate), c_void_p]),
     "paac_lr_step": (c_int, [c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p]),
     "paac_nstep_returns": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p,
                                    c_void_p, c_void_p]),

@@ -99,6 +99,17 @@ class ActorLearner(object):
                                  "sort), got %d" % (_lib.MINIBATCH_MAX_ROWS, rows))
         # optimizer steps of one cycle = rows of ppo_loss / ppo_stats
         self.ppo_steps = self.ppo_epochs * (self.ppo_minibatches if self.minibatch_on else 1)
+        # --ppo_target_kl D (include/paac_hip.h has the contract): Namespaces / args.json files without the field, and 0, mean
+        # off; D > 0 is read only when K > 1: a gated step (one whose backward writes a ppo_stats row) whose approx_kl exceeds
+        # float32(1.5 * D) is skipped on the device, with every step after it in the cycle
+        D = getattr(args, "ppo_target_kl", 0.0)
+        if isinstance(D, (bool, np.bool_)) or not isinstance(D, (int, float, np.integer, np.floating)) or \
+                not (0.0 <= float(D) and math.isfinite(float(D))):          # (NaN fails the comparison)
+            raise ValueError("ppo_target_kl %r: expected a finite number >= 0 (0 = off)" % (D,))
+        self.ppo_target_kl = float(D)
+        self.target_kl_on = self.ppo_epochs > 1 and self.ppo_target_kl > 0.0
+        self.kl_thr = float(np.float32(1.5 * self.ppo_target_kl))
+        self.first_gated_step = 0 if self.minibatch_on else 1
         self.clip_norm = args.clip_norm
         self.clip_norm_type = args.clip_norm_type
         if self.clip_norm_type == 'ignore':
@@ -126,7 +137,12 @@ class ActorLearner(object):
         torch.cuda.set_device(dev)
         self.torch_device = dev
         n = self.network.layout["total"]
-        self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
+        # the gradient store: what the exchange sends.  --ppo_target_kl under data parallelism: 4 floats behind the gradient,
+        # element n carrying the step's approx_kl through the step's one all-reduce; self.grad stays the n-float view every
+        # kernel sees
+        self.kl_in_store = self.target_kl_on and parallel.collectives_active()
+        self.grad_store = torch.zeros(n + (4 if self.kl_in_store else 0), dtype=torch.float32, device=dev)
+        self.grad = self.grad_store[:n]
         if self.optimizer == "adam":
             # slots m, v (zeros) and the fp32 bias-correction powers {beta1_power, beta2_power}, advanced on the device
             self.adam_m = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -151,6 +167,13 @@ class ActorLearner(object):
             self.p_old = torch.zeros(self.emulator_counts * self.max_local_steps, dtype=torch.float32, device=dev)
             self.ppo_loss = torch.zeros((self.ppo_steps, 4), dtype=torch.float32, device=dev)
             self.ppo_stats = torch.zeros((self.ppo_steps, 3 if self.vclip_on else 2), dtype=torch.float32, device=dev)
+        # --ppo_target_kl: per-cycle scratch like the above.  kl_stop = the cycle's sticky stop flag; row s of ppo_applied /
+        # ppo_kl_checked = was gated step s applied / the value its gate compared (ungated step 0 of an M = 1 cycle: 1 / 0)
+        self.kl_stop = self.ppo_applied = self.ppo_kl_checked = None
+        if self.target_kl_on:
+            self.kl_stop = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.ppo_applied = torch.ones(self.ppo_steps, dtype=torch.int32, device=dev)
+            self.ppo_kl_checked = torch.zeros(self.ppo_steps, dtype=torch.float32, device=dev)
         # --adv_norm: adv_n [T*N] is what the actor term reads, adv_stats = {mean, std} of the last rollout (fp64);
         # --ppo_vclip: v_old [T*N], epoch 1's values.  Per-cycle scratch like p_old
         self.adv_n = self.adv_stats = self.v_old = None
@@ -249,8 +272,34 @@ class ActorLearner(object):
             self.beta_powers.copy_(torch.from_numpy(np.array(powers, dtype=np.float32)))
 
     # -- the optimizer step on self.grad (already all-reduced): one place for the loops and the feed-dict path ----
-    def apply_gradients(self):
+    def is_gated_step(self, step):
+        """--ppo_target_kl: is optimizer step `step` of a cycle one the gate decides on (its backward wrote ppo_stats[step])?"""
+        return self.target_kl_on and step is not None and self.first_gated_step <= step < self.ppo_steps
+
+    def _kl_into_store(self, s):
+        """--ppo_target_kl, data parallel: gated step s's approx_kl rides behind its gradient through the step's all-reduce (one
+        4-byte device copy right after the backward that wrote it, captured like the v_old copy)."""
+        if self.kl_in_store and self.is_gated_step(s):
+            self.grad_store[self.grad.numel():self.grad.numel() + 1].copy_(self.ppo_stats[s, 1:2])
+
+    def apply_gradients(self, step=None):
+        """The optimizer step on self.grad.  step: its index in the cycle; a gated step (--ppo_target_kl) goes through the gated
+        entry, the first gated step of the cycle clearing the sticky stop flag.  None: ungated, whatever the flags say."""
         net = self.network
+        if self.is_gated_step(step):
+            n = self.grad.numel()
+            gate = dict(kl=self.grad_store[n:] if self.kl_in_store else self.ppo_stats[step, 1:2],
+                        kl_scale=self._grad_scale() if self.kl_in_store else 1.0, thr=self.kl_thr,
+                        first=step == self.first_gated_step, stop=self.kl_stop, applied=self.ppo_applied[step:step + 1],
+                        checked=self.ppo_kl_checked[step:step + 1])
+            if self.optimizer == "adam":
+                self.ctx.clip_adam_gated(net.params, self.grad, self.adam_m, self.adam_v, self.beta_powers, self.lr_dev,
+                                         self.beta1, self.beta2, self.e, self.clip_norm, self.clip_mode, self._grad_scale(),
+                                         self.gnorm_dev, **gate)
+            else:
+                self.ctx.clip_rmsprop_gated(net.params, self.grad, self.rms, self.mom, self.lr_dev, self.alpha, self.momentum,
+                                            self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev, **gate)
+            return
         if self.optimizer == "adam":
             self.ctx.clip_adam(net.params, self.grad, self.adam_m, self.adam_v, self.beta_powers, self.lr_dev, self.beta1,
                                self.beta2, self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
@@ -268,9 +317,10 @@ class ActorLearner(object):
             self.ctx.loss_backward_ppo_vclip(params, states, actions, y, adv, self.p_old, self.v_old, self.ppo_clip,
                                              self.ppo_vclip, self.entropy_beta, self.grad, self.ppo_loss[k], self.ppo_stats[k],
                                              forward_done=True, phase=phase)
-            return
-        self.ctx.loss_backward_ppo(params, states, actions, y, adv, self.p_old, self.ppo_clip, self.entropy_beta, self.grad,
-                                   self.ppo_loss[k], self.ppo_stats[k], forward_done=True, phase=phase)
+        else:
+            self.ctx.loss_backward_ppo(params, states, actions, y, adv, self.p_old, self.ppo_clip, self.entropy_beta, self.grad,
+                                       self.ppo_loss[k], self.ppo_stats[k], forward_done=True, phase=phase)
+        self._kl_into_store(k)
 
     def minibatch_record(self, actions, value_rows):
         """The record pass of an M > 1 cycle on the pending training forward (pre-update weights): p_old, and the values of
@@ -298,10 +348,11 @@ class ActorLearner(object):
             self.ctx.loss_backward_ppo_vclip(params, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
                                              mb["v_old"][r], self.ppo_clip, self.ppo_vclip, self.entropy_beta, self.grad,
                                              self.ppo_loss[s], self.ppo_stats[s], forward_done=True, phase=phase)
-            return
-        self.ctx.loss_backward_ppo(params, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
-                                   self.ppo_clip, self.entropy_beta, self.grad, self.ppo_loss[s], self.ppo_stats[s],
-                                   forward_done=True, phase=phase)
+        else:
+            self.ctx.loss_backward_ppo(params, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
+                                       self.ppo_clip, self.entropy_beta, self.grad, self.ppo_loss[s], self.ppo_stats[s],
+                                       forward_done=True, phase=phase)
+        self._kl_into_store(s)
 
     # -- one optimizer step from a reference-style feed dict (Session.run([train_step, ...], feed)) ----
     def _train_step_from_feed(self, feed_dict):
@@ -326,7 +377,7 @@ class ActorLearner(object):
         return parallel.grad_scale()
 
     def _allreduce_grad(self):
-        parallel.allreduce_sum_(self.grad)
+        parallel.allreduce_sum_(self.grad_store)
 
     # -- reference methods (actor_learner.py:89-127): same names and behaviour ------------------------------
     def save_vars(self, force=False):

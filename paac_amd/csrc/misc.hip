@@ -1608,10 +1608,44 @@ struct AdamPowers {
   float beta1, beta2;
 };
 
-template <bool LOCAL, bool ADAM>
+// --ppo_target_kl (include/paac_hip.h has the contract): the gate of a gated optimizer step.  Block 0 thread 0 of the norm
+// pass (GATED) takes the decision -- the thread that turns lr and the powers into alpha under Adam -- and every block of the
+// update launch (GATED) reads *stop before it touches anything: the launch boundary orders the decision before every
+// reader, exactly as it orders alpha.  Plain stores, no atomics: one writer, and the readers are in the next launch.
+struct KlGate {
+  const float* kl;     // the step's approx_kl (data parallel: the ranks' sum, inside the exchanged gradient store)
+  float scale;         // 1, or 1 / world size
+  float thr;           // float32(1.5 * target_kl)
+  int first;           // first gated step of the cycle: clears *stop before the comparison
+  int32_t* stop;       // sticky inside a cycle
+  int32_t* applied;    // nullable: !*stop after this step's decision
+  float* checked;      // nullable: the value compared
+};
+struct NoKlGate {};    // the ungated instantiations take no gate: their code is what it was before the flag
+template <bool GATED> using KlGateArg = std::conditional_t<GATED, KlGate, NoKlGate>;
+
+template <bool LOCAL, bool ADAM, bool GATED>
 __global__ __launch_bounds__(256) void norm_kernel(float* __restrict__ g, long n4, float scale, const NormArgs a,
-                                                   const LocalSpec ls, float* __restrict__ partials, const AdamPowers ap) {
-  if constexpr (ADAM) {
+                                                   const LocalSpec ls, float* __restrict__ partials, const AdamPowers ap,
+                                                   const KlGateArg<GATED> kg) {
+  if constexpr (GATED) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      int stop = kg.first ? 0 : *kg.stop;
+      const float k = *kg.kl * kg.scale;
+      if (!(k <= kg.thr)) stop = 1;          // (a NaN stops too)
+      *kg.stop = stop;
+      if (kg.checked) *kg.checked = k;
+      if (kg.applied) *kg.applied = stop ? 0 : 1;
+      if constexpr (ADAM) {
+        if (!stop) {
+          const float b1p = ap.powers[0], b2p = ap.powers[1];
+          *ap.alpha = *ap.lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
+          ap.powers[0] = b1p * ap.beta1;
+          ap.powers[1] = b2p * ap.beta2;
+        }
+      }
+    }
+  } else if constexpr (ADAM) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       const float b1p = ap.powers[0], b2p = ap.powers[1];
       *ap.alpha = *ap.lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
@@ -1845,14 +1879,19 @@ __device__ __forceinline__ void adam_update4(float4& gv, float4& m, float4& s, f
 // LOCAL: clip_mode is PAAC_CLIP_LOCAL -- every block folds the tensor-aligned partials into per-tensor sums of squares in
 // the same fixed order (the same factors everywhere), and each float4 takes the factor of the tensor it lies in.
 enum { RULE_RMSPROP = 0, RULE_RMSPROP_MOM = 1, RULE_ADAM = 2 };
-template <int RULE, bool LOCAL>
+// GATED (--ppo_target_kl): a block whose step the norm pass has stopped returns before it reads or writes anything -- weights,
+// packed copies, slots, the local factors and gnorm_out stay what the last applied step left.
+template <int RULE, bool LOCAL, bool GATED>
 __global__ __launch_bounds__(256) void update_kernel(float* __restrict__ var, const float* __restrict__ g,
                                                      float* __restrict__ ms, float* __restrict__ mom, long n4,
                                                      const float* __restrict__ lr_dev, float decay, float momentum,
                                                      float eps, float clip_norm, int clip_mode, float scale,
                                                      const float* __restrict__ partials, float* __restrict__ gnorm_out,
                                                      const PackSpec pk, const int fc_tiles, const int conv_tiles,
-                                                     const LocalSpec ls) {
+                                                     const LocalSpec ls, const KlGateArg<GATED> kg) {
+  if constexpr (GATED) {
+    if (*kg.stop != 0) return;               // block-uniform, in front of the first barrier
+  }
   constexpr bool MOM = RULE == RULE_RMSPROP_MOM;
   __shared__ float red[4];
   __shared__ float s_factor;
@@ -2700,12 +2739,13 @@ int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, i
 }
 }  // namespace paac
 
-// paac_clip_rmsprop / paac_clip_adam: one norm pass, one update launch.  ap == nullptr: RMSProp (s1 = ms, s2 = mom, h1 =
-// decay, h2 = momentum, step_dev = lr); otherwise Adam (s1 = m, s2 = v, h1 = beta1, h2 = beta2; the norm pass turns *lr_dev
-// and the powers into alpha, which the update reads).
+// paac_clip_rmsprop / paac_clip_adam and their gated twins: one norm pass, one update launch.  ap == nullptr: RMSProp (s1 = ms,
+// s2 = mom, h1 = decay, h2 = momentum, step_dev = lr); otherwise Adam (s1 = m, s2 = v, h1 = beta1, h2 = beta2; the norm pass
+// turns *lr_dev and the powers into alpha, which the update reads).  gate != nullptr: the GATED instantiations of both kernels
+// (--ppo_target_kl), the same grids.
 static int clip_step(const char* fn, paac_ctx* ctx, float* params, const float* grad, float* s1, float* s2, int64_t n,
                      const float* lr_dev, float h1, float h2, float eps, float clip_norm, int clip_mode, float grad_scale,
-                     float* gnorm_out, const AdamPowers* ap, hipStream_t s) {
+                     float* gnorm_out, const AdamPowers* ap, const KlGate* gate, hipStream_t s) {
   PAAC_REQUIRE(n > 0 && (n % 4) == 0, "%s: n=%ld must be a positive multiple of 4 (padded layout)", fn, (long)n);
   PAAC_REQUIRE(clip_mode == PAAC_CLIP_IGNORE || clip_mode == PAAC_CLIP_GLOBAL || clip_mode == PAAC_CLIP_LOCAL,
                "%s: clip mode %d (0 ignore, 1 global, 2 local)", fn, clip_mode);
@@ -2729,14 +2769,22 @@ static int clip_step(const char* fn, paac_ctx* ctx, float* params, const float* 
   AdamPowers none;
   memset(&none, 0, sizeof(none));
   const AdamPowers& pw = ap != nullptr ? *ap : none;
-#define PAAC_NORM_LAUNCH(KERNEL) \
-  launch_k(KERNEL, dim3((unsigned)np), dim3(256), s, PROF_FIRST, g, n4, grad_scale, na, ls, ctx->partials, pw)
+  const NoKlGate ungated;
+#define PAAC_NORM_LAUNCH(LOCAL, ADAM)                                                                                         \
+  {                                                                                                                           \
+    if (gate != nullptr)                                                                                                      \
+      launch_k(norm_kernel<LOCAL, ADAM, true>, dim3((unsigned)np), dim3(256), s, PROF_FIRST, g, n4, grad_scale, na, ls,       \
+               ctx->partials, pw, *gate);                                                                                     \
+    else                                                                                                                      \
+      launch_k(norm_kernel<LOCAL, ADAM, false>, dim3((unsigned)np), dim3(256), s, PROF_FIRST, g, n4, grad_scale, na, ls,      \
+               ctx->partials, pw, ungated);                                                                                   \
+  }
   if (ap != nullptr) {
-    if (local) PAAC_NORM_LAUNCH((norm_kernel<true, true>));
-    else PAAC_NORM_LAUNCH((norm_kernel<false, true>));
+    if (local) PAAC_NORM_LAUNCH(true, true)
+    else PAAC_NORM_LAUNCH(false, true)
   } else {
-    if (local) PAAC_NORM_LAUNCH((norm_kernel<true, false>));
-    else PAAC_NORM_LAUNCH((norm_kernel<false, false>));
+    if (local) PAAC_NORM_LAUNCH(true, false)
+    else PAAC_NORM_LAUNCH(false, false)
   }
 #undef PAAC_NORM_LAUNCH
   ctx->last_clip_local = local ? 1 : 0;
@@ -2746,21 +2794,40 @@ static int clip_step(const char* fn, paac_ctx* ctx, float* params, const float* 
   fill_pack_spec(ctx, &pk, &fc_tiles, &conv_tiles, &flat4);
   const dim3 grid((unsigned)(fc_tiles + conv_tiles + (flat4 + 256 * RMS_U - 1) / (256 * RMS_U)));
   const float* step_dev = ap != nullptr ? ap->alpha : lr_dev;
-#define PAAC_UPDATE_LAUNCH(KERNEL)                                                                                       \
-  launch_k(KERNEL, grid, dim3(256), s, PROF_LAST, params, grad, s1, s2, n4, step_dev, h1, h2, eps, clip_norm, clip_mode, \
-           grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles, ls)
+#define PAAC_UPDATE_LAUNCH(RULE, LOCAL)                                                                                       \
+  {                                                                                                                           \
+    if (gate != nullptr)                                                                                                      \
+      launch_k(update_kernel<RULE, LOCAL, true>, grid, dim3(256), s, PROF_LAST, params, grad, s1, s2, n4, step_dev, h1, h2,   \
+               eps, clip_norm, clip_mode, grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles, ls,   \
+               *gate);                                                                                                        \
+    else                                                                                                                      \
+      launch_k(update_kernel<RULE, LOCAL, false>, grid, dim3(256), s, PROF_LAST, params, grad, s1, s2, n4, step_dev, h1, h2,  \
+               eps, clip_norm, clip_mode, grad_scale, (const float*)ctx->partials, gnorm_out, pk, fc_tiles, conv_tiles, ls,   \
+               ungated);                                                                                                      \
+  }
   if (ap != nullptr) {
-    if (local) PAAC_UPDATE_LAUNCH((update_kernel<RULE_ADAM, true>));
-    else PAAC_UPDATE_LAUNCH((update_kernel<RULE_ADAM, false>));
+    if (local) PAAC_UPDATE_LAUNCH(RULE_ADAM, true)
+    else PAAC_UPDATE_LAUNCH(RULE_ADAM, false)
   } else if (h2 != 0.f) {
-    if (local) PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP_MOM, true>));
-    else PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP_MOM, false>));
+    if (local) PAAC_UPDATE_LAUNCH(RULE_RMSPROP_MOM, true)
+    else PAAC_UPDATE_LAUNCH(RULE_RMSPROP_MOM, false)
   } else {
-    if (local) PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP, true>));
-    else PAAC_UPDATE_LAUNCH((update_kernel<RULE_RMSPROP, false>));
+    if (local) PAAC_UPDATE_LAUNCH(RULE_RMSPROP, true)
+    else PAAC_UPDATE_LAUNCH(RULE_RMSPROP, false)
   }
 #undef PAAC_UPDATE_LAUNCH
   PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// The public gate -> the kernels' (same fields, same order); the refusals of the gated entries.
+static int kl_gate_of(const char* fn, const paac_kl_gate* gate, KlGate* out) {
+  PAAC_REQUIRE(gate != nullptr, "%s: null gate", fn);
+  PAAC_REQUIRE(gate->kl != nullptr && gate->stop != nullptr, "%s: the gate's kl and stop must not be null", fn);
+  PAAC_REQUIRE(gate->thr >= 0.f, "%s: gate thr=%g must be a number >= 0", fn, (double)gate->thr);      // (NaN fails)
+  PAAC_REQUIRE(gate->scale > 0.f && gate->scale < INFINITY, "%s: gate scale=%g must be finite and positive", fn,
+               (double)gate->scale);
+  *out = KlGate{gate->kl, gate->scale, gate->thr, gate->first ? 1 : 0, gate->stop, gate->applied, gate->checked};
   return 0;
 }
 
@@ -2771,19 +2838,46 @@ int paac_clip_rmsprop(paac_ctx* ctx, float* params, const float* grad, float* ms
                       float grad_scale, float* gnorm_out, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && grad && ms && mom && lr_dev, "paac_clip_rmsprop: null argument");
   return clip_step("paac_clip_rmsprop", ctx, params, grad, ms, mom, n, lr_dev, decay, momentum, eps, clip_norm, clip_mode,
-                   grad_scale, gnorm_out, nullptr, (hipStream_t)stream);
+                   grad_scale, gnorm_out, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int paac_clip_rmsprop_gated(paac_ctx* ctx, float* params, const float* grad, float* ms, float* mom, int64_t n,
+                            const float* lr_dev, float decay, float momentum, float eps, float clip_norm, int clip_mode,
+                            float grad_scale, float* gnorm_out, const paac_kl_gate* gate, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && grad && ms && mom && lr_dev, "paac_clip_rmsprop_gated: null argument");
+  KlGate kg;
+  if (const int rc = kl_gate_of("paac_clip_rmsprop_gated", gate, &kg)) return rc;
+  return clip_step("paac_clip_rmsprop_gated", ctx, params, grad, ms, mom, n, lr_dev, decay, momentum, eps, clip_norm,
+                   clip_mode, grad_scale, gnorm_out, nullptr, &kg, (hipStream_t)stream);
+}
+
+static int adam_args_ok(const char* fn, float beta1, float beta2, float eps) {
+  PAAC_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "%s: beta1=%g and beta2=%g must lie in [0, 1)", fn,
+               (double)beta1, (double)beta2);
+  PAAC_REQUIRE(eps > 0.f, "%s: eps=%g must be positive", fn, (double)eps);
+  return 0;
 }
 
 int paac_clip_adam(paac_ctx* ctx, float* params, const float* grad, float* m, float* v, float* beta_powers, int64_t n,
                    const float* lr_dev, float beta1, float beta2, float eps, float clip_norm, int clip_mode,
                    float grad_scale, float* gnorm_out, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && grad && m && v && beta_powers && lr_dev, "paac_clip_adam: null argument");
-  PAAC_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f,
-               "paac_clip_adam: beta1=%g and beta2=%g must lie in [0, 1)", (double)beta1, (double)beta2);
-  PAAC_REQUIRE(eps > 0.f, "paac_clip_adam: eps=%g must be positive", (double)eps);
+  if (const int rc = adam_args_ok("paac_clip_adam", beta1, beta2, eps)) return rc;
   const AdamPowers ap{beta_powers, lr_dev, ctx->partials + kAdamAlpha, beta1, beta2};
   return clip_step("paac_clip_adam", ctx, params, grad, m, v, n, lr_dev, beta1, beta2, eps, clip_norm, clip_mode, grad_scale,
-                   gnorm_out, &ap, (hipStream_t)stream);
+                   gnorm_out, &ap, nullptr, (hipStream_t)stream);
+}
+
+int paac_clip_adam_gated(paac_ctx* ctx, float* params, const float* grad, float* m, float* v, float* beta_powers, int64_t n,
+                         const float* lr_dev, float beta1, float beta2, float eps, float clip_norm, int clip_mode,
+                         float grad_scale, float* gnorm_out, const paac_kl_gate* gate, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && grad && m && v && beta_powers && lr_dev, "paac_clip_adam_gated: null argument");
+  if (const int rc = adam_args_ok("paac_clip_adam_gated", beta1, beta2, eps)) return rc;
+  KlGate kg;
+  if (const int rc = kl_gate_of("paac_clip_adam_gated", gate, &kg)) return rc;
+  const AdamPowers ap{beta_powers, lr_dev, ctx->partials + kAdamAlpha, beta1, beta2};
+  return clip_step("paac_clip_adam_gated", ctx, params, grad, m, v, n, lr_dev, beta1, beta2, eps, clip_norm, clip_mode,
+                   grad_scale, gnorm_out, &ap, &kg, (hipStream_t)stream);
 }
 
 int paac_grad_stats(paac_ctx* ctx, float* stats_out, paac_stream_t stream) {

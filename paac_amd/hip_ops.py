@@ -324,6 +324,45 @@ class Context(object):
                                            _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), _stream()),
                    "paac_clip_adam")
 
+    @staticmethod
+    def _kl_gate(kl, scale, thr, first, stop, applied, checked):
+        """-> _lib.KlGate (include/paac_hip.h: paac_kl_gate).  kl: float32 tensor whose first element is the statistic; stop:
+        int32[1]; applied (int32) / checked (float32): one-element views or None.  A kl / stop of None goes through as NULL
+        (the entry refuses it)."""
+        return _lib.KlGate(_ptr(kl, torch.float32, 1, "gate kl", True), float(scale), float(thr), 1 if first else 0,
+                           _ptr(stop, torch.int32, 1, "gate stop", True), _ptr(applied, torch.int32, 1, "gate applied", True),
+                           _ptr(checked, torch.float32, 1, "gate checked", True))
+
+    def clip_rmsprop_gated(self, params, grad, ms, mom, lr_dev, decay, momentum, eps, clip_norm, clip_mode, grad_scale=1.0,
+                           gnorm_out=None, *, kl, thr, first, stop, applied=None, checked=None, kl_scale=1.0):
+        """clip_rmsprop behind a --ppo_target_kl gate (include/paac_hip.h: paac_clip_rmsprop_gated): the step is skipped, and
+        *stop set, unless kl[0] * kl_scale <= thr and *stop was clear (first clears it before the comparison)."""
+        n = self.layout["total"]
+        gate = self._kl_gate(kl, kl_scale, thr, first, stop, applied, checked)
+        _lib.check(self.lib.paac_clip_rmsprop_gated(self.handle, _ptr(params, torch.float32, n, "params"),
+                                                    _ptr(grad, torch.float32, n, "grad"), _ptr(ms, torch.float32, n, "ms"),
+                                                    _ptr(mom, torch.float32, n, "mom"), n,
+                                                    _ptr(lr_dev, torch.float32, 1, "lr_dev"), float(decay), float(momentum),
+                                                    float(eps), float(clip_norm), int(clip_mode), float(grad_scale),
+                                                    _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), ctypes.byref(gate),
+                                                    _stream()),
+                   "paac_clip_rmsprop_gated")
+
+    def clip_adam_gated(self, params, grad, m, v, beta_powers, lr_dev, beta1, beta2, eps, clip_norm, clip_mode, grad_scale=1.0,
+                        gnorm_out=None, *, kl, thr, first, stop, applied=None, checked=None, kl_scale=1.0):
+        """clip_adam behind a --ppo_target_kl gate (include/paac_hip.h: paac_clip_adam_gated); a skipped step leaves the powers."""
+        n = self.layout["total"]
+        gate = self._kl_gate(kl, kl_scale, thr, first, stop, applied, checked)
+        _lib.check(self.lib.paac_clip_adam_gated(self.handle, _ptr(params, torch.float32, n, "params"),
+                                                 _ptr(grad, torch.float32, n, "grad"), _ptr(m, torch.float32, n, "m"),
+                                                 _ptr(v, torch.float32, n, "v"),
+                                                 _ptr(beta_powers, torch.float32, 2, "beta_powers"), n,
+                                                 _ptr(lr_dev, torch.float32, 1, "lr_dev"), float(beta1), float(beta2),
+                                                 float(eps), float(clip_norm), int(clip_mode), float(grad_scale),
+                                                 _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), ctypes.byref(gate),
+                                                 _stream()),
+                   "paac_clip_adam_gated")
+
     def keep_next_forward(self, train_row):
         """The next acting forward also leaves its rows' activations at rows [train_row, train_row + batch) of the training
         activation set (include/paac_hip.h: paac_keep_next_forward); -1 cancels."""

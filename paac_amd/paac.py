@@ -298,15 +298,16 @@ class DeviceRollout(object):
                 self._exchange(None)
             if before_last_update is not None and k == self.K - 1:
                 before_last_update()
-            self._update()
+            self._update(k)
 
     def _backward_conv(self, parity):
         L = self.L
         L.ctx.loss_backward(L.network.params, self.rollout_states(parity), self.actions.view(-1), self.y, self.adv,
                             L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=2)
 
-    def _update(self):
-        self.L.apply_gradients()
+    def _update(self, step):
+        """Optimizer step `step` of the cycle (--ppo_target_kl gates by it)."""
+        self.L.apply_gradients(step)
 
     def capture(self):
         """Capture the cycle into hipGraphs: one per observation-ring parity (and a separate update graph when a
@@ -327,7 +328,7 @@ class DeviceRollout(object):
             if with_update:
                 if self.graph_exchange:
                     self._exchange(None)          # recorded into the graph like the kernels around it
-                self._update()
+                self._update(0)
                 self._later_epochs(parity, self.graph_exchange)
 
         if self.graph_exchange:
@@ -372,11 +373,11 @@ class DeviceRollout(object):
                         self.graph_conv[parity] = captured(lambda: self._backward_conv(parity))
                     # the optimizer step of cycle k rides in front of cycle k+1's graph: two graph launches per
                     # cycle around the exchange instead of three (synchronize() flushes a pending step)
-                    self.graph_ua[parity] = captured(lambda: (self._update(), cycle(parity, False)))
-                    self.graph_epoch[parity] = [captured(lambda: (self._update(), self._epoch_backward(parity, k)))
+                    self.graph_ua[parity] = captured(lambda: (self._update(self.K - 1), cycle(parity, False)))
+                    self.graph_epoch[parity] = [captured(lambda: (self._update(k - 1), self._epoch_backward(parity, k)))
                                                 for k in range(1, self.K)]
             if self.phased:
-                self.graph_b = captured(self._update)
+                self.graph_b = captured(lambda: self._update(self.K - 1))
             else:
                 for p0 in (0, 1):
                     self.graph_multi[p0] = captured(lambda: [cycle((k + p0) & 1, True) for k in range(self.MULTI)])
@@ -390,7 +391,9 @@ class DeviceRollout(object):
         L = self.L
         ts = [self.states, self.actions, self.values, self.rewards, self.masks, self.probs, self.y, self.adv, self.ep_reward,
               self.ep_len, self.finished, self.tick, self.global_step_dev] + [t for _, t in L.update_state] + \
-             [L.grad, L.lr_dev, L.gnorm_dev, L.loss_dev] + [t for t in (L.p_old, L.ppo_loss, L.ppo_stats, L.adv_n, L.adv_stats, L.v_old) if t is not None]
+             [L.grad_store, L.lr_dev, L.gnorm_dev, L.loss_dev] + \
+             [t for t in (L.p_old, L.ppo_loss, L.ppo_stats, L.adv_n, L.adv_stats, L.v_old, L.kl_stop, L.ppo_applied, L.ppo_kl_checked)
+              if t is not None]
         if L.minibatch_on:      # (the staging block of states is rewritten by every epoch's gather before anything reads it)
             ts += [L.v_rec] + [t for k, t in L.mb.items() if t is not None and k != "states"]
         for name in ("raw", "walk_scratch", "mt_state", "env_state"):
@@ -415,7 +418,7 @@ class DeviceRollout(object):
         self._rollout_and_backward(0)
         self._exchange(None)
         eager = [L.grad.clone()]
-        self._update()                                    # (consumes what the backward left pending in the ctx)
+        self._update(0)                                   # (consumes what the backward left pending in the ctx)
         # (--ppo_epochs: the LAST epoch's exchanged gradient is compared -- it depends on every exchange before it)
         self._later_epochs(0, True, before_last_update=lambda: eager.__setitem__(0, L.grad.clone()))
         eager = eager[0]
@@ -489,7 +492,7 @@ class DeviceRollout(object):
                 self._rollout_and_backward(self.parity)
                 if self.phased:
                     self._exchange(None if self.single_exchange else (lambda: self._backward_conv(self.parity)))
-                self._update()
+                self._update(0)
                 self._later_epochs(self.parity, self.phased)
         self.parity ^= 1
 
@@ -499,7 +502,8 @@ class DeviceRollout(object):
         computes the conv head on ours; the update waits for both."""
         grad = self.L.grad
         if conv_backward is None:          # PAAC_ALLREDUCE=single: the backward is complete, one collective
-            parallel.allreduce_sum_(grad)  # a blocking-style call runs ON our stream: no cross-stream event hops
+            # (the whole store: under --ppo_target_kl the step's approx_kl travels behind the gradient)
+            parallel.allreduce_sum_(self.L.grad_store)  # a blocking-style call runs ON our stream: no cross-stream event hops
             return
         tail = parallel.allreduce_sum_async(grad[self.tail_offset:])
         conv_backward()
@@ -602,10 +606,15 @@ class PAACLearner(ActorLearner):
         loss = (self.ppo_loss[-1] if self.minibatch_on else self.loss_dev).cpu().numpy()
         stats = self.ctx.grad_stats(self.clip_norm, self.clip_mode)      # actor_learner.py:85-87 summaries
         self.metrics.write("gradients", global_step=int(self.global_step), **stats)
+        # --ppo_target_kl: which optimizer steps of the last cycle were applied, and the value each gate compared
+        applied = checked = None
+        if self.target_kl_on:
+            applied, checked = self.ppo_applied.cpu().numpy(), self.ppo_kl_checked.cpu().numpy()
         self.metrics.write("progress", global_step=int(self.global_step), steps_per_s=float(steps_per_s),
                            steps_per_s_avg=float(steps_per_s_avg), last_10_rewards_avg=float(last_ten),
                            lr=float(self.lr_dev.item()), grad_norm=float(self.gnorm_dev.item()), loss=float(loss[0]),
-                           actor_loss=float(loss[1]), critic_loss=float(loss[2]), entropy=float(loss[3]))
+                           actor_loss=float(loss[1]), critic_loss=float(loss[2]), entropy=float(loss[3]),
+                           **(dict(ppo_steps_applied=int(applied.sum())) if applied is not None else {}))
         if self.ppo_epochs > 1:          # one record per epoch of the last cycle (epoch 1: the update above, ratio == 1)
             losses, stats = self.ppo_loss.cpu().numpy(), self.ppo_stats.cpu().numpy()
             if not self.minibatch_on:
@@ -618,7 +627,9 @@ class PAACLearner(ActorLearner):
                                    actor_loss=float(losses[k, 1]), critic_loss=float(losses[k, 2]),
                                    entropy=float(losses[k, 3]), clip_fraction=float(stats[k, 0]),
                                    approx_kl=float(stats[k, 1]),
-                                   **(dict(value_clip_fraction=float(stats[k, 2])) if self.vclip_on else {}))
+                                   **(dict(value_clip_fraction=float(stats[k, 2])) if self.vclip_on else {}),
+                                   **(dict(applied=bool(applied[k]), kl_checked=float(checked[k])) if self.is_gated_step(k)
+                                      else {}))
         if self.adv_norm:                # the statistics the last rollout's advantages were normalised by (this rank's)
             mean, std = self.adv_stats.cpu().numpy()
             self.metrics.write("adv_norm", global_step=int(self.global_step), mean=float(mean), std=float(std))
@@ -942,7 +953,7 @@ class PAACLearner(ActorLearner):
                 for k in range(self.ppo_steps):
                     self.minibatch_step_backward(k, rows, acts, d_y, d_actor_adv, phase=0)
                     self._allreduce_grad()
-                    self.apply_gradients()
+                    self.apply_gradients(k)
             else:
                 if self.ppo_epochs > 1:
                     self.ctx.loss_backward_record(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
@@ -953,11 +964,11 @@ class PAACLearner(ActorLearner):
                 if self.vclip_on:         # v_old = the values epoch 1's heads just computed
                     self.ctx.train_values_into(self.v_old, T * N)
                 self._allreduce_grad()
-                self.apply_gradients()
+                self.apply_gradients(0)
                 for k in range(1, self.ppo_epochs):      # epochs 2..K on the frozen y / adv / p_old (/ v_old), the same lr
                     self.ppo_epoch_backward(k, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv, phase=0)
                     self._allreduce_grad()
-                    self.apply_gradients()
+                    self.apply_gradients(k)
             if getattr(self.args, "record_feeds", False):
                 self.last_feed = dict(states=d_states.view(T * N, 84, 84, 4).cpu().numpy(), y=d_y.cpu().numpy(),
                                       adv=d_adv.cpu().numpy(), actions=d_actions.view(-1).cpu().numpy(), lr=lr,

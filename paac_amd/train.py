@@ -99,6 +99,11 @@ BUILD_FLAGS = (
      "minibatches per PPO epoch: 1 = full-batch epochs; M in [2, 16] (a divisor of emulator_counts x max_local_steps, with "
      "ppo_epochs x M <= 64) = every epoch is M optimizer steps on a fresh shuffle of the rollout, drawn on the GPU from "
      "--sampler_seed; read only when --ppo_epochs is above 1"),
+    (("--ppo_target_kl",), "ppo_target_kl", 0.0, float,
+     "PPO KL early stopping D: 0 = off; above 0, an optimizer step of a rollout whose approx_kl (the mean of log p_old - log p "
+     "over the step's own batch, the ranks' mean under data parallelism) exceeds 1.5 x D is skipped on the GPU together with "
+     "every step after it in that rollout (the first full-batch step, whose ratio is 1, is never skipped); the skipped steps' "
+     "forward and backward still run, so a cycle takes the same time; read only when --ppo_epochs is above 1"),
     (("--adv_norm",), "adv_norm", False, bool_arg,
      "normalise each rollout's advantages by their own mean and standard deviation before the actor term reads them (per "
      "rank under data parallelism); the critic target and the recorded advantages are unchanged"),

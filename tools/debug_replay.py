@@ -35,7 +35,7 @@ with torch.cuda.stream(ro.stream):
             t.copy_(s)
         L.ctx.pack_weights(L.network.params)
     def eager():
-        ro._rollout_and_backward(0); ro._exchange(None); g = L.grad.clone(); ro._update()
+        ro._rollout_and_backward(0); ro._exchange(None); g = L.grad.clone(); ro._update(0)
         out = [g] + [t.clone() for t in state]; restore(); return out
     def replay():
         ro.graph_a[0].launch(); out = [L.grad.clone()] + [t.clone() for t in state]; restore(); return out

@@ -285,42 +285,39 @@ class ActorLearner(object):
     def apply_gradients(self, step=None):
         """The optimizer step on self.grad.  step: its index in the cycle; a gated step (--ppo_target_kl) goes through the gated
         entry, the first gated step of the cycle clearing the sticky stop flag.  None: ungated, whatever the flags say."""
-        net = self.network
+        adam = self.optimizer == "adam"
+        rule = ((self.adam_m, self.adam_v, self.beta_powers, self.lr_dev, self.beta1, self.beta2) if adam else
+                (self.rms, self.mom, self.lr_dev, self.alpha, self.momentum))
+        gate = {}
         if self.is_gated_step(step):
             n = self.grad.numel()
             gate = dict(kl=self.grad_store[n:] if self.kl_in_store else self.ppo_stats[step, 1:2],
                         kl_scale=self._grad_scale() if self.kl_in_store else 1.0, thr=self.kl_thr,
                         first=step == self.first_gated_step, stop=self.kl_stop, applied=self.ppo_applied[step:step + 1],
                         checked=self.ppo_kl_checked[step:step + 1])
-            if self.optimizer == "adam":
-                self.ctx.clip_adam_gated(net.params, self.grad, self.adam_m, self.adam_v, self.beta_powers, self.lr_dev,
-                                         self.beta1, self.beta2, self.e, self.clip_norm, self.clip_mode, self._grad_scale(),
-                                         self.gnorm_dev, **gate)
-            else:
-                self.ctx.clip_rmsprop_gated(net.params, self.grad, self.rms, self.mom, self.lr_dev, self.alpha, self.momentum,
-                                            self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev, **gate)
-            return
-        if self.optimizer == "adam":
-            self.ctx.clip_adam(net.params, self.grad, self.adam_m, self.adam_v, self.beta_powers, self.lr_dev, self.beta1,
-                               self.beta2, self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
+        entry = getattr(self.ctx, ("clip_adam" if adam else "clip_rmsprop") + ("_gated" if gate else ""))
+        entry(self.network.params, self.grad, *rule, self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev,
+              **gate)
+
+    def _surrogate_backward(self, slot, states, actions, y, adv, p_old, v_old, phase):
+        """The clipped-surrogate backward behind a finished training forward (trunk) into self.grad, loss and statistics into
+        row `slot` of ppo_loss / ppo_stats; with --ppo_vclip the critic term is clipped around the frozen v_old."""
+        params = self.network.params
+        if self.vclip_on:
+            self.ctx.loss_backward_ppo_vclip(params, states, actions, y, adv, p_old, v_old, self.ppo_clip, self.ppo_vclip,
+                                             self.entropy_beta, self.grad, self.ppo_loss[slot], self.ppo_stats[slot],
+                                             forward_done=True, phase=phase)
         else:
-            self.ctx.clip_rmsprop(net.params, self.grad, self.rms, self.mom, self.lr_dev, self.alpha, self.momentum,
-                                  self.e, self.clip_norm, self.clip_mode, self._grad_scale(), self.gnorm_dev)
+            self.ctx.loss_backward_ppo(params, states, actions, y, adv, p_old, self.ppo_clip, self.entropy_beta, self.grad,
+                                       self.ppo_loss[slot], self.ppo_stats[slot], forward_done=True, phase=phase)
+        self._kl_into_store(slot)
 
     def ppo_epoch_backward(self, k, states, actions, y, adv, phase):
         """Epoch k + 1 (k = 1 .. ppo_epochs - 1) up to its gradient: training forward (trunk) over the rollout rows on the
         current weights, then the clipped-surrogate backward on the frozen y / adv / p_old (adv: what the actor term reads,
         adv_n under --adv_norm; with --ppo_vclip the critic term is clipped around the frozen v_old)."""
-        params = self.network.params
-        self.ctx.train_forward_trunk(params, states)
-        if self.vclip_on:
-            self.ctx.loss_backward_ppo_vclip(params, states, actions, y, adv, self.p_old, self.v_old, self.ppo_clip,
-                                             self.ppo_vclip, self.entropy_beta, self.grad, self.ppo_loss[k], self.ppo_stats[k],
-                                             forward_done=True, phase=phase)
-        else:
-            self.ctx.loss_backward_ppo(params, states, actions, y, adv, self.p_old, self.ppo_clip, self.entropy_beta, self.grad,
-                                       self.ppo_loss[k], self.ppo_stats[k], forward_done=True, phase=phase)
-        self._kl_into_store(k)
+        self.ctx.train_forward_trunk(self.network.params, states)
+        self._surrogate_backward(k, states, actions, y, adv, self.p_old, self.v_old if self.vclip_on else None, phase)
 
     def minibatch_record(self, actions, value_rows):
         """The record pass of an M > 1 cycle on the pending training forward (pre-update weights): p_old, and the values of
@@ -342,17 +339,9 @@ class ActorLearner(object):
                                      self.p_old, mb["p_old"], self.v_old if self.vclip_on else None, mb["v_old"])
         b = mb["perms"].shape[1] // M
         r = slice(j * b, (j + 1) * b)
-        params = self.network.params
-        self.ctx.train_forward_trunk(params, mb["states"][r])
-        if self.vclip_on:
-            self.ctx.loss_backward_ppo_vclip(params, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
-                                             mb["v_old"][r], self.ppo_clip, self.ppo_vclip, self.entropy_beta, self.grad,
-                                             self.ppo_loss[s], self.ppo_stats[s], forward_done=True, phase=phase)
-        else:
-            self.ctx.loss_backward_ppo(params, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
-                                       self.ppo_clip, self.entropy_beta, self.grad, self.ppo_loss[s], self.ppo_stats[s],
-                                       forward_done=True, phase=phase)
-        self._kl_into_store(s)
+        self.ctx.train_forward_trunk(self.network.params, mb["states"][r])
+        self._surrogate_backward(s, mb["states"][r], mb["actions"][r], mb["y"][r], mb["adv"][r], mb["p_old"][r],
+                                 mb["v_old"][r] if self.vclip_on else None, phase)
 
     # -- one optimizer step from a reference-style feed dict (Session.run([train_step, ...], feed)) ----
     def _train_step_from_feed(self, feed_dict):

@@ -502,116 +502,91 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
   return 0;
 }
 
-int paac_loss_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
-                       const float* adv, int batch, float entropy_beta, float* grad, float* loss_out,
-                       int forward_done, int phase, paac_stream_t stream) {
-  PAAC_REQUIRE(ctx && params && states && actions && y && adv && grad, "paac_loss_backward: null argument");
-  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward: batch %d outside (0, max_batch=%d]", batch,
-               ctx->max_batch);
-  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward: phase %d", phase);
+// The fields of a paac_returns that do not depend on the entry: the rollout records, estimator, lambda, the schedule pointers.
+static int check_returns(const char* fn, const paac_returns* ret) {
+  PAAC_REQUIRE(ret->rewards && ret->masks && ret->values && ret->y_out && ret->adv_out, "%s: null rollout record", fn);
+  PAAC_REQUIRE(ret->estimator == PAAC_RETURNS_NSTEP || ret->estimator == PAAC_RETURNS_GAE,
+               "%s: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", fn, ret->estimator);
+  PAAC_REQUIRE(ret->gae_lambda >= 0.0 && ret->gae_lambda <= 1.0, "%s: gae_lambda %g outside [0, 1]", fn, ret->gae_lambda);
+  PAAC_REQUIRE(!ret->global_step_dev || (ret->lr_out_dev && ret->lr_annealing_steps > 0),
+               "%s: schedule bookkeeping needs lr_out_dev and lr_annealing_steps", fn);
+  return 0;
+}
+
+// What every paac_loss_backward* entry does behind the refusals of its own arguments: the shared checks (then those of the
+// returns record, for the two entries that take one: they read the batch), the training forward unless it has run, the
+// launch.  fn: the entry called, named in every message.
+static int loss_backward_entry(const char* fn, paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
+                               int batch, float entropy_beta, float* grad, float* loss_out, const BackwardCall& call,
+                               int forward_done, int phase, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && states && actions && grad && (call.ret || (call.y && call.adv)), "%s: null argument", fn);
+  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "%s: batch %d outside (0, max_batch=%d]", fn, batch, ctx->max_batch);
+  PAAC_REQUIRE(phase >= 0 && phase <= 3, "%s: phase %d", fn, phase);
+  if (const paac_returns* ret = call.ret) {
+    PAAC_REQUIRE(ret->T > 0 && ret->N > 0 && ret->T * ret->N == batch, "%s: T*N = %d*%d != batch %d", fn, ret->T, ret->N, batch);
+    if (const int rc = check_returns(fn, ret)) return rc;
+    PAAC_REQUIRE(ret->v_boot || (forward_done && batch + ret->N <= ctx->max_batch),
+                 "%s: v_boot == NULL takes the bootstrap values from rows [batch, batch + N) of a training forward that has "
+                 "already run over batch + N rows", fn);
+  }
   int rc = 0;
   if (!forward_done && phase != 2) {
     rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
     if (rc) return rc;
   }
   ctx->last_ws = 1;
-  rc = launch_backward(ctx, params, states, actions, y, adv, batch, entropy_beta, grad, loss_out, phase,
-                       (hipStream_t)stream);
+  rc = launch_backward(ctx, params, states, actions, batch, entropy_beta, grad, loss_out, phase, call, (hipStream_t)stream);
   if (rc) return rc;
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-static int loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
-                                 const paac_returns* ret, float* p_old_out, int batch, float entropy_beta, float* grad,
-                                 float* loss_out, int forward_done, int phase, paac_stream_t stream) {
-  PAAC_REQUIRE(ctx && params && states && actions && ret && grad, "paac_loss_backward_returns: null argument");
-  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_returns: batch %d outside (0, max_batch=%d]", batch,
-               ctx->max_batch);
-  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward_returns: phase %d", phase);
-  PAAC_REQUIRE(ret->T > 0 && ret->N > 0 && ret->T * ret->N == batch, "paac_loss_backward_returns: T*N = %d*%d != batch %d",
-               ret->T, ret->N, batch);
-  PAAC_REQUIRE(ret->rewards && ret->masks && ret->values && ret->y_out && ret->adv_out,
-               "paac_loss_backward_returns: null rollout record");
-  PAAC_REQUIRE(ret->v_boot || (forward_done && batch + ret->N <= ctx->max_batch),
-               "paac_loss_backward_returns: v_boot == NULL takes the bootstrap values from rows [batch, batch + N) of a "
-               "training forward that has already run over batch + N rows");
-  PAAC_REQUIRE(ret->estimator == PAAC_RETURNS_NSTEP || ret->estimator == PAAC_RETURNS_GAE,
-               "paac_loss_backward_returns: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", ret->estimator);
-  PAAC_REQUIRE(ret->gae_lambda >= 0.0 && ret->gae_lambda <= 1.0, "paac_loss_backward_returns: gae_lambda %g outside [0, 1]",
-               ret->gae_lambda);
-  PAAC_REQUIRE(!ret->global_step_dev || (ret->lr_out_dev && ret->lr_annealing_steps > 0),
-               "paac_loss_backward_returns: schedule bookkeeping needs lr_out_dev and lr_annealing_steps");
-  int rc = 0;
-  if (!forward_done && phase != 2) {
-    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  ctx->last_ws = 1;
-  // (p_old_out: this is epoch 1 of a --ppo_epochs cycle -- the same arithmetic, plus the store of p_old)
-  rc = launch_backward(ctx, params, states, actions, ret->y_out, ret->adv_out, batch, entropy_beta, grad, loss_out, phase,
-                       (hipStream_t)stream, ret, p_old_out ? 1 : 0, p_old_out);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+int paac_loss_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
+                       const float* adv, int batch, float entropy_beta, float* grad, float* loss_out,
+                       int forward_done, int phase, paac_stream_t stream) {
+  const BackwardCall call{.y = y, .adv = adv, .loss = kLossA3c};
+  return loss_backward_entry("paac_loss_backward", ctx, params, states, actions, batch, entropy_beta, grad, loss_out, call,
+                             forward_done, phase, stream);
 }
 
 int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                                const paac_returns* ret, int batch, float entropy_beta, float* grad, float* loss_out,
                                int forward_done, int phase, paac_stream_t stream) {
-  return loss_backward_returns(ctx, params, states, actions, ret, nullptr, batch, entropy_beta, grad, loss_out, forward_done,
-                               phase, stream);
+  PAAC_REQUIRE(ret, "paac_loss_backward_returns: null argument");
+  const BackwardCall call{.ret = ret, .loss = kLossA3c};
+  return loss_backward_entry("paac_loss_backward_returns", ctx, params, states, actions, batch, entropy_beta, grad, loss_out,
+                             call, forward_done, phase, stream);
 }
 
+// (p_old_out: this is epoch 1 of a --ppo_epochs cycle -- the same arithmetic, plus the store of p_old)
 int paac_loss_backward_returns_record(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                                       const paac_returns* ret, float* p_old_out, int batch, float entropy_beta, float* grad,
                                       float* loss_out, int forward_done, int phase, paac_stream_t stream) {
+  PAAC_REQUIRE(ret, "paac_loss_backward_returns_record: null argument");
   PAAC_REQUIRE(p_old_out, "paac_loss_backward_returns_record: null p_old_out");
-  return loss_backward_returns(ctx, params, states, actions, ret, p_old_out, batch, entropy_beta, grad, loss_out, forward_done,
-                               phase, stream);
+  const BackwardCall call{.ret = ret, .loss = kLossA3cRecord, .p_old_out = p_old_out};
+  return loss_backward_entry("paac_loss_backward_returns_record", ctx, params, states, actions, batch, entropy_beta, grad,
+                             loss_out, call, forward_done, phase, stream);
 }
 
 int paac_loss_backward_record(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                               const float* y, const float* adv, float* p_old_out, int batch, float entropy_beta, float* grad,
                               float* loss_out, int forward_done, int phase, paac_stream_t stream) {
-  PAAC_REQUIRE(ctx && params && states && actions && y && adv && grad, "paac_loss_backward_record: null argument");
   PAAC_REQUIRE(p_old_out, "paac_loss_backward_record: null p_old_out");
-  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_record: batch %d outside (0, max_batch=%d]", batch,
-               ctx->max_batch);
-  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward_record: phase %d", phase);
-  int rc = 0;
-  if (!forward_done && phase != 2) {
-    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  ctx->last_ws = 1;
-  rc = launch_backward(ctx, params, states, actions, y, adv, batch, entropy_beta, grad, loss_out, phase, (hipStream_t)stream,
-                       nullptr, 1, p_old_out);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  const BackwardCall call{.y = y, .adv = adv, .loss = kLossA3cRecord, .p_old_out = p_old_out};
+  return loss_backward_entry("paac_loss_backward_record", ctx, params, states, actions, batch, entropy_beta, grad, loss_out,
+                             call, forward_done, phase, stream);
 }
 
 int paac_loss_backward_ppo(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
                            const float* adv, const float* p_old, float clip_eps, int batch, float entropy_beta, float* grad,
                            float* loss_out, float* ppo_stats_out, int forward_done, int phase, paac_stream_t stream) {
-  PAAC_REQUIRE(ctx && params && states && actions && y && adv && grad, "paac_loss_backward_ppo: null argument");
   PAAC_REQUIRE(p_old, "paac_loss_backward_ppo: null p_old");
   PAAC_REQUIRE(clip_eps > 0.f && clip_eps < 1.f, "paac_loss_backward_ppo: clip_eps %g outside (0, 1)", (double)clip_eps);   // (NaN fails)
-  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_ppo: batch %d outside (0, max_batch=%d]", batch,
-               ctx->max_batch);
-  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward_ppo: phase %d", phase);
-  int rc = 0;
-  if (!forward_done && phase != 2) {
-    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  ctx->last_ws = 1;
-  rc = launch_backward(ctx, params, states, actions, y, adv, batch, entropy_beta, grad, loss_out, phase, (hipStream_t)stream,
-                       nullptr, 2, const_cast<float*>(p_old), clip_eps, ppo_stats_out);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  const BackwardCall call{.y = y, .adv = adv, .loss = kLossPpo, .p_old = p_old, .clip_eps = clip_eps,
+                          .ppo_stats_out = ppo_stats_out};
+  return loss_backward_entry("paac_loss_backward_ppo", ctx, params, states, actions, batch, entropy_beta, grad, loss_out, call,
+                             forward_done, phase, stream);
 }
 
 // Elements of activation `what` (paac_debug_activation) for `batch` rows of geometry `spec`; -1: no such activation.
@@ -631,14 +606,7 @@ int paac_returns_norm_tick(paac_ctx* ctx, const float* params, const paac_return
                            paac_stream_t stream) {
   PAAC_REQUIRE(ret && adv_n_out, "paac_returns_norm_tick: null argument");
   PAAC_REQUIRE(ret->T > 0 && ret->N > 0, "paac_returns_norm_tick: T=%d N=%d", ret->T, ret->N);
-  PAAC_REQUIRE(ret->rewards && ret->masks && ret->values && ret->y_out && ret->adv_out,
-               "paac_returns_norm_tick: null rollout record");
-  PAAC_REQUIRE(ret->estimator == PAAC_RETURNS_NSTEP || ret->estimator == PAAC_RETURNS_GAE,
-               "paac_returns_norm_tick: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", ret->estimator);
-  PAAC_REQUIRE(ret->gae_lambda >= 0.0 && ret->gae_lambda <= 1.0, "paac_returns_norm_tick: gae_lambda %g outside [0, 1]",
-               ret->gae_lambda);
-  PAAC_REQUIRE(!ret->global_step_dev || (ret->lr_out_dev && ret->lr_annealing_steps > 0),
-               "paac_returns_norm_tick: schedule bookkeeping needs lr_out_dev and lr_annealing_steps");
+  if (const int rc = check_returns("paac_returns_norm_tick", ret)) return rc;
   const float* v_boot = ret->v_boot;
   if (!v_boot) {
     const int64_t batch = (int64_t)ret->T * ret->N;
@@ -682,26 +650,15 @@ int paac_loss_backward_ppo_vclip(paac_ctx* ctx, const float* params, const uint8
                                  const float* y, const float* adv, const float* p_old, const float* v_old, float clip_eps,
                                  float vclip_eps, int batch, float entropy_beta, float* grad, float* loss_out,
                                  float* ppo_stats_out, int forward_done, int phase, paac_stream_t stream) {
-  PAAC_REQUIRE(ctx && params && states && actions && y && adv && grad, "paac_loss_backward_ppo_vclip: null argument");
   PAAC_REQUIRE(p_old, "paac_loss_backward_ppo_vclip: null p_old");
   PAAC_REQUIRE(v_old, "paac_loss_backward_ppo_vclip: null v_old");
   PAAC_REQUIRE(clip_eps > 0.f && clip_eps < 1.f, "paac_loss_backward_ppo_vclip: clip_eps %g outside (0, 1)", (double)clip_eps);   // (NaN fails)
   PAAC_REQUIRE(vclip_eps > 0.f, "paac_loss_backward_ppo_vclip: vclip_eps %g is not positive (0 = off: paac_loss_backward_ppo)",
                (double)vclip_eps);                                                                                                // (NaN fails)
-  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_loss_backward_ppo_vclip: batch %d outside (0, max_batch=%d]", batch,
-               ctx->max_batch);
-  PAAC_REQUIRE(phase >= 0 && phase <= 3, "paac_loss_backward_ppo_vclip: phase %d", phase);
-  int rc = 0;
-  if (!forward_done && phase != 2) {
-    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  ctx->last_ws = 1;
-  rc = launch_backward(ctx, params, states, actions, y, adv, batch, entropy_beta, grad, loss_out, phase, (hipStream_t)stream,
-                       nullptr, 3, const_cast<float*>(p_old), clip_eps, ppo_stats_out, v_old, vclip_eps);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  const BackwardCall call{.y = y, .adv = adv, .loss = kLossPpoVclip, .p_old = p_old, .clip_eps = clip_eps,
+                          .ppo_stats_out = ppo_stats_out, .v_old = v_old, .vclip_eps = vclip_eps};
+  return loss_backward_entry("paac_loss_backward_ppo_vclip", ctx, params, states, actions, batch, entropy_beta, grad, loss_out,
+                             call, forward_done, phase, stream);
 }
 
 int64_t paac_debug_activation_size(int arch, int what, int batch) {

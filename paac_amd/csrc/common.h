@@ -314,10 +314,22 @@ int launch_sample_env_step_heads(const float* partial, int ntiles, const float* 
                                  const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2, float* rewards,
                                  float* masks, float* ep_reward, int32_t* ep_len, void* finished, uint8_t* raw_scratch,
                                  const void* mt_ahead, hipStream_t s);
-int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
-                    const float* adv, int batch, float beta, float* grad, float* loss_out, int phase, hipStream_t s,
-                    const paac_returns* ret = nullptr, int loss = 0, float* p_old = nullptr, float clip_eps = 0.f,
-                    float* ppo_stats_out = nullptr,    // loss: heads.h kLossA3c / kLossA3cRecord / kLossPpo / kLossPpoVclip
-                    const float* v_old = nullptr, float vclip_eps = 0.f);
+// What the heads of one backward compute (heads.h has the arithmetic of each loss): the arrays a loss reads or writes, the
+// others null / zero.  ret: the returns are computed inside the heads launch and land in ret->y_out / adv_out (y / adv unused).
+constexpr int kLossA3c = 0, kLossA3cRecord = 1, kLossPpo = 2, kLossPpoVclip = 3;
+struct BackwardCall {
+  const float* y;
+  const float* adv;
+  const paac_returns* ret;
+  int loss;
+  float* p_old_out;        // kLossA3cRecord
+  const float* p_old;      // kLossPpo, kLossPpoVclip
+  float clip_eps;
+  float* ppo_stats_out;    // kLossPpo: [2], kLossPpoVclip: [3]; nullable
+  const float* v_old;      // kLossPpoVclip
+  float vclip_eps;
+};
+int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, int batch, float beta,
+                    float* grad, float* loss_out, int phase, const BackwardCall& call, hipStream_t s);
 
 }  // namespace paac

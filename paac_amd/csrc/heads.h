@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
 //                   vc = v_old + clamp(v - v_old, -EPSV, EPSV); l1 = (y-v)^2; l2 = (y-vc)^2; vclipped = l2 > l1
 //                   critic term = 0.25*max(l1, l2); dv = vclipped ? 0 : s*0.5*(v - y); pstats[2] = vclipped.
 //                   With v_old = v: vc = v, l2 = l1, and the row is the kLossPpo row bit for bit.
-constexpr int kLossA3c = 0, kLossA3cRecord = 1, kLossPpo = 2, kLossPpoVclip = 3;
+// (the ids themselves: common.h, beside BackwardCall)
 constexpr bool loss_is_ppo(int loss) { return loss == kLossPpo || loss == kLossPpoVclip; }
 template <int AP, int LOSS = kLossA3c>
 __device__ __forceinline__ void head_grad_row(const float (&pi)[AP], float v, int act, float y, float adv, float beta,
@@ -468,7 +468,10 @@ __device__ __forceinline__ void returns_row_from(const GaeArgs& r, const int i, 
 // The LOSS != kLossA3c instantiations carry three more arguments behind their estimator's block (every kLossA3c
 // instantiation keeps its block, and with it its arguments and its code).
 struct PpoArgs {
-  float* p_old;         // [B]: written by kLossA3cRecord, read by kLossPpo
+  union {               // one slot: a kernel uses the member the host set for its LOSS
+    float* p_old_out;   // [B]: written by kLossA3cRecord
+    const float* p_old; // [B]: read by kLossPpo / kLossPpoVclip
+  };
   float clip_eps;       // kLossPpo
   float* stat_rows;     // kLossPpo: [B][2] per-row {clipped, log(p_old+eps) - log(p+eps)}, summed by ppo_stats_kernel
 };
@@ -640,7 +643,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
     }
     if constexpr (LOSS == kLossA3cRecord) {
       const int ai = actions[i];
-      rt.ppo.p_old[i] = probs[(long)i * A + (ai >= 0 && ai < A ? ai : 0)];   // (an action outside [0, A) reads no other row)
+      rt.ppo.p_old_out[i] = probs[(long)i * A + (ai >= 0 && ai < A ? ai : 0)];   // (an action outside [0, A) reads no other row)
     }
     if constexpr (loss_is_ppo(LOSS)) {
       rt.ppo.stat_rows[2 * i] = pst[0];
@@ -776,7 +779,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(const float* __restric
         probs_ws[(long)i * A + a] = pa;
         logits_ws[(long)i * A + a] = lg[a];
         if constexpr (LOSS == kLossA3cRecord) {
-          if (a == act) rt.ppo.p_old[i] = pa;
+          if (a == act) rt.ppo.p_old_out[i] = pa;
         }
       }
     }

@@ -238,61 +238,50 @@ int launch_pack_dgrad(paac_ctx* ctx, const float* params, hipStream_t s) {
 // buffer, 95 % of its bytes); 2 = conv layers (the head of the flat buffer) + slab finalize.  The split lets a
 // data-parallel caller all-reduce the tail while phase 2 still computes.  3 = whole backward with the slab finalize
 // left to the norm pass of the next paac_clip_rmsprop on `grad` (one launch less; the same sums in the same order).
-// kLossPpo: clip fraction and approximate KL of the update = means over the rows of stat_rows, summed in block_sums_256's
-// fixed order (one workgroup; the rows were written by whichever heads kernel ran, so every route gives the same bits).
-__global__ __launch_bounds__(256) void ppo_stats_kernel(const float* __restrict__ stat_rows, int B, float* __restrict__ out2) {
-  __shared__ float smem[2 * 256 + 2 * 8];
-  __shared__ float red[2];
-  float acc[2] = {0.f, 0.f};
+// kLossPpo (NS = 2): clip fraction and approximate KL of the update = means over the rows of stat_rows, summed in
+// block_sums_256's fixed order (one workgroup; the rows were written by whichever heads kernel ran, so every route gives the
+// same bits).  kLossPpoVclip (NS = 3): plus value_clip_fraction = the mean of vclip_rows, in the same launch and order.
+template <int NS>
+__global__ __launch_bounds__(256) void ppo_stats_kernel(const float* __restrict__ stat_rows, int B, float* __restrict__ out,
+                                                        const float* __restrict__ vclip_rows) {
+  static_assert(NS == 2 || NS == 3, "two PPO statistics, or three with the value clip");
+  __shared__ float smem[NS * 256 + NS * 8];
+  __shared__ float red[NS];
+  float acc[NS] = {};
   for (int i = threadIdx.x; i < B; i += 256) {
     acc[0] += stat_rows[2 * i];
     acc[1] += stat_rows[2 * i + 1];
+    if constexpr (NS == 3) acc[2] += vclip_rows[i];
   }
-  block_sums_256<2>(acc, smem, red);
-  if (threadIdx.x < 2) out2[threadIdx.x] = red[threadIdx.x] / (float)B;
+  block_sums_256<NS>(acc, smem, red);
+  if (threadIdx.x < NS) out[threadIdx.x] = red[threadIdx.x] / (float)B;
 }
 
-// kLossPpoVclip: the same two means plus value_clip_fraction = the mean of vclip_rows, in the same launch and order.
-__global__ __launch_bounds__(256) void ppo_vclip_stats_kernel(const float* __restrict__ stat_rows,
-                                                              const float* __restrict__ vclip_rows, int B,
-                                                              float* __restrict__ out3) {
-  __shared__ float smem[3 * 256 + 3 * 8];
-  __shared__ float red[3];
-  float acc[3] = {0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < B; i += 256) {
-    acc[0] += stat_rows[2 * i];
-    acc[1] += stat_rows[2 * i + 1];
-    acc[2] += vclip_rows[i];
-  }
-  block_sums_256<3>(acc, smem, red);
-  if (threadIdx.x < 3) out3[threadIdx.x] = red[threadIdx.x] / (float)B;
+// The heads launch of one (loss, estimator) cell: go(est, loss, args) gets the cell's two integral constants and its argument
+// block -- the estimator's (ReturnsArgs / GaeArgs), with the PPO fields behind it for every LOSS != kLossA3c and the value-clip
+// fields behind those for kLossPpoVclip.  (kLossPpo / kLossPpoVclip read y / adv from the arrays whatever estimator made them:
+// one instantiation each, under the n-step block.)
+template <int V> using Int = std::integral_constant<int, V>;
+template <class Base>
+static WithPpo<Base> with_ppo(const Base& base, const PpoArgs& ppo) {
+  WithPpo<Base> ra;
+  static_cast<Base&>(ra) = base;
+  ra.ppo = ppo;
+  return ra;
 }
-
-// The heads launch of a LOSS != kLossA3c instantiation: its estimator's argument block with the PPO fields behind it.
-// (kLossPpo reads y / adv from the arrays whatever estimator made them: one instantiation, under the n-step block.)
 template <class Go>
 static void launch_ppo_heads(Go&& go, int loss, int estimator, const GaeArgs& rt, const PpoArgs& ppo, const VclipArgs& vc) {
-  using std::integral_constant;
-  if (loss == kLossPpoVclip) {                 // (like kLossPpo: one instantiation, under the n-step block)
-    WithVclip<ReturnsArgs> ra;
-    static_cast<ReturnsArgs&>(ra) = rt;
-    ra.ppo = ppo;
-    ra.vc = vc;
-    go(integral_constant<int, kEstNstep>{}, integral_constant<int, kLossPpoVclip>{}, ra);
-    return;
-  }
-  if (loss == kLossA3cRecord && estimator == kEstGae) {
-    WithPpo<GaeArgs> ra;
-    static_cast<GaeArgs&>(ra) = rt;
-    ra.ppo = ppo;
-    go(integral_constant<int, kEstGae>{}, integral_constant<int, kLossA3cRecord>{}, ra);
-    return;
-  }
-  WithPpo<ReturnsArgs> ra;
-  static_cast<ReturnsArgs&>(ra) = rt;
-  ra.ppo = ppo;
-  if (loss == kLossA3cRecord) go(integral_constant<int, kEstNstep>{}, integral_constant<int, kLossA3cRecord>{}, ra);
-  else go(integral_constant<int, kEstNstep>{}, integral_constant<int, kLossPpo>{}, ra);
+  const ReturnsArgs& rtn = rt;
+  const bool gae = estimator == kEstGae;
+  if (loss == kLossA3c && gae) return go(Int<kEstGae>{}, Int<kLossA3c>{}, rt);
+  if (loss == kLossA3c) return go(Int<kEstNstep>{}, Int<kLossA3c>{}, rtn);
+  if (loss == kLossA3cRecord && gae) return go(Int<kEstGae>{}, Int<kLossA3cRecord>{}, with_ppo(rt, ppo));
+  if (loss == kLossA3cRecord) return go(Int<kEstNstep>{}, Int<kLossA3cRecord>{}, with_ppo(rtn, ppo));
+  if (loss == kLossPpo) return go(Int<kEstNstep>{}, Int<kLossPpo>{}, with_ppo(rtn, ppo));
+  WithVclip<ReturnsArgs> ra;
+  static_cast<WithPpo<ReturnsArgs>&>(ra) = with_ppo(rtn, ppo);
+  ra.vc = vc;
+  go(Int<kEstNstep>{}, Int<kLossPpoVclip>{}, ra);
 }
 
 template <class NT>
@@ -327,8 +316,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       if (rc) return rc;
     }
   }
-  GaeArgs rtl = rt;                            // (the n-step kernels take its ReturnsArgs part: estimator chosen below)
-  const ReturnsArgs& rtn = rtl;
+  GaeArgs rtl = rt;
   if (rtl.boot_in_fwd && !fused_heads) {       // the separate heads launch has produced the bootstrap rows' values
     rtl.v_boot = W.values + batch;
     rtl.boot_in_fwd = 0;
@@ -336,9 +324,9 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
   // The heads-gradient launch also leaves dH as bf16 planes when this update's fc data gradient takes the split-once kernel
   // (fc_dgrad_once.h): decided here from the shapes and the switch alone, so that every route to the same update -- whole or
   // phased backward, either heads kernel, PPO epochs and minibatches -- runs the same arithmetic.
-  static const int gemm3_rows_once = env_int("PAAC_GEMM3_MIN_ROWS", 513);
+  static const int gemm3_min_rows = env_int("PAAC_GEMM3_MIN_ROWS", 513);
   const bool once_shape = ctx->fc_dgrad_once && ctx->dh_planes && dh_planes_supported(NT::H) && batch <= kFcOnceMaxRows &&
-                          batch < gemm3_rows_once && (NT::FLAT % 16) == 0;
+                          batch < gemm3_min_rows && (NT::FLAT % 16) == 0;
   bf16x8* dhp = once_shape ? reinterpret_cast<bf16x8*>(ctx->dh_planes) : nullptr;
   if (do_fc) ctx->dh_planes_rows = dhp ? batch : 0;      // (every heads launch below writes the planes it is handed)
   // (1) heads: dH, head weight/bias grads, loss scalars
@@ -347,49 +335,29 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     const int rows = ctx->heads_pending_rows;
     // (rows kept by the acting forwards hold finished fc activations: one "slab", zero bias -- fmaxf(h + 0, 0) == h)
     const float* fc_b = ctx->heads_pending_h ? (const float*)ctx->zeros : params + L.offset[i_wf + 1];
-    if (loss != kLossA3c) {
-      // (--ppo_epochs: epoch 1 also stores p_old; later epochs run the clipped surrogate on the frozen y / adv / p_old arrays)
-      auto go = [&](auto est, auto lossc, const auto& ra) {
-        launch_heads_train<NT::H, decltype(est)::value, decltype(lossc)::value>(
-            A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H, fc_b, wa,
-            params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A, batch, W.h, W.logits, W.probs, W.values, actions, y,
-            adv, beta, ctx->dh, ctx->dl_buf, dhp, ra);
-      };
-      launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
-    } else if (estimator == kEstGae)
-      launch_heads_train<NT::H, kEstGae>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
-                                         fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
-                                         batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, dhp, rtl);
-    else
-      launch_heads_train<NT::H, kEstNstep>(A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H,
-                                           fc_b, wa, params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A,
-                                           batch, W.h, W.logits, W.probs, W.values, actions, y, adv, beta, ctx->dh, ctx->dl_buf, dhp, rtn);
+    // (--ppo_epochs: epoch 1 also stores p_old; later epochs run the clipped surrogate on the frozen y / adv / p_old arrays)
+    auto go = [&](auto est, auto lossc, const auto& ra) {
+      launch_heads_train<NT::H, decltype(est)::value, decltype(lossc)::value>(
+          A, dim3(batch), s, (const float*)W.fc_slab, ctx->heads_pending_splits, (long)rows * NT::H, fc_b, wa,
+          params + L.offset[i_wa + 1], wc, params + L.offset[i_wc + 1], A, batch, W.h, W.logits, W.probs, W.values, actions, y,
+          adv, beta, ctx->dh, ctx->dl_buf, dhp, ra);
+    };
+    launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
     ctx->heads_pending_rows = 0;
     ctx->heads_pending_h = 0;
   } else if (do_fc) {
     ProfScope ps(ctx, F_HEADS_BWD, batch, s);
-    if (loss != kLossA3c) {
-      auto go = [&](auto est, auto lossc, const auto& ra) {
-        launch_heads_bwd<NT::H, decltype(est)::value, decltype(lossc)::value>(
-            A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y, adv, (const float*)W.h,
-            wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa], grad + L.offset[i_wa + 1], grad + L.offset[i_wc],
-            grad + L.offset[i_wc + 1], loss_out, dhp, ra);
-      };
-      launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
-    } else if (estimator == kEstGae)
-      launch_heads_bwd<NT::H, kEstGae>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
-                                       adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
-                                       grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, dhp, rtl);
-    else
-      launch_heads_bwd<NT::H, kEstNstep>(A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y,
-                                         adv, (const float*)W.h, wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa],
-                                         grad + L.offset[i_wa + 1], grad + L.offset[i_wc], grad + L.offset[i_wc + 1], loss_out, dhp, rtn);
+    auto go = [&](auto est, auto lossc, const auto& ra) {
+      launch_heads_bwd<NT::H, decltype(est)::value, decltype(lossc)::value>(
+          A, dim3(batch + NT::H / 32 + 1), s, (const float*)W.probs, (const float*)W.values, actions, y, adv, (const float*)W.h,
+          wa, wc, A, batch, beta, ctx->dh, grad + L.offset[i_wa], grad + L.offset[i_wa + 1], grad + L.offset[i_wc],
+          grad + L.offset[i_wc + 1], loss_out, dhp, ra);
+    };
+    launch_ppo_heads(go, loss, estimator, rtl, ppo, vc);
   }
-  if (do_fc && loss == kLossPpo && ppo_stats_out)
-    launch_k(ppo_stats_kernel, dim3(1), dim3(256), s, PROF_NONE, (const float*)ppo.stat_rows, batch, ppo_stats_out);
-  if (do_fc && loss == kLossPpoVclip && ppo_stats_out)
-    launch_k(ppo_vclip_stats_kernel, dim3(1), dim3(256), s, PROF_NONE, (const float*)ppo.stat_rows,
-             (const float*)vc.stat_rows, batch, ppo_stats_out);
+  if (do_fc && loss_is_ppo(loss) && ppo_stats_out)
+    launch_k(loss == kLossPpo ? ppo_stats_kernel<2> : ppo_stats_kernel<3>, dim3(1), dim3(256), s, PROF_NONE,
+             (const float*)ppo.stat_rows, batch, ppo_stats_out, (const float*)vc.stat_rows);
   const float* xf = (NT::NCONV == 3) ? W.act[2] : W.act[1];   // flattened last conv output
   float* dxf = (NT::NCONV == 3) ? ctx->dact[2] : ctx->dact[1];
   FinalizeArgs fin;
@@ -422,13 +390,11 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       static const bool pair2 = env_int("PAAC_WGRAD_PAIR", 1) != 0;
       int wcfg, wks, wxcd;
       resolve_wgrad<false, NT::H>(gw, 1, ctx->tune[OP_FC_WGRAD][cls], wcfg, wks, wxcd);
-      static const int gemm3_rows = env_int("PAAC_GEMM3_MIN_ROWS", 513);
-      fc_wgrad_held = pair2 && do_conv && ctx->tower_on && wcfg == 1 && !(batch >= gemm3_rows && (batch % 32) == 0);
+      fc_wgrad_held = pair2 && do_conv && ctx->tower_on && wcfg == 1 && !(batch >= gemm3_min_rows && (batch % 32) == 0);
       held_gw = gw;
       held_ks = wks;
       held_xcd = wxcd;
     }
-    static const int gemm3_min_rows = env_int("PAAC_GEMM3_MIN_ROWS", 513);
     if (!fc_wgrad_held && batch >= gemm3_min_rows && (batch % 32) == 0) {
       // dWf[FLAT, H] = X^T dH on the LDS-tiled split-bf16 GEMM (gemm3.h), 128 x 64 tiles, whole K (= rows) per workgroup:
       // written straight into the flat gradient; the row-block-0 workgroups also leave the bias gradient (column sums of dH)
@@ -651,23 +617,25 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
   return 0;
 }
 
-int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, const float* y,
-                    const float* adv, int batch, float beta, float* grad, float* loss_out, int phase, hipStream_t s,
-                    const paac_returns* ret, int loss, float* p_old, float clip_eps, float* ppo_stats_out,
-                    const float* v_old, float vclip_eps) {
+int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, int batch, float beta,
+                    float* grad, float* loss_out, int phase, const BackwardCall& c, hipStream_t s) {
   VclipArgs vc;
-  vc.v_old = v_old;
-  vc.vclip_eps = vclip_eps;
+  vc.v_old = c.v_old;
+  vc.vclip_eps = c.vclip_eps;
   vc.stat_rows = ctx->vclip_rows;
   PpoArgs ppo;
-  ppo.p_old = p_old;
-  ppo.clip_eps = clip_eps;
+  if (c.loss == kLossA3cRecord) ppo.p_old_out = c.p_old_out;
+  else ppo.p_old = c.p_old;
+  ppo.clip_eps = c.clip_eps;
   ppo.stat_rows = ctx->ppo_rows;
+  const paac_returns* ret = c.ret;
   const GaeArgs rt = returns_args(ret, ret ? ret->v_boot : nullptr);
   const int estimator = ret ? ret->estimator : kEstNstep;      // (validated by paac_loss_backward_returns)
+  const float* y = ret ? ret->y_out : c.y;                     // (in-launch returns land in the record's arrays)
+  const float* adv = ret ? ret->adv_out : c.adv;
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, vc, ppo_stats_out, s);
-  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, loss, ppo, vc, ppo_stats_out, s);
+    return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, c.loss, ppo, vc, c.ppo_stats_out, s);
+  return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, c.loss, ppo, vc, c.ppo_stats_out, s);
 }
 
 int64_t wslab_floats_needed(int arch) {

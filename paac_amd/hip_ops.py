@@ -178,22 +178,30 @@ class Context(object):
                                                      _ptr(states, torch.uint8, B * 28224, "states"), B, _stream()),
                    "paac_train_forward_trunk")
 
+    def _loss_backward(self, entry, params, states, actions, middle, entropy_beta, grad, loss_out, forward_done, phase,
+                       stats=None):
+        """One paac_loss_backward* call: every entry takes (handle, params, states, actions), then its own `middle` arguments
+        -- a (name, tensor[, optional]) tuple per float32[B] array, anything else as it is --, then (batch, beta, grad,
+        loss_out), its statistics output (tensor, floats) if it has one, and (forward_done, phase, stream).  The arrays are
+        validated in argument order."""
+        B = self._check_states(states)
+        args = [self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
+                _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions")]
+        args += [_ptr(m[1], torch.float32, B, m[0], *m[2:]) if isinstance(m, tuple) else m for m in middle]
+        args += [B, float(entropy_beta), _ptr(grad, torch.float32, self.layout["total"], "grad"),
+                 _ptr(loss_out, torch.float32, 4, "loss_out", True)]
+        if stats is not None:
+            args.append(_ptr(stats[0], torch.float32, stats[1], "ppo_stats_out", True))
+        _lib.check(getattr(self.lib, entry)(*args, 1 if forward_done else 0, int(phase), _stream()), entry)
+
     def loss_backward(self, params, states, actions, y, adv, entropy_beta, grad, loss_out=None, forward_done=False,
-                      phase=0):
-        B = states.shape[0]
-        if tuple(states.shape[1:]) != OBS_SHAPE:
-            raise ValueError("states must be [B,84,84,4] uint8, got %s" % (tuple(states.shape),))
-        if not (0 < B <= self.max_batch):
-            raise ValueError("batch %d outside (0, %d]" % (B, self.max_batch))
-        _lib.check(self.lib.paac_loss_backward(self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
-                                               _ptr(states, torch.uint8, B * 28224, "states"),
-                                               _ptr(actions, torch.int32, B, "actions"),
-                                               _ptr(y, torch.float32, B, "y"), _ptr(adv, torch.float32, B, "adv"), B,
-                                               float(entropy_beta),
-                                               _ptr(grad, torch.float32, self.layout["total"], "grad"),
-                                               _ptr(loss_out, torch.float32, 4, "loss_out", True),
-                                               1 if forward_done else 0, int(phase), _stream()),
-                   "paac_loss_backward")
+                      phase=0, p_old_out=None):
+        """p_old_out: float32[B], also receives p_old (include/paac_hip.h: paac_loss_backward_record); gradient and loss are
+        unchanged."""
+        record = p_old_out is not None
+        self._loss_backward("paac_loss_backward_record" if record else "paac_loss_backward", params, states, actions,
+                            (("y", y), ("adv", adv)) + ((("p_old_out", p_old_out),) if record else ()),
+                            entropy_beta, grad, loss_out, forward_done, phase)
 
     def loss_backward_returns(self, params, states, actions, v_boot, rewards, masks, values, gamma, y_out, adv_out,
                               entropy_beta, grad, loss_out=None, forward_done=False, phase=0, global_step_dev=None,
@@ -204,66 +212,40 @@ class Context(object):
         v_boot=None: the bootstrap values are rows [B, B + N) of the training forward that has already run.
         gae_lambda: None or 1.0 = the n-step return; anything else = GAE(lambda) instead (uses_gae).
         p_old_out: float32[B], also receives p_old (epoch 1 of a --ppo_epochs cycle); gradient and loss are unchanged."""
-        B = self._check_states(states)
         T, N = rewards.shape
-        if T * N != B:
-            raise ValueError("rollout records are [%d,%d] but the batch has %d rows" % (T, N, B))
+        if T * N != states.shape[0]:
+            raise ValueError("rollout records are [%d,%d] but the batch has %d rows" % (T, N, states.shape[0]))
         ret = _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
                               lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda)
-        if p_old_out is not None:          # include/paac_hip.h: paac_loss_backward_returns_record
-            _lib.check(self.lib.paac_loss_backward_returns_record(
-                self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
-                _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"), ctypes.byref(ret),
-                _ptr(p_old_out, torch.float32, B, "p_old_out"), B, float(entropy_beta),
-                _ptr(grad, torch.float32, self.layout["total"], "grad"), _ptr(loss_out, torch.float32, 4, "loss_out", True),
-                1 if forward_done else 0, int(phase), _stream()), "paac_loss_backward_returns_record")
-            return
-        _lib.check(self.lib.paac_loss_backward_returns(
-            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
-            _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"), ctypes.byref(ret), B,
-            float(entropy_beta), _ptr(grad, torch.float32, self.layout["total"], "grad"),
-            _ptr(loss_out, torch.float32, 4, "loss_out", True), 1 if forward_done else 0, int(phase), _stream()),
-            "paac_loss_backward_returns")
+        record = p_old_out is not None          # include/paac_hip.h: paac_loss_backward_returns_record
+        self._loss_backward("paac_loss_backward_returns_record" if record else "paac_loss_backward_returns", params, states,
+                            actions, (ctypes.byref(ret),) + ((("p_old_out", p_old_out),) if record else ()),
+                            entropy_beta, grad, loss_out, forward_done, phase)
 
     def loss_backward_record(self, params, states, actions, y, adv, p_old_out, entropy_beta, grad, loss_out=None,
                              forward_done=False, phase=0):
         """loss_backward that also writes p_old_out[i] = pi(a_i | s_i) as its own heads computed it (include/paac_hip.h:
         paac_loss_backward_record): epoch 1 of a --ppo_epochs cycle for a caller that computes y / adv itself."""
-        B = self._check_states(states)
-        _lib.check(self.lib.paac_loss_backward_record(
-            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
-            _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"),
-            _ptr(y, torch.float32, B, "y"), _ptr(adv, torch.float32, B, "adv"), _ptr(p_old_out, torch.float32, B, "p_old_out"),
-            B, float(entropy_beta), _ptr(grad, torch.float32, self.layout["total"], "grad"),
-            _ptr(loss_out, torch.float32, 4, "loss_out", True), 1 if forward_done else 0, int(phase), _stream()),
-            "paac_loss_backward_record")
+        if p_old_out is None:
+            raise ValueError("loss_backward_record needs p_old_out")
+        self.loss_backward(params, states, actions, y, adv, entropy_beta, grad, loss_out, forward_done, phase, p_old_out)
 
     def loss_backward_ppo(self, params, states, actions, y, adv, p_old, clip_eps, entropy_beta, grad, loss_out=None,
                           ppo_stats_out=None, forward_done=False, phase=0):
         """Epochs 2..K of a --ppo_epochs cycle: the clipped surrogate on the frozen y / adv / p_old (include/paac_hip.h:
         paac_loss_backward_ppo).  ppo_stats_out: float32[2] = {clip_fraction, approx_kl}."""
-        B = self._check_states(states)
-        _lib.check(self.lib.paac_loss_backward_ppo(
-            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
-            _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"),
-            _ptr(y, torch.float32, B, "y"), _ptr(adv, torch.float32, B, "adv"), _ptr(p_old, torch.float32, B, "p_old"),
-            float(clip_eps), B, float(entropy_beta), _ptr(grad, torch.float32, self.layout["total"], "grad"),
-            _ptr(loss_out, torch.float32, 4, "loss_out", True), _ptr(ppo_stats_out, torch.float32, 2, "ppo_stats_out", True),
-            1 if forward_done else 0, int(phase), _stream()), "paac_loss_backward_ppo")
+        self._loss_backward("paac_loss_backward_ppo", params, states, actions,
+                            (("y", y), ("adv", adv), ("p_old", p_old), float(clip_eps)),
+                            entropy_beta, grad, loss_out, forward_done, phase, stats=(ppo_stats_out, 2))
 
     def loss_backward_ppo_vclip(self, params, states, actions, y, adv, p_old, v_old, clip_eps, vclip_eps, entropy_beta, grad,
                                 loss_out=None, ppo_stats_out=None, forward_done=False, phase=0):
         """loss_backward_ppo with the value-clipped critic term of --ppo_vclip on the frozen v_old (include/paac_hip.h:
         paac_loss_backward_ppo_vclip).  ppo_stats_out: float32[3] = {clip_fraction, approx_kl, value_clip_fraction}."""
-        B = self._check_states(states)
-        _lib.check(self.lib.paac_loss_backward_ppo_vclip(
-            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
-            _ptr(states, torch.uint8, B * 28224, "states"), _ptr(actions, torch.int32, B, "actions"),
-            _ptr(y, torch.float32, B, "y"), _ptr(adv, torch.float32, B, "adv"), _ptr(p_old, torch.float32, B, "p_old", True),
-            _ptr(v_old, torch.float32, B, "v_old", True), float(clip_eps), float(vclip_eps), B, float(entropy_beta),
-            _ptr(grad, torch.float32, self.layout["total"], "grad"), _ptr(loss_out, torch.float32, 4, "loss_out", True),
-            _ptr(ppo_stats_out, torch.float32, 3, "ppo_stats_out", True), 1 if forward_done else 0, int(phase), _stream()),
-            "paac_loss_backward_ppo_vclip")
+        self._loss_backward("paac_loss_backward_ppo_vclip", params, states, actions,
+                            (("y", y), ("adv", adv), ("p_old", p_old, True), ("v_old", v_old, True), float(clip_eps),
+                             float(vclip_eps)),
+                            entropy_beta, grad, loss_out, forward_done, phase, stats=(ppo_stats_out, 3))
 
     def train_values_into(self, out, batch):
         """out[:batch] = the values the training-side heads computed last (paac_debug_activation(25) into the caller's
@@ -300,29 +282,30 @@ class Context(object):
             _ptr(adv_n_out, torch.float32, T * N, "adv_n_out"), _ptr(stats_out, torch.float64, 2, "stats_out", True), _stream()),
             "paac_returns_norm_tick")
 
+    def _clip_step(self, entry, params, grad, slots, powers, lr_dev, hyper, clip_norm, clip_mode, grad_scale, gnorm_out,
+                   gate=None):
+        """One optimizer entry: (params, grad, the rule's slot pair[, Adam's powers], n, lr, the rule's three hyper-parameters,
+        clip_norm, clip_mode, grad_scale, gnorm_out[, gate]).  gate: the _kl_gate of a gated entry."""
+        n = self.layout["total"]
+        tail = () if gate is None else (ctypes.byref(gate),)
+        _lib.check(getattr(self.lib, entry)(
+            self.handle, _ptr(params, torch.float32, n, "params"), _ptr(grad, torch.float32, n, "grad"),
+            *[_ptr(t, torch.float32, n, name) for name, t in slots], *powers, n, _ptr(lr_dev, torch.float32, 1, "lr_dev"),
+            *[float(h) for h in hyper], float(clip_norm), int(clip_mode), float(grad_scale),
+            _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), *tail, _stream()), entry)
+
     def clip_rmsprop(self, params, grad, ms, mom, lr_dev, decay, momentum, eps, clip_norm, clip_mode, grad_scale=1.0,
                      gnorm_out=None):
-        n = self.layout["total"]
-        _lib.check(self.lib.paac_clip_rmsprop(self.handle, _ptr(params, torch.float32, n, "params"),
-                                              _ptr(grad, torch.float32, n, "grad"), _ptr(ms, torch.float32, n, "ms"),
-                                              _ptr(mom, torch.float32, n, "mom"), n,
-                                              _ptr(lr_dev, torch.float32, 1, "lr_dev"), float(decay), float(momentum),
-                                              float(eps), float(clip_norm), int(clip_mode), float(grad_scale),
-                                              _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), _stream()),
-                   "paac_clip_rmsprop")
+        self._clip_step("paac_clip_rmsprop", params, grad, (("ms", ms), ("mom", mom)), (), lr_dev, (decay, momentum, eps),
+                        clip_norm, clip_mode, grad_scale, gnorm_out)
 
     def clip_adam(self, params, grad, m, v, beta_powers, lr_dev, beta1, beta2, eps, clip_norm, clip_mode, grad_scale=1.0,
                   gnorm_out=None):
         """The same clipped gradient through TF Adam instead of RMSProp (include/paac_hip.h: paac_clip_adam); beta_powers is
         the device float32[2] {beta1_power, beta2_power} the step reads and advances."""
-        n = self.layout["total"]
-        _lib.check(self.lib.paac_clip_adam(self.handle, _ptr(params, torch.float32, n, "params"),
-                                           _ptr(grad, torch.float32, n, "grad"), _ptr(m, torch.float32, n, "m"),
-                                           _ptr(v, torch.float32, n, "v"), _ptr(beta_powers, torch.float32, 2, "beta_powers"),
-                                           n, _ptr(lr_dev, torch.float32, 1, "lr_dev"), float(beta1), float(beta2),
-                                           float(eps), float(clip_norm), int(clip_mode), float(grad_scale),
-                                           _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), _stream()),
-                   "paac_clip_adam")
+        self._clip_step("paac_clip_adam", params, grad, (("m", m), ("v", v)),
+                        (_ptr(beta_powers, torch.float32, 2, "beta_powers"),), lr_dev, (beta1, beta2, eps), clip_norm,
+                        clip_mode, grad_scale, gnorm_out)
 
     @staticmethod
     def _kl_gate(kl, scale, thr, first, stop, applied, checked):
@@ -337,31 +320,17 @@ class Context(object):
                            gnorm_out=None, *, kl, thr, first, stop, applied=None, checked=None, kl_scale=1.0):
         """clip_rmsprop behind a --ppo_target_kl gate (include/paac_hip.h: paac_clip_rmsprop_gated): the step is skipped, and
         *stop set, unless kl[0] * kl_scale <= thr and *stop was clear (first clears it before the comparison)."""
-        n = self.layout["total"]
-        gate = self._kl_gate(kl, kl_scale, thr, first, stop, applied, checked)
-        _lib.check(self.lib.paac_clip_rmsprop_gated(self.handle, _ptr(params, torch.float32, n, "params"),
-                                                    _ptr(grad, torch.float32, n, "grad"), _ptr(ms, torch.float32, n, "ms"),
-                                                    _ptr(mom, torch.float32, n, "mom"), n,
-                                                    _ptr(lr_dev, torch.float32, 1, "lr_dev"), float(decay), float(momentum),
-                                                    float(eps), float(clip_norm), int(clip_mode), float(grad_scale),
-                                                    _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), ctypes.byref(gate),
-                                                    _stream()),
-                   "paac_clip_rmsprop_gated")
+        self._clip_step("paac_clip_rmsprop_gated", params, grad, (("ms", ms), ("mom", mom)), (), lr_dev,
+                        (decay, momentum, eps), clip_norm, clip_mode, grad_scale, gnorm_out,
+                        self._kl_gate(kl, kl_scale, thr, first, stop, applied, checked))
 
     def clip_adam_gated(self, params, grad, m, v, beta_powers, lr_dev, beta1, beta2, eps, clip_norm, clip_mode, grad_scale=1.0,
                         gnorm_out=None, *, kl, thr, first, stop, applied=None, checked=None, kl_scale=1.0):
         """clip_adam behind a --ppo_target_kl gate (include/paac_hip.h: paac_clip_adam_gated); a skipped step leaves the powers."""
-        n = self.layout["total"]
-        gate = self._kl_gate(kl, kl_scale, thr, first, stop, applied, checked)
-        _lib.check(self.lib.paac_clip_adam_gated(self.handle, _ptr(params, torch.float32, n, "params"),
-                                                 _ptr(grad, torch.float32, n, "grad"), _ptr(m, torch.float32, n, "m"),
-                                                 _ptr(v, torch.float32, n, "v"),
-                                                 _ptr(beta_powers, torch.float32, 2, "beta_powers"), n,
-                                                 _ptr(lr_dev, torch.float32, 1, "lr_dev"), float(beta1), float(beta2),
-                                                 float(eps), float(clip_norm), int(clip_mode), float(grad_scale),
-                                                 _ptr(gnorm_out, torch.float32, 1, "gnorm_out", True), ctypes.byref(gate),
-                                                 _stream()),
-                   "paac_clip_adam_gated")
+        self._clip_step("paac_clip_adam_gated", params, grad, (("m", m), ("v", v)),
+                        (_ptr(beta_powers, torch.float32, 2, "beta_powers"),), lr_dev, (beta1, beta2, eps), clip_norm,
+                        clip_mode, grad_scale, gnorm_out,
+                        self._kl_gate(kl, kl_scale, thr, first, stop, applied, checked))
 
     def keep_next_forward(self, train_row):
         """The next acting forward also leaves its rows' activations at rows [train_row, train_row + batch) of the training

@@ -242,12 +242,8 @@ class DeviceRollout(object):
             # then the backward on (y, adv_n); the rollout rows' heads still ride in the backward's first launch
             L.ctx.returns_norm_tick(params, None, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
                                     L.adv_stats, gae_lambda=L.gae_lambda, **self.cycle_tick)
-            if self.K > 1:
-                L.ctx.loss_backward_record(params, self.rollout_states(parity), self.actions.view(-1), self.y, L.adv_n, L.p_old,
-                                           L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=phase)
-            else:
-                L.ctx.loss_backward(params, self.rollout_states(parity), self.actions.view(-1), self.y, L.adv_n,
-                                    L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=phase)
+            L.ctx.loss_backward(params, self.rollout_states(parity), self.actions.view(-1), self.y, L.adv_n, L.entropy_beta,
+                                L.grad, L.loss_dev, forward_done=True, phase=phase, p_old_out=L.p_old if self.K > 1 else None)
             if L.vclip_on:
                 L.ctx.train_values_into(L.v_old, T * N)
             return
@@ -955,12 +951,9 @@ class PAACLearner(ActorLearner):
                     self._allreduce_grad()
                     self.apply_gradients(k)
             else:
-                if self.ppo_epochs > 1:
-                    self.ctx.loss_backward_record(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
-                                                  self.p_old, self.entropy_beta, self.grad, self.loss_dev)
-                else:
-                    self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
-                                           self.entropy_beta, self.grad, self.loss_dev)
+                self.ctx.loss_backward(params, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv,
+                                       self.entropy_beta, self.grad, self.loss_dev,
+                                       p_old_out=self.p_old if self.ppo_epochs > 1 else None)
                 if self.vclip_on:         # v_old = the values epoch 1's heads just computed
                     self.ctx.train_values_into(self.v_old, T * N)
                 self._allreduce_grad()

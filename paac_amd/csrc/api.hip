@@ -5,6 +5,7 @@
 #include <new>
 
 #include "common.h"
+#include "synth_dev.h"
 
 namespace paac {
 
@@ -372,14 +373,16 @@ int paac_forward_sample_synth_step(paac_ctx* ctx, const float* params, const uin
                                    uint32_t env_offset, int32_t* actions, uint64_t env_seed, uint32_t terminal_threshold,
                                    uint8_t* stack_out, float* rewards_out, float* masks_out, float* ep_reward,
                                    int32_t* ep_len, void* finished, paac_stream_t stream) {
-  PAAC_REQUIRE(ctx && params && states && actions && stack_out && rewards_out && masks_out && ep_reward && ep_len,
-               "paac_forward_sample_synth_step: null argument");
+  PAAC_REQUIRE(ctx && params && states && actions, "paac_forward_sample_synth_step: null argument");
+  SynthStep st;          // (the heads launch takes env_offset and the step id from the sampler's arguments, which are the step's)
+  if (synth_step_of("paac_forward_sample_synth_step", "null argument", false, &st, env_seed, env_offset, batch, terminal_threshold,
+                    step_base_dev, step_offset, states, stack_out, nullptr, rewards_out, masks_out, ep_reward, ep_len, finished,
+                    nullptr))
+    return -1;
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_forward_sample_synth_step: batch %d outside (0, max_batch=%d]",
                batch, ctx->max_batch);
-  PAAC_REQUIRE(states != stack_out, "paac_forward_sample_synth_step: the step cannot shift the stacks in place");
-  const int rc = launch_forward_sample_step(ctx, params, states, batch, probs, values, seed, step_base_dev, step_offset,
-                                            env_offset, actions, env_seed, terminal_threshold, stack_out, rewards_out,
-                                            masks_out, ep_reward, ep_len, finished, (hipStream_t)stream);
+  const int rc = launch_forward_sample(ctx, params, states, batch, probs, values, seed, step_base_dev, step_offset, env_offset,
+                                       actions, &st, (hipStream_t)stream);
   if (rc) return rc;
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
@@ -392,6 +395,8 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
                      void* finished, uint8_t* raw_scratch, void* walk_scratch, int64_t walk_scratch_bytes,
                      paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && states && mt_state && actions && probs_out && values_out, "paac_act_step_mt: null argument");
+  // the fc kernel's head partials, where a launch leaves them for the sampler launch to finish (launch_forward_trunk fills it)
+  HeadsPartials hp{nullptr, 0, nullptr, nullptr, values_out};
   if (stack_out == nullptr) {
     // policy forward + sampler only (the environments live on the host: paac.py:104-110 without :115-116): three launches up
     // to PAAC_ACT_STEP_MAX_ENVS environments, paac_forward + paac_sample_mt beyond
@@ -410,32 +415,30 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
       PAAC_CHECK_HIP(hipGetLastError());
       return 0;
     }
-    const float *partial, *ba, *bc;
-    int ntiles;
-    int rc = launch_forward_trunk(ctx, params, states, batch, &partial, &ntiles, &ba, &bc, (hipStream_t)stream);
+    SynthStep none{};            // no environment step: heads finish + sampler over `batch` rows
+    none.N = batch;
+    int rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
     if (rc) return rc;
-    rc = launch_sample_env_step_heads(partial, ntiles, ba, bc, probs_out, values_out, ctx->cfg.num_actions, mt_state, actions, 0, 0,
-                                      batch, 0, nullptr, 0, states, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                      nullptr, nullptr, (hipStream_t)stream);
+    rc = launch_sample_env_step_heads(hp, probs_out, ctx->cfg.num_actions, mt_state, actions, none, nullptr, (hipStream_t)stream);
     if (rc) return rc;
     PAAC_CHECK_HIP(hipGetLastError());
     return 0;
   }
-  PAAC_REQUIRE(rewards_out && masks_out && ep_reward && ep_len, "paac_act_step_mt: null argument");
+  SynthStep st;
+  if (synth_step_of("paac_act_step_mt", "null argument", false, &st, env_seed, env_offset, batch, terminal_threshold, step_base_dev,
+                    step_offset, states, stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, raw_scratch))
+    return -1;
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch && batch <= PAAC_ACT_STEP_MAX_ENVS_LARGE,
                "paac_act_step_mt: batch %d outside (0, min(max_batch=%d, %d)]", batch, ctx->max_batch,
                PAAC_ACT_STEP_MAX_ENVS_LARGE);
   PAAC_REQUIRE((int64_t)batch * (ctx->cfg.num_actions - 1) <= PAAC_FUSED_SAMPLE_MAX_DRAWS,
                "paac_act_step_mt: N*(A-1) = %ld exceeds %d (use paac_forward + paac_sample_mt + paac_synth_step)",
                (long)batch * (ctx->cfg.num_actions - 1), PAAC_FUSED_SAMPLE_MAX_DRAWS);
-  PAAC_REQUIRE(states != stack_out && states != stack_out2, "paac_act_step_mt: the step cannot shift the stacks in place");
   if (!forward_has_fc_heads(ctx)) {
     // no head partials on this geometry (fc_heads_waves == 0): paac_forward + paac_sample_mt_synth_step's launch
     int rc = launch_forward(ctx, 0, params, states, batch, nullptr, probs_out, values_out, (hipStream_t)stream);
     if (rc) return rc;
-    rc = launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, env_seed, env_offset, batch,
-                                     terminal_threshold, step_base_dev, step_offset, states, stack_out, stack_out2, rewards_out,
-                                     masks_out, ep_reward, ep_len, finished, walk_scratch, walk_scratch_bytes, raw_scratch,
+    rc = launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, st, walk_scratch, walk_scratch_bytes,
                                      nullptr, (hipStream_t)stream);
     if (rc) return rc;
     PAAC_CHECK_HIP(hipGetLastError());
@@ -460,24 +463,19 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
       return (v && *v) ? (atoi(v) != 0 ? 1 : 0) : -1;
     }();
     const bool fold = fold_knob >= 0 ? fold_knob == 1 : ctx->cfg.num_actions <= 8;
-    HeadsPartials hp{nullptr, 0, nullptr, nullptr, values_out};
     int rc;
     if (tail && fold && sampler_folds_heads(batch, ctx->cfg.num_actions, walk_scratch))
-      rc = launch_forward_trunk(ctx, params, states, batch, &hp.partial, &hp.ntiles, &hp.ba, &hp.bc, (hipStream_t)stream);
+      rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
     else
       rc = launch_forward(ctx, 0, params, states, batch, nullptr, probs_out, values_out, (hipStream_t)stream);
     ctx->ahead_state = nullptr;
     if (rc) return rc;
-    rc = launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, env_seed, env_offset, batch,
-                                     terminal_threshold, step_base_dev, step_offset, states, stack_out, stack_out2, rewards_out,
-                                     masks_out, ep_reward, ep_len, finished, walk_scratch, walk_scratch_bytes, raw_scratch,
+    rc = launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, st, walk_scratch, walk_scratch_bytes,
                                      tail ? ctx->mt_ahead : nullptr, (hipStream_t)stream, hp.partial ? &hp : nullptr);
     if (rc) return rc;
     PAAC_CHECK_HIP(hipGetLastError());
     return 0;
   }
-  const float *partial, *ba, *bc;
-  int ntiles;
   // Up to 64 environments the sampler's state blocks and doubles already hide behind the loads of the head partials
   // (misc.hip: synth_step_a_mth_kernel): making them one launch ahead (csrc/mt_ahead.h) measured SLOWER here -- 658 k against
   // 669 k env-steps/s at the headline shape, the extra loads sit at the head of the sampler workgroup's chain --, so it is off
@@ -490,13 +488,11 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
     ctx->ahead_state = mt_state;
     ctx->ahead_D = batch * (ctx->cfg.num_actions - 1);
   }
-  int rc = launch_forward_trunk(ctx, params, states, batch, &partial, &ntiles, &ba, &bc, (hipStream_t)stream);
+  int rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
   ctx->ahead_state = nullptr;
   if (rc) return rc;
-  rc = launch_sample_env_step_heads(partial, ntiles, ba, bc, probs_out, values_out, ctx->cfg.num_actions, mt_state, actions,
-                                    env_seed, env_offset, batch, terminal_threshold, step_base_dev, step_offset, states,
-                                    stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, raw_scratch,
-                                    ahead_on ? ctx->mt_ahead : nullptr, (hipStream_t)stream);
+  rc = launch_sample_env_step_heads(hp, probs_out, ctx->cfg.num_actions, mt_state, actions, st, ahead_on ? ctx->mt_ahead : nullptr,
+                                    (hipStream_t)stream);
   if (rc) return rc;
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;

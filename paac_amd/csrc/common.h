@@ -231,15 +231,10 @@ int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv
 int launch_record_policy(paac_ctx* ctx, const int32_t* actions, int batch, int vrows, float* p_old, float* v_out, hipStream_t s);
 int launch_forward(paac_ctx* ctx, int ws, const float* params, const uint8_t* states, int batch, float* logits,
                    float* probs, float* values, hipStream_t s);
-struct SynthStepArgs;
+struct SynthStep;      // one environment step's arguments (synth_dev.h); step == nullptr / an inactive one: no environment step
 int launch_forward_sample(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
                           float* values, uint64_t seed, const uint64_t* step_base, uint64_t step_off,
-                          uint32_t env_offset, int32_t* actions, const SynthStepArgs* step, hipStream_t s);
-int launch_forward_sample_step(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
-                               float* values, uint64_t seed, const uint64_t* step_base, uint64_t step_off,
-                               uint32_t env_offset, int32_t* actions, uint64_t env_seed, uint32_t thresh,
-                               uint8_t* stack_out, float* rewards, float* masks, float* ep_reward, int32_t* ep_len,
-                               void* finished, hipStream_t s);
+                          uint32_t env_offset, int32_t* actions, const SynthStep* step, hipStream_t s);
 int launch_pack_weights(paac_ctx* ctx, const float* params, hipStream_t s);
 int launch_pack_dgrad(paac_ctx* ctx, const float* params, hipStream_t s);
 // the fc kernel's per-tile head partials of an acting forward whose heads a later launch finishes (csrc/fc_heads.h)
@@ -252,11 +247,12 @@ struct HeadsPartials {
 size_t mt_ahead_bytes();
 bool sampler_folds_heads(int N, int A, const void* walk_scratch);
 bool tower2_available();
-int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, int32_t* actions, uint64_t seed, uint32_t env_offset,
-                                int N, uint32_t terminal_threshold, const uint64_t* step_base_dev, uint64_t step_offset,
-                                const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2, float* rewards_out,
-                                float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, void* walk_scratch,
-                                int64_t walk_scratch_bytes, uint8_t* raw_scratch, const void* mt_ahead, hipStream_t stream,
+int synth_step_of(const char* fn, const char* what, bool in_place_ok, SynthStep* st, uint64_t seed, uint32_t env_offset, int N,
+                  uint32_t thresh, const uint64_t* step_base, uint64_t step_off, const uint8_t* stack_in, uint8_t* stack_out,
+                  uint8_t* stack_out2, float* rewards, float* masks, float* ep_reward, int32_t* ep_len, void* finished,
+                  uint8_t* raw_scratch);
+int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, int32_t* actions, const SynthStep& st,
+                                void* walk_scratch, int64_t walk_scratch_bytes, const void* mt_ahead, hipStream_t stream,
                                 const HeadsPartials* heads = nullptr);
 // sampler only, from finished probabilities (no environment step): N <= 64 environments, N * (A - 1) <= 1024 draws
 int launch_sample_mt_probs(const float* probs, int A, uint32_t* mt_state, int32_t* actions, int N, hipStream_t stream);
@@ -306,14 +302,9 @@ __device__ __forceinline__ void cycle_tick(const CycleTick& ct) {
 
 bool norm_head_fits(const paac_ctx* ctx);
 int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row, hipStream_t s);
-int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, const float** partial,
-                         int* ntiles, const float** ba, const float** bc, hipStream_t s);
-int launch_sample_env_step_heads(const float* partial, int ntiles, const float* ba, const float* bc, float* probs_out,
-                                 float* values_out, int A, uint32_t* mt_state, int32_t* actions, uint64_t seed,
-                                 uint32_t env_offset, int N, uint32_t thresh, const uint64_t* step_base, uint64_t step_off,
-                                 const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2, float* rewards,
-                                 float* masks, float* ep_reward, int32_t* ep_len, void* finished, uint8_t* raw_scratch,
-                                 const void* mt_ahead, hipStream_t s);
+int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, HeadsPartials* hp, hipStream_t s);
+int launch_sample_env_step_heads(const HeadsPartials& hp, float* probs_out, int A, uint32_t* mt_state, int32_t* actions,
+                                 const SynthStep& st, const void* mt_ahead, hipStream_t s);
 // What the heads of one backward compute (heads.h has the arithmetic of each loss): the arrays a loss reads or writes, the
 // others null / zero.  ret: the returns are computed inside the heads launch and land in ret->y_out / adv_out (y / adv unused).
 constexpr int kLossA3c = 0, kLossA3cRecord = 1, kLossPpo = 2, kLossPpoVclip = 3;

@@ -1256,21 +1256,16 @@ __global__ __launch_bounds__(256) void preprocess_stack_kernel(const uint8_t* __
 // =============================================================================================
 // Synthetic environments (spec: paac_amd/synthetic.py); device helpers in synth_dev.h.
 // Path A: one new 84x84 plane per step.  grid (N, 7), 256 threads; one dword (pixel x 4 channels) per thread-iteration.
-__global__ __launch_bounds__(256) void synth_step_a_kernel(uint64_t seed, uint32_t env_offset, int N,
-                                                           const int32_t* __restrict__ actions, uint32_t thresh,
-                                                           const uint64_t* __restrict__ step_base, uint64_t step_off,
-                                                           int force_reset, const uint32_t* stack_in,
-                                                           uint32_t* stack_out,
-                                                           uint32_t* __restrict__ stack_out2, float* rewards_out,
-                                                           float* masks_out, float* ep_reward, int32_t* ep_len,
-                                                           FinishedRing* fin) {
+// force_reset: step 0 of every environment from an empty history (paac_synth_reset; st.stack_in == st.stack_out, no records).
+__global__ __launch_bounds__(256) void synth_step_a_kernel(const SynthStep st, const int32_t* __restrict__ actions,
+                                                           int force_reset) {
   const int e = blockIdx.x;
   const int band = blockIdx.y;
-  const uint64_t id = force_reset ? 0ull : (step_base ? *step_base : 0ull) + step_off + 1ull;
+  const uint64_t id = force_reset ? 0ull : st.id();
   if (!force_reset && band == 0 && threadIdx.x == 0)
-    synth_bookkeep(synth_key(seed, env_offset + (uint32_t)e, id), e, actions, thresh, rewards_out, masks_out, ep_reward, ep_len,
-                   fin);
-  synth_shift_band(seed, env_offset, id, thresh, e * PRE_BANDS + band, stack_in, stack_out, stack_out2, force_reset != 0);
+    synth_bookkeep(synth_key(st.seed, st.env_offset + (uint32_t)e, id), e, actions, st.thresh, st.rec);
+  synth_shift_band(st.seed, st.env_offset, id, st.thresh, e * PRE_BANDS + band, st.stack_in, st.stack_out, st.stack_out2,
+                   force_reset != 0);
 }
 
 // The device games (catch, bricks, rally: one trait G each, csrc/game_dev.h and the game's header).  The shape of
@@ -1287,9 +1282,7 @@ __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t 
                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
                                                         int32_t* __restrict__ state_out2,
                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
-                                                        uint32_t* __restrict__ stack_out2, float* rewards_out,
-                                                        float* masks_out, float* ep_reward, int32_t* ep_len,
-                                                        FinishedRing* fin, int opt) {
+                                                        uint32_t* __restrict__ stack_out2, const EnvRecords rec, int opt) {
   const QuadThread t = quad_thread();
   const int e = t.e;
   uint4 old = make_uint4(0u, 0u, 0u, 0u);
@@ -1307,7 +1300,7 @@ __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t 
   if (t.band == 0 && t.i == 0) {
     G::store(state_out, e, s);
     if (state_out2) G::store(state_out2, e, s);
-    if (state_in) env_bookkeep(r, term, e, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
+    if (state_in) env_bookkeep(r, term, e, rec.ep_reward[e], rec.ep_len[e], rec);
   }
   if (!t.owner) return;
   const uint4 outv = G::shift_quad(s, t.q, old, term);     // a terminal step drops the history it loaded
@@ -1397,6 +1390,12 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
   reinterpret_cast<uint4*>(stack_out)[th.quad] = G::shift_quad(s, th.q, old, term);
 }
 
+// One (environment, band) unit of the step's frame work: path B's raw screen pair (the preprocess launch follows) or the shift.
+__device__ __forceinline__ void step_unit(const SynthStep& st, uint64_t id, int unit) {
+  if (st.raw) synth_raw_unit(st.seed, st.env_offset, id, unit, st.raw);
+  else synth_shift_band(st.seed, st.env_offset, id, st.thresh, unit, st.stack_in, st.stack_out, st.stack_out2);
+}
+
 // Path A with the numpy-parity sampler folded in: workgroup 0 runs the (inherently serial) MT19937 sampler and then
 // the per-env bookkeeping, the other N*7 workgroups shift the observation stacks meanwhile -- the new frame and the
 // terminal flag of the synthetic environments do not depend on the action, only reward bookkeeping does.  One launch
@@ -1406,25 +1405,19 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
 template <int LDSC, bool FOLD = false>
 __global__ __launch_bounds__(256) void synth_step_a_mt_kernel(const float* __restrict__ probs, int A,
                                                               uint32_t* __restrict__ mt_state,
-                                                              int32_t* __restrict__ actions, uint64_t seed,
-                                                              uint32_t env_offset, int N, uint32_t thresh,
-                                                              const uint64_t* __restrict__ step_base, uint64_t step_off,
-                                                              const uint32_t* __restrict__ stack_in,
-                                                              uint32_t* __restrict__ stack_out,
-                                                              uint32_t* __restrict__ stack_out2, float* rewards_out,
-                                                              float* masks_out, float* ep_reward, int32_t* ep_len,
-                                                              FinishedRing* fin, const MultiWalk mw,
-                                                              uint32_t* __restrict__ raw, const MtAhead* __restrict__ ahead,
+                                                              int32_t* __restrict__ actions, const SynthStep st,
+                                                              const MultiWalk mw, const MtAhead* __restrict__ ahead,
                                                               const RowsHeadsHook hs) {
-  const uint64_t id = (step_base ? *step_base : 0ull) + step_off + 1ull;
+  const int N = st.N;
+  const uint64_t id = st.id();
   const int samplers = mw.W > 0 ? mw.W : 1;          // sampler workgroups in front of the shift workgroups
   if ((int)blockIdx.x < samplers) {
     __shared__ int16_t act_s[mt_lds_d(LDSC)];
     // the running episode totals do not depend on the sampler: request them before it (first 256 environments)
     const int e0 = threadIdx.x < N ? threadIdx.x : 0;
-    const bool env_step = rewards_out != nullptr;    // false: sampler only (launch_sample_mt_probs; one workgroup)
-    const float ep_reward0 = env_step ? ep_reward[e0] : 0.f;
-    const int32_t ep_len0 = env_step ? ep_len[e0] : 0;
+    // (no step: sampler only -- launch_sample_mt_probs; one workgroup)
+    const float ep_reward0 = st.active() ? st.rec.ep_reward[e0] : 0.f;
+    const int32_t ep_len0 = st.active() ? st.rec.ep_len[e0] : 0;
     // (ends past a barrier; with several sampler workgroups only the one that finishes the walks goes on)
     // hs.partial: the heads were NOT finished by a launch of their own -- every sampler workgroup finishes those of the
     // environments its walks visit (paac_act_step_mt, large shards); otherwise `probs` holds all of them
@@ -1436,14 +1429,14 @@ __global__ __launch_bounds__(256) void synth_step_a_mt_kernel(const float* __res
     else
       go_on = sample_mt_body<LDSC>(probs, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, nullptr, nullptr,
                                    NoProbsHook(), mw, ahead);
-    if (!go_on || !env_step) return;
+    if (!go_on || !st.active()) return;
     MISC_STAMP(7);
     for (int e = threadIdx.x; e < N; e += 256) {
-      const uint32_t key = synth_key(seed, env_offset + (uint32_t)e, id);
+      const uint32_t key = synth_key(st.seed, st.env_offset + (uint32_t)e, id);
       if (e < 256)
-        synth_bookkeep_with(key, e, act_s[e], thresh, ep_reward0, ep_len0, rewards_out, masks_out, ep_reward, ep_len, fin);
+        synth_bookkeep_with(key, e, act_s[e], st.thresh, ep_reward0, ep_len0, st.rec);
       else
-        synth_bookkeep_with(key, e, act_s[e], thresh, ep_reward[e], ep_len[e], rewards_out, masks_out, ep_reward, ep_len, fin);
+        synth_bookkeep_with(key, e, act_s[e], st.thresh, st.rec.ep_reward[e], st.rec.ep_len[e], st.rec);
     }
     MISC_STAMP(8);
     return;
@@ -1453,18 +1446,19 @@ __global__ __launch_bounds__(256) void synth_step_a_mt_kernel(const float* __res
     // over as many shift workgroups as fit beside the sampler workgroups in ONE round of the CUs
     const int nshift = (int)gridDim.x - samplers;
     for (int u = (int)blockIdx.x - samplers; u < N * PRE_BANDS; u += nshift) {
-      if (raw) synth_raw_unit(seed, env_offset, id, u, raw);       // path B: the step's raw screen pair instead of the shift
-      else synth_shift_band(seed, env_offset, id, thresh, u, stack_in, stack_out, stack_out2);
+      step_unit(st, id, u);
     }
   } else {
-    if (raw) synth_raw_unit(seed, env_offset, id, (int)blockIdx.x - samplers, raw);
-    else synth_shift_band(seed, env_offset, id, thresh, (int)blockIdx.x - samplers, stack_in, stack_out, stack_out2);
+    step_unit(st, id, (int)blockIdx.x - samplers);
   }
 }
 
 // The same launch with the heads finish in front of the sampler: workgroup 0 sums the fc kernel's per-tile head partials
 // (csrc/fc_heads.h), adds the biases, takes the softmax -- probabilities straight into LDS for the sampler (and to HBM for
 // the learner's records) -- then samples and does the bookkeeping.  One launch per step for heads + sampler + env step.
+// (The step's arguments one by one, not a SynthStep by value like the other step kernels: with the block by value the compiler
+// fetches all of it in the entry block, the values the bookkeeping needs after the sampler then sit in SGPRs through the sampler
+// instead of being loaded behind it, and the launch measured 7.16 us against 6.84 us at 32 x 4.  DESIGN.md.)
 __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __restrict__ partial, int ntiles,
                                                                const float* __restrict__ ba, const float* __restrict__ bc,
                                                                float* __restrict__ probs_out, float* __restrict__ values_out,
@@ -1488,7 +1482,7 @@ __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __re
 #pragma unroll
     for (int k = 0; k < 3; ++k) stw[k] = mt_state[min((int)threadIdx.x + k * 256, 624)];
     const int e0 = threadIdx.x < N ? threadIdx.x : 0;
-    const bool env_step = rewards_out != nullptr;          // false: policy + sampler only (host environments do the stepping)
+    const bool env_step = rewards_out != nullptr;          // SynthStep::active(); false: policy + sampler only (host environments)
     const float ep_reward0 = env_step ? ep_reward[e0] : 0.f;
     const int32_t ep_len0 = env_step ? ep_len[e0] : 0;
     // ... and the action-independent half of environment e0's bookkeeping
@@ -1516,7 +1510,7 @@ __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __re
     }
     // (the sampler body ends past a barrier; its last wave is still writing the stream position back)
     if (env_step && (int)threadIdx.x < N)       // N <= 64 here: one environment per thread
-      synth_bookkeep_hashed(hr5, term0, e0, act_s[e0], ep_reward0, ep_len0, rewards_out, masks_out, ep_reward, ep_len, fin);
+      synth_bookkeep_hashed(hr5, term0, e0, act_s[e0], ep_reward0, ep_len0, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, fin});
     return;
   }
   if (raw) synth_raw_unit(seed, env_offset, id, (int)blockIdx.x - 1, raw);     // path B: the preprocess launch follows
@@ -1525,17 +1519,13 @@ __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __re
 
 // Path B, stage 1: generate the two raw 210x160 gray frames of this step + bookkeeping.
 // grid (N, 8), 256 threads; 16800 dwords per env.
-__global__ __launch_bounds__(256) void synth_raw_kernel(uint64_t seed, uint32_t env_offset, int N,
-                                                        const int32_t* __restrict__ actions, uint32_t thresh,
-                                                        const uint64_t* __restrict__ step_base, uint64_t step_off,
-                                                        int force_reset, uint32_t* __restrict__ raw, float* rewards_out,
-                                                        float* masks_out, float* ep_reward, int32_t* ep_len,
-                                                        FinishedRing* fin) {
+__global__ __launch_bounds__(256) void synth_raw_kernel(const SynthStep st, const int32_t* __restrict__ actions,
+                                                        int force_reset) {
   const int e = blockIdx.x;
-  const uint64_t id = force_reset ? 0ull : (step_base ? *step_base : 0ull) + step_off + 1ull;
-  const uint32_t key = synth_key(seed, env_offset + (uint32_t)e, id);
-  if (!force_reset && blockIdx.y == 0 && threadIdx.x == 0)
-    synth_bookkeep(key, e, actions, thresh, rewards_out, masks_out, ep_reward, ep_len, fin);
+  const uint64_t id = force_reset ? 0ull : st.id();
+  const uint32_t key = synth_key(st.seed, st.env_offset + (uint32_t)e, id);
+  if (!force_reset && blockIdx.y == 0 && threadIdx.x == 0) synth_bookkeep(key, e, actions, st.thresh, st.rec);
+  uint32_t* __restrict__ raw = st.raw;
   const uint32_t rkey = key ^ 0x5bd1e995u;
   constexpr int WORDS = 2 * PAAC_RAW_H * PAAC_RAW_W / 4;  // 16800
   uint4* out = reinterpret_cast<uint4*>(raw + (long)e * WORDS);
@@ -2236,29 +2226,39 @@ static void fill_pack_spec(const paac_ctx* ctx, PackSpec* pk, int* fc_tiles, int
 // Path B, second launch of a step: the observation stacks from the raw screen pairs the step launch has just written
 // (max of the two screens, PIL-nearest resize, history push; environments whose mask is 0 -- terminal -- restart from an
 // empty history, like paac_synth_step's path B).
-static void launch_preprocess_after_step(const uint8_t* raw_scratch, int N, const uint8_t* stack_in, uint8_t* stack_out,
-                                         uint8_t* stack_out2, const float* masks, hipStream_t s) {
-  ProfScope ps(g_prof_ctx, F_PREPROCESS_STACK, N, s);
-  launch_k(preprocess_stack_kernel<false>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, raw_scratch, N,
-           (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, (const uint8_t*)nullptr,
-           (const uint8_t*)nullptr, masks);
+static void launch_preprocess_after_step(const SynthStep& st, hipStream_t s) {
+  ProfScope ps(g_prof_ctx, F_PREPROCESS_STACK, st.N, s);
+  launch_k(preprocess_stack_kernel<false>, dim3(st.N, PRE_BANDS), dim3(256), s, PROF_WHOLE, (const uint8_t*)st.raw, st.N,
+           st.stack_in, st.stack_out, st.stack_out2, (const uint8_t*)nullptr, (const uint8_t*)nullptr,
+           (const float*)st.rec.masks);
 }
 
-int launch_sample_env_step_heads(const float* partial, int ntiles, const float* ba, const float* bc, float* probs_out,
-                                 float* values_out, int A, uint32_t* mt_state, int32_t* actions, uint64_t seed,
-                                 uint32_t env_offset, int N, uint32_t thresh, const uint64_t* step_base, uint64_t step_off,
-                                 const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2, float* rewards,
-                                 float* masks, float* ep_reward, int32_t* ep_len, void* finished, uint8_t* raw_scratch,
-                                 const void* mt_ahead, hipStream_t s) {
+// The arguments of one environment step as an entry point receives them -> st, behind the refusals the step entries share:
+// null stacks or records (`what`: the entry's words for that), and, where the entry forbids it, stacks shifted in place.
+int synth_step_of(const char* fn, const char* what, bool in_place_ok, SynthStep* st, uint64_t seed, uint32_t env_offset, int N,
+                  uint32_t thresh, const uint64_t* step_base, uint64_t step_off, const uint8_t* stack_in, uint8_t* stack_out,
+                  uint8_t* stack_out2, float* rewards, float* masks, float* ep_reward, int32_t* ep_len, void* finished,
+                  uint8_t* raw_scratch) {
+  PAAC_REQUIRE(stack_in && stack_out && rewards && masks && ep_reward && ep_len, "%s: %s", fn, what);
+  PAAC_REQUIRE(in_place_ok || (stack_in != stack_out && stack_in != stack_out2), "%s: the step cannot shift the stacks in place",
+               fn);
+  *st = SynthStep{seed, env_offset, N, thresh, step_base, step_off, (const uint32_t*)stack_in, (uint32_t*)stack_out,
+                  (uint32_t*)stack_out2, EnvRecords{rewards, masks, ep_reward, ep_len, (FinishedRing*)finished},
+                  (uint32_t*)raw_scratch};
+  return 0;
+}
+
+// (st.N rows; an inactive st -- no environment step -- runs workgroup 0 alone: heads finish + sampler)
+int launch_sample_env_step_heads(const HeadsPartials& hp, float* probs_out, int A, uint32_t* mt_state, int32_t* actions,
+                                 const SynthStep& st, const void* mt_ahead, hipStream_t s) {
   {
-    ProfScope ps(g_prof_ctx, F_SAMPLE_ENV_STEP, N, s);
-    // (stack_out == nullptr: no environment step -- workgroup 0 alone: heads finish + sampler)
-    launch_k(synth_step_a_mth_kernel, dim3(stack_out ? 1 + N * PRE_BANDS : 1), dim3(256), s, PROF_WHOLE, partial, ntiles, ba, bc, probs_out,
-             values_out, A, mt_state, actions, seed, env_offset, N, thresh, step_base, step_off, (const uint32_t*)stack_in,
-             (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards, masks, ep_reward, ep_len, (FinishedRing*)finished,
-             (uint32_t*)raw_scratch, reinterpret_cast<const MtAhead*>(mt_ahead));
+    ProfScope ps(g_prof_ctx, F_SAMPLE_ENV_STEP, st.N, s);
+    launch_k(synth_step_a_mth_kernel, dim3(st.active() ? 1 + st.N * PRE_BANDS : 1), dim3(256), s, PROF_WHOLE, hp.partial,
+             hp.ntiles, hp.ba, hp.bc, probs_out, hp.values_out, A, mt_state, actions, st.seed, st.env_offset, st.N, st.thresh,
+             st.step_base, st.step_off, st.stack_in, st.stack_out, st.stack_out2, st.rec.rewards, st.rec.masks, st.rec.ep_reward,
+             st.rec.ep_len, st.rec.fin, st.raw, reinterpret_cast<const MtAhead*>(mt_ahead));
   }
-  if (raw_scratch) launch_preprocess_after_step(raw_scratch, N, stack_in, stack_out, stack_out2, masks, s);
+  if (st.raw) launch_preprocess_after_step(st, s);
   return 0;
 }
 
@@ -2296,8 +2296,7 @@ static int game_reset(const char* name, uint64_t seed, uint32_t env_offset, int 
   PAAC_REQUIRE(N > 0 && state_out && stack_out, "%s: bad arguments", name);
   hipLaunchKernelGGL(game_step_kernel<G>, dim3(N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
                      (const int32_t*)nullptr, (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr,
-                     (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                     (int32_t*)nullptr, (FinishedRing*)nullptr, 0);
+                     (uint32_t*)stack_out, (uint32_t*)nullptr, EnvRecords{}, 0);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2305,17 +2304,15 @@ static int game_reset(const char* name, uint64_t seed, uint32_t env_offset, int 
 template <class G>
 static int game_step(const char* name, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions,
                      const int32_t* state_in, int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in,
-                     uint8_t* stack_out, uint8_t* stack_out2, float* rewards_out, float* masks_out, float* ep_reward,
-                     int32_t* ep_len, void* finished, int opt, paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rewards_out && masks_out && ep_reward &&
-               ep_len, "%s: bad arguments", name);
+                     uint8_t* stack_out, uint8_t* stack_out2, const EnvRecords& rec, int opt, paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rec.rewards && rec.masks && rec.ep_reward &&
+               rec.ep_len, "%s: bad arguments", name);
   PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
                "%s: the step cannot run in place (every band workgroup of an environment reads state_in)", name);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
   launch_k(game_step_kernel<G>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in, state_out,
-           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out,
-           ep_reward, ep_len, (FinishedRing*)finished, opt);
+           state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rec, opt);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2517,15 +2514,13 @@ int paac_synth_reset(uint64_t seed, uint32_t env_offset, int N, uint8_t* stack_o
                      paac_stream_t stream) {
   PAAC_REQUIRE(N > 0 && stack_out, "paac_synth_reset: bad arguments");
   hipStream_t s = (hipStream_t)stream;
+  SynthStep st{};              // what a forced reset reads: the key, and the stacks shifted in place from an empty history
+  st.seed = seed, st.env_offset = env_offset, st.N = N;
+  st.stack_in = st.stack_out = (uint32_t*)stack_out, st.raw = (uint32_t*)raw_scratch;
   if (!raw_scratch) {
-    hipLaunchKernelGGL(synth_step_a_kernel, dim3(N, PRE_BANDS), dim3(256), 0, s, seed, env_offset, N,
-                       (const int32_t*)nullptr, 0u, (const uint64_t*)nullptr, 0ull, 1, (const uint32_t*)stack_out,
-                       (uint32_t*)stack_out, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                       (int32_t*)nullptr, (FinishedRing*)nullptr);
+    hipLaunchKernelGGL(synth_step_a_kernel, dim3(N, PRE_BANDS), dim3(256), 0, s, st, (const int32_t*)nullptr, 1);
   } else {
-    hipLaunchKernelGGL(synth_raw_kernel, dim3(N, 8), dim3(256), 0, s, seed, env_offset, N, (const int32_t*)nullptr, 0u,
-                       (const uint64_t*)nullptr, 0ull, 1, (uint32_t*)raw_scratch, (float*)nullptr, (float*)nullptr,
-                       (float*)nullptr, (int32_t*)nullptr, (FinishedRing*)nullptr);
+    hipLaunchKernelGGL(synth_raw_kernel, dim3(N, 8), dim3(256), 0, s, st, (const int32_t*)nullptr, 1);
     // reset_mask = every env: reuse push semantics with an all-zero "mask" float is not available here,
     // so clear the stack first and push with reset handled by the zero fill.
     PAAC_CHECK_HIP(hipMemsetAsync(stack_out, 0, (size_t)N * PAAC_OBS_BYTES, s));
@@ -2541,26 +2536,18 @@ int paac_synth_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     const uint64_t* step_base_dev, uint64_t step_offset, const uint8_t* stack_in, uint8_t* stack_out,
                     uint8_t* stack_out2, float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len,
                     void* finished, uint8_t* raw_scratch, paac_stream_t stream) {
-  PAAC_REQUIRE(N > 0 && actions && stack_in && stack_out && rewards_out && masks_out && ep_reward && ep_len,
-               "paac_synth_step: bad arguments");
+  PAAC_REQUIRE(N > 0 && actions, "paac_synth_step: bad arguments");
+  SynthStep st;
+  if (synth_step_of("paac_synth_step", "bad arguments", true, &st, seed, env_offset, N, terminal_threshold, step_base_dev,
+                    step_offset, stack_in, stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, raw_scratch))
+    return -1;
   hipStream_t s = (hipStream_t)stream;
-  if (!raw_scratch) {
+  {
     ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
-    launch_k(synth_step_a_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions,
-             terminal_threshold, step_base_dev, step_offset, 0, (const uint32_t*)stack_in, (uint32_t*)stack_out,
-             (uint32_t*)stack_out2, rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished);
-  } else {
-    {
-      ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
-      launch_k(synth_raw_kernel, dim3(N, 8), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, terminal_threshold,
-               step_base_dev, step_offset, 0, (uint32_t*)raw_scratch, rewards_out, masks_out, ep_reward, ep_len,
-               (FinishedRing*)finished);
-    }
-    ProfScope ps(g_prof_ctx, F_PREPROCESS_STACK, N, s);
-    launch_k(preprocess_stack_kernel<false>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, raw_scratch, N,
-             (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, (const uint8_t*)nullptr,
-             (const uint8_t*)nullptr, (const float*)masks_out);
+    if (!raw_scratch) launch_k(synth_step_a_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, st, actions, 0);
+    else launch_k(synth_raw_kernel, dim3(N, 8), dim3(256), s, PROF_WHOLE, st, actions, 0);
   }
+  if (raw_scratch) launch_preprocess_after_step(st, s);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2574,8 +2561,8 @@ int paac_catch_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                     paac_stream_t stream) {
-  return game_step<CatchGame>("paac_catch_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
-                              stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, 0, stream);
+  return game_step<CatchGame>("paac_catch_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
+                   stack_out2, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, 0, stream);
 }
 
 int paac_bricks_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
@@ -2587,8 +2574,8 @@ int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* a
                      int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                      float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, int single_life,
                      paac_stream_t stream) {
-  return game_step<BricksGame>("paac_bricks_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
-                               stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, single_life, stream);
+  return game_step<BricksGame>("paac_bricks_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
+                    stack_out2, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, single_life, stream);
 }
 
 int paac_rally_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
@@ -2600,8 +2587,8 @@ int paac_rally_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                     paac_stream_t stream) {
-  return game_step<RallyGame>("paac_rally_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
-                              stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished, 0, stream);
+  return game_step<RallyGame>("paac_rally_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
+                   stack_out2, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, 0, stream);
 }
 
 int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
@@ -2644,9 +2631,13 @@ int paac_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, int
                               uint64_t step_offset, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                               float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                               void* walk_scratch, int64_t walk_scratch_bytes, uint8_t* raw_scratch, paac_stream_t stream) {
-  return launch_sample_mt_synth_step(probs, A, mt_state, actions, seed, env_offset, N, terminal_threshold, step_base_dev,
-                                     step_offset, stack_in, stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len,
-                                     finished, walk_scratch, walk_scratch_bytes, raw_scratch, nullptr, (hipStream_t)stream, nullptr);
+  SynthStep st;
+  if (synth_step_of("paac_sample_mt_synth_step", "null argument", true, &st, seed, env_offset, N, terminal_threshold,
+                    step_base_dev, step_offset, stack_in, stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len,
+                    finished, raw_scratch))
+    return -1;
+  return launch_sample_mt_synth_step(probs, A, mt_state, actions, st, walk_scratch, walk_scratch_bytes, nullptr,
+                                     (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"
@@ -2666,12 +2657,12 @@ bool sampler_folds_heads(int N, int A, const void* walk_scratch) {
 int launch_sample_mt_probs(const float* probs, int A, uint32_t* mt_state, int32_t* actions, int N, hipStream_t stream) {
   PAAC_REQUIRE(probs && mt_state && actions && N > 0 && N <= 64 && A >= 2 && A <= 32 && (int64_t)N * (A - 1) <= MT_LDS_D,
                "launch_sample_mt_probs: N=%d A=%d", N, A);
+  SynthStep st{};              // no environment step: the sampler workgroup alone
+  st.N = N;
   {
     ProfScope ps(g_prof_ctx, F_SAMPLE_ENV_STEP, N, stream);
-    launch_k(synth_step_a_mt_kernel<1>, dim3(1), dim3(256), stream, PROF_WHOLE, probs, A, mt_state, actions, (uint64_t)0,
-             (uint32_t)0, N, (uint32_t)0, (const uint64_t*)nullptr, (uint64_t)0, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-             (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (int32_t*)nullptr, (FinishedRing*)nullptr,
-             MultiWalk{nullptr, nullptr, nullptr, 0}, (uint32_t*)nullptr, (const MtAhead*)nullptr,
+    launch_k(synth_step_a_mt_kernel<1>, dim3(1), dim3(256), stream, PROF_WHOLE, probs, A, mt_state, actions, st,
+             MultiWalk{nullptr, nullptr, nullptr, 0}, (const MtAhead*)nullptr,
              RowsHeadsHook{nullptr, 0, N, A, nullptr, nullptr, nullptr, nullptr});
   }
   PAAC_CHECK_HIP(hipGetLastError());
@@ -2679,20 +2670,17 @@ int launch_sample_mt_probs(const float* probs, int A, uint32_t* mt_state, int32_
 }
 
 // mt_ahead (nullable): the record a spare workgroup of the preceding fc launch left (csrc/mt_ahead.h)
-int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, int32_t* actions, uint64_t seed, uint32_t env_offset,
-                                int N, uint32_t terminal_threshold, const uint64_t* step_base_dev, uint64_t step_offset,
-                                const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2, float* rewards_out,
-                                float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, void* walk_scratch,
-                                int64_t walk_scratch_bytes, uint8_t* raw_scratch, const void* mt_ahead, hipStream_t stream,
+int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, int32_t* actions, const SynthStep& st,
+                                void* walk_scratch, int64_t walk_scratch_bytes, const void* mt_ahead, hipStream_t stream,
                                 const HeadsPartials* heads) {
+  const int N = st.N;
   PAAC_REQUIRE(N > 0 && A >= 2 && A <= 32, "paac_sample_mt_synth_step: N=%d A=%d", N, A);
   PAAC_REQUIRE((int64_t)N * (A - 1) <= MT_LDS_D2, "paac_sample_mt_synth_step: N*(A-1)=%ld exceeds the fused kernel's limit %d "
                "(use paac_sample_mt + paac_synth_step)", (long)N * (A - 1), MT_LDS_D2);
-  PAAC_REQUIRE(probs && mt_state && actions && stack_in && stack_out && rewards_out && masks_out && ep_reward && ep_len,
-               "paac_sample_mt_synth_step: null argument");
+  PAAC_REQUIRE(probs && mt_state && actions, "paac_sample_mt_synth_step: null argument");
   RowsHeadsHook hs{nullptr, 0, N, A, nullptr, nullptr, nullptr, nullptr};
   {
-  ProfScope ps(g_prof_ctx, F_SAMPLE_ENV_STEP, N, (hipStream_t)stream);
+  ProfScope ps(g_prof_ctx, F_SAMPLE_ENV_STEP, N, stream);
   // small shards: the small-LDS sampler, one shift workgroup per band; beyond 1024 draws or 64 environments (where the
   // two-level chase needs the large first-hit table): the large-LDS sampler, one shift workgroup per environment
   const bool large = sampler_is_large(N, A);
@@ -2717,23 +2705,15 @@ int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, i
   const int samplers = mw.W > 0 ? mw.W : 1;
   int nshift = N * PRE_BANDS;                       // large path: one round of the 256 CUs (one workgroup per CU there)
   if (nshift > 256 - samplers) nshift = 256 - samplers > 32 ? 256 - samplers : 32;
-  if (large && hs.partial)
-    launch_k((synth_step_a_mt_kernel<2, true>), dim3(samplers + nshift), dim3(256), (hipStream_t)stream, PROF_WHOLE, probs, A,
-             mt_state, actions, seed, env_offset, N, terminal_threshold, step_base_dev, step_offset, (const uint32_t*)stack_in,
-             (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished, mw,
-             (uint32_t*)raw_scratch, reinterpret_cast<const MtAhead*>(mt_ahead), hs);
-  else if (large)
-    launch_k(synth_step_a_mt_kernel<2>, dim3(samplers + nshift), dim3(256), (hipStream_t)stream, PROF_WHOLE, probs, A,
-             mt_state, actions, seed, env_offset, N, terminal_threshold, step_base_dev, step_offset, (const uint32_t*)stack_in,
-             (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished, mw,
-             (uint32_t*)raw_scratch, reinterpret_cast<const MtAhead*>(mt_ahead), hs);
-  else
-    launch_k(synth_step_a_mt_kernel<1>, dim3(1 + N * PRE_BANDS), dim3(256), (hipStream_t)stream, PROF_WHOLE, probs, A, mt_state,
-             actions, seed, env_offset, N, terminal_threshold, step_base_dev, step_offset, (const uint32_t*)stack_in,
-             (uint32_t*)stack_out, (uint32_t*)stack_out2, rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished, mw,
-             (uint32_t*)raw_scratch, (const MtAhead*)nullptr, hs);
+  const auto launch = [&](auto kernel, int grid, const void* ahead) {
+    launch_k(kernel, dim3(grid), dim3(256), stream, PROF_WHOLE, probs, A, mt_state, actions, st, mw,
+             reinterpret_cast<const MtAhead*>(ahead), hs);
+  };
+  if (large && hs.partial) launch(synth_step_a_mt_kernel<2, true>, samplers + nshift, mt_ahead);
+  else if (large) launch(synth_step_a_mt_kernel<2>, samplers + nshift, mt_ahead);
+  else launch(synth_step_a_mt_kernel<1>, 1 + N * PRE_BANDS, nullptr);
   }
-  if (raw_scratch) launch_preprocess_after_step(raw_scratch, N, stack_in, stack_out, stack_out2, masks_out, (hipStream_t)stream);
+  if (st.raw) launch_preprocess_after_step(st, stream);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -267,7 +267,7 @@ static void launch_tower2(paac_ctx* ctx, Workspace& W, const float* params, cons
 
 template <class NT>
 static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8_t* states, int batch, float* logits,
-                        float* probs, float* values, const PhiloxArgs& ph, const SynthStepArgs& st, hipStream_t s,
+                        float* probs, float* values, const PhiloxArgs& ph, const SynthStep& st, hipStream_t s,
                         bool defer_heads = false, bool trunk_only = false) {
   const paac_layout& L = ctx->layout;
   Workspace& W = ctx->ws[wsi];
@@ -307,18 +307,18 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
   }
   const bool keep_acts = wsi == 1 || !ctx->managed_weights;          // fp32 conv activations / h kept for backward and read-back
   constexpr int NW = fc_heads_waves(NT::FLAT);      // 0: this fc geometry has no fc + head partials kernel
-  const bool small_tail = NW > 0 && batch <= kFcHeadsMaxRows && !ph.enabled && !st.enabled;   // fc + head partials kernel (fc_heads.h)
+  const bool small_tail = NW > 0 && batch <= kFcHeadsMaxRows && !ph.enabled && !st.active();   // fc + head partials kernel (fc_heads.h)
   // conv3 -> fc hand-off in the fc kernel's fragment order: rows are padded to 16 inside the activation buffer (max_batch
   // is rounded up at allocation)
   // ... and acting batches of up to 256 rows (the 128- / 256-environment shards) take the same fc kernel, finished by a
   // few workgroups (heads_finish_rows_kernel) instead of split-K slabs + a per-row heads launch
   const bool mid_tail = !small_tail && (tower || tower2) && !keep_acts && wsi == 0 && batch <= kFcHeadsMidRows && !ph.enabled &&
-                        !st.enabled && !trunk_only;
+                        !st.active() && !trunk_only;
   Workspace* keepW = nullptr;
   if (keep_row >= 0) {
     // (the fc + head partials routes, or -- the counter-based sampler's forwards -- the split-K fc with its per-row heads
     // launch, which then leaves the finished fc activations in the training set instead of the acting one)
-    const bool generic_ok = !small_tail && !mid_tail && (ph.enabled || st.enabled) && !defer_heads && !trunk_only;
+    const bool generic_ok = !small_tail && !mid_tail && (ph.enabled || st.active()) && !defer_heads && !trunk_only;
     if (!((tower || tower2) && !keep_acts && (small_tail || mid_tail || generic_ok) && keep_row + batch <= ctx->max_batch)) {
       set_error("paac_keep_next_forward: rows [%d, %d) cannot be kept -- needs a stock trunk's conv tower, managed weights, an "
                 "acting forward of at most %d rows (any size with the counter-based sampler) and keep_row + batch <= max_batch "
@@ -440,11 +440,10 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
   }
   {
     ProfScope ps(ctx, F_HEADS_FWD, batch, s);
-    SynthStepArgs stl = st;
-    if (stl.enabled) stl.stack_in = reinterpret_cast<const uint32_t*>(states);   // the stacks just observed
-    launch_heads_fwd<NT::H>(A, dim3(stl.enabled ? batch + batch * PRE_BANDS : batch), s, (const float*)W.fc_slab, splits,
+    // (a step inside this launch shifts the stacks just observed: st.stack_in == states, paac_forward_sample_synth_step)
+    launch_heads_fwd<NT::H>(A, dim3(st.active() ? batch + batch * PRE_BANDS : batch), s, (const float*)W.fc_slab, splits,
                             (long)batch * NT::H, bf, wa, ba, wc, bc, A, keepW ? keepW->fc_slab + (size_t)keep_row * NT::H : W.h,
-                            W.logits, W.probs, W.values, logits, probs, values, ph, batch, stl);
+                            W.logits, W.probs, W.values, logits, probs, values, ph, batch, st);
   }
   return 0;
 }
@@ -453,8 +452,7 @@ int launch_forward(paac_ctx* ctx, int ws, const float* params, const uint8_t* st
                    float* probs, float* values, hipStream_t s) {
   PhiloxArgs ph;
   memset(&ph, 0, sizeof(ph));
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
+  const SynthStep st{};
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
     return forward_impl<NatureNet>(ctx, ws, params, states, batch, logits, probs, values, ph, st, s);
   return forward_impl<OtherNet>(ctx, ws, params, states, batch, logits, probs, values, ph, st, s);
@@ -465,8 +463,7 @@ int launch_forward(paac_ctx* ctx, int ws, const float* params, const uint8_t* st
 int launch_forward_trunk_train(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, hipStream_t s) {
   PhiloxArgs ph;
   memset(&ph, 0, sizeof(ph));
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
+  const SynthStep st{};
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
     return forward_impl<NatureNet>(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, false, true);
   return forward_impl<OtherNet>(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, false, true);
@@ -482,8 +479,7 @@ int launch_deferred_heads(paac_ctx* ctx, const float* params, hipStream_t s) {
   Workspace& W = ctx->ws[1];
   PhiloxArgs ph;
   memset(&ph, 0, sizeof(ph));
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
+  const SynthStep st{};
   const int A = ctx->cfg.num_actions, H = ctx->spec.fc;
   // (rows kept by acting forwards hold finished fc activations: a zero bias and one "slab" reproduce them exactly)
   const float *bf = ctx->heads_pending_h ? ctx->zeros : params + L.offset[nt - 5], *wa = params + L.offset[nt - 4],
@@ -516,8 +512,7 @@ int launch_bootstrap_heads(paac_ctx* ctx, const float* params, int batch, int N,
   Workspace& W = ctx->ws[1];
   PhiloxArgs ph;
   memset(&ph, 0, sizeof(ph));
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
+  const SynthStep st{};
   const int A = ctx->cfg.num_actions, H = ctx->spec.fc;
   const float *bf = ctx->heads_pending_h ? ctx->zeros : params + L.offset[nt - 5], *wa = params + L.offset[nt - 4],
               *ba = params + L.offset[nt - 3], *wc = params + L.offset[nt - 2], *bc = params + L.offset[nt - 1];
@@ -539,21 +534,19 @@ bool forward_has_fc_heads(const paac_ctx* ctx) {
 }
 
 // Acting trunk up to the per-tile head partials (fc_heads.h); the caller's sampler launch finishes the heads.
-int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, const float** partial,
-                         int* ntiles, const float** ba, const float** bc, hipStream_t s) {
+int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, HeadsPartials* hp, hipStream_t s) {
   PhiloxArgs ph;
   memset(&ph, 0, sizeof(ph));
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
+  const SynthStep st{};
   const paac_layout& L = ctx->layout;
   const int nt = L.num_tensors;
-  *ba = params + L.offset[nt - 3];
-  *bc = params + L.offset[nt - 1];
-  *partial = ctx->ws[0].fc_slab;
+  hp->ba = params + L.offset[nt - 3];
+  hp->bc = params + L.offset[nt - 1];
+  hp->partial = ctx->ws[0].fc_slab;
   const int rc = (ctx->cfg.arch == PAAC_ARCH_NATURE)
                      ? forward_impl<NatureNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true)
                      : forward_impl<OtherNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true);
-  *ntiles = ctx->heads_ntiles;       // (this launch's: whole or quarter tiles, fc_heads.h)
+  hp->ntiles = ctx->heads_ntiles;       // (this launch's: whole or quarter tiles, fc_heads.h)
   return rc;
 }
 
@@ -563,8 +556,7 @@ int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* stat
 int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row, hipStream_t s) {
   PhiloxArgs ph;
   memset(&ph, 0, sizeof(ph));
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
+  const SynthStep st{};
   ctx->keep_row = train_row;
   ctx->keep_h_only = 1;          // the backward covers the rollout rows only: of the bootstrap rows it reads the fc activations
   int rc;
@@ -583,10 +575,8 @@ int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* st
 
 int launch_forward_sample(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
                           float* values, uint64_t seed, const uint64_t* step_base, uint64_t step_off,
-                          uint32_t env_offset, int32_t* actions, const SynthStepArgs* step, hipStream_t s) {
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
-  if (step) st = *step;
+                          uint32_t env_offset, int32_t* actions, const SynthStep* step, hipStream_t s) {
+  const SynthStep st = step ? *step : SynthStep{};
   PhiloxArgs ph;
   ph.enabled = 1;
   ph.seed = seed;
@@ -597,26 +587,6 @@ int launch_forward_sample(paac_ctx* ctx, const float* params, const uint8_t* sta
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
     return forward_impl<NatureNet>(ctx, 0, params, states, batch, nullptr, probs, values, ph, st, s);
   return forward_impl<OtherNet>(ctx, 0, params, states, batch, nullptr, probs, values, ph, st, s);
-}
-
-int launch_forward_sample_step(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
-                               float* values, uint64_t seed, const uint64_t* step_base, uint64_t step_off,
-                               uint32_t env_offset, int32_t* actions, uint64_t env_seed, uint32_t thresh,
-                               uint8_t* stack_out, float* rewards, float* masks, float* ep_reward, int32_t* ep_len,
-                               void* finished, hipStream_t s) {
-  SynthStepArgs st;
-  memset(&st, 0, sizeof(st));
-  st.enabled = 1;
-  st.seed = env_seed;
-  st.thresh = thresh;
-  st.stack_out = reinterpret_cast<uint32_t*>(stack_out);
-  st.rewards = rewards;
-  st.masks = masks;
-  st.ep_reward = ep_reward;
-  st.ep_len = ep_len;
-  st.fin = reinterpret_cast<FinishedRing*>(finished);
-  return launch_forward_sample(ctx, params, states, batch, probs, values, seed, step_base, step_off, env_offset, actions, &st,
-                               s);
 }
 
 #ifdef PAAC_DMM_STAMPS

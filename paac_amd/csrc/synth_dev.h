@@ -25,6 +25,32 @@ struct FinishedRing {
   int32_t len[4096];
 };
 
+// What a step records per environment: clipped reward and continuation mask of this step, the running episode totals, the
+// ring of finished episodes (nullable).
+struct EnvRecords {
+  float *rewards, *masks, *ep_reward;
+  int32_t* ep_len;
+  FinishedRing* fin;
+};
+
+// One step of N synthetic environments: the generator's key (seed, first global environment, step id = *step_base + step_off
+// + 1), the stacks read and written (stack_out2: the observation ring's wrap-around copy; raw: path B's screen pairs instead
+// of the shift) and the records.  A value-initialised SynthStep is "no environment step": active() is the one test of that.
+struct SynthStep {
+  uint64_t seed;
+  uint32_t env_offset;
+  int N;
+  uint32_t thresh;
+  const uint64_t* step_base;
+  uint64_t step_off;
+  const uint32_t* stack_in;
+  uint32_t *stack_out, *stack_out2;
+  EnvRecords rec;
+  uint32_t* raw;
+  __host__ __device__ bool active() const { return rec.rewards != nullptr; }
+  __device__ uint64_t id() const { return (step_base ? *step_base : 0ull) + step_off + 1ull; }
+};
+
 // Per-env bookkeeping shared by both paths: emulator_runner.py:30-31 + paac.py:119-138.  ep_reward0 / ep_len0 = the
 // running totals before this step (callers that have something to wait for load them early).
 // hr5 = lowbias32(key ^ 0xA511E9B3) % 5 and term = lowbias32(key ^ 0x3C6EF372) < thresh do not depend on the action:
@@ -32,44 +58,37 @@ struct FinishedRing {
 __device__ __forceinline__ uint32_t synth_reward_slot(uint32_t key) { return lowbias32(key ^ 0xA511E9B3u) % 5u; }
 __device__ __forceinline__ bool synth_terminal(uint32_t key, uint32_t thresh) { return lowbias32(key ^ 0x3C6EF372u) < thresh; }
 // env_bookkeep: the same records for a step whose unclipped reward r and terminal flag are already known (csrc/catch_dev.h).
-__device__ __forceinline__ bool env_bookkeep(float r, bool term, int e, float ep_reward0, int32_t ep_len0, float* rewards_out,
-                                             float* masks_out, float* ep_reward, int32_t* ep_len, FinishedRing* fin) {
-  rewards_out[e] = fminf(fmaxf(r, -1.f), 1.f);   // actor_learner.py:95-101
-  masks_out[e] = term ? 0.f : 1.f;               // paac.py:119
+__device__ __forceinline__ bool env_bookkeep(float r, bool term, int e, float ep_reward0, int32_t ep_len0, const EnvRecords& rec) {
+  rec.rewards[e] = fminf(fmaxf(r, -1.f), 1.f);   // actor_learner.py:95-101
+  rec.masks[e] = term ? 0.f : 1.f;               // paac.py:119
   const float tot = ep_reward0 + r;
   const int len = ep_len0 + 1;
   if (term) {
-    if (fin) {
-      const int slot = atomicAdd(&fin->count, 1) & 4095;
-      fin->reward[slot] = tot;
-      fin->len[slot] = len;
+    if (rec.fin) {
+      const int slot = atomicAdd(&rec.fin->count, 1) & 4095;
+      rec.fin->reward[slot] = tot;
+      rec.fin->len[slot] = len;
     }
-    ep_reward[e] = 0.f;
-    ep_len[e] = 0;
+    rec.ep_reward[e] = 0.f;
+    rec.ep_len[e] = 0;
   } else {
-    ep_reward[e] = tot;
-    ep_len[e] = len;
+    rec.ep_reward[e] = tot;
+    rec.ep_len[e] = len;
   }
   return term;
 }
 __device__ __forceinline__ bool synth_bookkeep_hashed(uint32_t hr5, bool term, int e, int act, float ep_reward0,
-                                                      int32_t ep_len0, float* rewards_out, float* masks_out,
-                                                      float* ep_reward, int32_t* ep_len, FinishedRing* fin) {
+                                                      int32_t ep_len0, const EnvRecords& rec) {
   const float table[5] = {-2.f, 0.f, 0.f, 1.f, 3.f};
-  return env_bookkeep(table[(hr5 + (uint32_t)act) % 5u], term, e, ep_reward0, ep_len0, rewards_out, masks_out, ep_reward, ep_len,
-                      fin);
+  return env_bookkeep(table[(hr5 + (uint32_t)act) % 5u], term, e, ep_reward0, ep_len0, rec);
 }
 __device__ __forceinline__ bool synth_bookkeep_with(uint32_t key, int e, int act, uint32_t thresh, float ep_reward0,
-                                                    int32_t ep_len0, float* rewards_out, float* masks_out,
-                                                    float* ep_reward, int32_t* ep_len, FinishedRing* fin) {
-  return synth_bookkeep_hashed(synth_reward_slot(key), synth_terminal(key, thresh), e, act, ep_reward0, ep_len0, rewards_out,
-                               masks_out, ep_reward, ep_len, fin);
+                                                    int32_t ep_len0, const EnvRecords& rec) {
+  return synth_bookkeep_hashed(synth_reward_slot(key), synth_terminal(key, thresh), e, act, ep_reward0, ep_len0, rec);
 }
 __device__ __forceinline__ bool synth_bookkeep(uint32_t key, int e, const int32_t* actions, uint32_t thresh,
-                                               float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len,
-                                               FinishedRing* fin) {
-  return synth_bookkeep_with(key, e, actions ? actions[e] : 0, thresh, ep_reward[e], ep_len[e], rewards_out, masks_out,
-                             ep_reward, ep_len, fin);
+                                               const EnvRecords& rec) {
+  return synth_bookkeep_with(key, e, actions ? actions[e] : 0, thresh, rec.ep_reward[e], rec.ep_len[e], rec);
 }
 
 // Frame shift of one (env, band) unit of path A: push the step's new 84x84 plane into the 4-deep history

@@ -38,6 +38,32 @@ def _ptr(t, dtype, numel=None, name="tensor", optional=False):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _lent(t):
+    """(pointer, bytes) of an optional uint8 scratch tensor."""
+    return (ctypes.c_void_p(t.data_ptr()), int(t.numel())) if t is not None else (ctypes.c_void_p(0), 0)
+
+
+def _step_ptrs(N, stack_out=None, rewards_out=None, masks_out=None, ep_reward=None, ep_len=None, finished=None, stack_out2=None,
+               stack_in=None, states=None):
+    """What one environment step of N environments writes, as every step entry takes it (csrc/synth_dev.h: SynthStep), in the C
+    order: stack_out, stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished -- behind the checks the entries share.
+    stack_in: the stacks a separate step reads (shape-checked here, passed by the entry); states: the observations an entry
+    that also runs the policy reads, which its step cannot shift in place.  No stack_out: no environment step, seven nulls."""
+    if stack_out is None:
+        return [ctypes.c_void_p(0)] * 7
+    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out), ("stack_out2", stack_out2)):
+        if t is not None and tuple(t.shape) != (N,) + OBS_SHAPE:
+            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
+    if states is not None and states.data_ptr() in [t.data_ptr() for t in (stack_out, stack_out2) if t is not None]:
+        raise ValueError("the step cannot shift the stacks in place")
+    if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
+        raise ValueError("finished ring too small")
+    return [_ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(stack_out2, torch.uint8, N * 28224, "stack_out2", True),
+            _ptr(rewards_out, torch.float32, N, "rewards_out"), _ptr(masks_out, torch.float32, N, "masks_out"),
+            _ptr(ep_reward, torch.float32, N, "ep_reward"), _ptr(ep_len, torch.int32, N, "ep_len"),
+            ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0)]
+
+
 # (filters, kernel size, stride) of the stock trunks' conv layers and their fc width (networks.py)
 STOCK_GEOMETRY = {_lib.ARCH_NATURE: ([(32, 8, 4), (64, 4, 2), (64, 3, 1)], 512),
                   _lib.ARCH_NIPS: ([(16, 8, 4), (32, 4, 2)], 256)}
@@ -144,20 +170,13 @@ class Context(object):
                              (tuple(states.shape), tuple(stack_out.shape)))
         if not (0 < B <= self.max_batch):
             raise ValueError("batch %d outside (0, %d]" % (B, self.max_batch))
-        if states.data_ptr() == stack_out.data_ptr():
-            raise ValueError("the step cannot shift the stacks in place")
-        if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
-            raise ValueError("finished ring too small")
+        out, _, *records = _step_ptrs(B, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, states=states)
         _lib.check(self.lib.paac_forward_sample_synth_step(
             self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
             _ptr(states, torch.uint8, B * 28224, "states"), B, _ptr(probs, torch.float32, B * A, "probs", True),
             _ptr(values, torch.float32, B, "values", True), int(seed), _ptr(step_base_dev, torch.int64, 1, "step_base", True),
             int(step_offset), int(env_offset), _ptr(actions, torch.int32, B, "actions"), int(env_seed),
-            int(terminal_threshold), _ptr(stack_out, torch.uint8, B * 28224, "stack_out"),
-            _ptr(rewards_out, torch.float32, B, "rewards_out"), _ptr(masks_out, torch.float32, B, "masks_out"),
-            _ptr(ep_reward, torch.float32, B, "ep_reward"), _ptr(ep_len, torch.int32, B, "ep_len"),
-            ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0), _stream()),
-            "paac_forward_sample_synth_step")
+            int(terminal_threshold), out, *records, _stream()), "paac_forward_sample_synth_step")
 
     def train_forward(self, params, states, values=None):
         B = states.shape[0]
@@ -354,39 +373,30 @@ class Context(object):
         N, A = self._check_states(states), self.num_actions
         if N > ACT_STEP_MAX_ENVS_LARGE or N * (A - 1) > FUSED_SAMPLE_MAX_DRAWS:
             raise ValueError("act_step_mt supports N <= %d and N*(A-1) <= %d" % (ACT_STEP_MAX_ENVS_LARGE, FUSED_SAMPLE_MAX_DRAWS))
-        if tuple(stack_out.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("stack_out must be [%d,84,84,4], got %s" % (N, tuple(stack_out.shape)))
-        if states.data_ptr() == stack_out.data_ptr() or (stack_out2 is not None and states.data_ptr() == stack_out2.data_ptr()):
-            raise ValueError("the step cannot shift the stacks in place")
-        if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
-            raise ValueError("finished ring too small")
+        if stack_out is None:
+            raise ValueError("stack_out is required")
+        step = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, states=states)
+        self._act(N, params, states, mt_state, actions, probs_out, values_out, step, env_seed, env_offset, terminal_threshold,
+                  step_base_dev, step_offset, raw_scratch, walk_scratch)
+
+    def act_mt(self, params, states, mt_state, actions, probs_out, values_out):
+        """Policy forward + numpy-parity sampler in three launches, no environment step (paac_act_step_mt with stack_out =
+        NULL): what the host-plugin loop runs per step (paac.py:104-110).  N <= ACT_STEP_MAX_ENVS, N*(A-1) <= 1024."""
+        N = self._check_states(states)
+        self._act(N, params, states, mt_state, actions, probs_out, values_out, _step_ptrs(N))
+
+    def _act(self, N, params, states, mt_state, actions, probs_out, values_out, step, env_seed=0, env_offset=0,
+             terminal_threshold=0, step_base_dev=None, step_offset=0, raw_scratch=None, walk_scratch=None):
+        """paac_act_step_mt; step: _step_ptrs' list."""
+        A = self.num_actions
         _lib.check(self.lib.paac_act_step_mt(
             self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
             _ptr(states, torch.uint8, N * 28224, "states"), N, _ptr(mt_state, torch.int32, 625, "mt_state"),
             _ptr(actions, torch.int32, N, "actions"), _ptr(probs_out, torch.float32, N * A, "probs_out"),
             _ptr(values_out, torch.float32, N, "values_out"), int(env_seed), int(env_offset), int(terminal_threshold),
-            _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
-            _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(stack_out2, torch.uint8, N * 28224, "stack_out2", True),
-            _ptr(rewards_out, torch.float32, N, "rewards_out"),
-            _ptr(masks_out, torch.float32, N, "masks_out"), _ptr(ep_reward, torch.float32, N, "ep_reward"),
-            _ptr(ep_len, torch.int32, N, "ep_len"),
-            ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0),
+            _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset), *step,
             _ptr(raw_scratch, torch.uint8, N * 2 * RAW_H * RAW_W, "raw_scratch", True),
-            ctypes.c_void_p(walk_scratch.data_ptr()) if walk_scratch is not None else ctypes.c_void_p(0),
-            int(walk_scratch.numel()) if walk_scratch is not None else 0, _stream()),
-            "paac_act_step_mt")
-
-    def act_mt(self, params, states, mt_state, actions, probs_out, values_out):
-        """Policy forward + numpy-parity sampler in three launches, no environment step (paac_act_step_mt with stack_out =
-        NULL): what the host-plugin loop runs per step (paac.py:104-110).  N <= ACT_STEP_MAX_ENVS, N*(A-1) <= 1024."""
-        N, A = self._check_states(states), self.num_actions
-        z = ctypes.c_void_p(0)
-        _lib.check(self.lib.paac_act_step_mt(
-            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
-            _ptr(states, torch.uint8, N * 28224, "states"), N, _ptr(mt_state, torch.int32, 625, "mt_state"),
-            _ptr(actions, torch.int32, N, "actions"), _ptr(probs_out, torch.float32, N * A, "probs_out"),
-            _ptr(values_out, torch.float32, N, "values_out"), 0, 0, 0, z, 0, z, z, z, z, z, z, z, z, z, 0, _stream()),
-            "paac_act_step_mt")
+            *_lent(walk_scratch), _stream()), "paac_act_step_mt")
 
     def pack_weights(self, params):
         """Refresh the ctx's pre-split copy of the conv weights (include/paac_hip.h: paac_pack_weights)."""
@@ -695,21 +705,10 @@ def synth_reset(seed, env_offset, stack_out, raw_scratch=None):
 def synth_step(seed, env_offset, actions, terminal_threshold, step_base_dev, step_offset, stack_in, stack_out,
                rewards_out, masks_out, ep_reward, ep_len, finished=None, stack_out2=None, raw_scratch=None):
     N = actions.shape[0]
-    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out)):
-        if tuple(t.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
-    if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
-        raise ValueError("finished ring too small")
+    step = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
     _lib.check(_lib.load().paac_synth_step(int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
                                            int(terminal_threshold), _ptr(step_base_dev, torch.int64, 1, "step_base", True),
-                                           int(step_offset), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"),
-                                           _ptr(stack_out, torch.uint8, N * 28224, "stack_out"),
-                                           _ptr(stack_out2, torch.uint8, N * 28224, "stack_out2", True),
-                                           _ptr(rewards_out, torch.float32, N, "rewards_out"),
-                                           _ptr(masks_out, torch.float32, N, "masks_out"),
-                                           _ptr(ep_reward, torch.float32, N, "ep_reward"),
-                                           _ptr(ep_len, torch.int32, N, "ep_len"),
-                                           ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0),
+                                           int(step_offset), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), *step,
                                            _ptr(raw_scratch, torch.uint8, N * 2 * RAW_H * RAW_W, "raw_scratch", True),
                                            _stream()), "paac_synth_step")
 
@@ -740,23 +739,14 @@ def _stateful_step(entry, words, seed, env_offset, actions, state_in, state_out,
     """paac_<game>_step: the shape checks and the argument list the stateful games share; `extra` = the game's own integer
     arguments, which follow `finished`."""
     N = actions.shape[0]
-    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out), ("stack_out2", stack_out2)):
-        if t is not None and tuple(t.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
+    step = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
     for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
         if t is not None and tuple(t.shape) != (N, words):
             raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
-    if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
-        raise ValueError("finished ring too small")
     args = [int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
             _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
-            _ptr(state_out2, torch.int32, N * words, "state_out2", True),
-            _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), _ptr(stack_out, torch.uint8, N * 28224, "stack_out"),
-            _ptr(stack_out2, torch.uint8, N * 28224, "stack_out2", True),
-            _ptr(rewards_out, torch.float32, N, "rewards_out"), _ptr(masks_out, torch.float32, N, "masks_out"),
-            _ptr(ep_reward, torch.float32, N, "ep_reward"), _ptr(ep_len, torch.int32, N, "ep_len"),
-            ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0)]
-    _lib.check(getattr(_lib.load(), entry)(*(args + [int(x) for x in extra] + [_stream()])), entry)
+            _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in")]
+    _lib.check(getattr(_lib.load(), entry)(*(args + step + [int(x) for x in extra] + [_stream()])), entry)
 
 
 def game_reset(kind, seed, env_offset, state_out, stack_out):
@@ -832,23 +822,13 @@ def sample_mt_synth_step(probs, mt_state, actions, seed, env_offset, terminal_th
     N, A = probs.shape
     if N * (A - 1) > FUSED_SAMPLE_MAX_DRAWS:
         raise ValueError("fused sampler+env step supports N*(A-1) <= %d" % FUSED_SAMPLE_MAX_DRAWS)
-    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out)):
-        if tuple(t.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
-    if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
-        raise ValueError("finished ring too small")
+    step = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
     _lib.check(_lib.load().paac_sample_mt_synth_step(
         _ptr(probs, torch.float32, N * A, "probs"), A, _ptr(mt_state, torch.int32, 625, "mt_state"),
         _ptr(actions, torch.int32, N, "actions"), int(seed), int(env_offset), N, int(terminal_threshold),
         _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
-        _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), _ptr(stack_out, torch.uint8, N * 28224, "stack_out"),
-        _ptr(stack_out2, torch.uint8, N * 28224, "stack_out2", True),
-        _ptr(rewards_out, torch.float32, N, "rewards_out"), _ptr(masks_out, torch.float32, N, "masks_out"),
-        _ptr(ep_reward, torch.float32, N, "ep_reward"), _ptr(ep_len, torch.int32, N, "ep_len"),
-        ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0),
-        ctypes.c_void_p(walk_scratch.data_ptr()) if walk_scratch is not None else ctypes.c_void_p(0),
-        int(walk_scratch.numel()) if walk_scratch is not None else 0,
-        _ptr(raw_scratch, torch.uint8, N * 2 * RAW_H * RAW_W, "raw_scratch", True), _stream()),
+        _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), *step,
+        *_lent(walk_scratch), _ptr(raw_scratch, torch.uint8, N * 2 * RAW_H * RAW_W, "raw_scratch", True), _stream()),
         "paac_sample_mt_synth_step")
 
 

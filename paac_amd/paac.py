@@ -81,7 +81,7 @@ class DeviceRollout(object):
         # records beside the observation ring, slot for slot (a step reads slot t and writes slot t + 1: nothing is updated in
         # place, and the wrap-around second output goes to slot 0 of both)
         self.stateful = STATEFUL_KINDS.get(env_spec.get("kind", "synthetic"))
-        self.catch = env_spec.get("kind", "synthetic") == "catch"
+        self.catch = env_spec.get("kind", "synthetic") == "catch"       # (read by the games' device-loop tests only)
         self.env_state = None
         if self.stateful:
             self.env_state = torch.zeros((2 * T + 1, N, self.stateful["words"]), dtype=torch.int32, device=dev)
@@ -145,6 +145,9 @@ class DeviceRollout(object):
         towered = getattr(L.network, "ARCH", None) in ("NATURE", "NIPS") and os.environ.get("PAAC_TOWER", "1") != "0"
         self.act_step_large = os.environ.get("PAAC_MT_AHEAD", "1") != "0" and N <= hip_ops.ACT_STEP_MAX_ENVS_LARGE and towered
         self.reuse_acting = os.environ.get("PAAC_REUSE_ACTING", "1") != "0" and towered and N <= hip_ops.KEEP_FORWARD_MAX_ROWS
+        self.route = self._route()
+        # what step t records, as every route's step call takes it (the per-cycle counterpart: cycle_tick above)
+        self.records = [(self.rewards[t], self.masks[t], self.ep_reward, self.ep_len, self.finished) for t in range(T)]
         if self.stateful:
             self.stateful["reset"](env_spec["seed"], self.env_offset, self.env_state[0], self.states[0])
         else:
@@ -161,75 +164,73 @@ class DeviceRollout(object):
         T, N = self.T, self.N
         return self.states[parity * T:(parity + 1) * T].view(T * N, 84, 84, 4)
 
+    def _route(self):
+        """How an acting step runs (_act_step), decided once.  stateful: forward (+ sampler), then the game's step.  act_step (numpy
+        sampler): the whole step in three launches -- conv tower, fc + head partials, heads finish + sampler + env step -- or, for
+        the large shards (act_step_large), four.  fused: numpy sampler and env step in one launch behind the forward.  heads_step:
+        counter-based sampler AND env step inside the heads kernel.  separate: forward + sampler, then the env step.  (Path B --
+        self.raw -- rides act_step and fused too: they write the raw screen pairs and the preprocess launch follows.)"""
+        N, draws = self.N, self.N * (self.A - 1)
+        if self.stateful:
+            return "stateful"
+        if self.sampler != "numpy":
+            return "heads_step" if self.raw is None else "separate"
+        if draws > hip_ops.FUSED_SAMPLE_MAX_DRAWS:
+            return "separate"
+        small = N <= hip_ops.ACT_STEP_MAX_ENVS and draws <= hip_ops.ACT_STEP_MAX_DRAWS
+        return "act_step" if (self.act_step_large or small) else "fused"
+
+    def _act_step(self, parity, t):
+        """Acting step t of a cycle: observation slot t -> action, value and records t, observation slot t + 1."""
+        L, route = self.L, self.route
+        params, slot, records = L.network.params, self._slot(parity, t), self.records[t]
+        obs, nxt = self.states[slot], self.states[slot + 1]
+        # the ring wraps after an odd cycle: its last step also writes slot 0 (the next even cycle's first slot)
+        wrap = self.states[0] if (parity == 1 and t == self.T - 1) else None
+        seed = self.env_spec["seed"]
+        if self.reuse_acting:
+            L.ctx.keep_next_forward(t * self.N)
+        if route == "act_step":
+            L.ctx.act_step_mt(params, obs, self.mt_state, self.actions[t], self.probs, self.values[t], seed, self.env_offset,
+                              self.env_spec["terminal_threshold"], self.tick, t, nxt, *records, stack_out2=wrap,
+                              raw_scratch=self.raw, walk_scratch=self.walk_scratch)
+        elif route == "heads_step":
+            L.ctx.forward_sample_synth_step(params, obs, self.sampler_seed, self.tick, t, self.env_offset, self.actions[t], seed,
+                                            self.env_spec["terminal_threshold"], nxt, *records, probs=self.probs,
+                                            values=self.values[t])
+            if wrap is not None:          # this launch has no second output
+                wrap.copy_(nxt)
+        else:
+            if self.sampler != "numpy":
+                L.ctx.forward_sample(params, obs, self.sampler_seed, self.tick, t, self.env_offset, self.actions[t],
+                                     probs=self.probs, values=self.values[t])
+            else:
+                L.ctx.forward(params, obs, probs=self.probs, values=self.values[t])
+                if route != "fused":
+                    hip_ops.sample_mt(self.probs, self.mt_state, self.mt_scratch, self.actions[t])
+            if route == "stateful":
+                self.stateful["step"](seed, self.env_offset, self.actions[t], self.env_state[slot], self.env_state[slot + 1], obs,
+                                      nxt, *records, stack_out2=wrap, state_out2=self.env_state[0] if wrap is not None else None,
+                                      **self.env_step_kwargs)
+            elif route == "fused":
+                hip_ops.sample_mt_synth_step(self.probs, self.mt_state, self.actions[t], seed, self.env_offset,
+                                             self.env_spec["terminal_threshold"], self.tick, t, obs, nxt, *records,
+                                             stack_out2=wrap, walk_scratch=self.walk_scratch, raw_scratch=self.raw)
+            else:
+                hip_ops.synth_step(seed, self.env_offset, self.actions[t], self.env_spec["terminal_threshold"], self.tick, t, obs,
+                                   nxt, *records, stack_out2=wrap, raw_scratch=self.raw)
+
     def _rollout_and_backward(self, parity):
         L, T, N = self.L, self.T, self.N
         params = L.network.params
-        st = [self.states[self._slot(parity, t)] for t in range(T + 1)]
         keep = self.reuse_acting
         for t in range(T):
-            if keep:
-                L.ctx.keep_next_forward(t * N)
-            # the ring wraps after an odd cycle: its last step also writes slot 0 (the next even cycle's first slot)
-            wrap = self.states[0] if (parity == 1 and t == T - 1) else None
-            if self.stateful:
-                # the generic route only: forward (+ sampler), then the environment step on the sampled actions
-                if self.sampler == "numpy":
-                    L.ctx.forward(params, st[t], probs=self.probs, values=self.values[t])
-                    hip_ops.sample_mt(self.probs, self.mt_state, self.mt_scratch, self.actions[t])
-                else:
-                    L.ctx.forward_sample(params, st[t], self.sampler_seed, self.tick, t, self.env_offset,
-                                         self.actions[t], probs=self.probs, values=self.values[t])
-                slot = self._slot(parity, t)
-                self.stateful["step"](self.env_spec["seed"], self.env_offset, self.actions[t], self.env_state[slot],
-                                      self.env_state[slot + 1], st[t], st[t + 1], self.rewards[t], self.masks[t],
-                                      self.ep_reward, self.ep_len, self.finished, stack_out2=wrap,
-                                      state_out2=self.env_state[0] if wrap is not None else None, **self.env_step_kwargs)
-                continue
-            # (path B -- self.raw -- rides the same fused launches: they write the raw screen pairs instead of shifting the
-            # stacks and the preprocess launch follows)
-            fused = self.sampler == "numpy" and N * (self.A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS
-            if fused and (self.act_step_large or (N <= hip_ops.ACT_STEP_MAX_ENVS and N * (self.A - 1) <= hip_ops.ACT_STEP_MAX_DRAWS)):
-                # the whole step in three launches: conv tower, fc + head partials, heads finish + sampler + env step -- or, for
-                # the large shards, four (heads finish on its own; the sampler's MT19937 doubles made meanwhile by a spare
-                # workgroup of the fc launch)
-                L.ctx.act_step_mt(params, st[t], self.mt_state, self.actions[t], self.probs, self.values[t],
-                                  self.env_spec["seed"], self.env_offset, self.env_spec["terminal_threshold"], self.tick, t,
-                                  st[t + 1], self.rewards[t], self.masks[t], self.ep_reward, self.ep_len, self.finished,
-                                  stack_out2=wrap, raw_scratch=self.raw, walk_scratch=self.walk_scratch)
-                continue
-            if fused:
-                # numpy-parity sampler and env step in one launch (the frame shift does not need the action)
-                L.ctx.forward(params, st[t], probs=self.probs, values=self.values[t])
-                hip_ops.sample_mt_synth_step(self.probs, self.mt_state, self.actions[t], self.env_spec["seed"],
-                                             self.env_offset, self.env_spec["terminal_threshold"], self.tick, t,
-                                             st[t], st[t + 1], self.rewards[t], self.masks[t], self.ep_reward,
-                                             self.ep_len, self.finished, stack_out2=wrap, walk_scratch=self.walk_scratch,
-                                             raw_scratch=self.raw)
-                continue
-            if self.sampler == "numpy":
-                L.ctx.forward(params, st[t], probs=self.probs, values=self.values[t])
-                hip_ops.sample_mt(self.probs, self.mt_state, self.mt_scratch, self.actions[t])
-            elif self.raw is None:      # counter-based sampler AND the env step inside the heads kernel
-                L.ctx.forward_sample_synth_step(params, st[t], self.sampler_seed, self.tick, t, self.env_offset,
-                                                self.actions[t], self.env_spec["seed"],
-                                                self.env_spec["terminal_threshold"], st[t + 1], self.rewards[t],
-                                                self.masks[t], self.ep_reward, self.ep_len, self.finished,
-                                                probs=self.probs, values=self.values[t])
-                if wrap is not None:          # this launch has no second output
-                    wrap.copy_(st[t + 1])
-                continue
-            else:       # counter-based sampler fused into the heads kernel
-                L.ctx.forward_sample(params, st[t], self.sampler_seed, self.tick, t, self.env_offset,
-                                     self.actions[t], probs=self.probs, values=self.values[t])
-            hip_ops.synth_step(self.env_spec["seed"], self.env_offset, self.actions[t],
-                               self.env_spec["terminal_threshold"], self.tick, t, st[t], st[t + 1],
-                               self.rewards[t], self.masks[t], self.ep_reward, self.ep_len, self.finished,
-                               stack_out2=wrap, raw_scratch=self.raw)
+            self._act_step(parity, t)
         # training forward over the T*N rollout rows with the N bootstrap observations appended (paac.py:140-142)
         # (the forward stops after the fc layer: the heads of the rollout rows AND the value head of the bootstrap rows are
         # finished inside the backward's first launch)
         if keep:
-            L.ctx.bootstrap_forward_trunk(params, st[T], T * N)
+            L.ctx.bootstrap_forward_trunk(params, self.states[self._slot(parity, T)], T * N)
         else:
             L.ctx.train_forward_trunk(params, self.states[parity * T:(parity + 1) * T + 1].view((T + 1) * N, 84, 84, 4))
         phase = ((0 if self.single_exchange else 1) if self.phased else 3)

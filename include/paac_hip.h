@@ -211,6 +211,27 @@ typedef struct {
   int32_t estimator;          /* PAAC_RETURNS_NSTEP (0: the n-step return above) or PAAC_RETURNS_GAE */
   double gae_lambda;          /* in [0, 1]; read by PAAC_RETURNS_GAE only.  Both zero = a struct from before these fields */
 } paac_returns;
+/* --bootstrap_truncated: partial-episode bootstrapping (Pardo et al., arXiv 1712.00378) of the return at a step that was
+ * terminal only because the game's step cap was reached.  The reference has no counterpart; this is the contract.
+ *   The plane travels behind the block: paac_returns keeps its layout (callers compiled against it are served as before), and
+ *   a caller that has a plane passes the `ret` member of a paac_returns_truncs with PAAC_RETURNS_TRUNCS or'ed into
+ *   ret.estimator -- the flag says that `truncs` follows.  Every entry that takes a paac_returns reads it that way.
+ *   No flag, or truncs == NULL: the entry launches the kernels it always launched, with the arguments it always passed;
+ *   nothing below applies.  With a plane, tr = truncs[t, e] (such a step has mask 0), V_t = values[t, e] (the
+ *   acting value of the state the step left -- the observation the cap cut off is overwritten by the reset, so this is the
+ *   value of the last state seen), fp32 inputs promoted to fp64, every operation a separate round-to-nearest operation:
+ *     n-step, tr = 1:  R_t = r_t + gamma*V_t            (an fp64 product at every t, t = T-1 included: the fp32 first product
+ *                                                         belongs to the v_boot term, which a masked step does not read)
+ *     GAE,    tr = 1:  delta_t = (r_t + gamma*V_t) - V_t;  A_t = delta_t  (the recursion is cut as at any terminal);
+ *                      y_t = f32(A_t + V_t)
+ *   and every step with tr = 0 is the step of paac_nstep_returns / paac_gae_returns.  An all-zero plane gives their bits.
+ *   The plane is read by the truncation-aware instantiations of the kernels that compute returns (chosen at compile time,
+ *   like the estimator): the backward's first launch, paac_returns_norm_tick, paac_returns_scan. */
+#define PAAC_RETURNS_TRUNCS 0x100
+typedef struct {
+  paac_returns ret;
+  const float* truncs;        /* [T,N] nullable: 1 = the step ended its episode at the step cap alone, else 0 */
+} paac_returns_truncs;
 int paac_loss_backward_returns(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                                const paac_returns* ret, int batch, float entropy_beta, float* grad, float* loss_out,
                                int forward_done, int phase, paac_stream_t stream);
@@ -476,6 +497,11 @@ int paac_gae_returns_tick(const float* v_boot, const float* rewards, const float
  * forward gets the heads of those N rows finished here (one launch; the rollout rows stay pending, kept rows stay kept, and
  * the backward's first launch finishes them as usual).  With ret->v_boot set, ctx and params may be NULL. */
 int paac_adv_normalize(const float* adv, int B, float* adv_n_out, double* stats_out, paac_stream_t stream);
+/* paac_nstep_returns[_tick] / paac_gae_returns[_tick] from the argument block: the estimator by ret->estimator, the
+ * bookkeeping of the _tick entries when ret->global_step_dev is set (tick_dev optional as there), y_out / adv_out written,
+ * v_boot required -- and the truncation plane read (contract: paac_returns_truncs above).  No plane launches the kernel of the entry
+ * named first with its arguments; an all-zero plane gives the same bits through the truncation-aware kernel. */
+int paac_returns_scan(const paac_returns* ret, paac_stream_t stream);
 int paac_returns_norm_tick(paac_ctx* ctx, const float* params, const paac_returns* ret, float* adv_n_out, double* stats_out,
                            paac_stream_t stream);
 
@@ -588,6 +614,25 @@ int paac_rally_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
  *            The caller zeroes score / length / done and sets *alive = N before step 0.
  * The rollout bookkeeping (ep_reward / ep_len / finished ring) is not touched.  Refused with a message, without a launch:
  * the in-place buffers above, N <= 0, A outside [2, 32], noops < 0, a game id that is none of the three. */
+/* What one step of the device games records, as one block (paac_game_step): the five records of paac_catch_step, then
+ * truncs f32[N] (nullable: nothing is written) = 1 where the step was terminal ONLY because the game's step cap was reached
+ * (bricks: steps == 500 and the step did not also lose the last life, or any life under single_life; rally: steps == 1000 and
+ * neither side reached five points on the step), else 0.  A step that is both a real ending and at the cap is not truncated;
+ * catch never is (13 steps is its rule, not a limit).  rewards / masks keep their meaning: a truncated step is terminal. */
+typedef struct {
+  float* rewards;
+  float* masks;
+  float* ep_reward;
+  int32_t* ep_len;
+  void* finished;
+  float* truncs;
+} paac_env_records;
+/* paac_catch_step / paac_bricks_step / paac_rally_step by the game's id (PAAC_EVAL_CATCH / _BRICKS / _RALLY below), the
+ * records as a block; option = bricks' single_life (ignored by the other games).  Same launch, outputs and refusals; with
+ * rec->truncs == NULL the same stores. */
+int paac_game_step(int game, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                   int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                   const paac_env_records* rec, int option, paac_stream_t stream);
 #define PAAC_EVAL_CATCH 0
 #define PAAC_EVAL_BRICKS 1
 #define PAAC_EVAL_RALLY 2

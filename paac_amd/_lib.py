@@ -15,6 +15,7 @@ PROF_FAMILIES = 16
 ARCH_NIPS, ARCH_NATURE, ARCH_USER = 0, 1, 2
 CLIP_IGNORE, CLIP_GLOBAL, CLIP_LOCAL = 0, 1, 2
 RETURNS_NSTEP, RETURNS_GAE = 0, 1
+RETURNS_TRUNCS = 0x100         # PAAC_RETURNS_TRUNCS
 PPO_EPOCHS_MAX = 16            # PAAC_PPO_EPOCHS_MAX
 PPO_MINIBATCHES_MAX = 16       # PAAC_PPO_MINIBATCHES_MAX
 PPO_STEPS_MAX = 64             # PAAC_PPO_STEPS_MAX: optimizer steps (epochs x minibatches) of one cycle
@@ -44,6 +45,18 @@ class Returns(ctypes.Structure):
                 ("global_step_dev", c_void_p), ("increment", c_int64), ("initial_lr", ctypes.c_double),
                 ("lr_annealing_steps", c_int64), ("lr_out_dev", c_void_p), ("tick_dev", c_void_p), ("tick_inc", c_uint64),
                 ("estimator", c_int32), ("gae_lambda", ctypes.c_double)]
+
+
+class ReturnsTruncs(ctypes.Structure):
+    """paac_returns_truncs (include/paac_hip.h): a paac_returns with the truncation plane of --bootstrap_truncated behind it;
+    RETURNS_TRUNCS in ret.estimator says so, and the entries take a pointer to `ret`."""
+    _fields_ = [("ret", Returns), ("truncs", c_void_p)]
+
+
+class EnvRecords(ctypes.Structure):
+    """paac_env_records (include/paac_hip.h): what one step of the device games records, the truncation plane included."""
+    _fields_ = [("rewards", c_void_p), ("masks", c_void_p), ("ep_reward", c_void_p), ("ep_len", c_void_p),
+                ("finished", c_void_p), ("truncs", c_void_p)]
 
 
 class KlGate(ctypes.Structure):
@@ -90,6 +103,8 @@ _SIGNATURES = {
     "paac_record_policy": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "paac_adv_normalize": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "paac_returns_norm_tick": (c_int, [c_void_p, c_void_p, POINTER(Returns), c_void_p, c_void_p, c_void_p]),
+    "paac_returns_scan": (c_int, [POINTER(Returns), c_void_p]),
+    "paac_game_step": (c_int, [c_int, c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_clip_rmsprop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,

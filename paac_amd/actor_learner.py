@@ -72,6 +72,12 @@ class ActorLearner(object):
         if not isinstance(self.adv_norm, (bool, np.bool_)):
             raise ValueError("adv_norm %r: expected True or False" % (self.adv_norm,))
         self.adv_norm = bool(self.adv_norm)
+        # --bootstrap_truncated (include/paac_hip.h: paac_returns.truncs has the contract): Namespaces / args.json files without
+        # the field mean off.  On: the loops carry a truncation plane beside the masks (paac.py) where the game has a step cap
+        self.bootstrap_truncated = getattr(args, "bootstrap_truncated", False)
+        if not isinstance(self.bootstrap_truncated, (bool, np.bool_)):
+            raise ValueError("bootstrap_truncated %r: expected True or False" % (self.bootstrap_truncated,))
+        self.bootstrap_truncated = bool(self.bootstrap_truncated)
         self.ppo_vclip = float(getattr(args, "ppo_vclip", 0.0))
         if not (0.0 <= self.ppo_vclip and math.isfinite(self.ppo_vclip)):          # (NaN fails the comparison)
             raise ValueError("ppo_vclip %r: expected a finite value >= 0 (0 = off)" % (self.ppo_vclip,))

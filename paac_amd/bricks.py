@@ -40,6 +40,9 @@ Spec (all hashing reuses lowbias32 and key = synth_key(seed, env, id) of synthet
                         else        the ball moves to (nx, ny)
                    4. steps += 1; steps == MAX_STEPS: the step is terminal whatever else happened
                    5. on a terminal step the environment starts episode k + 1 at once (catch's rule)
+                 truncated: the step is terminal ONLY because of rule 4 -- it did not also lose the last life (or, in a
+                 single_life environment, any life).  A step that is both a real ending and at the cap is not truncated.
+                 The cap is a time limit, not a property of the state: --bootstrap_truncated bootstraps the return there
                  at most 1.0 of reward per step
   plane(state)   a pixel in cell (cy, cx) = 255 if (cy, cx) == (by, bx), else 128 if cy == 13 and cx in (px, px + 1), else 64
                  if 2 <= cy <= 4 and the brick is present, else 0
@@ -90,6 +93,12 @@ def start_state(seed, env, k):
 def step_state(seed, env, state, a, single_life=False):
     """One step of `state` under action a -> (state, reward, terminal).  The state returned is the one the next step starts
     from: after a terminal step that is the start state of episode k + 1 (the device record's rule)."""
+    return step_state_truncated(seed, env, state, a, single_life)[:3]
+
+
+def step_state_truncated(seed, env, state, a, single_life=False):
+    """step_state with the reason of a terminal step -> (state, reward, terminal, truncated): truncated = the step is terminal
+    only because steps reached MAX_STEPS."""
     bx, by, dx, dy, px, lives, steps, k, r0, r1, r2 = state
     rows = [r0, r1, r2]
     if a == 1:
@@ -119,13 +128,14 @@ def step_state(seed, env, state, a, single_life=False):
             lost = True
             terminal = lives == 0 or bool(single_life)
     steps += 1
+    truncated = not terminal and steps == MAX_STEPS
     terminal = terminal or steps == MAX_STEPS
     if terminal:
-        return start_state(seed, env, k + 1), reward, True
+        return start_state(seed, env, k + 1), reward, True, truncated
     state = (nx, ny, dx, dy, px, lives, steps, k, rows[0], rows[1], rows[2])
     if lost:
         state = serve(seed, env, state, LIVES - lives)
-    return state, reward, False
+    return state, reward, False, False
 
 
 def plane(state):
@@ -175,6 +185,7 @@ class BricksEnvironment(BaseEnvironment):
         self.single_life = bool(single_life)
         self.state = start_state(self.seed, self.actor_id, 0)
         self.stack = np.zeros((84, 84, 4), dtype=np.uint8)
+        self.last_step_truncated = False       # the last next() ended its episode at the step cap alone (runners.py reads it)
 
     @property
     def k(self):
@@ -191,7 +202,8 @@ class BricksEnvironment(BaseEnvironment):
 
     def next(self, action):
         a = int(np.argmax(action))
-        self.state, reward, terminal = step_state(self.seed, self.actor_id, self.state, a, self.single_life)
+        self.state, reward, terminal, self.last_step_truncated = step_state_truncated(self.seed, self.actor_id, self.state, a,
+                                                                                      self.single_life)
         self.stack[..., :3] = self.stack[..., 1:]
         self.stack[..., 3] = plane(self.state)
         return np.copy(self.stack), reward, terminal

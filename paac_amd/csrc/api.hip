@@ -501,8 +501,8 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
 // The fields of a paac_returns that do not depend on the entry: the rollout records, estimator, lambda, the schedule pointers.
 static int check_returns(const char* fn, const paac_returns* ret) {
   PAAC_REQUIRE(ret->rewards && ret->masks && ret->values && ret->y_out && ret->adv_out, "%s: null rollout record", fn);
-  PAAC_REQUIRE(ret->estimator == PAAC_RETURNS_NSTEP || ret->estimator == PAAC_RETURNS_GAE,
-               "%s: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", fn, ret->estimator);
+  PAAC_REQUIRE(returns_estimator(ret) == PAAC_RETURNS_NSTEP || returns_estimator(ret) == PAAC_RETURNS_GAE,
+               "%s: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", fn, returns_estimator(ret));
   PAAC_REQUIRE(ret->gae_lambda >= 0.0 && ret->gae_lambda <= 1.0, "%s: gae_lambda %g outside [0, 1]", fn, ret->gae_lambda);
   PAAC_REQUIRE(!ret->global_step_dev || (ret->lr_out_dev && ret->lr_annealing_steps > 0),
                "%s: schedule bookkeeping needs lr_out_dev and lr_annealing_steps", fn);

@@ -75,9 +75,9 @@ struct BricksGame {
 
   // One step of state s under action a (1 = left, 2 = right, anything else = stay), a pure function of its arguments: the
   // state the next step starts from (the next episode's start state after a terminal step), the reward and the terminal flag.
-  // single_life != 0: losing a ball ends the episode.
+  // single_life != 0: losing a ball ends the episode.  *trunc: the step is terminal only because steps reached the cap.
   static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, int single_life, float* reward,
-                                                  bool* term) {
+                                                  bool* term, bool* trunc = nullptr) {
     const bool single = single_life != 0;
     if (a == 1) s.px = max(s.px - 1, 0);
     else if (a == 2) s.px = min(s.px + 1, BRICKS_CELLS - 2);
@@ -118,6 +118,7 @@ struct BricksGame {
     s.bx = nx;
     s.by = ny;
     s.steps += 1;
+    if (trunc) *trunc = !over && s.steps == BRICKS_MAX_STEPS;
     over = over || s.steps == BRICKS_MAX_STEPS;
     *reward = r;
     *term = over;

@@ -47,8 +47,10 @@ struct CatchGame {
 
   // One step of state s under action a (1 = left, 2 = right, anything else = stay), a pure function of its arguments: the
   // state the next step starts from (the next episode's start state after a terminal step), the reward and the terminal flag.
+  // Never truncated: 13 steps is the game's rule, not a limit.
   static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, int /*opt*/, float* reward,
-                                                  bool* term) {
+                                                  bool* term, bool* trunc = nullptr) {
+    if (trunc) *trunc = false;
     if (a == 1) s.px = max(s.px - 1, 0);
     else if (a == 2) s.px = min(s.px + 1, CATCH_CELLS - 1);
     int nx = s.bx + s.dx;

@@ -12,6 +12,13 @@ namespace paac {
 
 void set_error(const char* fmt, ...);
 
+// A paac_returns as its caller meant it: the estimator without the flag, and the truncation plane of the paac_returns_truncs
+// the block is the head of (nullptr without the flag).
+inline int returns_estimator(const paac_returns* ret) { return ret->estimator & ~PAAC_RETURNS_TRUNCS; }
+inline const float* returns_truncs(const paac_returns* ret) {
+  return (ret->estimator & PAAC_RETURNS_TRUNCS) ? reinterpret_cast<const paac_returns_truncs*>(ret)->truncs : nullptr;
+}
+
 #define PAAC_CHECK_HIP(expr)                                                              \
   do {                                                                                    \
     hipError_t _e = (expr);                                                               \
@@ -276,6 +283,20 @@ __device__ __forceinline__ void nstep_step(const double gamma, const bool first,
                                            double& R) {
   const double prod = first ? (double)__fmul_rn((float)gamma, vb) : __dmul_rn(gamma, R);
   R = __dadd_rn((double)rw, __dmul_rn(prod, (double)mk));
+}
+// --bootstrap_truncated (include/paac_hip.h: paac_returns.truncs has the contract): one step of either scan for the
+// truncation-aware instantiations.  tr != 0: the step ended its episode at the step cap alone (its mask is 0), and the return
+// bootstraps from V = V_t, the acting value of the state the step left -- an fp64 product at every t, t = T - 1 included (the
+// fp32 first product belongs to the v_boot term, which a masked step does not read).  tr == 0: nstep_step / gae_step.
+__device__ __forceinline__ void nstep_step_tr(const double gamma, const bool first, const float vb, const float rw, const float mk,
+                                              const float tr, const double V, double& R) {
+  if (tr != 0.f) R = __dadd_rn((double)rw, __dmul_rn(gamma, V));
+  else nstep_step(gamma, first, vb, rw, mk, R);
+}
+__device__ __forceinline__ void gae_step_tr(const double gamma, const double gl, const float rw, const float mk, const float tr,
+                                            const double V, const double Vn, double& A) {
+  if (tr != 0.f) A = __dsub_rn(__dadd_rn((double)rw, __dmul_rn(gamma, V)), V);      // the recursion is cut as at any terminal
+  else gae_step(gamma, gl, rw, mk, V, Vn, A);
 }
 
 // The per-cycle bookkeeping (paac.py:127,156; actor_learner.py:119-123), done by one thread of whichever launch computes

@@ -4,8 +4,12 @@
 //   State, kWords                                    the state record in registers, its int32 words in memory
 //   load(state, e), store(state, e, s)               record e of a [N, kWords] buffer
 //   start(seed, env)                                 episode 0's start state
-//   advance(seed, env, s, a, opt, &reward, &term)    one step, a pure function of its arguments (opt: the game's one integer
-//                                                    option, bricks' single_life; 0 where a game has none)
+//   advance(seed, env, s, a, opt, &reward, &term[, &trunc])
+//                                                    one step, a pure function of its arguments (opt: the game's one integer
+//                                                    option, bricks' single_life; 0 where a game has none).  trunc (optional,
+//                                                    --bootstrap_truncated): the step was terminal ONLY because the game's step
+//                                                    cap was reached -- a step that also ends the episode for a real reason is
+//                                                    not truncated, a game without a cap (catch) never is; term keeps its meaning
 //   shift_quad(s, q, old, fresh)                     quad q of the observation: the plane of s pushed into `old`
 #pragma once
 #include "synth_dev.h"

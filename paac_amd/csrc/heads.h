@@ -371,19 +371,30 @@ struct GaeArgs : ReturnsArgs {
 };
 // Host: the argument block from the C struct (ret == nullptr: all zero, the returns are not computed in the launch).  The
 // n-step instantiations take its ReturnsArgs part.  v_boot: what the kernel reads; nullptr = bootstrap rows of the forward.
-inline GaeArgs returns_args(const paac_returns* ret, const float* v_boot) {
-  GaeArgs rt;
+// --bootstrap_truncated: the truncation-aware instantiations (EST = kEstTrunc) take the records' truncation plane behind the
+// GAE block and pick the estimator at run time (one uniform flag: two more cells per kernel family, not four), so the n-step
+// and GAE instantiations keep their arguments and their code.  One step is nstep_step_tr / gae_step_tr (common.h).
+constexpr int kEstTrunc = 2;
+struct TruncArgs : GaeArgs {
+  const float* truncs;      // [T,N] 1.f where the step ended its episode at the step cap alone; nullptr: the plain instantiations run
+  int gae;                  // the estimator: 0 = n-step, 1 = GAE
+};
+inline TruncArgs returns_args(const paac_returns* ret, const float* v_boot) {
+  TruncArgs rt;
   memset(&rt, 0, sizeof(rt));
   if (!ret) return rt;
   rt.v_boot = v_boot; rt.boot_in_fwd = v_boot ? 0 : 1; rt.rewards = ret->rewards; rt.masks = ret->masks; rt.values_act = ret->values;
   rt.T = ret->T; rt.N = ret->N; rt.gamma = ret->gamma; rt.y_out = ret->y_out; rt.adv_out = ret->adv_out;
   rt.ct = CycleTick{ret->global_step_dev, ret->increment, ret->initial_lr, ret->lr_annealing_steps, ret->lr_out_dev,
                     ret->tick_dev, ret->tick_inc};
-  if (ret->estimator == PAAC_RETURNS_GAE) rt.gl = ret->gamma * ret->gae_lambda;
+  rt.gae = returns_estimator(ret) == PAAC_RETURNS_GAE;
+  if (rt.gae) rt.gl = ret->gamma * ret->gae_lambda;
+  rt.truncs = returns_truncs(ret);
   return rt;
 }
 template <int EST> struct ReturnsOf { using type = ReturnsArgs; };
 template <> struct ReturnsOf<kEstGae> { using type = GaeArgs; };
+template <> struct ReturnsOf<kEstTrunc> { using type = TruncArgs; };
 
 __device__ __forceinline__ void gae_row_from(const GaeArgs& r, const int i, const float vb, float& y, float& adv) {
   const int t = i / r.N, e = i - t * r.N;
@@ -438,9 +449,84 @@ __device__ __forceinline__ void gae_row_from(const GaeArgs& r, const int i, cons
   y = (float)__dadd_rn(A, V);
 }
 
-// One spelling for both estimators inside the kernels: the argument block's type picks the scan.
+// The truncation-aware scan of either estimator (S: the return R or the advantage A; V ends as V_t), plain and preloaded: the
+// preload carries the later steps' acting values for the n-step return too -- a truncated step reads its own.
+__device__ __forceinline__ void trunc_step(const TruncArgs& r, const bool first, const float vb, const float rw, const float mk,
+                                           const float tr, const double V, const double Vn, double& S) {
+  if (r.gae) gae_step_tr(r.gamma, r.gl, rw, mk, tr, V, Vn, S);
+  else nstep_step_tr(r.gamma, first, vb, rw, mk, tr, V, S);
+}
+__device__ __forceinline__ void trunc_finish(const TruncArgs& r, const double S, const double V, float& y, float& adv) {
+  if (r.gae) {
+    adv = (float)S;
+    y = (float)__dadd_rn(S, V);
+  } else {
+    y = (float)S;
+    adv = (float)__dsub_rn(S, V);
+  }
+}
+__device__ __forceinline__ void trunc_row_from(const TruncArgs& r, const int i, const float vb, float& y, float& adv) {
+  const int t = i / r.N, e = i - t * r.N;
+  double S = 0.0, Vn = (double)vb, V = Vn;
+  for (int tt = r.T - 1; tt >= t; --tt) {
+    const long k = (long)tt * r.N + e;
+    V = (double)r.values_act[k];
+    trunc_step(r, tt == r.T - 1, vb, r.rewards[k], r.masks[k], r.truncs[k], V, Vn, S);
+    Vn = V;
+  }
+  trunc_finish(r, S, V, y, adv);
+}
+struct TruncPre {
+  float rw[kNstepPre], mk[kNstepPre], va[kNstepPre], tr[kNstepPre];
+};
+__device__ __forceinline__ TruncPre trunc_preload(const TruncArgs& r, const int i) {
+  TruncPre p;
+  const int t = i / r.N, e = i - t * r.N;
+#pragma unroll
+  for (int k = 0; k < kNstepPre; ++k) {
+    const int tt = r.T - 1 - k;
+    const long at = (long)(tt >= t ? tt : t) * r.N + e;
+    p.rw[k] = r.rewards[at];
+    p.mk[k] = r.masks[at];
+    p.va[k] = r.values_act[at];
+    p.tr[k] = r.truncs[at];
+  }
+  return p;
+}
+__device__ __forceinline__ void trunc_row_from(const TruncArgs& r, const int i, const float vb, const TruncPre& p, float& y,
+                                               float& adv) {
+  const int t = i / r.N, e = i - t * r.N;
+  double S = 0.0, Vn = (double)vb, V = Vn;
+#pragma unroll
+  for (int k = 0; k < kNstepPre; ++k) {
+    const int tt = r.T - 1 - k;
+    if (tt >= t) {
+      V = (double)p.va[k];
+      trunc_step(r, k == 0, vb, p.rw[k], p.mk[k], p.tr[k], V, Vn, S);
+      Vn = V;
+    }
+  }
+  for (int tt = r.T - 1 - kNstepPre; tt >= t; --tt) {
+    const long k = (long)tt * r.N + e;
+    V = (double)r.values_act[k];
+    trunc_step(r, false, vb, r.rewards[k], r.masks[k], r.truncs[k], V, Vn, S);
+    Vn = V;
+  }
+  trunc_finish(r, S, V, y, adv);
+}
+
+// One spelling for the estimators inside the kernels: the argument block's type picks the scan.
 template <int EST> struct PreOf { using type = NstepPre; };
 template <> struct PreOf<kEstGae> { using type = GaePre; };
+template <> struct PreOf<kEstTrunc> { using type = TruncPre; };
+__device__ __forceinline__ void returns_row(const TruncArgs& r, const int i, float& y, float& adv) {
+  trunc_row_from(r, i, r.v_boot[i % r.N], y, adv);
+}
+__device__ __forceinline__ TruncPre returns_preload(const TruncArgs& r, const int i) { return trunc_preload(r, i); }
+__device__ __forceinline__ void returns_row_from(const TruncArgs& r, const int i, const float vb, const TruncPre& p, float& y,
+                                                 float& adv) {
+  trunc_row_from(r, i, vb, p, y, adv);
+}
 __device__ __forceinline__ void returns_row(const ReturnsArgs& r, const int i, float& y, float& adv) { nstep_row(r, i, y, adv); }
 __device__ __forceinline__ void returns_row(const GaeArgs& r, const int i, float& y, float& adv) {
   gae_row_from(r, i, r.v_boot[i % r.N], y, adv);

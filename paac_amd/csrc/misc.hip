@@ -27,11 +27,16 @@ __device__ unsigned long long* g_misc_stamps = nullptr;   // diagnostic build: p
 // The returns of one rollout, standalone: the n-step return (paac.py:140-149; fp64 scan like the reference's numpy buffers)
 // or generalized advantage estimation, chosen at compile time.  One step is nstep_step / gae_step (common.h: the arithmetic
 // contracts), shared with the scans inside the heads gradient kernels (heads.h).  gl = gamma * lambda, read by GAE alone.
-template <int EST>
+// PLANE (--bootstrap_truncated): NoPlane -- the plain instantiations, whose code is what it was (the empty struct is one
+// byte at the end of the kernel arguments, which no instruction reads) -- or the truncation plane's pointer: the scan then
+// also loads the plane with the chunk and steps by nstep_step_tr / gae_step_tr.
+struct NoPlane {};
+template <int EST, class PLANE = NoPlane>
 __global__ void returns_scan_kernel(const float* __restrict__ v_boot, const float* __restrict__ rewards,
                                     const float* __restrict__ masks, const float* __restrict__ values, int T, int N,
                                     double gamma, double gl, float* __restrict__ y, float* __restrict__ adv,
-                                    const CycleTick ct) {
+                                    const CycleTick ct, const PLANE truncs) {
+  constexpr bool TR = !std::is_same<PLANE, NoPlane>::value;
   // 128 threads: wave 0 scans 64 environments, wave 1 of workgroup 0 does the cycle bookkeeping -- its
   // read-modify-write round trip runs beside the scan's instead of in front of it
   const int e = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -46,7 +51,7 @@ __global__ void returns_scan_kernel(const float* __restrict__ v_boot, const floa
   const float vb = v_boot[e];
   double S = 0.0, Vn = (double)vb;      // S: the return R (n-step) / the advantage A (GAE); Vn: GAE's V_{t+1}, v_boot at t = T - 1
   for (int t0 = T - 1; t0 >= 0; t0 -= CH) {
-    float r[CH], m[CH], v[CH];
+    float r[CH], m[CH], v[CH], tr[CH];
 #pragma unroll
     for (int u = 0; u < CH; ++u) {
       const int t = t0 - u;
@@ -54,6 +59,7 @@ __global__ void returns_scan_kernel(const float* __restrict__ v_boot, const floa
       r[u] = rewards[i];
       m[u] = masks[i];
       v[u] = values[i];
+      if constexpr (TR) tr[u] = truncs[i];
     }
 #pragma unroll
     for (int u = 0; u < CH; ++u) {
@@ -62,12 +68,14 @@ __global__ void returns_scan_kernel(const float* __restrict__ v_boot, const floa
         const long i = (long)t * N + e;
         const double V = (double)v[u];
         if constexpr (EST == kEstGae) {
-          gae_step(gamma, gl, r[u], m[u], V, Vn, S);
+          if constexpr (TR) gae_step_tr(gamma, gl, r[u], m[u], tr[u], V, Vn, S);
+          else gae_step(gamma, gl, r[u], m[u], V, Vn, S);
           adv[i] = (float)S;
           y[i] = (float)__dadd_rn(S, V);
           Vn = V;
         } else {
-          nstep_step(gamma, t == T - 1, vb, r[u], m[u], S);
+          if constexpr (TR) nstep_step_tr(gamma, t == T - 1, vb, r[u], m[u], tr[u], V, S);
+          else nstep_step(gamma, t == T - 1, vb, r[u], m[u], S);
           y[i] = (float)S;
           adv[i] = (float)__dsub_rn(S, V);
         }
@@ -1288,19 +1296,22 @@ __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t 
   uint4 old = make_uint4(0u, 0u, 0u, 0u);
   typename G::State s;
   float r = 0.f;
-  bool term = false;
+  bool term = false, trunc = false;
   if (state_in) {
     // every thread loads (the four that own no quad read the band's first one): with the load under a condition the compiler
     // pulls the history's shift up behind it, and with the shift the wait -- the state record would be asked for only then
     old = reinterpret_cast<const uint4*>(stack_in)[t.load_quad];
-    s = G::advance(seed, env_offset + (uint32_t)e, G::load(state_in, e), actions[e], opt, &r, &term);
+    s = G::advance(seed, env_offset + (uint32_t)e, G::load(state_in, e), actions[e], opt, &r, &term, &trunc);
   } else {
     s = G::start(seed, env_offset + (uint32_t)e);
   }
   if (t.band == 0 && t.i == 0) {
     G::store(state_out, e, s);
     if (state_out2) G::store(state_out2, e, s);
-    if (state_in) env_bookkeep(r, term, e, rec.ep_reward[e], rec.ep_len[e], rec);
+    if (state_in) {
+      env_bookkeep(r, term, e, rec.ep_reward[e], rec.ep_len[e], rec);
+      if (rec.truncs) rec.truncs[e] = trunc ? 1.f : 0.f;     // --bootstrap_truncated: why the episode ended (game_dev.h)
+    }
   }
   if (!t.owner) return;
   const uint4 outv = G::shift_quad(s, t.q, old, term);     // a terminal step drops the history it loaded
@@ -1510,7 +1521,7 @@ __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __re
     }
     // (the sampler body ends past a barrier; its last wave is still writing the stream position back)
     if (env_step && (int)threadIdx.x < N)       // N <= 64 here: one environment per thread
-      synth_bookkeep_hashed(hr5, term0, e0, act_s[e0], ep_reward0, ep_len0, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, fin});
+      synth_bookkeep_hashed(hr5, term0, e0, act_s[e0], ep_reward0, ep_len0, StepRecords{rewards_out, masks_out, ep_reward, ep_len, fin});
     return;
   }
   if (raw) synth_raw_unit(seed, env_offset, id, (int)blockIdx.x - 1, raw);     // path B: the preprocess launch follows
@@ -2243,7 +2254,7 @@ int synth_step_of(const char* fn, const char* what, bool in_place_ok, SynthStep*
   PAAC_REQUIRE(in_place_ok || (stack_in != stack_out && stack_in != stack_out2), "%s: the step cannot shift the stacks in place",
                fn);
   *st = SynthStep{seed, env_offset, N, thresh, step_base, step_off, (const uint32_t*)stack_in, (uint32_t*)stack_out,
-                  (uint32_t*)stack_out2, EnvRecords{rewards, masks, ep_reward, ep_len, (FinishedRing*)finished},
+                  (uint32_t*)stack_out2, StepRecords{rewards, masks, ep_reward, ep_len, (FinishedRing*)finished},
                   (uint32_t*)raw_scratch};
   return 0;
 }
@@ -2264,9 +2275,12 @@ int launch_sample_env_step_heads(const HeadsPartials& hp, float* probs_out, int 
 
 // (arguments validated by paac_returns_norm_tick, csrc/api.hip)
 int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv_n, double* stats, hipStream_t s) {
-  const GaeArgs rt = returns_args(ret, v_boot);
-  if (ret->estimator == PAAC_RETURNS_GAE) {
-    launch_k(returns_norm_kernel<GaeArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rt, adv_n, stats);
+  const TruncArgs rt = returns_args(ret, v_boot);
+  if (rt.truncs) {
+    launch_k(returns_norm_kernel<TruncArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rt, adv_n, stats);
+  } else if (rt.gae) {
+    const GaeArgs& rg = rt;
+    launch_k(returns_norm_kernel<GaeArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rg, adv_n, stats);
   } else {
     const ReturnsArgs& rn = rt;
     launch_k(returns_norm_kernel<ReturnsArgs>, dim3(1), dim3(kNormThreads), s, PROF_WHOLE, rn, adv_n, stats);
@@ -2278,13 +2292,20 @@ int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv
 // the bookkeeping pointers): `name` is the entry point's, for the message.
 static int launch_returns_scan(const char* name, int estimator, const float* v_boot, const float* rewards, const float* masks,
                                const float* values, int T, int N, double gamma, double gae_lambda, float* y, float* adv,
-                               const CycleTick& ct, paac_stream_t stream) {
+                               const CycleTick& ct, paac_stream_t stream, const float* truncs = nullptr) {
   PAAC_REQUIRE(T > 0 && N > 0, "%s: T=%d N=%d", name, T, N);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(g_prof_ctx, F_NSTEP_RETURNS, N * T, s);
+  if (truncs) {       // --bootstrap_truncated: the truncation-aware scan (paac_returns_scan with a plane)
+    auto* kernel = estimator == kEstGae ? returns_scan_kernel<kEstGae, const float*> : returns_scan_kernel<kEstNstep, const float*>;
+    launch_k(kernel, dim3((N + 63) / 64), dim3(128), s, PROF_WHOLE, v_boot, rewards, masks, values, T, N, gamma,
+             gamma * gae_lambda, y, adv, ct, truncs);
+    PAAC_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   auto* kernel = estimator == kEstGae ? returns_scan_kernel<kEstGae> : returns_scan_kernel<kEstNstep>;
   launch_k(kernel, dim3((N + 63) / 64), dim3(128), s, PROF_WHOLE, v_boot, rewards, masks, values, T, N, gamma,
-           gamma * gae_lambda, y, adv, ct);
+           gamma * gae_lambda, y, adv, ct, NoPlane{});
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2372,6 +2393,24 @@ int paac_gae_returns_tick(const float* v_boot, const float* rewards, const float
   return launch_returns_scan("paac_gae_returns_tick", kEstGae, v_boot, rewards, masks, values, T, N, gamma, gae_lambda, y, adv,
                              CycleTick{global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_dev, tick_dev, tick_inc},
                              stream);
+}
+
+// The four entries above from the argument block (estimator and bookkeeping by its fields), with the truncation plane.
+int paac_returns_scan(const paac_returns* ret, paac_stream_t stream) {
+  PAAC_REQUIRE(ret && ret->v_boot && ret->rewards && ret->masks && ret->values && ret->y_out && ret->adv_out,
+               "paac_returns_scan: null argument");
+  PAAC_REQUIRE(returns_estimator(ret) == PAAC_RETURNS_NSTEP || returns_estimator(ret) == PAAC_RETURNS_GAE,
+               "paac_returns_scan: estimator %d (PAAC_RETURNS_NSTEP = 0, PAAC_RETURNS_GAE = 1)", returns_estimator(ret));
+  PAAC_REQUIRE(ret->gae_lambda >= 0.0 && ret->gae_lambda <= 1.0, "paac_returns_scan: gae_lambda %g outside [0, 1]",
+               ret->gae_lambda);
+  PAAC_REQUIRE(!ret->global_step_dev || (ret->lr_out_dev && ret->lr_annealing_steps > 0),
+               "paac_returns_scan: schedule bookkeeping needs lr_out_dev and lr_annealing_steps");
+  const CycleTick ct{ret->global_step_dev, ret->increment, ret->initial_lr, ret->lr_annealing_steps, ret->lr_out_dev,
+                     ret->tick_dev, ret->tick_inc};
+  const bool gae = returns_estimator(ret) == PAAC_RETURNS_GAE;
+  return launch_returns_scan("paac_returns_scan", gae ? kEstGae : kEstNstep, ret->v_boot, ret->rewards, ret->masks, ret->values,
+                             ret->T, ret->N, ret->gamma, gae ? ret->gae_lambda : 0.0, ret->y_out, ret->adv_out, ct, stream,
+                             returns_truncs(ret));
 }
 
 int paac_adv_normalize(const float* adv, int B, float* adv_n_out, double* stats_out, paac_stream_t stream) {
@@ -2562,7 +2601,7 @@ int paac_catch_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                     paac_stream_t stream) {
   return game_step<CatchGame>("paac_catch_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
-                   stack_out2, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, 0, stream);
+                   stack_out2, EnvRecords{{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, nullptr}, 0, stream);
 }
 
 int paac_bricks_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
@@ -2575,7 +2614,7 @@ int paac_bricks_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* a
                      float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished, int single_life,
                      paac_stream_t stream) {
   return game_step<BricksGame>("paac_bricks_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
-                    stack_out2, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, single_life, stream);
+                    stack_out2, EnvRecords{{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, nullptr}, single_life, stream);
 }
 
 int paac_rally_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
@@ -2588,7 +2627,26 @@ int paac_rally_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len, void* finished,
                     paac_stream_t stream) {
   return game_step<RallyGame>("paac_rally_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
-                   stack_out2, EnvRecords{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, 0, stream);
+                   stack_out2, EnvRecords{{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, nullptr}, 0, stream);
+}
+
+// paac_<game>_step by the game's id, with the records as one block -- the truncation plane among them.
+int paac_game_step(int game, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                   int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                   const paac_env_records* rec, int option, paac_stream_t stream) {
+  PAAC_REQUIRE(game == PAAC_EVAL_CATCH || game == PAAC_EVAL_BRICKS || game == PAAC_EVAL_RALLY,
+               "paac_game_step: game %d is none of catch (%d), bricks (%d), rally (%d)", game, PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS,
+               PAAC_EVAL_RALLY);
+  PAAC_REQUIRE(rec, "paac_game_step: null records");
+  const EnvRecords r{{rec->rewards, rec->masks, rec->ep_reward, rec->ep_len, (FinishedRing*)rec->finished}, rec->truncs};
+  if (game == PAAC_EVAL_CATCH)
+    return game_step<CatchGame>("paac_game_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
+                                stack_out, stack_out2, r, 0, stream);
+  if (game == PAAC_EVAL_BRICKS)
+    return game_step<BricksGame>("paac_game_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
+                                 stack_out, stack_out2, r, option, stream);
+  return game_step<RallyGame>("paac_game_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
+                              stack_out, stack_out2, r, 0, stream);
 }
 
 int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,

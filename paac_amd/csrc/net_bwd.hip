@@ -270,12 +270,17 @@ static WithPpo<Base> with_ppo(const Base& base, const PpoArgs& ppo) {
   return ra;
 }
 template <class Go>
-static void launch_ppo_heads(Go&& go, int loss, int estimator, const GaeArgs& rt, const PpoArgs& ppo, const VclipArgs& vc) {
+static void launch_ppo_heads(Go&& go, int loss, int estimator, const TruncArgs& rt, const PpoArgs& ppo, const VclipArgs& vc) {
   const ReturnsArgs& rtn = rt;
+  const GaeArgs& rtg = rt;
   const bool gae = estimator == kEstGae;
-  if (loss == kLossA3c && gae) return go(Int<kEstGae>{}, Int<kLossA3c>{}, rt);
+  // --bootstrap_truncated: a truncation plane takes the two cells that compute returns to their kEstTrunc instantiations (either
+  // estimator); without one every cell below is launched with the block it always had
+  if (loss == kLossA3c && rt.truncs) return go(Int<kEstTrunc>{}, Int<kLossA3c>{}, rt);
+  if (loss == kLossA3cRecord && rt.truncs) return go(Int<kEstTrunc>{}, Int<kLossA3cRecord>{}, with_ppo(rt, ppo));
+  if (loss == kLossA3c && gae) return go(Int<kEstGae>{}, Int<kLossA3c>{}, rtg);
   if (loss == kLossA3c) return go(Int<kEstNstep>{}, Int<kLossA3c>{}, rtn);
-  if (loss == kLossA3cRecord && gae) return go(Int<kEstGae>{}, Int<kLossA3cRecord>{}, with_ppo(rt, ppo));
+  if (loss == kLossA3cRecord && gae) return go(Int<kEstGae>{}, Int<kLossA3cRecord>{}, with_ppo(rtg, ppo));
   if (loss == kLossA3cRecord) return go(Int<kEstNstep>{}, Int<kLossA3cRecord>{}, with_ppo(rtn, ppo));
   if (loss == kLossPpo) return go(Int<kEstNstep>{}, Int<kLossPpo>{}, with_ppo(rtn, ppo));
   WithVclip<ReturnsArgs> ra;
@@ -287,7 +292,7 @@ static void launch_ppo_heads(Go&& go, int loss, int estimator, const GaeArgs& rt
 template <class NT>
 static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions,
                          const float* y, const float* adv, int batch, float beta, float* grad, float* loss_out,
-                         int phase, const GaeArgs& rt, int estimator, int loss, const PpoArgs& ppo, const VclipArgs& vc,
+                         int phase, const TruncArgs& rt, int estimator, int loss, const PpoArgs& ppo, const VclipArgs& vc,
                          float* ppo_stats_out, hipStream_t s) {
   const paac_layout& L = ctx->layout;
   Workspace& W = ctx->ws[1];
@@ -316,7 +321,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
       if (rc) return rc;
     }
   }
-  GaeArgs rtl = rt;
+  TruncArgs rtl = rt;
   if (rtl.boot_in_fwd && !fused_heads) {       // the separate heads launch has produced the bootstrap rows' values
     rtl.v_boot = W.values + batch;
     rtl.boot_in_fwd = 0;
@@ -629,8 +634,8 @@ int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, c
   ppo.clip_eps = c.clip_eps;
   ppo.stat_rows = ctx->ppo_rows;
   const paac_returns* ret = c.ret;
-  const GaeArgs rt = returns_args(ret, ret ? ret->v_boot : nullptr);
-  const int estimator = ret ? ret->estimator : kEstNstep;      // (validated by paac_loss_backward_returns)
+  const TruncArgs rt = returns_args(ret, ret ? ret->v_boot : nullptr);
+  const int estimator = ret ? returns_estimator(ret) : kEstNstep;      // (validated by paac_loss_backward_returns)
   const float* y = ret ? ret->y_out : c.y;                     // (in-launch returns land in the record's arrays)
   const float* adv = ret ? ret->adv_out : c.adv;
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)

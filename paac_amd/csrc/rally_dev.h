@@ -85,8 +85,9 @@ struct RallyGame {
   // function of its arguments: the state the next step starts from (the next episode's start state after a terminal step), the
   // reward and the terminal flag.  Everything here is the same for all threads of a workgroup (one environment per workgroup
   // column): the branches and the opponent's look-ahead loop, of at most RALLY_REACT_ROW iterations, are uniform.
+  // *trunc: the step is terminal only because steps reached the cap (neither side reached RALLY_POINTS on it).
   static __device__ __forceinline__ State advance(uint64_t seed, uint32_t env, State s, int a, int /*opt*/, float* reward,
-                                                  bool* term) {
+                                                  bool* term, bool* trunc = nullptr) {
     const uint32_t h = synth_key(seed, env, (uint64_t)(uint32_t)s.k);
     if (a == 2 || a == 4) s.px = min(s.px + 1, RALLY_CELLS - 2);
     else if (a == 3 || a == 5) s.px = max(s.px - 1, 0);
@@ -130,7 +131,9 @@ struct RallyGame {
     s.bx = nx;
     s.by = ny;
     s.steps += 1;
-    const bool over = s.mine == RALLY_POINTS || s.theirs == RALLY_POINTS || s.steps == RALLY_MAX_STEPS;
+    const bool decided = s.mine == RALLY_POINTS || s.theirs == RALLY_POINTS;
+    const bool over = decided || s.steps == RALLY_MAX_STEPS;
+    if (trunc) *trunc = !decided && s.steps == RALLY_MAX_STEPS;
     *reward = r;
     *term = over;
     if (over) return start(seed, env, s.k + 1);

@@ -27,10 +27,16 @@ struct FinishedRing {
 
 // What a step records per environment: clipped reward and continuation mask of this step, the running episode totals, the
 // ring of finished episodes (nullable).
-struct EnvRecords {
+struct StepRecords {
   float *rewards, *masks, *ep_reward;
   int32_t* ep_len;
   FinishedRing* fin;
+};
+// ... and, for the device games' step (game_step_kernel), the truncation plane of --bootstrap_truncated beside them
+// (nullable: nothing is written, nothing is read).  The synthetic step never truncates: SynthStep carries the block above,
+// and the kernels that take one keep their arguments.
+struct EnvRecords : StepRecords {
+  float* truncs;   // [N] for the step; 1.f truncated, 0.f otherwise
 };
 
 // One step of N synthetic environments: the generator's key (seed, first global environment, step id = *step_base + step_off
@@ -45,7 +51,7 @@ struct SynthStep {
   uint64_t step_off;
   const uint32_t* stack_in;
   uint32_t *stack_out, *stack_out2;
-  EnvRecords rec;
+  StepRecords rec;
   uint32_t* raw;
   __host__ __device__ bool active() const { return rec.rewards != nullptr; }
   __device__ uint64_t id() const { return (step_base ? *step_base : 0ull) + step_off + 1ull; }
@@ -58,7 +64,7 @@ struct SynthStep {
 __device__ __forceinline__ uint32_t synth_reward_slot(uint32_t key) { return lowbias32(key ^ 0xA511E9B3u) % 5u; }
 __device__ __forceinline__ bool synth_terminal(uint32_t key, uint32_t thresh) { return lowbias32(key ^ 0x3C6EF372u) < thresh; }
 // env_bookkeep: the same records for a step whose unclipped reward r and terminal flag are already known (csrc/catch_dev.h).
-__device__ __forceinline__ bool env_bookkeep(float r, bool term, int e, float ep_reward0, int32_t ep_len0, const EnvRecords& rec) {
+__device__ __forceinline__ bool env_bookkeep(float r, bool term, int e, float ep_reward0, int32_t ep_len0, const StepRecords& rec) {
   rec.rewards[e] = fminf(fmaxf(r, -1.f), 1.f);   // actor_learner.py:95-101
   rec.masks[e] = term ? 0.f : 1.f;               // paac.py:119
   const float tot = ep_reward0 + r;
@@ -78,16 +84,16 @@ __device__ __forceinline__ bool env_bookkeep(float r, bool term, int e, float ep
   return term;
 }
 __device__ __forceinline__ bool synth_bookkeep_hashed(uint32_t hr5, bool term, int e, int act, float ep_reward0,
-                                                      int32_t ep_len0, const EnvRecords& rec) {
+                                                      int32_t ep_len0, const StepRecords& rec) {
   const float table[5] = {-2.f, 0.f, 0.f, 1.f, 3.f};
   return env_bookkeep(table[(hr5 + (uint32_t)act) % 5u], term, e, ep_reward0, ep_len0, rec);
 }
 __device__ __forceinline__ bool synth_bookkeep_with(uint32_t key, int e, int act, uint32_t thresh, float ep_reward0,
-                                                    int32_t ep_len0, const EnvRecords& rec) {
+                                                    int32_t ep_len0, const StepRecords& rec) {
   return synth_bookkeep_hashed(synth_reward_slot(key), synth_terminal(key, thresh), e, act, ep_reward0, ep_len0, rec);
 }
 __device__ __forceinline__ bool synth_bookkeep(uint32_t key, int e, const int32_t* actions, uint32_t thresh,
-                                               const EnvRecords& rec) {
+                                               const StepRecords& rec) {
   return synth_bookkeep_with(key, e, actions ? actions[e] : 0, thresh, rec.ep_reward[e], rec.ep_len[e], rec);
 }
 

@@ -225,17 +225,18 @@ class Context(object):
     def loss_backward_returns(self, params, states, actions, v_boot, rewards, masks, values, gamma, y_out, adv_out,
                               entropy_beta, grad, loss_out=None, forward_done=False, phase=0, global_step_dev=None,
                               increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None, tick_dev=None, tick_inc=0,
-                              gae_lambda=None, p_old_out=None):
+                              gae_lambda=None, p_old_out=None, truncs=None):
         """n-step returns (+ the cycle's schedule bookkeeping) inside the backward's first launch
         (include/paac_hip.h: paac_loss_backward_returns) == nstep_returns_tick followed by loss_backward.
         v_boot=None: the bootstrap values are rows [B, B + N) of the training forward that has already run.
         gae_lambda: None or 1.0 = the n-step return; anything else = GAE(lambda) instead (uses_gae).
-        p_old_out: float32[B], also receives p_old (epoch 1 of a --ppo_epochs cycle); gradient and loss are unchanged."""
+        p_old_out: float32[B], also receives p_old (epoch 1 of a --ppo_epochs cycle); gradient and loss are unchanged.
+        truncs: float32[T,N] truncation plane of --bootstrap_truncated (include/paac_hip.h: paac_returns); None = off."""
         T, N = rewards.shape
         if T * N != states.shape[0]:
             raise ValueError("rollout records are [%d,%d] but the batch has %d rows" % (T, N, states.shape[0]))
         ret = _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
-                              lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda)
+                              lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda, truncs)
         record = p_old_out is not None          # include/paac_hip.h: paac_loss_backward_returns_record
         self._loss_backward("paac_loss_backward_returns_record" if record else "paac_loss_backward_returns", params, states,
                             actions, (ctypes.byref(ret),) + ((("p_old_out", p_old_out),) if record else ()),
@@ -288,14 +289,14 @@ class Context(object):
 
     def returns_norm_tick(self, params, v_boot, rewards, masks, values, gamma, y_out, adv_out, adv_n_out, stats_out=None,
                           global_step_dev=None, increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None,
-                          tick_dev=None, tick_inc=0, gae_lambda=None):
+                          tick_dev=None, tick_inc=0, gae_lambda=None, truncs=None):
         """Returns of either estimator + the cycle's schedule bookkeeping + --adv_norm's normalisation in one launch
         (include/paac_hip.h: paac_returns_norm_tick).  v_boot=None: the bootstrap values are rows [T*N, T*N + N) of the
         training forward that has already run on this ctx (the heads of those rows are finished here when they are pending).
-        stats_out: float64[2] = {mean, std}."""
+        stats_out: float64[2] = {mean, std}.  truncs: the truncation plane of --bootstrap_truncated, None = off."""
         T, N = rewards.shape
         ret = _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
-                              lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda)
+                              lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda, truncs)
         _lib.check(self.lib.paac_returns_norm_tick(
             self.handle, _ptr(params, torch.float32, self.layout["total"], "params"), ctypes.byref(ret),
             _ptr(adv_n_out, torch.float32, T * N, "adv_n_out"), _ptr(stats_out, torch.float64, 2, "stats_out", True), _stream()),
@@ -490,9 +491,11 @@ def lr_step(global_step_dev, increment, initial_lr, lr_annealing_steps, lr_out_d
 
 
 def _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
-                    lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda):
+                    lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda, truncs=None):
     T, N = rewards.shape
-    return _lib.Returns(
+    if truncs is not None and tuple(truncs.shape) != (T, N):
+        raise ValueError("truncs must be [%d,%d] like the rewards, got %s" % (T, N, tuple(truncs.shape)))
+    fields = dict(
         v_boot=_ptr(v_boot, torch.float32, N, "v_boot", True), rewards=_ptr(rewards, torch.float32, T * N, "rewards"),
         masks=_ptr(masks, torch.float32, T * N, "masks"), values=_ptr(values, torch.float32, T * N, "values"), T=T, N=N,
         gamma=float(gamma), y_out=_ptr(y_out, torch.float32, T * N, "y_out"), adv_out=_ptr(adv_out, torch.float32, T * N, "adv_out"),
@@ -502,6 +505,12 @@ def _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, globa
         tick_dev=_ptr(tick_dev, torch.int64, 1, "tick", True), tick_inc=int(tick_inc),
         estimator=_lib.RETURNS_GAE if uses_gae(gae_lambda) else _lib.RETURNS_NSTEP,
         gae_lambda=float(gae_lambda) if uses_gae(gae_lambda) else 0.0)
+    if truncs is None:
+        return _lib.Returns(**fields)
+    # the plane travels behind the block (include/paac_hip.h: paac_returns_truncs): the entries get the `ret` member, which
+    # keeps the whole record alive
+    fields["estimator"] |= _lib.RETURNS_TRUNCS
+    return _lib.ReturnsTruncs(_lib.Returns(**fields), _ptr(truncs, torch.float32, T * N, "truncs")).ret
 
 
 def adv_normalize(adv, adv_n_out, stats_out=None):
@@ -515,12 +524,12 @@ def adv_normalize(adv, adv_n_out, stats_out=None):
 
 def returns_norm_tick(v_boot, rewards, masks, values, gamma, y_out, adv_out, adv_n_out, stats_out=None, global_step_dev=None,
                       increment=0, initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None, tick_dev=None, tick_inc=0,
-                      gae_lambda=None):
+                      gae_lambda=None, truncs=None):
     """paac_returns_norm_tick with the bootstrap values given (no ctx): == nstep_returns_tick / gae_returns_tick followed by
-    adv_normalize, in one launch."""
+    adv_normalize, in one launch.  truncs: the truncation plane of --bootstrap_truncated, None = off."""
     T, N = rewards.shape
     ret = _returns_struct(v_boot, rewards, masks, values, gamma, y_out, adv_out, global_step_dev, increment, initial_lr,
-                          lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda)
+                          lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda, truncs)
     if not ret.v_boot:
         raise ValueError("returns_norm_tick: v_boot is required without a ctx (Context.returns_norm_tick takes it from the "
                          "training forward)")
@@ -536,17 +545,39 @@ def uses_gae(gae_lambda):
     return gae_lambda is not None and float(gae_lambda) != 1.0
 
 
-def returns(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None):
-    """nstep_returns or gae_returns by the routing rule (uses_gae)."""
-    if uses_gae(gae_lambda):
+def returns_scan(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None, truncs=None, global_step_dev=None, increment=0,
+                 initial_lr=0.0, lr_annealing_steps=1, lr_out_dev=None, tick_dev=None, tick_inc=0, estimator=None):
+    """The standalone scan from the argument block (include/paac_hip.h: paac_returns_scan): the estimator by the routing rule
+    (uses_gae), the _tick entries' bookkeeping when global_step_dev is given, and the truncation plane of
+    --bootstrap_truncated (float32[T,N]; None runs the plain kernels).  estimator="gae": GAE whatever the rule says (GAE(1),
+    which gae_returns also accepts)."""
+    if v_boot is None:
+        raise ValueError("returns_scan: v_boot is required")
+    ret = _returns_struct(v_boot, rewards, masks, values, gamma, y, adv, global_step_dev, increment, initial_lr,
+                          lr_annealing_steps, lr_out_dev, tick_dev, tick_inc, gae_lambda, truncs)
+    if estimator == "gae":
+        ret.estimator = (ret.estimator & _lib.RETURNS_TRUNCS) | _lib.RETURNS_GAE
+        ret.gae_lambda = float(gae_lambda)
+    elif estimator is not None:
+        raise ValueError("returns_scan: estimator %r (None or 'gae')" % (estimator,))
+    _lib.check(_lib.load().paac_returns_scan(ctypes.byref(ret), _stream()), "paac_returns_scan")
+
+
+def returns(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None, truncs=None):
+    """nstep_returns or gae_returns by the routing rule (uses_gae); with a truncation plane, returns_scan."""
+    if truncs is not None:
+        returns_scan(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda, truncs)
+    elif uses_gae(gae_lambda):
         gae_returns(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv)
     else:
         nstep_returns(v_boot, rewards, masks, values, gamma, y, adv)
 
 
-def returns_tick(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None, **tick):
+def returns_tick(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda=None, truncs=None, **tick):
     """nstep_returns_tick or gae_returns_tick by the same rule; tick: their bookkeeping keyword arguments."""
-    if uses_gae(gae_lambda):
+    if truncs is not None:
+        returns_scan(v_boot, rewards, masks, values, gamma, y, adv, gae_lambda, truncs, **tick)
+    elif uses_gae(gae_lambda):
         gae_returns_tick(v_boot, rewards, masks, values, gamma, gae_lambda, y, adv, **tick)
     else:
         nstep_returns_tick(v_boot, rewards, masks, values, gamma, y, adv, **tick)
@@ -753,9 +784,34 @@ def game_reset(kind, seed, env_offset, state_out, stack_out):
     _stateful_reset("paac_%s_reset" % kind, DEVICE_GAMES[kind]["words"], seed, env_offset, state_out, stack_out)
 
 
+def game_step_records(kind, seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward,
+                      ep_len, finished=None, stack_out2=None, state_out2=None, truncs_out=None, **option):
+    """paac_game_step (include/paac_hip.h): game_step by the game's id with the records as one block, truncs_out float32[N]
+    (--bootstrap_truncated: 1 where the step ended its episode at the step cap alone; None: not written) among them."""
+    game = DEVICE_GAMES[kind]
+    name, words = game["step_option"], game["words"]
+    if set(option) - {name}:
+        raise TypeError("%s_step: unexpected keyword arguments %s" % (kind, sorted(set(option) - {name})))
+    N = actions.shape[0]
+    out, out2, *records = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
+    for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
+        if t is not None and tuple(t.shape) != (N, words):
+            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
+    rec = _lib.EnvRecords(*records, _ptr(truncs_out, torch.float32, N, "truncs_out", True))
+    _lib.check(_lib.load().paac_game_step(
+        game["eval_id"], int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
+        _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
+        _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), out, out2,
+        ctypes.byref(rec), int(bool(option.get(name, False))) if name else 0, _stream()), "paac_game_step")
+
+
 def game_step(kind, seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
-              finished=None, stack_out2=None, state_out2=None, **option):
-    """`option`: the game's step option by its keyword (DEVICE_GAMES: bricks' single_life, False if not given)."""
+              finished=None, stack_out2=None, state_out2=None, truncs_out=None, **option):
+    """`option`: the game's step option by its keyword (DEVICE_GAMES: bricks' single_life, False if not given).  truncs_out: the
+    step goes through game_step_records, which writes the truncation plane; None is the game's own entry, as always."""
+    if truncs_out is not None:
+        return game_step_records(kind, seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out,
+                                 ep_reward, ep_len, finished, stack_out2, state_out2, truncs_out, **option)
     game = DEVICE_GAMES[kind]
     name = game["step_option"]
     if set(option) - {name}:

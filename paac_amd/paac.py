@@ -21,26 +21,30 @@ import torch
 
 from . import hip_ops, logger_utils, parallel
 from .actor_learner import ActorLearner
-from .runners import EmulatorRunner, RawEmulatorRunner, Runners
+from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Runners
 
 
 # Device environments that carry a state record from step to step, by env_spec["kind"]: int32 words of a record and the reset
 # and step wrappers (one argument list, catch's) from hip_ops.DEVICE_GAMES, the keys of the spec the step wrapper takes as
-# keyword arguments, and the longest episode of the game in steps (what bounds an evaluation: paac_amd/evaluation.py).
-def _stateful_kind(kind, spec_kwargs, max_episode_steps):
+# keyword arguments, the longest episode of the game in steps (what bounds an evaluation: paac_amd/evaluation.py), and whether
+# that length is a step cap the game can be cut off at (--bootstrap_truncated: the step then records a truncation plane) or
+# the game's own rule (catch).
+def _stateful_kind(kind, spec_kwargs, max_episode_steps, truncates):
     return dict(words=hip_ops.DEVICE_GAMES[kind]["words"], reset=functools.partial(hip_ops.game_reset, kind),
-                step=functools.partial(hip_ops.game_step, kind), spec_kwargs=spec_kwargs, max_episode_steps=max_episode_steps)
+                step=functools.partial(hip_ops.game_step, kind), spec_kwargs=spec_kwargs, max_episode_steps=max_episode_steps,
+                truncates=truncates)
 
 
 STATEFUL_KINDS = {
-    "catch": _stateful_kind("catch", (), 13),
-    "bricks": _stateful_kind("bricks", ("single_life",), 500),
-    "rally": _stateful_kind("rally", (), 1000),
+    "catch": _stateful_kind("catch", (), 13, False),
+    "bricks": _stateful_kind("bricks", ("single_life",), 500, True),
+    "rally": _stateful_kind("rally", (), 1000, True),
 }
 
 
 class DeviceRollout(object):
     """Device-resident rollout/update cycle for N local environments x T steps."""
+    truncs = None      # --bootstrap_truncated: the [T, N] truncation plane, allocated by __init__ only where it applies
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
                  total_envs=None):
@@ -86,6 +90,11 @@ class DeviceRollout(object):
         if self.stateful:
             self.env_state = torch.zeros((2 * T + 1, N, self.stateful["words"]), dtype=torch.int32, device=dev)
             self.env_step_kwargs = {k: env_spec[k] for k in self.stateful["spec_kwargs"]}
+        # --bootstrap_truncated: the truncation plane beside rewards and masks -- step t writes row t, whatever computes the
+        # cycle's returns reads it.  Only with the flag on and a game that has a step cap: otherwise no plane exists, the step
+        # goes through the game's own entry and every returns launch is the one it always was.  Shard-local, like the masks.
+        if getattr(L, "bootstrap_truncated", False) and self.stateful and self.stateful["truncates"]:
+            self.truncs = torch.zeros((T, N), dtype=torch.float32, device=dev)
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
         if env_spec.get("raw_frames"):
@@ -211,6 +220,7 @@ class DeviceRollout(object):
             if route == "stateful":
                 self.stateful["step"](seed, self.env_offset, self.actions[t], self.env_state[slot], self.env_state[slot + 1], obs,
                                       nxt, *records, stack_out2=wrap, state_out2=self.env_state[0] if wrap is not None else None,
+                                      **(dict(truncs_out=self.truncs[t]) if self.truncs is not None else {}),
                                       **self.env_step_kwargs)
             elif route == "fused":
                 hip_ops.sample_mt_synth_step(self.probs, self.mt_state, self.actions[t], seed, self.env_offset,
@@ -242,7 +252,7 @@ class DeviceRollout(object):
             # heads of the bootstrap rows, then returns + statistics + normalisation + the cycle's bookkeeping in one launch,
             # then the backward on (y, adv_n); the rollout rows' heads still ride in the backward's first launch
             L.ctx.returns_norm_tick(params, None, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
-                                    L.adv_stats, gae_lambda=L.gae_lambda, **self.cycle_tick)
+                                    L.adv_stats, gae_lambda=L.gae_lambda, truncs=self.truncs, **self.cycle_tick)
             L.ctx.loss_backward(params, self.rollout_states(parity), self.actions.view(-1), self.y, L.adv_n, L.entropy_beta,
                                 L.grad, L.loss_dev, forward_done=True, phase=phase, p_old_out=L.p_old if self.K > 1 else None)
             if L.vclip_on:
@@ -256,7 +266,7 @@ class DeviceRollout(object):
         L.ctx.loss_backward_returns(params, self.rollout_states(parity), self.actions.view(-1), None, self.rewards,
                                     self.masks, self.values, L.gamma, self.y, self.adv, L.entropy_beta, L.grad,
                                     L.loss_dev, forward_done=True, phase=phase, gae_lambda=L.gae_lambda,
-                                    p_old_out=L.p_old if self.K > 1 else None, **self.cycle_tick)
+                                    p_old_out=L.p_old if self.K > 1 else None, truncs=self.truncs, **self.cycle_tick)
         if L.vclip_on:         # --ppo_vclip: v_old = the values epoch 1's heads just computed (one captured copy)
             L.ctx.train_values_into(L.v_old, T * N)
 
@@ -271,10 +281,10 @@ class DeviceRollout(object):
         v_boot = L.v_rec[B:]
         if L.adv_norm:
             hip_ops.returns_norm_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
-                                      L.adv_stats, gae_lambda=L.gae_lambda, **self.cycle_tick)
+                                      L.adv_stats, gae_lambda=L.gae_lambda, truncs=self.truncs, **self.cycle_tick)
         else:
             hip_ops.returns_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.gae_lambda,
-                                 **self.cycle_tick)
+                                 truncs=self.truncs, **self.cycle_tick)
         L.minibatch_perms(self.sampler_seed, self.tick)
         L.minibatch_step_backward(0, self.rollout_states(parity), self.actions.view(-1), self.y, self.actor_adv, phase)
 
@@ -393,7 +403,7 @@ class DeviceRollout(object):
               if t is not None]
         if L.minibatch_on:      # (the staging block of states is rewritten by every epoch's gather before anything reads it)
             ts += [L.v_rec] + [t for k, t in L.mb.items() if t is not None and k != "states"]
-        for name in ("raw", "walk_scratch", "mt_state", "env_state"):
+        for name in ("raw", "walk_scratch", "mt_state", "env_state", "truncs"):
             t = getattr(self, name, None)
             if t is not None:
                 ts.append(t)
@@ -589,12 +599,33 @@ class PAACLearner(ActorLearner):
         self.rollout = None
         self.metrics = None
         self.stop_requested = False      # set by the signal handler (train.py); honoured at the next cycle boundary
+        self.host_truncated_steps = None   # host loop under --bootstrap_truncated: ones in the last rollout's truncation plane
 
     def _open_metrics(self):
         """metrics.jsonl in the debugging folder (rank 0 only): what the reference sends to TensorBoard."""
         if self.metrics is None and parallel.rank() == 0 and getattr(self.args, "metrics", True):
             self.metrics = logger_utils.MetricsWriter(self.debugging_folder)
         return self.metrics
+
+    def truncated_steps(self):
+        """--bootstrap_truncated: the number of ones in the last rollout's truncation plane (this rank's); None when no plane
+        exists -- the flag is off, or the environments have no step cap to report."""
+        if self.rollout is not None and self.rollout.truncs is not None:
+            return int(self.rollout.truncs.sum().item())
+        return self.host_truncated_steps
+
+    def _truncation_applies(self):
+        """Whether --bootstrap_truncated has anything to act on; logs the one line that says so when it has not."""
+        if not self.bootstrap_truncated:
+            return False
+        if self._use_device_envs():
+            kind = STATEFUL_KINDS.get(self.environment_creator.device_env_spec.get("kind", "synthetic"))
+            on = bool(kind and kind["truncates"])
+        else:
+            on = any(hasattr(e, TRUNCATED_ATTRIBUTE) for e in self.emulators)
+        if not on:
+            logging.info("--bootstrap_truncated true does nothing here: these environments report no step-cap endings")
+        return on
 
     def _progress_record(self, steps_per_s, steps_per_s_avg, last_ten):
         if self.metrics is None:
@@ -611,7 +642,8 @@ class PAACLearner(ActorLearner):
                            steps_per_s_avg=float(steps_per_s_avg), last_10_rewards_avg=float(last_ten),
                            lr=float(self.lr_dev.item()), grad_norm=float(self.gnorm_dev.item()), loss=float(loss[0]),
                            actor_loss=float(loss[1]), critic_loss=float(loss[2]), entropy=float(loss[3]),
-                           **(dict(ppo_steps_applied=int(applied.sum())) if applied is not None else {}))
+                           **(dict(ppo_steps_applied=int(applied.sum())) if applied is not None else {}),
+                           **(dict(truncated_steps=self.truncated_steps()) if self.truncated_steps() is not None else {}))
         if self.ppo_epochs > 1:          # one record per epoch of the last cycle (epoch 1: the update above, ratio == 1)
             losses, stats = self.ppo_loss.cpu().numpy(), self.ppo_stats.cpu().numpy()
             if not self.minibatch_on:
@@ -663,6 +695,7 @@ class PAACLearner(ActorLearner):
         """Main actor learner loop for parallel advantage actor critic learning (paac.py:59-183)."""
         self.global_step = self.init_network()
         logging.debug("Starting training at Step {}".format(self.global_step))
+        self.truncation_on = self._truncation_applies()
         if self._use_device_envs():
             self._train_device()
         else:
@@ -787,6 +820,9 @@ class PAACLearner(ActorLearner):
         global_step_start = self.global_step
         total_rewards = []
         raw_mode = bool(getattr(self.args, "device_preprocess", False))
+        # --bootstrap_truncated: one more shared array carries the last step's truncation flags (runners.py), one more [T, N]
+        # plane travels to the device with the masks; off, nothing below exists
+        truncation_on = getattr(self, "truncation_on", False)
         if raw_mode:
             # environments hand out raw screen pairs; observations are built on the GPU (DeviceObservations)
             if not all(hasattr(e, "next_raw") and hasattr(e, "initial_raw") for e in self.emulators):
@@ -794,10 +830,11 @@ class PAACLearner(ActorLearner):
             first = np.stack([emulator.initial_raw() for emulator in self.emulators]).astype(np.uint8)
             variables = [first, np.full(N, first.shape[1], dtype=np.float32), np.zeros(N, dtype=np.float32),
                          np.asarray([False] * N, dtype=np.float32), np.zeros((N, A), dtype=np.float32)]
+            variables += [np.zeros(N, dtype=np.float32)] if truncation_on else []
             self.runners = Runners(RawEmulatorRunner, self.emulators, self.workers, variables)
             self.runners.start()
             shared_raw, shared_counts, shared_rewards, shared_episode_over, shared_actions = \
-                self.runners.get_shared_variables()
+                self.runners.get_shared_variables()[:5]
             observations = DeviceObservations(N, first.shape[1], dev)
             observations.update(shared_raw, shared_counts)
             current_states = lambda: observations.current
@@ -806,15 +843,19 @@ class PAACLearner(ActorLearner):
                          (np.zeros(N, dtype=np.float32)),
                          (np.asarray([False] * N, dtype=np.float32)),
                          (np.zeros((N, A), dtype=np.float32))]
+            variables += [np.zeros(N, dtype=np.float32)] if truncation_on else []
             self.runners = Runners(EmulatorRunner, self.emulators, self.workers, variables)
             self.runners.start()
-            shared_states, shared_rewards, shared_episode_over, shared_actions = self.runners.get_shared_variables()
+            shared_states, shared_rewards, shared_episode_over, shared_actions = self.runners.get_shared_variables()[:4]
             host_states = torch.from_numpy(shared_states)
             # page-lock the shared observation array in place: the per-step H2D is then one DMA straight out of the
             # memory the emulator workers write, instead of a staged pageable copy
             pinned = hip_ops.pin_host_array(host_states)
             current_states = lambda: host_states
 
+        shared_truncs = self.runners.get_shared_variables()[-1] if truncation_on else None
+        truncs = np.zeros((T, N), dtype=np.float32) if truncation_on else None
+        d_truncs = torch.zeros((T, N), dtype=torch.float32, device=dev) if truncation_on else None
         emulator_steps = np.zeros(N, dtype=np.int64)
         total_episode_rewards = np.zeros(N, dtype=np.float64)
         d_states = torch.zeros((T, N, 84, 84, 4), dtype=torch.uint8, device=dev)
@@ -848,10 +889,12 @@ class PAACLearner(ActorLearner):
 
         stock_rescale = type(self).rescale_reward is ActorLearner.rescale_reward
 
-        def bookkeeping(t, step_rewards, step_overs):
+        def bookkeeping(t, step_rewards, step_overs, step_truncs=None):
             """paac.py:119-138 for one step, vectorised over the environments that did not end an episode; the finished
             ones are visited in index order with the global_step the reference's per-environment loop would show them."""
             masks[t] = 1.0 - step_overs
+            if step_truncs is not None:
+                truncs[t] = step_truncs
             total_episode_rewards[:] += step_rewards
             if stock_rescale:
                 rewards[t] = np.clip(step_rewards, -1.0, 1.0)      # rescale_reward, actor_learner.py:95-101
@@ -926,13 +969,17 @@ class PAACLearner(ActorLearner):
                 self.runners.wait_updated()
                 if raw_mode:
                     observations.update(shared_raw, shared_counts)
-                pending = (t, shared_rewards.astype(np.float32), shared_episode_over.astype(np.float32))
+                pending = (t, shared_rewards.astype(np.float32), shared_episode_over.astype(np.float32),
+                           shared_truncs.astype(np.float32) if truncation_on else None)
             bookkeeping(*pending)
             d_cur.copy_(current_states())
             self.ctx.forward(params, d_cur, values=d_vboot)
             d_rewards.copy_(torch.from_numpy(rewards))
             d_masks.copy_(torch.from_numpy(masks))
-            hip_ops.returns(d_vboot, d_rewards, d_masks, d_values, self.gamma, d_y, d_adv, self.gae_lambda)
+            if truncation_on:
+                d_truncs.copy_(torch.from_numpy(truncs))
+                self.host_truncated_steps = int(truncs.sum())
+            hip_ops.returns(d_vboot, d_rewards, d_masks, d_values, self.gamma, d_y, d_adv, self.gae_lambda, truncs=d_truncs)
             d_actor_adv = d_adv
             if self.adv_norm:         # the actor term reads the normalised advantages; d_adv stays the recorded raw array
                 hip_ops.adv_normalize(d_adv, self.adv_n, self.adv_stats)
@@ -968,7 +1015,8 @@ class PAACLearner(ActorLearner):
                                       adv=d_adv.cpu().numpy(), actions=d_actions.view(-1).cpu().numpy(), lr=lr,
                                       values=d_values.cpu().numpy(), global_step=self.global_step,
                                       rewards=d_rewards.cpu().numpy(), masks=d_masks.cpu().numpy(),
-                                      v_boot=d_vboot.cpu().numpy())
+                                      v_boot=d_vboot.cpu().numpy(),
+                                      **(dict(truncs=d_truncs.cpu().numpy()) if truncation_on else {}))
                 if getattr(self.args, "feed_callback", None):
                     self.args.feed_callback(self.last_feed)
             if getattr(self.args, "cycle_callback", None):      # bench hook: one call per finished cycle, nothing copied

@@ -39,6 +39,8 @@ env_offset + e, k = the episode index):
                    5. steps += 1; terminal if mine == POINTS or theirs == POINTS or steps == MAX_STEPS
                    6. a terminal step starts episode k + 1 at once; a non-terminal step that scored a point is followed by
                       serve mine + theirs
+                 truncated: the step is terminal ONLY because steps == MAX_STEPS -- neither side reached POINTS on it.  A step
+                 that is both the fifth point and at the cap is not truncated (--bootstrap_truncated reads this)
   plane(state)   a pixel in cell (cy, cx) = 255 if (cy, cx) == (by, bx), else 128 if cy == 13 and cx in (px, px + 1), else 64
                  if cy == 0 and cx in (ox, ox + 1), else 0
   observation    bricks' rule: the previous stack shifted by one channel with the new plane as channel 3; at construction and
@@ -111,6 +113,13 @@ def opponent_moves(seed, env, state):
 def step_state(seed, env, state, a):
     """One step of `state` under action a -> (state, reward, terminal).  The state returned is the one the next step starts
     from: after a terminal step that is the start state of episode k + 1 (the device record's rule)."""
+    return step_state_truncated(seed, env, state, a)[:3]
+
+
+def step_state_truncated(seed, env, state, a):
+    """step_state with the reason of a terminal step -> (state, reward, terminal, truncated): truncated = the step is terminal
+    only because steps reached MAX_STEPS (neither side reached POINTS on it).  The cap is a time limit, not a property of the
+    state: --bootstrap_truncated bootstraps the return there."""
     bx, by, dx, dy, px, ox, mine, theirs, steps, k = state
     if a in (RIGHT, RIGHTFIRE):
         px = min(px + 1, CELLS - 2)
@@ -141,12 +150,13 @@ def step_state(seed, env, state, a):
             mine += 1
             reward = 1.0
     steps += 1
-    if mine == POINTS or theirs == POINTS or steps == MAX_STEPS:
-        return start_state(seed, env, k + 1), reward, True
+    decided = mine == POINTS or theirs == POINTS
+    if decided or steps == MAX_STEPS:
+        return start_state(seed, env, k + 1), reward, True, not decided
     state = (nx, ny, dx, dy, px, ox, mine, theirs, steps, k)
     if reward != 0.0:
         state = serve(seed, env, state, mine + theirs, reward < 0.0)
-    return state, reward, False
+    return state, reward, False, False
 
 
 def plane(state):
@@ -188,6 +198,7 @@ class RallyEnvironment(BaseEnvironment):
         self.seed = int(seed)
         self.state = start_state(self.seed, self.actor_id, 0)
         self.stack = np.zeros((84, 84, 4), dtype=np.uint8)
+        self.last_step_truncated = False       # the last next() ended its episode at the step cap alone (runners.py reads it)
 
     @property
     def k(self):
@@ -204,7 +215,7 @@ class RallyEnvironment(BaseEnvironment):
 
     def next(self, action):
         a = int(np.argmax(action))
-        self.state, reward, terminal = step_state(self.seed, self.actor_id, self.state, a)
+        self.state, reward, terminal, self.last_step_truncated = step_state_truncated(self.seed, self.actor_id, self.state, a)
         self.stack[..., :3] = self.stack[..., 1:]
         self.stack[..., 3] = plane(self.state)
         return np.copy(self.stack), reward, terminal

@@ -22,11 +22,24 @@ import numpy as np
 _CTYPES = {np.dtype(np.float32): "f", np.dtype(np.uint8): "B", np.dtype(np.float64): "d"}
 
 
+TRUNCATED_ATTRIBUTE = "last_step_truncated"      # the optional plugin attribute behind --bootstrap_truncated
+
+
+def step_truncated(emulator, episode_over):
+    """1.0 when the step `emulator` has just taken ended its episode at a step cap alone: the plugin's optional attribute
+    last_step_truncated, read right after next() (absent: never truncated; it can only qualify a terminal step)."""
+    return float(bool(episode_over) and bool(getattr(emulator, TRUNCATED_ATTRIBUTE, False)))
+
+
 def step_emulators(emulators, variables):
-    """emulator_runner.py:24-31 for a slice of environments."""
-    states, rewards, overs, actions = variables
+    """emulator_runner.py:24-31 for a slice of environments.  A fifth shared array (--bootstrap_truncated) receives
+    step_truncated of every environment."""
+    states, rewards, overs, actions = variables[:4]
+    truncs = variables[4] if len(variables) > 4 else None
     for i, (emulator, action) in enumerate(zip(emulators, actions)):
         new_s, reward, episode_over = emulator.next(action)
+        if truncs is not None:
+            truncs[i] = step_truncated(emulator, episode_over)
         if episode_over:
             states[i] = emulator.get_initial_state()
         else:
@@ -40,9 +53,12 @@ def step_emulators_raw(emulators, variables):
     raw[i] is the step's screen pair and counts[i] == 1; after a terminal the environment is reset and its slots hold
     the pairs that build the initial observation (counts[i] == number of slots).  The GPU turns them into
     observations (paac_preprocess_stack)."""
-    raw, counts, rewards, overs, actions = variables
+    raw, counts, rewards, overs, actions = variables[:5]
+    truncs = variables[5] if len(variables) > 5 else None
     for i, (emulator, action) in enumerate(zip(emulators, actions)):
         pair, reward, episode_over = emulator.next_raw(action)
+        if truncs is not None:
+            truncs[i] = step_truncated(emulator, episode_over)
         if episode_over:
             raw[i] = emulator.initial_raw()
             counts[i] = raw.shape[1]

@@ -107,6 +107,11 @@ BUILD_FLAGS = (
     (("--adv_norm",), "adv_norm", False, bool_arg,
      "normalise each rollout's advantages by their own mean and standard deviation before the actor term reads them (per "
      "rank under data parallelism); the critic target and the recorded advantages are unchanged"),
+    (("--bootstrap_truncated",), "bootstrap_truncated", False, bool_arg,
+     "--emulator bricks|rally: a step that ends its episode only because the game's step cap was reached (500 / 1000 steps) "
+     "bootstraps its return from the value of the last state seen, r + gamma x V, instead of counting the state as worth "
+     "nothing (partial-episode bootstrapping; either estimator, every update option, device and host loops); the step is "
+     "still terminal and the environment still resets; accepted and without effect for catch, synthetic and ale"),
     (("--eval_every",), "eval_every", 0, int,
      "device loop, --emulator catch|bricks|rally: score the current policy on --eval_count held-out game instances (seed random_seed "
      "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "

@@ -633,6 +633,25 @@ typedef struct {
 int paac_game_step(int game, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
                    int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                    const paac_env_records* rec, int option, paac_stream_t stream);
+/* Device-resident duel environments: rally played against the learner itself (spec in paac_amd/duel.py).  N rows = N / 2
+ * boards of the rally board; row e < N / 2 is the bottom player of board e, row e + N / 2 the top player of the same board,
+ * and each row sees the board from its own side: own paddle (128) in the bottom row, the other's (64) in the top row.
+ *   state: i32 [N,12], rally's record.  A bottom row holds the board {bx, by, dx, dy, px, ox, mine, theirs, steps, k, 0, 0};
+ *          a top row holds its mirror {bx, 13 - by, dx, -dy, ox, px, theirs, mine, steps, k, 0, 0}.  The hashes are keyed by
+ *          (seed, env_offset + board, k); the first serve goes towards the bottom player in even episodes, the top player
+ *          in odd ones.
+ *   step:  row e reads actions[e] AND actions[(e + N / 2) % N]: the board advances by rally's rules with the scripted opponent
+ *          replaced by the top player's paddle move (2, 4 = right; 3, 5 = left).  Both rows of a board compute the same board
+ *          step; no row writes what another reads.  rewards: the bottom row's is rally's, the top row's 0 - that (+0.0 for
+ *          0); masks and rec->truncs (nullable) are the same for both.  Records, outputs and the second outputs as
+ *          paac_game_step's.  One launch.
+ * Refused with a message, without a launch: N odd or below 2, null actions / state / stack / records pointers, in-place
+ * buffers.  There is no evaluation id: a duel policy is scored as a rally agent (PAAC_EVAL_RALLY). */
+int paac_duel_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                    paac_stream_t stream);
+int paac_duel_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                   int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                   const paac_env_records* rec, paac_stream_t stream);
 #define PAAC_EVAL_CATCH 0
 #define PAAC_EVAL_BRICKS 1
 #define PAAC_EVAL_RALLY 2

@@ -174,6 +174,9 @@ for _game in ("catch", "bricks", "rally"):
     _SIGNATURES["paac_%s_reset" % _game] = (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p])
     _SIGNATURES["paac_%s_step" % _game] = (c_int, [c_uint64, c_uint32, c_int] + [c_void_p] * 12 +
                                            ([c_int] if _game == "bricks" else []) + [c_void_p])
+# the paired game (hip_ops.PAIRED_GAMES): catch's reset list; the step takes its records as paac_game_step does, as one block
+_SIGNATURES["paac_duel_reset"] = _SIGNATURES["paac_catch_reset"]
+_SIGNATURES["paac_duel_step"] = (c_int, [c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_void_p])
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

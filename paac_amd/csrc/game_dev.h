@@ -11,10 +11,25 @@
 //                                                    cap was reached -- a step that also ends the episode for a real reason is
 //                                                    not truncated, a game without a cap (catch) never is; term keeps its meaning
 //   shift_quad(s, q, old, fresh)                     quad q of the observation: the plane of s pushed into `old`
+// A PAIRED game (duel_dev.h) declares `static constexpr bool kPaired = true`: its N rows are N / 2 boards with two players
+// each, and a row's step is a pure function of (state_in[e], actions[e], actions[partner(e, N)]).  It provides instead
+//   is_top(e, N), board(e, N), partner(e, N)         the row's side, its board (the hash key is env_offset + board) and the
+//                                                    row that plays the other side
+//   start(seed, env_offset, e, N)                    episode 0's start record of row e
+//   advance(seed, g, s, a_own, a_partner, is_top, &reward, &term, &trunc)
+// and has no evaluation form (eval_step_kernel is not instantiated for it).
 #pragma once
+#include <type_traits>
+
 #include "synth_dev.h"
 
 namespace paac {
+
+// Whether trait G is a paired game: true only where G says so.
+template <class G, class = void>
+struct game_is_paired : std::false_type {};
+template <class G>
+struct game_is_paired<G, std::void_t<decltype(G::kPaired)>> : std::bool_constant<G::kPaired> {};
 
 constexpr int QUADS_PER_ROW = OBS_W / 4;                  // 21
 constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;   // 252: 12 rows of 21 quads

@@ -5,6 +5,7 @@
 #include "catch_dev.h"
 #include "bricks_dev.h"
 #include "rally_dev.h"
+#include "duel_dev.h"
 #include "fc_heads.h"
 #include "heads.h"
 #include "tower.h"
@@ -1284,6 +1285,9 @@ __global__ __launch_bounds__(256) void synth_step_a_kernel(const SynthStep st, c
 // bookkeeping.  Nothing in the launch writes what the launch reads: state_in / state_out and stack_in / stack_out are different
 // buffers.  state_in == nullptr: reset -- episode 0's start state, an empty history; actions / stack_in / the records are not
 // touched.
+// A paired game (duel: game_dev.h, duel_dev.h) widens that contract by one word: the new state of row e is a pure function of
+// (state_in[e], actions[e], actions[partner of e]) -- one more 4-byte load beside the own action's, of a value the launch
+// before this one wrote; N is even.  Still no row writes what another row reads, no atomics, no LDS.
 template <class G>
 __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t env_offset, int N,
                                                         const int32_t* __restrict__ actions,
@@ -1301,9 +1305,16 @@ __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t 
     // every thread loads (the four that own no quad read the band's first one): with the load under a condition the compiler
     // pulls the history's shift up behind it, and with the shift the wait -- the state record would be asked for only then
     old = reinterpret_cast<const uint4*>(stack_in)[t.load_quad];
-    s = G::advance(seed, env_offset + (uint32_t)e, G::load(state_in, e), actions[e], opt, &r, &term, &trunc);
+    if constexpr (game_is_paired<G>::value) {
+      // a paired game (game_dev.h): the other player's action too -- the sampler's launch wrote both before this one started
+      s = G::advance(seed, env_offset + (uint32_t)G::board(e, N), G::load(state_in, e), actions[e], actions[G::partner(e, N)],
+                     G::is_top(e, N), &r, &term, &trunc);
+    } else {
+      s = G::advance(seed, env_offset + (uint32_t)e, G::load(state_in, e), actions[e], opt, &r, &term, &trunc);
+    }
   } else {
-    s = G::start(seed, env_offset + (uint32_t)e);
+    if constexpr (game_is_paired<G>::value) s = G::start(seed, env_offset, e, N);
+    else s = G::start(seed, env_offset + (uint32_t)e);
   }
   if (t.band == 0 && t.i == 0) {
     G::store(state_out, e, s);
@@ -2628,6 +2639,23 @@ int paac_rally_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* ac
                     paac_stream_t stream) {
   return game_step<RallyGame>("paac_rally_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
                    stack_out2, EnvRecords{{rewards_out, masks_out, ep_reward, ep_len, (FinishedRing*)finished}, nullptr}, 0, stream);
+}
+
+// Duel: rally against the learner itself, two rows per board (csrc/duel_dev.h).  The records come as paac_game_step's block.
+int paac_duel_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                    paac_stream_t stream) {
+  PAAC_REQUIRE(N >= 2 && N % 2 == 0, "paac_duel_reset: N=%d is not an even number of rows >= 2 (two rows per board)", N);
+  return game_reset<DuelGame>("paac_duel_reset", seed, env_offset, N, state_out, stack_out, stream);
+}
+
+int paac_duel_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                   int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
+                   const paac_env_records* rec, paac_stream_t stream) {
+  PAAC_REQUIRE(N >= 2 && N % 2 == 0, "paac_duel_step: N=%d is not an even number of rows >= 2 (two rows per board)", N);
+  PAAC_REQUIRE(rec, "paac_duel_step: null records");
+  const EnvRecords r{{rec->rewards, rec->masks, rec->ep_reward, rec->ep_len, (FinishedRing*)rec->finished}, rec->truncs};
+  return game_step<DuelGame>("paac_duel_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
+                             stack_out2, r, 0, stream);
 }
 
 // paac_<game>_step by the game's id, with the records as one block -- the truncation plane among them.

@@ -6,11 +6,12 @@ environments of paac_amd/synthetic.py; `num_actions` per game is ALE's minimal a
 breakout/qbert/seaquest by the reference's pretrained/*/checkpoints/*.index actor_output_biases shapes).
 `--emulator catch` creates the catch game of paac_amd/catch.py instead (3 actions, whatever `-g` says), `--emulator bricks`
 the brick-wall game of paac_amd/bricks.py (3 actions, lives: `--single_life_episodes` applies), `--emulator rally` the
-two-paddle game of paac_amd/rally.py (6 actions, ALE Pong's minimal set; no lives).
+two-paddle game of paac_amd/rally.py (6 actions, ALE Pong's minimal set; no lives), `--emulator duel` rally played against the
+learner itself (paac_amd/duel.py: device loop only, an even `-ec`; the host environment created is rally's).
 A user environment plugs in exactly as in the reference: subclass BaseEnvironment and return it from
 create_environment(i).
 """
-from . import bricks, catch, rally
+from . import bricks, catch, duel, rally
 from .synthetic import SyntheticEnvironment, terminal_threshold
 
 # ALE minimal action set sizes.
@@ -26,6 +27,12 @@ DEVICE_GAMES = {
     "catch": (catch, catch.CatchEnvironment, ()),
     "bricks": (bricks, bricks.BricksEnvironment, ("single_life",)),
     "rally": (rally, rally.RallyEnvironment, ()),
+}
+
+# --emulator duel: the paired games (paac.PAIRED_KINDS) -- the spec module and the HOST environment of the game a run is scored
+# on (duel: rally against its scripted opponent; there is no host twin of the paired game itself).
+PAIRED_GAMES = {
+    "duel": (duel, rally.RallyEnvironment),
 }
 
 
@@ -53,6 +60,22 @@ class EnvironmentCreator(object):
             module, env_class, _ = DEVICE_GAMES[self._game]
             self.num_actions = module.NUM_ACTIONS
             self.create_environment = lambda i: env_class(i, seed=self._seed(), **self._game_options())
+            return
+        if self._game in PAIRED_GAMES:
+            # a paired game (paac_amd/duel.py): device loop only -- a row needs its partner's action, and the host loop steps
+            # environments one by one.  What is created for the host (paac_amd.test) is the game it is scored on.
+            if self._raw():
+                raise ValueError("--emulator %s has no raw 210x160 frames: --synthetic_raw_frames applies to --emulator "
+                                 "synthetic only" % self._game)
+            module, env_class = PAIRED_GAMES[self._game]
+            if getattr(args, "host_environments", False):
+                raise ValueError("--host_environments true cannot be combined with --emulator %s: the host loop would step %s "
+                                 "and silently train against the scripted opponent" % (self._game, env_class.__name__))
+            if int(getattr(args, "emulator_counts", 2)) % 2 or int(getattr(args, "emulator_counts", 2)) < 2:
+                raise ValueError("-ec / --emulator_counts %s: --emulator %s plays two rows per board and needs an even number "
+                                 "of environments per rank" % (getattr(args, "emulator_counts", None), self._game))
+            self.num_actions = module.NUM_ACTIONS
+            self.create_environment = lambda i: env_class(i, seed=self._seed())
             return
         self.num_actions = int(getattr(args, "num_actions_override", 0) or GAME_NUM_ACTIONS.get(game, 6))
         # args.random_seed is set by train.get_network_and_environment_creator AFTER this constructor runs
@@ -83,5 +106,7 @@ class EnvironmentCreator(object):
             return None
         if self._game in DEVICE_GAMES:
             return dict(kind=self._game, seed=self._seed(), **self._game_options())
+        if self._game in PAIRED_GAMES:
+            return dict(kind=self._game, seed=self._seed())
         return dict(kind="synthetic", seed=self._seed(), terminal_threshold=terminal_threshold(self._terminal_p()),
                     raw_frames=self._raw())

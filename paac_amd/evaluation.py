@@ -157,7 +157,8 @@ def check_train_flags(args, world_size=1):
     check_count(getattr(args, "eval_count", 64), "eval_count")
     if getattr(args, "host_environments", False):
         raise ValueError("--eval_every evaluates on the device games: it cannot be combined with --host_environments true")
-    if getattr(args, "emulator", "synthetic") not in ("catch", "bricks", "rally"):
+    # (duel: a paired game, evaluated as rally against the scripted opponent -- paac.eval_env_spec)
+    if getattr(args, "emulator", "synthetic") not in ("catch", "bricks", "rally", "duel"):
         raise ValueError("--eval_every needs a game resident on the GPU: --emulator catch|bricks|rally (got '%s')"
                          % getattr(args, "emulator", "synthetic"))
     if int(world_size) > 1:

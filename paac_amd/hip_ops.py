@@ -827,6 +827,34 @@ for _kind, _game in DEVICE_GAMES.items():
                       _kind.upper() + "_STATE_WORDS": _game["words"]})
 EVAL_GAMES = {kind: (game["eval_id"], game["words"]) for kind, game in DEVICE_GAMES.items()}
 
+# The paired games (csrc/game_dev.h): N rows = N / 2 boards, a row's step reads its partner's action too.  A table of their
+# own: they have no evaluation id and no entry in paac_game_step.  Entry points paac_<game>_reset / paac_<game>_step.
+PAIRED_GAMES = {"duel": dict(words=12)}
+DUEL_STATE_WORDS = PAIRED_GAMES["duel"]["words"]
+
+
+def duel_reset(seed, env_offset, state_out, stack_out):
+    """paac_duel_reset (include/paac_hip.h; spec in paac_amd/duel.py): an even number of rows, two per board."""
+    _stateful_reset("paac_duel_reset", DUEL_STATE_WORDS, seed, env_offset, state_out, stack_out)
+
+
+def duel_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
+              finished=None, stack_out2=None, state_out2=None, truncs_out=None):
+    """paac_duel_step: game_step's argument list without the kind; row e also reads actions[(e + N / 2) % N].  truncs_out
+    float32[N] (None: not written) as game_step_records'.  The library refuses an odd N, N < 2 and in-place buffers."""
+    words = DUEL_STATE_WORDS
+    N = actions.shape[0]
+    out, out2, *records = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
+    for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
+        if t is not None and tuple(t.shape) != (N, words):
+            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
+    rec = _lib.EnvRecords(*records, _ptr(truncs_out, torch.float32, N, "truncs_out", True))
+    _lib.check(_lib.load().paac_duel_step(
+        int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
+        _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
+        _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), out, out2,
+        ctypes.byref(rec), _stream()), "paac_duel_step")
+
 
 def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
               stack_in, stack_out, actions_out, score, length, done, alive):

@@ -41,6 +41,29 @@ STATEFUL_KINDS = {
     "rally": _stateful_kind("rally", (), 1000, True),
 }
 
+# The paired kinds (hip_ops.PAIRED_GAMES, paac_amd/duel.py): the same fields -- to the rollout a paired game is a stateful game
+# with N rows -- and eval_kind, the kind of STATEFUL_KINDS a run of this kind is evaluated as (duel has no evaluation of its
+# own: its policy is scored as a rally agent, against the scripted opponent).  N must be even: two rows per board.
+PAIRED_KINDS = {
+    "duel": dict(words=hip_ops.PAIRED_GAMES["duel"]["words"], reset=hip_ops.duel_reset, step=hip_ops.duel_step, spec_kwargs=(),
+                 max_episode_steps=1000, truncates=True, eval_kind="rally"),
+}
+
+
+def device_kind(env_spec):
+    """The STATEFUL_KINDS or PAIRED_KINDS entry of a device env spec; None for the synthetic environments (or no spec)."""
+    kind = (env_spec or {}).get("kind", "synthetic")
+    return STATEFUL_KINDS.get(kind) or PAIRED_KINDS.get(kind)
+
+
+def eval_env_spec(env_spec, **changes):
+    """The env spec a run on `env_spec` is evaluated on: the spec itself with `changes` (the evaluation's seed, bricks'
+    single_life off), or, for a paired kind, its eval_kind with the seed alone -- a duel run is scored on rally."""
+    kind = None if env_spec is None else env_spec.get("kind", "synthetic")
+    if kind in PAIRED_KINDS:
+        return dict(kind=PAIRED_KINDS[kind]["eval_kind"], seed=changes.get("seed", env_spec["seed"]))
+    return dict(env_spec, **changes) if env_spec is not None else None
+
 
 class DeviceRollout(object):
     """Device-resident rollout/update cycle for N local environments x T steps."""
@@ -84,7 +107,11 @@ class DeviceRollout(object):
         # a stateful kind (STATEFUL_KINDS: catch, bricks, rally): the environments carry state from step to step -- a ring of state
         # records beside the observation ring, slot for slot (a step reads slot t and writes slot t + 1: nothing is updated in
         # place, and the wrap-around second output goes to slot 0 of both)
-        self.stateful = STATEFUL_KINDS.get(env_spec.get("kind", "synthetic"))
+        # (a paired kind -- PAIRED_KINDS: duel -- is one more of them here: N rows, two per board, the same call)
+        self.stateful = device_kind(env_spec)
+        if env_spec.get("kind") in PAIRED_KINDS and N % 2:
+            raise ValueError("-ec / --emulator_counts %d: --emulator %s plays two rows per board and needs an even number of "
+                             "environments per rank" % (N, env_spec["kind"]))
         self.catch = env_spec.get("kind", "synthetic") == "catch"       # (read by the games' device-loop tests only)
         self.env_state = None
         if self.stateful:
@@ -619,7 +646,7 @@ class PAACLearner(ActorLearner):
         if not self.bootstrap_truncated:
             return False
         if self._use_device_envs():
-            kind = STATEFUL_KINDS.get(self.environment_creator.device_env_spec.get("kind", "synthetic"))
+            kind = device_kind(self.environment_creator.device_env_spec)
             on = bool(kind and kind["truncates"])
         else:
             on = any(hasattr(e, TRUNCATED_ATTRIBUTE) for e in self.emulators)
@@ -741,7 +768,8 @@ class PAACLearner(ActorLearner):
             seed = int(getattr(args, "random_seed", 3)) + 1
             eval_ctx = hip_ops.Context(self.network.arch_id, self.num_actions, max_batch=min(count, evaluation.MAX_CHUNK),
                                        device_index=self.torch_device.index or 0)
-            spec = dict(self.environment_creator.device_env_spec, seed=seed, single_life=False)
+            spec = eval_env_spec(self.environment_creator.device_env_spec, seed=seed, single_life=False)
+            scripted = self.environment_creator.device_env_spec.get("kind") in PAIRED_KINDS       # duel: scored on rally
             evaluator = evaluation.DeviceEvaluator(self.network, eval_ctx, spec, count, noops=30,
                                                    greedy=bool(getattr(args, "eval_greedy", True)), seed=seed,
                                                    use_graph=getattr(args, "use_graph", True), stream=self.rollout.stream)
@@ -795,6 +823,8 @@ class PAACLearner(ActorLearner):
                 self.rollout.synchronize()
                 scores, lengths, seconds = evaluator.timed_run()
                 record = evaluator.summary(scores, lengths, seconds)
+                if scripted:
+                    record["opponent"] = "scripted"
                 next_eval = (self.global_step // eval_every + 1) * eval_every
                 logging.info("Evaluation at {} steps: {} episodes ({}), mean {:.3f}, min {:.3f}, max {:.3f}, std {:.3f}, mean "
                              "length {:.1f}, {:.3f} s".format(self.global_step, record["count"],

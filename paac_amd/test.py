@@ -9,8 +9,8 @@ Flags as upstream (-f, -tc, -np, -gn, -gf, -d).  One deliberate difference: the 
 it only stops when all environments happen to finish on the same step and keeps adding post-episode rewards; here an
 environment's score is frozen when its first episode ends.
 
---device_environments true (runs of --emulator catch|bricks|rally) plays the games on the GPU instead (paac_amd/evaluation.py:
-DeviceEvaluator): -tc up to 4096, --greedy true for the argmax action, --eval_seed for the game instances, the no-op counts
+--device_environments true (runs of --emulator catch|bricks|rally, and duel runs as rally) plays the games on the GPU instead
+(paac_amd/evaluation.py: DeviceEvaluator): -tc up to 4096, --greedy true for the argmax action, --eval_seed for the game instances, the no-op counts
 and the sampled actions; the summary gains a 'Mean length' line.  --gif_name is refused there.
 """
 import argparse
@@ -21,7 +21,7 @@ import time
 import numpy as np
 
 from . import hip_ops, logger_utils
-from .paac import PAACLearner
+from .paac import PAACLearner, eval_env_spec
 from .session import Session
 from .train import bool_arg, get_network_and_environment_creator
 
@@ -126,7 +126,7 @@ def evaluate_on_device(cli, args):
     from . import evaluation
     seed = cli.eval_seed if cli.eval_seed is not None else int(getattr(args, "random_seed", 3))
     network_creator, env_creator = get_network_and_environment_creator(args, random_seed=seed)
-    spec = getattr(env_creator, "device_env_spec", None)
+    spec = eval_env_spec(getattr(env_creator, "device_env_spec", None))     # a duel run is scored on rally
     evaluation.check_env_spec(spec)
     network = network_creator()
     ctx = hip_ops.Context(network.arch_id, env_creator.num_actions, max_batch=min(cli.test_count, evaluation.MAX_CHUNK),

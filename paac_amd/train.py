@@ -70,7 +70,11 @@ BUILD_FLAGS = (
      "--synthetic_terminal_p, --synthetic_raw_frames and --random_start do not), 'rally' (paac_amd/rally.py: a two-paddle game "
      "against a scripted opponent on the GPU, the 6 actions of ALE Pong, rewards of both signs, first to five points, episodes "
      "of up to 1000 steps; --single_life_episodes, -g, --synthetic_terminal_p, --synthetic_raw_frames and --random_start do not "
-     "apply) or 'ale' (Atari through an installed Arcade "
+     "apply), 'duel' (paac_amd/duel.py: rally played against the learner itself on the GPU -- -ec rows are -ec / 2 boards, the "
+     "network plays both paddles, each row seeing the board from its own side; device loop only, -ec must be even, the logged "
+     "returns average 0 by construction: use --eval_every, which scores the policy against rally's scripted opponent; "
+     "--host_environments true is refused, --single_life_episodes, -g, --synthetic_terminal_p, --synthetic_raw_frames and "
+     "--random_start do not apply) or 'ale' (Atari through an installed Arcade "
      "Learning Environment)"),
     (("--device_preprocess",), "device_preprocess", False, bool_arg,
      "host environments hand out raw screen pairs; max + resize + frame history run on the GPU"),
@@ -132,7 +136,7 @@ def get_arg_parser():
         if kind is not None:
             kwargs["type"] = kind
         if dest in ("sampler", "emulator", "checkpoint_format", "optimizer"):
-            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "rally", "ale"],
+            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "rally", "duel", "ale"],
                                  "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"]}[dest]
         parser.add_argument(*options, **kwargs)
     return parser

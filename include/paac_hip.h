@@ -646,7 +646,8 @@ int paac_game_step(int game, uint64_t seed, uint32_t env_offset, int N, const in
  *          0); masks and rec->truncs (nullable) are the same for both.  Records, outputs and the second outputs as
  *          paac_game_step's.  One launch.
  * Refused with a message, without a launch: N odd or below 2, null actions / state / stack / records pointers, in-place
- * buffers.  There is no evaluation id: a duel policy is scored as a rally agent (PAAC_EVAL_RALLY). */
+ * buffers.  There is no evaluation id: a duel policy is scored as a rally agent (PAAC_EVAL_RALLY), or against another policy
+ * on the duel board itself by paac_match_step below. */
 int paac_duel_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
                     paac_stream_t stream);
 int paac_duel_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
@@ -659,6 +660,25 @@ int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint6
                    const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
                    const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out,
                    float* score, int32_t* length, int32_t* done, int32_t* alive, paac_stream_t stream);
+/* A head-to-head match on the duel board (spec: paac_amd/match.py): one step of N rows = N / 2 boards in one launch, behind the
+ * TWO acting forwards that wrote probs [N, 6] -- rows [0, N / 2) by the bottom players' policy, rows [N / 2, N) by the top
+ * players'.  paac_eval_step's argument list without `game`; rows, records and the board key g = env_offset + board are
+ * paac_duel_step's, reset is paac_duel_reset.  With t = *step_base_dev + step_offset (base NULL = 0):
+ *   no-ops   noops_g as paac_eval_step's, keyed by the BOARD: both rows of a board play action 0 while t < noops_g
+ *   action   paac_eval_step's two rules on the row's own probs, counter {g, t lo, t hi, stream}, key eval_seed; stream
+ *            0x45560001 for a bottom row (its actions are an evaluation's), 0x45560003 for a top row: the two players of a
+ *            board never share a random word.  Each row also works out its partner's action from probs[(e + N / 2) % N] by the
+ *            same rule on the partner's stream -- both rows of a board hold the same pair.  actions_out[e] = the row's own
+ *   game     paac_duel_step's board step on the pair (seed env_seed); not in place
+ *   accounts paac_eval_step's, per ROW with the row's own reward: score[b + N / 2] == -score[b], length and done are equal
+ *            within a board.  The caller zeroes score / length / done and sets *alive = N (rows) before step 0; each row
+ *            takes one off on its own first scored terminal step.
+ * Refused with a message naming the argument, without a launch: N odd or below 2, A != 6, noops < 0, a null pointer (all but
+ * step_base_dev), state_in == state_out or stack_in == stack_out. */
+int paac_match_step(const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops, const uint64_t* step_base_dev,
+                    uint64_t step_offset, uint64_t env_seed, uint32_t env_offset, const int32_t* state_in, int32_t* state_out,
+                    const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out, float* score, int32_t* length,
+                    int32_t* done, int32_t* alive, paac_stream_t stream);
 
 /* paac_sample_mt + paac_synth_step (path A) in ONE launch: workgroup 0 samples (numpy-parity MT19937 stream) and does
  * the per-env bookkeeping while the other workgroups shift the observation stacks (stack_out2, nullable: a second copy

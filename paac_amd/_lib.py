@@ -138,6 +138,9 @@ _SIGNATURES = {
     "paac_eval_step": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_void_p, c_uint64, c_uint64, c_uint32,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "paac_match_step": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_void_p, c_uint64, c_uint64, c_uint32,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
     "paac_act_step_mt": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                  c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

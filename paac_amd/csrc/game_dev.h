@@ -17,7 +17,8 @@
 //                                                    row that plays the other side
 //   start(seed, env_offset, e, N)                    episode 0's start record of row e
 //   advance(seed, g, s, a_own, a_partner, is_top, &reward, &term, &trunc)
-// and has no evaluation form (eval_step_kernel is not instantiated for it).
+// and has no evaluation form (eval_step_kernel is not instantiated for it); what it has instead is the match form,
+// match_step_kernel in csrc/misc.hip: two policies' probabilities in one block, one on each side of every board.
 #pragma once
 #include <type_traits>
 

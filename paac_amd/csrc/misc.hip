@@ -1412,6 +1412,119 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
   reinterpret_cast<uint4*>(stack_out)[th.quad] = G::shift_quad(s, th.q, old, term);
 }
 
+// =============================================================================================
+// Head-to-head matches (spec: paac_amd/match.py): one step of N rows = N / 2 duel boards per launch, two policies' probs in
+// one [N, 6] block -- rows [0, N / 2) the bottom players', rows [N / 2, N) the top players'.  eval_step_kernel's shape and
+// reasons: grid (N, 7), 256 threads, 252 own one quad, the stack load requested first by every thread, one 16-byte store, no
+// LDS.  Every band workgroup of row e works out, uniformly and in registers, the board's no-op count, its own action from
+// probs[e] and its partner's from probs[partner] -- the same device function on the other stream, so both rows of a board hold
+// the same pair bit for bit -- and the new record (DuelGame::advance).  Thread 0 of band 0 writes the record, the row's own
+// action and the row's accounts; `alive` counts ROWS.  Nothing the launch reads is written by it: no row writes what another
+// row reads (the partner's probs are the forward's output, the partner's action is recomputed, not loaded).
+// The top player's Philox stream; the bottom player's is kEvalStreamAction, so the bottom rows' actions are an evaluation's.
+// paac_amd/match.py: MATCH_STREAM_TOP is the same number.
+constexpr uint32_t kMatchStreamTop = 0x45560003u;
+
+constexpr int kMatchActions = 6;          // the duel board's (paac_match_step refuses any other A)
+
+// One row of probs in registers: six unconditional loads, so that both rows of a board are asked for before anything is
+// computed on either (uniform in the workgroup: scalar loads).
+struct MatchRow {
+  float p[kMatchActions];
+};
+__device__ __forceinline__ MatchRow match_row(const float* __restrict__ probs, int e) {
+  MatchRow row;
+#pragma unroll
+  for (int j = 0; j < kMatchActions; ++j) row.p[j] = probs[(long)e * kMatchActions + j];
+  return row;
+}
+
+// evaluation.eval_action's two rules on one row of probs: the action of board g at step t on `stream`.  (A restatement of the
+// choice inside eval_step_kernel, kept beside it rather than shared with it: that kernel's device code stays as it was.)
+// Unrolled and without an early exit: the running sums are the same float32 additions in the same order, and the first hit
+// keeps the action.
+__device__ __forceinline__ int match_action(const MatchRow& row, int greedy, uint64_t seed, uint32_t g, uint64_t t,
+                                            uint32_t stream) {
+  int act = 0;
+  if (greedy) {
+    float best = row.p[0];
+#pragma unroll
+    for (int j = 1; j < kMatchActions; ++j) {
+      const float v = row.p[j];
+      if (v > best) {                                      // strictly: the lowest index wins a tie
+        best = v;
+        act = j;
+      }
+    }
+  } else {
+    uint32_t c[4] = {g, (uint32_t)t, (uint32_t)(t >> 32), stream};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float u = (float)(c[0] >> 8) * (1.0f / 16777216.0f);
+    act = kMatchActions - 1;
+    bool chosen = false;
+    float cum = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMatchActions - 1; ++j) {
+      cum += row.p[j];
+      if (!chosen && u < cum) {
+        act = j;
+        chosen = true;
+      }
+    }
+  }
+  return act;
+}
+
+__global__ __launch_bounds__(256) void match_step_kernel(const float* __restrict__ probs, int greedy, uint64_t eval_seed,
+                                                         int noops, const uint64_t* __restrict__ step_base, uint64_t step_off,
+                                                         uint64_t env_seed, uint32_t env_offset, int N,
+                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
+                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                         int32_t* __restrict__ actions_out, float* score, int32_t* length,
+                                                         int32_t* done, int32_t* alive) {
+  typedef DuelGame G;
+  const QuadThread th = quad_thread();
+  const int e = th.e;
+  // every thread loads (the four that own no quad read the band's first one): see game_step_kernel
+  const uint4 old = reinterpret_cast<const uint4*>(stack_in)[th.load_quad];
+  const bool top = G::is_top(e, N);
+  // everything the step reads is asked for here, whether or not the board is past its no-ops: one round trip to memory, not
+  // one per player behind the no-op count
+  const uint64_t t = (step_base ? *step_base : 0ull) + step_off;
+  const MatchRow own = match_row(probs, e), other = match_row(probs, G::partner(e, N));
+  const G::State s0 = G::load(state_in, e);
+  const uint32_t g = env_offset + (uint32_t)G::board(e, N);          // the BOARD's key: no-ops and both streams hang on it
+  uint32_t noops_g = 0u;
+  if (noops > 0) {
+    uint32_t c[4] = {g, 0u, 0u, kEvalStreamNoop};
+    philox4x32_10(c, (uint32_t)eval_seed, (uint32_t)(eval_seed >> 32));
+    noops_g = c[0] % ((uint32_t)noops + 1u);
+  }
+  const bool playing = t >= (uint64_t)noops_g;
+  int a_own = 0, a_partner = 0;                            // the no-op, for both players of the board
+  if (playing) {
+    a_own = match_action(own, greedy, eval_seed, g, t, top ? kMatchStreamTop : kEvalStreamAction);
+    a_partner = match_action(other, greedy, eval_seed, g, t, top ? kEvalStreamAction : kMatchStreamTop);
+  }
+  float r = 0.f;
+  bool term = false, trunc = false;
+  const G::State s = G::advance(env_seed, g, s0, a_own, a_partner, top, &r, &term, &trunc);
+  if (th.band == 0 && th.i == 0) {
+    G::store(state_out, e, s);
+    actions_out[e] = a_own;
+    if (playing && done[e] == 0) {                         // the first episode that starts after the no-ops, its last step included
+      score[e] += r;
+      length[e] += 1;
+      if (term) {
+        done[e] = 1;
+        atomicSub(alive, 1);
+      }
+    }
+  }
+  if (!th.owner) return;
+  reinterpret_cast<uint4*>(stack_out)[th.quad] = G::shift_quad(s, th.q, old, term);
+}
+
 // One (environment, band) unit of the step's frame work: path B's raw screen pair (the preprocess launch follows) or the shift.
 __device__ __forceinline__ void step_unit(const SynthStep& st, uint64_t id, int unit) {
   if (st.raw) synth_raw_unit(st.seed, st.env_offset, id, unit, st.raw);
@@ -2697,6 +2810,31 @@ int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint6
                                               : (game == PAAC_EVAL_BRICKS ? launch_eval_step<BricksGame> : launch_eval_step<RallyGame>);
   launch(s, probs, N, A, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out, stack_in,
          stack_out, actions_out, score, length, done, alive);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// One step of a head-to-head match on N / 2 duel boards (spec: paac_amd/match.py).  An entry of its own: the paired game has
+// no PAAC_EVAL_* id.
+int paac_match_step(const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops, const uint64_t* step_base_dev,
+                    uint64_t step_offset, uint64_t env_seed, uint32_t env_offset, const int32_t* state_in, int32_t* state_out,
+                    const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out, float* score, int32_t* length,
+                    int32_t* done, int32_t* alive, paac_stream_t stream) {
+  PAAC_REQUIRE(N >= 2 && N % 2 == 0, "paac_match_step: N=%d is not an even number of rows >= 2 (two rows per board)", N);
+  PAAC_REQUIRE(A == kMatchActions, "paac_match_step: A=%d is not the 6 actions of the duel board", A);
+  PAAC_REQUIRE(noops >= 0, "paac_match_step: noops=%d is negative", noops);
+  PAAC_REQUIRE(probs, "paac_match_step: null probs");
+  PAAC_REQUIRE(state_in && state_out, "paac_match_step: null state_in / state_out");
+  PAAC_REQUIRE(stack_in && stack_out, "paac_match_step: null stack_in / stack_out");
+  PAAC_REQUIRE(actions_out, "paac_match_step: null actions_out");
+  PAAC_REQUIRE(score && length && done && alive, "paac_match_step: null score / length / done / alive");
+  PAAC_REQUIRE(state_in != state_out && stack_in != stack_out,
+               "paac_match_step: the step cannot run in place (every band workgroup of a row reads state_in)");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+  launch_k(match_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, greedy, eval_seed, noops, step_base_dev,
+           step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in, (uint32_t*)stack_out,
+           actions_out, score, length, done, alive);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

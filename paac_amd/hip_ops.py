@@ -887,6 +887,34 @@ def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset,
         _ptr(alive, torch.int32, 1, "alive"), _stream()), "paac_eval_step")
 
 
+def match_step(probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
+               stack_in, stack_out, actions_out, score, length, done, alive):
+    """One step of a head-to-head match on N / 2 duel boards (include/paac_hip.h: paac_match_step; spec in paac_amd/match.py):
+    eval_step's argument list without the game.  probs [N, 6]: rows [0, N / 2) are the bottom players' policy's, rows
+    [N / 2, N) the top players'.  Shapes are checked here; the library refuses an odd N, N < 2, A != 6, negative noops and
+    in-place buffers with a PaacHipError, before any launch."""
+    words = DUEL_STATE_WORDS
+    if probs.dim() != 2:
+        raise ValueError("probs must be [N, A], got %s" % (tuple(probs.shape),))
+    N, A = probs.shape
+    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out)):
+        if tuple(t.shape) != (N,) + OBS_SHAPE:
+            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
+    for nm, t in (("state_in", state_in), ("state_out", state_out)):
+        if tuple(t.shape) != (N, words):
+            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
+    if not 0 <= int(env_offset) <= 0xFFFFFFFF - N:
+        raise ValueError("match_step: env_offset %r" % (env_offset,))
+    _lib.check(_lib.load().paac_match_step(
+        _ptr(probs, torch.float32, N * A, "probs"), N, A, 1 if greedy else 0, int(eval_seed) & 0xFFFFFFFFFFFFFFFF,
+        int(noops), _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
+        int(env_seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), _ptr(state_in, torch.int32, N * words, "state_in"),
+        _ptr(state_out, torch.int32, N * words, "state_out"), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"),
+        _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(actions_out, torch.int32, N, "actions_out"),
+        _ptr(score, torch.float32, N, "score"), _ptr(length, torch.int32, N, "length"), _ptr(done, torch.int32, N, "done"),
+        _ptr(alive, torch.int32, 1, "alive"), _stream()), "paac_match_step")
+
+
 FUSED_SAMPLE_MAX_DRAWS = 2304
 ACT_STEP_MAX_DRAWS = 1024
 ACT_STEP_MAX_ENVS = 64

@@ -1,0 +1,240 @@
+"""Head-to-head matches: two policies play duel boards (paac_amd/duel.py) against each other, scored on the GPU.
+
+This is the SPEC of a match, as evaluation.py is the spec of an evaluation; the same numbers are produced
+  * on the host by the plain-numpy functions below (`match_actions`, `replay_match`, with evaluation.eval_noops / account and
+    duel.DuelBoards), and
+  * on the device by paac_match_step (csrc/misc.hip; include/paac_hip.h has the contract), one step of N rows = N / 2 boards
+    per launch, driven by `DeviceMatch`.
+
+Spec
+  rows         a match of n boards is 2n rows in duel's layout: row b < n is the bottom player of board b, row b + n the top
+               player, each seeing the board from its own side.  The board key is g = env_offset + b
+  no-ops       noops_g = evaluation.eval_noops(seed, g, noops), keyed by the BOARD: both rows play action 0 while t < noops_g
+  action       evaluation.eval_action's two rules, unchanged, on the row's own probabilities; counter (g, t lo, t hi, stream),
+               key the match's seed.  A bottom row draws from EVAL_STREAM_ACTION -- the bottom rows' actions are exactly
+               evaluation.eval_action(probs[:n], seed, t, g, greedy) -- and a top row from MATCH_STREAM_TOP: the two players of
+               a board never share a random word, and nothing depends on n or on the chunking
+  game         duel.step_row / DuelBoards, seeded by the game seed
+  accounting   evaluation.account per row with the row's own reward: score[b + n] == -score[b]; length and done are equal for
+               both rows of a board
+  bound        max_steps = noops + 1000 (duel's longest episode)
+  sides        fixed by the board index, so that side and serve asymmetry cancel: X is the bottom player on boards
+               [0, ceil(count / 2)) and the top player on the rest; swap_sides reverses this
+"""
+import time
+
+import numpy as np
+
+from . import duel
+from .evaluation import MAX_CHUNK, account, check_count, eval_action, eval_noops, philox_word0
+
+MATCH_STREAM_TOP = 0x45560003          # csrc/misc.hip: kMatchStreamTop
+MATCH_KINDS = ("rally", "duel")        # the runs whose agents play this board: 6 actions, the same planes
+MAX_EPISODE_STEPS = duel.MAX_STEPS
+
+
+def match_actions(probs_f32, seed, step, board_ids, greedy):
+    """-> int32 [2n]: the action of every row of probs_f32 [2n, A] at step `step` (past the boards' no-ops); board_ids [n] are
+    the boards' keys g, rows [0, n) their bottom players and rows [n, 2n) their top players."""
+    p = np.asarray(probs_f32, dtype=np.float32)
+    board_ids = np.asarray(board_ids)
+    n = board_ids.shape[0]
+    if p.ndim != 2 or p.shape[0] != 2 * n:
+        raise ValueError("match_actions: probs %s for %d boards: expected [%d, A]" % (p.shape, n, 2 * n))
+    bottom = eval_action(p[:n], seed, step, board_ids, greedy)
+    if greedy:
+        return np.concatenate([bottom, np.argmax(p[n:], axis=1).astype(np.int32)])
+    A = p.shape[1]
+    u = (philox_word0(seed, step, board_ids, MATCH_STREAM_TOP) >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    top = np.full(n, A - 1, dtype=np.int32)
+    chosen = np.zeros(n, dtype=bool)
+    c = np.zeros(n, dtype=np.float32)
+    for j in range(A - 1):                                   # eval_action's running sums, on the top player's stream
+        c = (c + p[n:, j]).astype(np.float32)
+        hit = (~chosen) & (u < c)
+        top[hit] = j
+        chosen |= hit
+    return np.concatenate([bottom, top])
+
+
+def replay_match(game_seed, env_offset, actions_trace, noops):
+    """Steps DuelBoards through a recorded [steps, 2n] action trace under the accounting rule (the no-op wherever t < noops_b,
+    whatever the trace holds) -> (scores float32 [2n], lengths int32 [2n]).  noops: the per-board counts [n] (or one for all)."""
+    trace = np.asarray(actions_trace)
+    steps, rows = trace.shape
+    n = rows // 2
+    noops = np.tile(np.broadcast_to(np.asarray(noops, dtype=np.int64), (n,)), 2)
+    boards = duel.DuelBoards(rows, seed=game_seed, env_offset=env_offset)
+    boards.reset()
+    rewards, terminals = np.zeros((steps, rows), dtype=np.float32), np.zeros((steps, rows), dtype=bool)
+    for t in range(steps):
+        _, _, rewards[t], terminals[t], _ = boards.step(np.where(t < noops, 0, trace[t]))
+    score, length, _ = account(rewards, terminals, noops)
+    return score, length
+
+
+def x_is_bottom(count, swap_sides=False):
+    """-> bool [count]: the boards on which player X is the bottom player."""
+    count = int(count)
+    first = np.arange(count) < (count + 1) // 2
+    return ~first if swap_sides else first
+
+
+def legs(count, chunk, swap_sides=False):
+    """The chunks a match of `count` boards is played in -> [(env_offset, boards, X is bottom), ...]: two legs, one per side
+    of X, each in chunks of at most `chunk` boards; board b is board b in any chunking."""
+    count, chunk = int(count), int(chunk)
+    half = (count + 1) // 2
+    out = []
+    for lo, hi, bottom in ((0, half, not swap_sides), (half, count, bool(swap_sides))):
+        for off in range(lo, hi, chunk):
+            out.append((off, min(chunk, hi - off), bottom))
+    return out
+
+
+def check_train_flags(args):
+    """Start-up refusals of --eval_match (train.py) -> on?; a Namespace from before the flag: off."""
+    boards = getattr(args, "eval_match", 0)
+    if isinstance(boards, bool) or int(boards) != boards or not 0 <= int(boards) <= 4096:
+        raise ValueError("--eval_match %r: expected a number of boards in [0, 4096] (0 = off)" % (boards,))
+    if int(boards) == 0:
+        return False
+    if int(getattr(args, "eval_every", 0)) <= 0:
+        raise ValueError("--eval_match %d plays its boards at the evaluations: it needs --eval_every STEPS" % int(boards))
+    if getattr(args, "emulator", "synthetic") != "duel":
+        raise ValueError("--eval_match plays the live weights against an earlier copy of themselves on the duel board: it needs "
+                         "--emulator duel (got '%s')" % getattr(args, "emulator", "synthetic"))
+    return True
+
+
+class DeviceMatch(object):
+    """Plays `count` duel boards, one scored episode each, between player X (params_x through ctx_x) and player Y -- nothing
+    crosses to the host but one int32 per block of steps.
+
+    params_*: flat float32 parameter tensors, read at every run().  ctx_*: a hip_ops.Context of that player's geometry that
+    the match may use freely (its acting forwards only); the same unmanaged context may serve both players when their
+    geometries agree -- its forwards repack what they are handed.  seed: the match's own (no-ops and sampled actions);
+    game_seed: the boards'.  Each leg (a side of X) is played in chunks of at most min(ctx.max_batch, MAX_CHUNK) boards,
+    env_offset advancing.  steps_per_launch: steps per block (made even: the ping-pong closes), one hipGraph per (chunk size,
+    offset, leg) when use_graph; record=True runs eagerly and keeps the action trace."""
+
+    def __init__(self, params_x, ctx_x, params_y, ctx_y, count, noops=30, greedy=False, seed=0, game_seed=0, steps_per_launch=16,
+                 record=False, use_graph=True, stream=None, swap_sides=False):
+        import torch
+        from . import hip_ops
+        self.count = check_count(count)
+        if isinstance(noops, bool) or int(noops) != noops or int(noops) < 0:
+            raise ValueError("noops %r: expected an integer >= 0" % (noops,))
+        if int(steps_per_launch) < 1:
+            raise ValueError("steps_per_launch %r: expected a positive integer" % (steps_per_launch,))
+        for who, params, ctx in (("X", params_x, ctx_x), ("Y", params_y, ctx_y)):
+            if ctx.num_actions != duel.NUM_ACTIONS:
+                raise ValueError("player %s: a context of %d actions; the duel board has %d" % (who, ctx.num_actions, duel.NUM_ACTIONS))
+            if params.numel() != ctx.layout["total"]:
+                raise ValueError("player %s: %d parameters; the context's geometry has %d" % (who, params.numel(), ctx.layout["total"]))
+        self.players = ((params_x, ctx_x), (params_y, ctx_y))
+        self.hip_ops = hip_ops
+        self.noops, self.greedy, self.seed, self.game_seed = int(noops), bool(greedy), int(seed), int(game_seed)
+        self.record, self.swap_sides = bool(record), bool(swap_sides)
+        self.block = (int(steps_per_launch) + 1) // 2 * 2
+        self.max_steps = self.noops + MAX_EPISODE_STEPS
+        self.use_graph = bool(use_graph) and not self.record
+        self.chunk = min(self.count, ctx_x.max_batch, ctx_y.max_batch, MAX_CHUNK)
+        dev = params_x.device
+        rows, A = 2 * self.chunk, duel.NUM_ACTIONS
+        self.stacks = [torch.zeros((rows, 84, 84, 4), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.states = [torch.zeros((rows, duel.STATE_WORDS), dtype=torch.int32, device=dev) for _ in range(2)]
+        self.probs = torch.zeros((rows, A), dtype=torch.float32, device=dev)
+        self.actions = torch.zeros((self.block, rows), dtype=torch.int32, device=dev)
+        self.score = torch.zeros(rows, dtype=torch.float32, device=dev)
+        self.length = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.done = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.alive = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
+        self.graphs = {}                                   # (boards of a chunk, offset, X is bottom) -> the captured block
+        self.launches = 0                                  # blocks issued by the last run()
+
+    def _block(self, n, env_offset, x_bottom):
+        """`block` x [the bottom player's forward, the top player's forward, one match step] on n boards, then the counter."""
+        ops = self.hip_ops
+        (pb, cb), (pt, ct) = self.players if x_bottom else self.players[::-1]
+        for j in range(self.block):
+            a, b = j & 1, (j & 1) ^ 1
+            cb.forward(pb, self.stacks[a][:n], probs=self.probs[:n])
+            ct.forward(pt, self.stacks[a][n:2 * n], probs=self.probs[n:2 * n])
+            ops.match_step(self.probs[:2 * n], self.greedy, self.seed, self.noops, self.step, j, self.game_seed, env_offset,
+                           self.states[a][:2 * n], self.states[b][:2 * n], self.stacks[a][:2 * n], self.stacks[b][:2 * n],
+                           self.actions[j][:2 * n], self.score[:2 * n], self.length[:2 * n], self.done[:2 * n], self.alive)
+        ops.counter_add(self.step, self.block)
+
+    def _captured(self, n, env_offset, x_bottom):
+        key = (n, env_offset, x_bottom)
+        if key not in self.graphs:
+            g = self.hip_ops.Graph()
+            g.begin()
+            try:
+                self._block(n, env_offset, x_bottom)
+            except Exception:
+                g.abort()
+                raise
+            g.end()
+            self.graphs[key] = g
+        return self.graphs[key]
+
+    def run(self):
+        """-> (X's scores float32 [count], lengths int32 [count]) in board order; with record=True also the action trace int32
+        [steps, 2 count] (column b: the bottom player of board b, column count + b: its top player; zero where a chunk had
+        stopped earlier) and the per-board no-op counts int32 [count]."""
+        import torch
+        scores, lengths = np.zeros(self.count, dtype=np.float32), np.zeros(self.count, dtype=np.int32)
+        traces = []
+        self.launches = 0
+        with torch.cuda.stream(self.stream):
+            for env_offset, n, x_bottom in legs(self.count, self.chunk, self.swap_sides):
+                self.hip_ops.duel_reset(self.game_seed, env_offset, self.states[0][:2 * n], self.stacks[0][:2 * n])
+                for t in (self.score, self.length, self.done, self.step):
+                    t.zero_()
+                self.alive.fill_(2 * n)
+                trace, steps = [], 0
+                while steps < self.max_steps:
+                    if self.use_graph:
+                        self._captured(n, env_offset, x_bottom).launch()
+                    else:
+                        self._block(n, env_offset, x_bottom)
+                    steps += self.block
+                    self.launches += 1
+                    if self.record:
+                        trace.append(self.actions[:, :2 * n].cpu().numpy().copy())
+                    if int(self.alive.cpu().item()) == 0:          # (synchronises the stream: the block has run)
+                        break
+                mine = slice(0, n) if x_bottom else slice(n, 2 * n)
+                scores[env_offset:env_offset + n] = self.score[mine].cpu().numpy()
+                lengths[env_offset:env_offset + n] = self.length[mine].cpu().numpy()
+                traces.append((env_offset, n, np.concatenate(trace) if trace else None))
+        if not self.record:
+            return scores, lengths
+        full = np.zeros((max(len(t) for _, _, t in traces), 2 * self.count), dtype=np.int32)
+        for off, n, t in traces:
+            full[:len(t), off:off + n] = t[:, :n]
+            full[:len(t), self.count + off:self.count + off + n] = t[:, n:]
+        return scores, lengths, full, eval_noops(self.seed, np.arange(self.count), self.noops)
+
+    def summary(self, scores, lengths, seconds):
+        """evaluator.summary's fields, of X's scores, plus the fractions of boards X won, drew and lost."""
+        scores = np.asarray(scores)
+        return dict(count=self.count, greedy=self.greedy, mean=float(np.mean(scores)), min=float(np.min(scores)),
+                    max=float(np.max(scores)), std=float(np.std(scores)), mean_length=float(np.mean(lengths)),
+                    seconds=float(seconds), wins=float(np.mean(scores > 0)), draws=float(np.mean(scores == 0)),
+                    losses=float(np.mean(scores < 0)))
+
+    def timed_run(self):
+        """run() with its wall time -> (scores, lengths, seconds)."""
+        start = time.time()
+        scores, lengths = self.run()[:2]
+        return scores, lengths, time.time() - start
+
+    def close(self):
+        for g in self.graphs.values():
+            g.close()
+        self.graphs = {}

@@ -763,10 +763,16 @@ class PAACLearner(ActorLearner):
         from . import evaluation
         evaluator = eval_ctx = None
         eval_every = int(getattr(args, "eval_every", 0)) if evaluation.check_train_flags(args, world) else 0
+        # --eval_match: at every evaluation the live weights also play duel boards against a device copy of the weights of the
+        # previous evaluation (paac_amd/match.py: DeviceMatch) -- on the evaluator's context, its own streams and buffers
+        from . import match
+        matcher = snapshot = None
+        match_boards = int(getattr(args, "eval_match", 0)) if match.check_train_flags(args) else 0
         if eval_every:
             count = int(getattr(args, "eval_count", 64))
             seed = int(getattr(args, "random_seed", 3)) + 1
-            eval_ctx = hip_ops.Context(self.network.arch_id, self.num_actions, max_batch=min(count, evaluation.MAX_CHUNK),
+            eval_ctx = hip_ops.Context(self.network.arch_id, self.num_actions,
+                                       max_batch=min(max(count, match_boards), evaluation.MAX_CHUNK),
                                        device_index=self.torch_device.index or 0)
             spec = eval_env_spec(self.environment_creator.device_env_spec, seed=seed, single_life=False)
             scripted = self.environment_creator.device_env_spec.get("kind") in PAIRED_KINDS       # duel: scored on rally
@@ -774,6 +780,14 @@ class PAACLearner(ActorLearner):
                                                    greedy=bool(getattr(args, "eval_greedy", True)), seed=seed,
                                                    use_graph=getattr(args, "use_graph", True), stream=self.rollout.stream)
             next_eval = (self.global_step // eval_every + 1) * eval_every
+            if match_boards:
+                with torch.cuda.stream(self.rollout.stream):
+                    snapshot = self.network.params.clone()          # the weights the run started or resumed from
+                self.rollout.stream.synchronize()
+                snapshot_step = int(self.global_step)
+                matcher = match.DeviceMatch(self.network.params, eval_ctx, snapshot, eval_ctx, match_boards, noops=30,
+                                            greedy=bool(getattr(args, "eval_greedy", True)), seed=seed, game_seed=seed,
+                                            use_graph=getattr(args, "use_graph", True), stream=self.rollout.stream)
         while self.global_step < self.max_global_steps:
             if next_check is not None and counter >= next_check:
                 if next_check == 1:
@@ -834,8 +848,26 @@ class PAACLearner(ActorLearner):
                 if metrics is not None:
                     metrics.write("eval", global_step=int(self.global_step), **record)
                     metrics.flush()
+                if matcher is not None:
+                    scores, lengths, seconds = matcher.timed_run()
+                    record = matcher.summary(scores, lengths, seconds)
+                    logging.info("Match at {} steps against the weights of {} steps: {} boards ({}), mean {:.3f}, wins / draws / "
+                                 "losses {:.3f} / {:.3f} / {:.3f}, mean length {:.1f}, {:.3f} s"
+                                 .format(self.global_step, snapshot_step, record["count"],
+                                         "greedy" if record["greedy"] else "sampled", record["mean"], record["wins"],
+                                         record["draws"], record["losses"], record["mean_length"], seconds))
+                    if metrics is not None:
+                        metrics.write("match", global_step=int(self.global_step), opponent="previous",
+                                      opponent_global_step=snapshot_step, **record)
+                        metrics.flush()
+                    with torch.cuda.stream(self.rollout.stream):
+                        snapshot.copy_(self.network.params)          # the next match's opponent
+                    self.rollout.stream.synchronize()
+                    snapshot_step = int(self.global_step)
             self.save_vars()          # _sync_device() flushes the rollout first when a checkpoint is due
         self.rollout.synchronize()
+        if matcher is not None:
+            matcher.close()
         if evaluator is not None:
             evaluator.close()
             eval_ctx.close()

@@ -12,6 +12,10 @@ environment's score is frozen when its first episode ends.
 --device_environments true (runs of --emulator catch|bricks|rally, and duel runs as rally) plays the games on the GPU instead
 (paac_amd/evaluation.py: DeviceEvaluator): -tc up to 4096, --greedy true for the argmax action, --eval_seed for the game instances, the no-op counts
 and the sampled actions; the summary gains a 'Mean length' line.  --gif_name is refused there.
+
+--versus FOLDER_B (with --device_environments true; runs of --emulator rally|duel) plays -tc duel boards between the two folders'
+checkpoints instead (paac_amd/match.py: DeviceMatch), -f's agent being player X: the summary is of its scores and gains a
+'Wins / Draws / Losses' line.
 """
 import argparse
 import os
@@ -40,6 +44,10 @@ FLAGS = (
     (("--eval_seed",), "eval_seed", None, int, False,
      "with --device_environments true: seed of the game instances, the no-op counts and the sampled actions (default: the "
      "training run's random_seed)"),
+    (("--versus",), "versus", None, str, False,
+     "with --device_environments true: a second training folder; -tc duel boards are played between the two checkpoints "
+     "(paac_amd/match.py; --emulator rally|duel runs only), -f's agent on the bottom of the first half of the boards and on the "
+     "top of the rest"),
 )
 
 
@@ -95,10 +103,11 @@ def evaluate(network, env_creator, session, test_count, noops=30, max_steps=None
     return scores
 
 
-def restore_settings(cli):
-    """The training run's args.json with the evaluation overrides of test.py:32-48 applied on top."""
+def restore_settings(cli, folder=None):
+    """The training run's args.json (of cli.folder, or of `folder`) with the evaluation overrides of test.py:32-48 applied on
+    top."""
     settings = argparse.Namespace(**vars(cli))
-    for k, v in logger_utils.load_args(os.path.join(cli.folder, 'args.json')).items():
+    for k, v in logger_utils.load_args(os.path.join(folder or cli.folder, 'args.json')).items():
         setattr(settings, k, v)
     overrides = dict(device=cli.device, debugging_folder='/tmp/logs', max_global_steps=0, random_start=False,
                      single_life_episodes=False, actor_id=0)
@@ -142,6 +151,70 @@ def evaluate_on_device(cli, args):
         ctx.close()
 
 
+def check_versus_flags(cli):
+    """Start-up refusals of --versus (before anything touches the GPU)."""
+    if not cli.device_environments:
+        raise ValueError("--versus plays its boards on the GPU: it needs --device_environments true")
+    if cli.gif_name:
+        raise ValueError("--versus cannot be combined with --gif_name: the boards are on the GPU and there are no host screens "
+                         "to record")
+    check_device_flags(cli)
+
+
+def check_versus_runs(runs):
+    """runs: [(folder, restored settings)] of the two players -> a ValueError naming the folder that cannot play a match."""
+    from . import match
+    from .build import parse_user_arch
+    user = []
+    for folder, args in runs:
+        if getattr(args, "emulator", "synthetic") not in match.MATCH_KINDS:
+            raise ValueError("--versus: %s is a run of --emulator %s; a match is played by agents of the duel board: --emulator "
+                             "rally|duel" % (folder, getattr(args, "emulator", "synthetic")))
+        if getattr(args, "user_arch", ""):
+            user.append((folder, parse_user_arch(args.user_arch)))
+    if len(user) == 2 and user[0][1] != user[1][1]:
+        raise ValueError("--versus: %s was trained with --user_arch %s and %s with another one: a process loads ONE kernel "
+                         "library, which serves one user architecture beside NIPS and NATURE"
+                         % (user[1][0], runs[1][1].user_arch, user[0][0]))
+
+
+def match_on_device(cli):
+    """--versus: a DeviceMatch (paac_amd/match.py) between the checkpoints of cli.folder (X) and cli.versus (Y) ->
+    (X's scores float32 [test_count], lengths int32 [test_count], the summary's fields)."""
+    from . import evaluation, match
+    runs = [(folder, restore_settings(cli, folder)) for folder in (cli.folder, cli.versus)]
+    check_versus_runs(runs)
+    seed = cli.eval_seed if cli.eval_seed is not None else int(getattr(runs[0][1], "random_seed", 3))
+    # both creators before the first network: a user architecture chooses the library the process loads
+    creators = [get_network_and_environment_creator(args, random_seed=seed) for _, args in runs]
+    players, opened = [], []
+    try:
+        for (folder, _), (network_creator, env_creator) in zip(runs, creators):
+            network = network_creator()
+            ctx = hip_ops.Context(network.arch_id, env_creator.num_actions, max_batch=min(cli.test_count, evaluation.MAX_CHUNK),
+                                  device_index=network.torch_device.index or 0)
+            opened.append(ctx)
+            session = Session(network, ctx)
+            opened.append(session)
+            network.init(os.path.join(folder, 'checkpoints'), network.make_saver(), session)
+            players += [network.params, ctx]
+        game = match.DeviceMatch(*players, count=cli.test_count, noops=cli.noops, greedy=cli.greedy, seed=seed, game_seed=seed)
+        opened.append(game)
+        scores, lengths, seconds = game.timed_run()
+        return scores, lengths, game.summary(scores, lengths, seconds)
+    finally:
+        for x in reversed(opened):
+            x.close()
+
+
+def print_match_summary(cli, record):
+    print('Performed {} matches: {} vs {}'.format(cli.test_count, cli.folder, cli.versus))
+    for label, key in (('Mean', 'mean'), ('Min', 'min'), ('Max', 'max'), ('Std', 'std')):
+        print('{0}: {1:.2f}'.format(label, record[key]))
+    print('Wins / Draws / Losses: {0:.3f} / {1:.3f} / {2:.3f}'.format(record['wins'], record['draws'], record['losses']))
+    print('Mean length: {0:.2f}'.format(record['mean_length']))
+
+
 def print_summary(args, rewards, lengths=None):
     print('Performed {} tests for {}.'.format(args.test_count, args.game))
     for label, stat in (('Mean', np.mean), ('Min', np.min), ('Max', np.max), ('Std', np.std)):
@@ -152,6 +225,11 @@ def print_summary(args, rewards, lengths=None):
 
 def main(argv=None):
     cli = get_arg_parser().parse_args(argv)
+    if cli.versus is not None:
+        check_versus_flags(cli)
+        rewards, _, record = match_on_device(cli)
+        print_match_summary(cli, record)
+        return rewards
     if cli.device_environments:
         check_device_flags(cli)
         args = restore_settings(cli)

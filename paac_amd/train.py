@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import environment_creator, evaluation, logger_utils, parallel
+from . import environment_creator, evaluation, logger_utils, match, parallel
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -123,6 +123,12 @@ BUILD_FLAGS = (
     (("--eval_count",), "eval_count", 64, int, "environments (one episode each) of an --eval_every evaluation, 1 to 4096"),
     (("--eval_greedy",), "eval_greedy", True, bool_arg,
      "--eval_every evaluations take the argmax action (true) or sample from the policy on a Philox stream of their own (false)"),
+    (("--eval_match",), "eval_match", 0, int,
+     "--emulator duel with --eval_every: at every evaluation the live weights also play this many duel boards (1 to 4096; 0 = "
+     "off), one episode each, against a copy of the weights taken at the previous evaluation (at the first one: the weights "
+     "the run started or resumed from), on the GPU (paac_amd/match.py), with --eval_greedy, up to 30 no-op steps and seed "
+     "random_seed + 1, and a 'match' record goes to metrics.jsonl: the self-play learning curve.  Training is bit-identical "
+     "with it on or off"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),
@@ -204,6 +210,7 @@ def main(args):
     world = parallel.init_from_env(args)          # before anything touches a GPU
     logging.debug('Configuration: %s', args)
     check_eval_flags(args, world)                 # --eval_every's refusals, before a learner exists
+    match.check_train_flags(args)                 # ... and --eval_match's
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)
     setup_kill_signal_handler(learner)

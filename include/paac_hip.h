@@ -679,6 +679,29 @@ int paac_match_step(const float* probs, int N, int A, int greedy, uint64_t eval_
                     uint64_t step_offset, uint64_t env_seed, uint32_t env_offset, const int32_t* state_in, int32_t* state_out,
                     const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out, float* score, int32_t* length,
                     int32_t* done, int32_t* alive, paac_stream_t stream);
+/* Duel against a pool of past selves (--duel_pool; spec: paac_amd/duel_pool.py): one training step of N BOARDS in one launch,
+ * behind the learner's acting forward and sampler (actions [N]) and a frozen opponent's acting forward (ghost_probs [N, A],
+ * A must be 6).  Every learner row is the bottom player of its own board; the top player is a ghost row of the opponent.
+ * One pooled step is paac_duel_step on 2N rows with the ghosts as rows [N, 2N): the board key is g = env_offset + b.
+ *   state    i32 [N,12]: the board in the bottom player's frame, the only record kept (the ghost's is its mirror)
+ *   ghost    always sampled: paac_eval_step's inverse CDF on ghost_probs[b] with u = philox(ctr = {g, t lo, t hi, 0x44500001};
+ *            key = sampler_seed), t = *step_base_dev + step_offset (base NULL = 0); written to ghost_actions_out[b] (i32 [N]:
+ *            with `actions` it replays the step on the host twin)
+ *   learner  stack_in -> stack_out (and stack_out2), state_out (and state_out2), the records of rec (rec->truncs nullable):
+ *            what paac_duel_step writes for a bottom row
+ *   ghosts   ghost_stack_in -> ghost_stack_out (and ghost_stack_out2, nullable): the plane a top row sees; nothing else
+ * paac_duel_ghost_reset: episode 0's start boards and an empty history on both sides -- paac_duel_reset on 2N rows, split.
+ * Refused with a message naming the argument, without a launch: N < 1, A != 6, a null pointer (all but step_base_dev, the
+ * second outputs, rec->finished and rec->truncs), an input that is one of its outputs, learner and ghost stacks that are the
+ * same buffer.  Both are capturable. */
+int paac_duel_ghost_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                          uint8_t* ghost_stack_out, paac_stream_t stream);
+int paac_duel_ghost_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const float* ghost_probs, int A,
+                         uint64_t sampler_seed, const uint64_t* step_base_dev, uint64_t step_offset, const int32_t* state_in,
+                         int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                         uint8_t* stack_out2, const uint8_t* ghost_stack_in, uint8_t* ghost_stack_out,
+                         uint8_t* ghost_stack_out2, const paac_env_records* rec, int32_t* ghost_actions_out,
+                         paac_stream_t stream);
 
 /* paac_sample_mt + paac_synth_step (path A) in ONE launch: workgroup 0 samples (numpy-parity MT19937 stream) and does
  * the per-env bookkeeping while the other workgroups shift the observation stacks (stack_out2, nullable: a second copy

@@ -180,6 +180,11 @@ for _game in ("catch", "bricks", "rally"):
 # the paired game (hip_ops.PAIRED_GAMES): catch's reset list; the step takes its records as paac_game_step does, as one block
 _SIGNATURES["paac_duel_reset"] = _SIGNATURES["paac_catch_reset"]
 _SIGNATURES["paac_duel_step"] = (c_int, [c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_void_p])
+# --duel_pool (paac_amd/duel_pool.py): boards with a ghost row on top -- reset: state, learner stack, ghost stack; step: actions,
+# ghost probs, A, sampler seed, tick pointer and offset, 3 state and 6 stack pointers, the records block, the ghost actions
+_SIGNATURES["paac_duel_ghost_reset"] = (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p])
+_SIGNATURES["paac_duel_ghost_step"] = (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_uint64] +
+                                       [c_void_p] * 9 + [POINTER(EnvRecords), c_void_p, c_void_p])
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -1525,6 +1525,78 @@ __global__ __launch_bounds__(256) void match_step_kernel(const float* __restrict
   reinterpret_cast<uint4*>(stack_out)[th.quad] = G::shift_quad(s, th.q, old, term);
 }
 
+// =============================================================================================
+// Duel against a pool of past selves (spec: paac_amd/duel_pool.py): one training step of N BOARDS per launch.  Every learner
+// row is the bottom player of its own board; the top player is a ghost, a row of a frozen earlier copy of the policy, whose
+// probabilities ghost_probs [N, 6] a second context's forward wrote.  The shape and reasons of the kernels above: grid (2N, 7),
+// 256 threads, 252 own one quad, the stack quad requested first by every thread, one 16-byte store (and the optional wrap
+// store), no LDS.  Workgroup column e < N is the learner row of board e, column e >= N the ghost of board e - N.  Every
+// workgroup of board b asks up front for state_in[b] -- the board in the bottom player's frame, the only record kept --
+// actions[b], the six floats of ghost_probs[b] (uniform: scalar loads) and the tick, works out the ghost's action (always
+// sampled: match_action's inverse CDF on one Philox block, counter {g, t lo, t hi, kGhostStream}, key the sampler's seed) and
+// the board step (DuelGame::advance as a bottom row).  A learner column does what game_step_kernel<DuelGame> does for a bottom
+// row, and thread 0 of its band 0 also writes the ghost's action (the plane a rollout is replayed from).  A ghost column pushes
+// the plane of duel_mirror(new record) -- in registers, never stored -- into the ghost's stack and writes nothing else; a
+// terminal step drops the history on both sides.  Nothing the launch writes is read by it.
+// state_in == nullptr: reset -- episode 0's start board, an empty history on both sides; actions / ghost_probs / the stacks
+// read / the records / ghost_actions_out are not touched.
+// paac_amd/duel_pool.py: GHOST_STREAM is the same number.
+constexpr uint32_t kGhostStream = 0x44500001u;
+
+__global__ __launch_bounds__(256) void ghost_step_kernel(uint64_t seed, uint32_t env_offset, int N,
+                                                         const int32_t* __restrict__ actions,
+                                                         const float* __restrict__ ghost_probs, uint64_t sampler_seed,
+                                                         const uint64_t* __restrict__ step_base, uint64_t step_off,
+                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
+                                                         int32_t* __restrict__ state_out2,
+                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                         uint32_t* __restrict__ stack_out2,
+                                                         const uint32_t* __restrict__ ghost_stack_in,
+                                                         uint32_t* __restrict__ ghost_stack_out,
+                                                         uint32_t* __restrict__ ghost_stack_out2, const EnvRecords rec,
+                                                         int32_t* __restrict__ ghost_actions_out) {
+  typedef DuelGame G;
+  const QuadThread th = quad_thread();
+  const bool ghost = th.e >= N;                            // uniform in the workgroup
+  const int b = ghost ? th.e - N : th.e;
+  // the column's own stack buffers hold N rows each: the quad indices count from the board, not from the column
+  const long shift = ghost ? (long)N * (OBS_PIX / 4) : 0l;
+  uint4 old = make_uint4(0u, 0u, 0u, 0u);
+  G::State s;
+  float r = 0.f;
+  bool term = false, trunc = false;
+  int a_ghost = 0;
+  const uint32_t g = env_offset + (uint32_t)b;             // the BOARD's key
+  if (state_in) {
+    // every thread loads (the four that own no quad read the band's first one): see game_step_kernel
+    old = reinterpret_cast<const uint4*>(ghost ? ghost_stack_in : stack_in)[th.load_quad - shift];
+    const uint64_t t = (step_base ? *step_base : 0ull) + step_off;
+    const MatchRow probs = match_row(ghost_probs, b);
+    const G::State s0 = G::load(state_in, b);
+    const int a_learner = actions[b];
+    a_ghost = match_action(probs, 0, sampler_seed, g, t, kGhostStream);
+    s = G::advance(seed, g, s0, a_learner, a_ghost, /*top=*/false, &r, &term, &trunc);
+  } else {
+    s = duel_start_board(seed, g, 0);
+  }
+  if (!ghost && th.band == 0 && th.i == 0) {
+    G::store(state_out, b, s);
+    if (state_out2) G::store(state_out2, b, s);
+    if (state_in) {
+      env_bookkeep(r, term, b, rec.ep_reward[b], rec.ep_len[b], rec);
+      if (rec.truncs) rec.truncs[b] = trunc ? 1.f : 0.f;
+      ghost_actions_out[b] = a_ghost;
+    }
+  }
+  if (!th.owner) return;
+  // the ghost sees the board from the top: the mirrored record's plane (selects only: `ghost` is uniform)
+  const uint4 outv = RallyGame::shift_quad(duel_mirror(s, ghost), th.q, old, term);
+  uint32_t* __restrict__ out = ghost ? ghost_stack_out : stack_out;
+  uint32_t* __restrict__ out2 = ghost ? ghost_stack_out2 : stack_out2;
+  reinterpret_cast<uint4*>(out)[th.quad - shift] = outv;
+  if (out2) reinterpret_cast<uint4*>(out2)[th.quad - shift] = outv;   // second copy (the observation ring's wrap-around slot)
+}
+
 // One (environment, band) unit of the step's frame work: path B's raw screen pair (the preprocess launch follows) or the shift.
 __device__ __forceinline__ void step_unit(const SynthStep& st, uint64_t id, int unit) {
   if (st.raw) synth_raw_unit(st.seed, st.env_offset, id, unit, st.raw);
@@ -2835,6 +2907,62 @@ int paac_match_step(const float* probs, int N, int A, int greedy, uint64_t eval_
   launch_k(match_step_kernel, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, greedy, eval_seed, noops, step_base_dev,
            step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in, (uint32_t*)stack_out,
            actions_out, score, length, done, alive);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// Duel against a pool of past selves (spec: paac_amd/duel_pool.py): N boards, the learner at the bottom of each, a ghost row
+// of a frozen policy at the top.  Reset and step are ghost_step_kernel, as the games' are game_step_kernel.
+int paac_duel_ghost_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                          uint8_t* ghost_stack_out, paac_stream_t stream) {
+  PAAC_REQUIRE(N >= 1, "paac_duel_ghost_reset: N=%d boards: expected at least 1", N);
+  PAAC_REQUIRE(state_out, "paac_duel_ghost_reset: null state_out");
+  PAAC_REQUIRE(stack_out, "paac_duel_ghost_reset: null stack_out");
+  PAAC_REQUIRE(ghost_stack_out, "paac_duel_ghost_reset: null ghost_stack_out");
+  PAAC_REQUIRE(stack_out != ghost_stack_out, "paac_duel_ghost_reset: stack_out and ghost_stack_out are the same buffer");
+  hipLaunchKernelGGL(ghost_step_kernel, dim3(2 * N, PRE_BANDS), dim3(256), 0, (hipStream_t)stream, seed, env_offset, N,
+                     (const int32_t*)nullptr, (const float*)nullptr, (uint64_t)0, (const uint64_t*)nullptr, (uint64_t)0,
+                     (const int32_t*)nullptr, state_out, (int32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)stack_out,
+                     (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)ghost_stack_out, (uint32_t*)nullptr, EnvRecords{},
+                     (int32_t*)nullptr);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_duel_ghost_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const float* ghost_probs, int A,
+                         uint64_t sampler_seed, const uint64_t* step_base_dev, uint64_t step_offset, const int32_t* state_in,
+                         int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                         uint8_t* stack_out2, const uint8_t* ghost_stack_in, uint8_t* ghost_stack_out,
+                         uint8_t* ghost_stack_out2, const paac_env_records* rec, int32_t* ghost_actions_out,
+                         paac_stream_t stream) {
+  PAAC_REQUIRE(N >= 1, "paac_duel_ghost_step: N=%d boards: expected at least 1", N);
+  PAAC_REQUIRE(A == kMatchActions, "paac_duel_ghost_step: A=%d is not the 6 actions of the duel board", A);
+  PAAC_REQUIRE(actions, "paac_duel_ghost_step: null actions");
+  PAAC_REQUIRE(ghost_probs, "paac_duel_ghost_step: null ghost_probs");
+  PAAC_REQUIRE(state_in && state_out, "paac_duel_ghost_step: null state_in / state_out");
+  PAAC_REQUIRE(stack_in && stack_out, "paac_duel_ghost_step: null stack_in / stack_out");
+  PAAC_REQUIRE(ghost_stack_in && ghost_stack_out, "paac_duel_ghost_step: null ghost_stack_in / ghost_stack_out");
+  PAAC_REQUIRE(rec, "paac_duel_ghost_step: null records");
+  PAAC_REQUIRE(rec->rewards && rec->masks && rec->ep_reward && rec->ep_len,
+               "paac_duel_ghost_step: null records rewards / masks / ep_reward / ep_len");
+  PAAC_REQUIRE(ghost_actions_out, "paac_duel_ghost_step: null ghost_actions_out");
+  PAAC_REQUIRE(state_in != state_out && state_in != state_out2,
+               "paac_duel_ghost_step: state_in is state_out or state_out2: the step cannot run in place (every band workgroup "
+               "of a board reads state_in)");
+  PAAC_REQUIRE(stack_in != stack_out && stack_in != stack_out2,
+               "paac_duel_ghost_step: stack_in is stack_out or stack_out2: the step cannot run in place");
+  PAAC_REQUIRE(ghost_stack_in != ghost_stack_out && ghost_stack_in != ghost_stack_out2,
+               "paac_duel_ghost_step: ghost_stack_in is ghost_stack_out or ghost_stack_out2: the step cannot run in place");
+  PAAC_REQUIRE(stack_in != ghost_stack_out && stack_in != ghost_stack_out2 && ghost_stack_in != stack_out &&
+               ghost_stack_in != stack_out2 && stack_out != ghost_stack_out,
+               "paac_duel_ghost_step: the learner's and the ghost's stack buffers overlap");
+  const EnvRecords r{{rec->rewards, rec->masks, rec->ep_reward, rec->ep_len, (FinishedRing*)rec->finished}, rec->truncs};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, 2 * N, s);
+  launch_k(ghost_step_kernel, dim3(2 * N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, ghost_probs,
+           sampler_seed, step_base_dev, step_offset, state_in, state_out, state_out2, (const uint32_t*)stack_in,
+           (uint32_t*)stack_out, (uint32_t*)stack_out2, (const uint32_t*)ghost_stack_in, (uint32_t*)ghost_stack_out,
+           (uint32_t*)ghost_stack_out2, r, ghost_actions_out);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -107,6 +107,9 @@ class EnvironmentCreator(object):
         if self._game in DEVICE_GAMES:
             return dict(kind=self._game, seed=self._seed(), **self._game_options())
         if self._game in PAIRED_GAMES:
-            return dict(kind=self._game, seed=self._seed())
+            # --duel_pool K (paac_amd/duel_pool.py): the rows are boards played against a pool of frozen opponents; the key
+            # exists only with the pool on (read by the training rollout alone: evaluation and matches never see it)
+            pool = int(getattr(self.args, "duel_pool", 0) or 0)
+            return dict(kind=self._game, seed=self._seed(), **(dict(pool=pool) if pool > 0 else {}))
         return dict(kind="synthetic", seed=self._seed(), terminal_threshold=terminal_threshold(self._terminal_p()),
                     raw_frames=self._raw())

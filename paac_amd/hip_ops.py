@@ -856,6 +856,57 @@ def duel_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_ou
         ctypes.byref(rec), _stream()), "paac_duel_step")
 
 
+def duel_ghost_reset(seed, env_offset, state_out, stack_out, ghost_stack_out):
+    """paac_duel_ghost_reset (include/paac_hip.h; spec in paac_amd/duel_pool.py): N boards, the learner's rows and the ghosts'
+    observations -- duel_reset on 2N rows, split."""
+    words = DUEL_STATE_WORDS
+    N = stack_out.shape[0]
+    for nm, t in (("stack_out", stack_out), ("ghost_stack_out", ghost_stack_out)):
+        if tuple(t.shape) != (N,) + OBS_SHAPE:
+            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
+    if tuple(state_out.shape) != (N, words):
+        raise ValueError("state_out must be [%d,%d], got %s" % (N, words, tuple(state_out.shape)))
+    _lib.check(_lib.load().paac_duel_ghost_reset(
+        int(seed), int(env_offset), N, _ptr(state_out, torch.int32, N * words, "state_out"),
+        _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(ghost_stack_out, torch.uint8, N * 28224, "ghost_stack_out"),
+        _stream()), "paac_duel_ghost_reset")
+
+
+def duel_ghost_step(seed, env_offset, actions, ghost_probs, sampler_seed, step_base_dev, step_offset, state_in, state_out,
+                    stack_in, stack_out, ghost_stack_in, ghost_stack_out, ghost_actions_out, rewards_out, masks_out, ep_reward,
+                    ep_len, finished=None, stack_out2=None, state_out2=None, ghost_stack_out2=None, truncs_out=None):
+    """paac_duel_ghost_step: one pooled step of N boards -- actions int32 [N] the learner's (bottom) rows', ghost_probs
+    float32 [N, 6] the frozen opponent's forward on ghost_stack_in; the ghost's action is sampled on its own Philox stream at
+    tick *step_base_dev + step_offset (None: 0) and written to ghost_actions_out int32 [N].  Records and second outputs as
+    duel_step's, for the learner's rows; the ghosts get their next observations (and ghost_stack_out2) only.  Shapes are
+    checked here; the library refuses N < 1, A != 6, null pointers and in-place buffers before any launch."""
+    words = DUEL_STATE_WORDS
+    N = actions.shape[0]
+    out, out2, *records = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
+    for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
+        if t is not None and tuple(t.shape) != (N, words):
+            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
+    for nm, t in (("ghost_stack_in", ghost_stack_in), ("ghost_stack_out", ghost_stack_out), ("ghost_stack_out2", ghost_stack_out2)):
+        if t is not None and tuple(t.shape) != (N,) + OBS_SHAPE:
+            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
+    if ghost_probs.dim() != 2 or ghost_probs.shape[0] != N:
+        raise ValueError("ghost_probs must be [%d, A], got %s" % (N, tuple(ghost_probs.shape)))
+    A = ghost_probs.shape[1]
+    if not 0 <= int(env_offset) <= 0xFFFFFFFF - N:
+        raise ValueError("duel_ghost_step: env_offset %r" % (env_offset,))
+    rec = _lib.EnvRecords(*records, _ptr(truncs_out, torch.float32, N, "truncs_out", True))
+    _lib.check(_lib.load().paac_duel_ghost_step(
+        int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
+        _ptr(ghost_probs, torch.float32, N * A, "ghost_probs"), A, int(sampler_seed) & 0xFFFFFFFFFFFFFFFF,
+        _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
+        _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
+        _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), out, out2,
+        _ptr(ghost_stack_in, torch.uint8, N * 28224, "ghost_stack_in"),
+        _ptr(ghost_stack_out, torch.uint8, N * 28224, "ghost_stack_out"),
+        _ptr(ghost_stack_out2, torch.uint8, N * 28224, "ghost_stack_out2", True), ctypes.byref(rec),
+        _ptr(ghost_actions_out, torch.int32, N, "ghost_actions_out"), _stream()), "paac_duel_ghost_step")
+
+
 def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
               stack_in, stack_out, actions_out, score, length, done, alive):
     """One evaluation step of N environments of `game` ('catch' / 'bricks' / 'rally') on probs [N, A] (include/paac_hip.h:

@@ -33,6 +33,24 @@ MATCH_KINDS = ("rally", "duel")        # the runs whose agents play this board: 
 MAX_EPISODE_STEPS = duel.MAX_STEPS
 
 
+def sampled_on_stream(probs_f32, seed, step, board_ids, stream):
+    """-> int32 [n]: evaluation.eval_action's sampling rule on probs_f32 [n, A] -- the inverse CDF over float32 running sums,
+    the first hit keeping the action -- with u from Philox word 0 of counter (g, step lo, step hi, stream), key `seed`.  The
+    top players' rule of a match, and the ghosts' of a pooled duel step (paac_amd/duel_pool.py) on its own stream."""
+    p = np.asarray(probs_f32, dtype=np.float32)
+    n, A = p.shape
+    u = (philox_word0(seed, step, board_ids, stream) >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    acts = np.full(n, A - 1, dtype=np.int32)
+    chosen = np.zeros(n, dtype=bool)
+    c = np.zeros(n, dtype=np.float32)
+    for j in range(A - 1):                                   # eval_action's running sums
+        c = (c + p[:, j]).astype(np.float32)
+        hit = (~chosen) & (u < c)
+        acts[hit] = j
+        chosen |= hit
+    return acts
+
+
 def match_actions(probs_f32, seed, step, board_ids, greedy):
     """-> int32 [2n]: the action of every row of probs_f32 [2n, A] at step `step` (past the boards' no-ops); board_ids [n] are
     the boards' keys g, rows [0, n) their bottom players and rows [n, 2n) their top players."""
@@ -44,17 +62,7 @@ def match_actions(probs_f32, seed, step, board_ids, greedy):
     bottom = eval_action(p[:n], seed, step, board_ids, greedy)
     if greedy:
         return np.concatenate([bottom, np.argmax(p[n:], axis=1).astype(np.int32)])
-    A = p.shape[1]
-    u = (philox_word0(seed, step, board_ids, MATCH_STREAM_TOP) >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    top = np.full(n, A - 1, dtype=np.int32)
-    chosen = np.zeros(n, dtype=bool)
-    c = np.zeros(n, dtype=np.float32)
-    for j in range(A - 1):                                   # eval_action's running sums, on the top player's stream
-        c = (c + p[n:, j]).astype(np.float32)
-        hit = (~chosen) & (u < c)
-        top[hit] = j
-        chosen |= hit
-    return np.concatenate([bottom, top])
+    return np.concatenate([bottom, sampled_on_stream(p[n:], seed, step, board_ids, MATCH_STREAM_TOP)])
 
 
 def replay_match(game_seed, env_offset, actions_trace, noops):

@@ -68,6 +68,7 @@ def eval_env_spec(env_spec, **changes):
 class DeviceRollout(object):
     """Device-resident rollout/update cycle for N local environments x T steps."""
     truncs = None      # --bootstrap_truncated: the [T, N] truncation plane, allocated by __init__ only where it applies
+    pool = None        # --duel_pool: the duel_pool.DevicePool, created by __init__ only with the pool on
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
                  total_envs=None):
@@ -122,6 +123,21 @@ class DeviceRollout(object):
         # goes through the game's own entry and every returns launch is the one it always was.  Shard-local, like the masks.
         if getattr(L, "bootstrap_truncated", False) and self.stateful and self.stateful["truncates"]:
             self.truncs = torch.zeros((T, N), dtype=torch.float32, device=dev)
+        # --duel_pool K (env_spec["pool"], paac_amd/duel_pool.py): the N rows are N boards, each learner row at the bottom and a
+        # ghost row of a frozen opponent at the top.  The ghosts have an observation ring of their own, slot for slot like
+        # self.states (wrap output included), their probabilities and the actions they took (the plane a rollout is replayed
+        # from on the twin), and the pool its tensors and a context of its own.  Off: none of this exists
+        if env_spec.get("kind") == "duel" and int(env_spec.get("pool", 0) or 0) > 0:
+            from . import duel_pool
+            largs = getattr(L, "args", None)
+            self.ghost_states = torch.zeros((2 * T + 1, N, 84, 84, 4), dtype=torch.uint8, device=dev)
+            self.ghost_probs = torch.zeros((N, A), dtype=torch.float32, device=dev)
+            self.ghost_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
+            self.pool = duel_pool.DevicePool(L.network.params, L.network.arch_id, A, N, int(env_spec["pool"]),
+                                             int(getattr(largs, "duel_pool_every", 102400)),
+                                             float(getattr(largs, "duel_pool_latest_p", 0.5)),
+                                             int(getattr(largs, "random_seed", env_spec["seed"])), int(L.global_step),
+                                             device_index=dev.index or 0)
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
         if env_spec.get("raw_frames"):
@@ -184,7 +200,9 @@ class DeviceRollout(object):
         self.route = self._route()
         # what step t records, as every route's step call takes it (the per-cycle counterpart: cycle_tick above)
         self.records = [(self.rewards[t], self.masks[t], self.ep_reward, self.ep_len, self.finished) for t in range(T)]
-        if self.stateful:
+        if self.pool is not None:
+            hip_ops.duel_ghost_reset(env_spec["seed"], self.env_offset, self.env_state[0], self.states[0], self.ghost_states[0])
+        elif self.stateful:
             self.stateful["reset"](env_spec["seed"], self.env_offset, self.env_state[0], self.states[0])
         else:
             hip_ops.synth_reset(env_spec["seed"], self.env_offset, self.states[0], self.raw)
@@ -244,7 +262,18 @@ class DeviceRollout(object):
                 L.ctx.forward(params, obs, probs=self.probs, values=self.values[t])
                 if route != "fused":
                     hip_ops.sample_mt(self.probs, self.mt_state, self.mt_scratch, self.actions[t])
-            if route == "stateful":
+            if self.pool is not None:
+                # the ghosts' forward on the pool's own context, behind the learner's (whose kept-forward state it never
+                # sees), then the pooled step: the ghost's action is sampled inside it
+                second = wrap is not None
+                self.pool.ctx.forward(self.pool.opponent, self.ghost_states[slot], probs=self.ghost_probs)
+                hip_ops.duel_ghost_step(seed, self.env_offset, self.actions[t], self.ghost_probs, self.sampler_seed, self.tick, t,
+                                        self.env_state[slot], self.env_state[slot + 1], obs, nxt, self.ghost_states[slot],
+                                        self.ghost_states[slot + 1], self.ghost_actions[t], *records, stack_out2=wrap,
+                                        state_out2=self.env_state[0] if second else None,
+                                        ghost_stack_out2=self.ghost_states[0] if second else None,
+                                        truncs_out=self.truncs[t] if self.truncs is not None else None)
+            elif route == "stateful":
                 self.stateful["step"](seed, self.env_offset, self.actions[t], self.env_state[slot], self.env_state[slot + 1], obs,
                                       nxt, *records, stack_out2=wrap, state_out2=self.env_state[0] if wrap is not None else None,
                                       **(dict(truncs_out=self.truncs[t]) if self.truncs is not None else {}),
@@ -430,7 +459,7 @@ class DeviceRollout(object):
               if t is not None]
         if L.minibatch_on:      # (the staging block of states is rewritten by every epoch's gather before anything reads it)
             ts += [L.v_rec] + [t for k, t in L.mb.items() if t is not None and k != "states"]
-        for name in ("raw", "walk_scratch", "mt_state", "env_state", "truncs"):
+        for name in ("raw", "walk_scratch", "mt_state", "env_state", "truncs", "ghost_states", "ghost_probs", "ghost_actions"):
             t = getattr(self, name, None)
             if t is not None:
                 ts.append(t)
@@ -766,6 +795,10 @@ class PAACLearner(ActorLearner):
         # --eval_match: at every evaluation the live weights also play duel boards against a device copy of the weights of the
         # previous evaluation (paac_amd/match.py: DeviceMatch) -- on the evaluator's context, its own streams and buffers
         from . import match
+        # --duel_pool: the rollout's pool of frozen opponents (paac_amd/duel_pool.py); its events cap the chunk as the
+        # evaluations do
+        from . import duel_pool
+        pool = self.rollout.pool
         matcher = snapshot = None
         match_boards = int(getattr(args, "eval_match", 0)) if match.check_train_flags(args) else 0
         if eval_every:
@@ -813,6 +846,8 @@ class PAACLearner(ActorLearner):
                 if evaluator is not None:
                     until_eval = -(-(next_eval - self.global_step) // steps_per_cycle)
                     chunk = max(1, min(chunk, until_eval))
+                if pool is not None:
+                    chunk = max(1, min(chunk, duel_pool.until_pool(pool.schedule.next_event, self.global_step, steps_per_cycle)))
             if next_check is not None:
                 chunk = max(1, min(chunk, next_check - counter))
             self.rollout.run_cycles(chunk)
@@ -833,6 +868,18 @@ class PAACLearner(ActorLearner):
                     episodes_seen = count
                     self._progress_record(chunk * steps_per_cycle / (curr_time - loop_start_time),
                                           (self.global_step - global_step_start) / (curr_time - start_time), last_ten)
+            if pool is not None and pool.schedule.due(self.global_step):
+                # a pool event, between two run_cycles calls and on the rollout's stream: two device-to-device copies and the
+                # repack, queued behind the cycles already issued -- nothing here waits for the GPU
+                with torch.cuda.stream(self.rollout.stream):
+                    record = pool.event(self.global_step, self.network.params)
+                logging.info("Duel pool at {} steps: live weights into slot {} ({} of {} taken), next opponent slot {} (the "
+                             "weights of {} steps{})".format(record["global_step"], record["slot"], record["size"], pool.schedule.K,
+                                                             record["opponent_slot"], record["opponent_global_step"],
+                                                             ", the newest" if record["latest"] else ""))
+                if metrics is not None:
+                    metrics.write("duel_pool", **record)
+                    metrics.flush()
             if evaluator is not None and self.global_step >= next_eval:
                 self.rollout.synchronize()
                 scores, lengths, seconds = evaluator.timed_run()
@@ -1123,6 +1170,8 @@ class PAACLearner(ActorLearner):
             self.runners = None
         if self.rollout is not None:
             self.rollout.close()
+            if self.rollout.pool is not None:
+                self.rollout.pool.close()
         if self.metrics is not None:
             self.metrics.close()
             self.metrics = None

@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import environment_creator, evaluation, logger_utils, match, parallel
+from . import duel_pool, environment_creator, evaluation, logger_utils, match, parallel
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -129,6 +129,17 @@ BUILD_FLAGS = (
      "the run started or resumed from), on the GPU (paac_amd/match.py), with --eval_greedy, up to 30 no-op steps and seed "
      "random_seed + 1, and a 'match' record goes to metrics.jsonl: the self-play learning curve.  Training is bit-identical "
      "with it on or off"),
+    (("--duel_pool",), "duel_pool", 0, int,
+     "--emulator duel: 0 = off (every board is played by the live weights on both sides); K in [1, 16] = -ec rows are -ec "
+     "boards, every learner row the bottom player of its own board, and the top player is a frozen earlier copy of the policy "
+     "drawn from a pool of up to K such copies (paac_amd/duel_pool.py); the logged training return is then the learner's "
+     "against the pool, no longer 0 by construction; one GPU only; the pool is not checkpointed"),
+    (("--duel_pool_every",), "duel_pool_every", 102400, int,
+     "global steps between pool events: the live weights are frozen into the pool and the next opponent is drawn (a design "
+     "choice, not a measured optimum); read only when --duel_pool is above 0"),
+    (("--duel_pool_latest_p",), "duel_pool_latest_p", 0.5, float,
+     "probability in [0, 1] that the opponent of the next period is the newest frozen copy rather than a uniformly drawn pool "
+     "member (a design choice, not a measured optimum); read only when --duel_pool is above 0"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),
@@ -211,6 +222,7 @@ def main(args):
     logging.debug('Configuration: %s', args)
     check_eval_flags(args, world)                 # --eval_every's refusals, before a learner exists
     match.check_train_flags(args)                 # ... and --eval_match's
+    duel_pool.check_train_flags(args, world)      # ... and --duel_pool's
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)
     setup_kill_signal_handler(learner)

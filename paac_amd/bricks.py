@@ -3,7 +3,7 @@ for every brick struck; a ball that passes the paddle costs one of three lives.
 
 This is the SPEC of the bricks environment family; the same numbers are produced
   * on the host by `BricksEnvironment` (a BaseEnvironment plugin, numpy and pure Python), and
-  * on the device by paac_bricks_reset / paac_bricks_step (csrc/bricks_dev.h, csrc/misc.hip), N envs per launch.
+  * on the device by paac_bricks_reset / paac_bricks_step (csrc/bricks_dev.h, csrc/games.hip), N envs per launch.
 Catch (catch.py) is a 13-step bandit: one reward, fixed length, no lives.  This game has a long horizon with dense delayed
 reward, episodes of variable length, lives (what --single_life_episodes refers to), a field that changes the observation,
 and a ball whose direction cannot be read from one plane -- the frame history is needed.  Call pattern as CatchEnvironment's:

@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpaac_hip.so")
-SOURCES = ["api.hip", "net_fwd.hip", "net_bwd.hip", "misc.hip"]
+SOURCES = ["api.hip", "net_fwd.hip", "net_bwd.hip", "misc.hip", "games.hip", "optim.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "paac_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
@@ -68,8 +68,9 @@ def _build_locked(force, verbose, extra_flags, lib, obj_suffix):
         if verbose and r.stderr.strip():
             print(r.stderr[-4000:], file=sys.stderr)
 
-    with ThreadPoolExecutor(max_workers=4) as ex:
-        list(ex.map(run, jobs))
+    if jobs:
+        with ThreadPoolExecutor(max_workers=len(jobs)) as ex:      # one hipcc per stale source
+            list(ex.map(run, jobs))
     if jobs or force or _stale(lib, objs):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
     return lib

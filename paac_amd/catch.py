@@ -2,7 +2,7 @@
 
 This is the SPEC of the catch environment family; the same numbers are produced
   * on the host by `CatchEnvironment` (a BaseEnvironment plugin, numpy and pure Python), and
-  * on the device by paac_catch_reset / paac_catch_step (csrc/catch_dev.h, csrc/misc.hip), N envs per launch.
+  * on the device by paac_catch_reset / paac_catch_step (csrc/catch_dev.h, csrc/games.hip), N envs per launch.
 The synthetic family (synthetic.py) measures the hot path, but its reward is a hash: there is nothing to learn.  This one
 is stateful and action-dependent, is rendered into the same 84x84x4 uint8 observations and is small enough to be learned in
 seconds at the device loop's speed.  Call pattern as SyntheticEnvironment's: get_initial_state() / next(one_hot) ->

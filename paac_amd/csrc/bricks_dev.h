@@ -1,5 +1,5 @@
 // The bricks environments on the device (spec: paac_amd/bricks.py): the game trait BricksGame (see csrc/game_dev.h) of the
-// step and evaluation kernels in csrc/misc.hip.
+// step and evaluation kernels in csrc/games.hip.
 #pragma once
 #include "game_dev.h"
 

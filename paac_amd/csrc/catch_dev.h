@@ -1,5 +1,5 @@
 // The catch environments on the device (spec: paac_amd/catch.py): the game trait CatchGame (see csrc/game_dev.h) of the step
-// and evaluation kernels in csrc/misc.hip.
+// and evaluation kernels in csrc/games.hip.
 #pragma once
 #include "game_dev.h"
 

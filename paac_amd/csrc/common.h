@@ -130,7 +130,7 @@ struct paac_ctx {
   float* wslab;    // wgrad split-K slabs (all layers)
   int64_t wslab_floats;
   float* partials; // norm / gradient-summary partials of the last paac_clip_rmsprop / paac_clip_adam (5 x kNormPartialsMax
-                   // floats), then the per-tensor factors of a local-mode step, then Adam's step size (misc.hip: kAdamAlpha)
+                   // floats), then the per-tensor factors of a local-mode step, then Adam's step size (optim.hip: kAdamAlpha)
   int last_clip_local;             // 1: the last optimizer step ran in PAAC_CLIP_LOCAL (tensor-aligned partials)
   // paac_loss_backward(phase = 3) leaves the slab reduction of the conv weight gradients to the next paac_clip_rmsprop on
   // the same gradient buffer (its norm pass does it): the segments, and the buffer they belong to
@@ -319,6 +319,23 @@ __device__ __forceinline__ void cycle_tick(const CycleTick& ct) {
     *ct.lr_out = (float)lr;
   }
   if (ct.tick) *ct.tick += ct.tick_inc;
+}
+
+// Philox4x32-10 (oracle/sampler.py:sample_philox): the counter-based generator of the throughput sampler and the minibatch
+// shuffles (csrc/misc.hip) and of the evaluation / match / ghost action streams (csrc/games.hip).
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+    const uint32_t n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    const uint32_t n3 = (uint32_t)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
 }
 
 bool norm_head_fits(const paac_ctx* ctx);

@@ -1,7 +1,7 @@
 // The duel environments on the device (spec: paac_amd/duel.py): rally played against the learner itself.  N rows = N / 2
 // boards of the rally board; row e < N / 2 is the bottom player of board e, row e + N / 2 the top player of the same board, and
 // each row keeps the board as seen from its own side (a top row's record is mirror(the bottom row's)).  The game trait DuelGame
-// (see csrc/game_dev.h) of game_step_kernel in csrc/misc.hip: a PAIRED trait -- a row's step reads its partner's action beside
+// (see csrc/game_dev.h) of game_step_kernel in csrc/games.hip: a PAIRED trait -- a row's step reads its partner's action beside
 // its own.  State, record, serve and pixels are rally's (rally_dev.h), unchanged.
 #pragma once
 #include "rally_dev.h"

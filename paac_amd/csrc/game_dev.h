@@ -1,5 +1,5 @@
 // What the device games share (catch_dev.h, bricks_dev.h, rally_dev.h; kernels: game_step_kernel and eval_step_kernel in
-// csrc/misc.hip): where a thread's quad is, and the push of a new plane into an observation's history.
+// csrc/games.hip): where a thread's quad is, and the push of a new plane into an observation's history.
 // A game is one trait struct G in its header:
 //   State, kWords                                    the state record in registers, its int32 words in memory
 //   load(state, e), store(state, e, s)               record e of a [N, kWords] buffer
@@ -18,7 +18,7 @@
 //   start(seed, env_offset, e, N)                    episode 0's start record of row e
 //   advance(seed, g, s, a_own, a_partner, is_top, &reward, &term, &trunc)
 // and has no evaluation form (eval_step_kernel is not instantiated for it); what it has instead is the match form,
-// match_step_kernel in csrc/misc.hip: two policies' probabilities in one block, one on each side of every board.
+// match_step_kernel in csrc/games.hip: two policies' probabilities in one block, one on each side of every board.
 #pragma once
 #include <type_traits>
 

@@ -1,5 +1,5 @@
 // The rally environments on the device (spec: paac_amd/rally.py): the game trait RallyGame (see csrc/game_dev.h) of the step
-// and evaluation kernels in csrc/misc.hip.
+// and evaluation kernels in csrc/games.hip.
 #pragma once
 #include "game_dev.h"
 

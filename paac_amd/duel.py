@@ -3,7 +3,7 @@ paddles, each row seeing the board from its own side.  To the learner it is a de
 
 This is the SPEC of the duel environment family; the same numbers are produced
   * on the host by the reference functions below and the numpy batch twin `DuelBoards`, and
-  * on the device by paac_duel_reset / paac_duel_step (csrc/duel_dev.h, csrc/misc.hip), N rows per launch.
+  * on the device by paac_duel_reset / paac_duel_step (csrc/duel_dev.h, csrc/games.hip), N rows per launch.
 There is no BaseEnvironment plugin: the host loop steps environments one by one in worker processes, and a row here needs its
 partner's action.  `--emulator duel` runs on the device loop only; what `paac_amd.test` steps on the host for a duel run is
 rally.RallyEnvironment -- the scripted opponent is the yardstick a duel policy is scored against.

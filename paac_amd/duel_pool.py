@@ -4,7 +4,7 @@ policy instead of against the live weights (fictitious self-play: pure mirror pl
 This is the SPEC of the pooled step and of the pool's schedule; the same numbers are produced
   * on the host by the plain-numpy functions and the twin `PooledBoards` below (on top of duel.py, match.py and
     evaluation.philox_word0), and
-  * on the device by paac_duel_ghost_reset / paac_duel_ghost_step (csrc/misc.hip: ghost_step_kernel; include/paac_hip.h has
+  * on the device by paac_duel_ghost_reset / paac_duel_ghost_step (csrc/games.hip: ghost_step_kernel; include/paac_hip.h has
     the contract), N boards per launch, driven by paac.DeviceRollout with the tensors of `DevicePool`.
 
 Spec
@@ -41,7 +41,7 @@ from . import duel
 from .evaluation import philox_word0
 from .match import sampled_on_stream
 
-GHOST_STREAM = 0x44500001              # csrc/misc.hip: kGhostStream
+GHOST_STREAM = 0x44500001              # csrc/games.hip: kGhostStream
 POOL_STREAM_LATEST = 0x44500002        # the schedule's two streams (host only)
 POOL_STREAM_SLOT = 0x44500003
 MAX_POOL = 16

@@ -2,7 +2,7 @@
 
 This is the SPEC of an evaluation, as catch.py, bricks.py and rally.py are the specs of the games; the same numbers are produced
   * on the host by the plain-numpy functions below (`eval_noops`, `eval_action`, `account`, `replay_on_twins`), and
-  * on the device by paac_eval_step (csrc/misc.hip; include/paac_hip.h has the contract), one evaluation step of N
+  * on the device by paac_eval_step (csrc/games.hip; include/paac_hip.h has the contract), one evaluation step of N
     environments per launch, driven by `DeviceEvaluator`.
 
 Spec
@@ -28,8 +28,8 @@ import time
 
 import numpy as np
 
-EVAL_STREAM_ACTION = 0x45560001        # csrc/misc.hip: kEvalStreamAction
-EVAL_STREAM_NOOP = 0x45560002          # csrc/misc.hip: kEvalStreamNoop
+EVAL_STREAM_ACTION = 0x45560001        # csrc/games.hip: kEvalStreamAction
+EVAL_STREAM_NOOP = 0x45560002          # csrc/games.hip: kEvalStreamNoop
 MAX_COUNT = 4096                       # environments of one evaluation
 MAX_CHUNK = 1024                       # ... of one acting forward of it
 
@@ -167,7 +167,110 @@ def check_train_flags(args, world_size=1):
     return True
 
 
-class DeviceEvaluator(object):
+class DeviceDriver(object):
+    """What DeviceEvaluator and match.DeviceMatch share: `count` boards of a device game, one scored episode each, played in
+    chunks on buffers of the largest chunk's rows (rows_per_board rows a board) -- blocks of `block` steps, one hipGraph per
+    chunk when use_graph, until the chunk's `alive` count, the one int32 that crosses to the host per block, reaches zero.
+
+    A chunk is a tuple (boards n, env_offset, ...) and the key of its captured block.  A subclass sets max_steps and supplies
+    _chunks() -> the chunks of a run, _reset(*chunk), _block(*chunk) = `block` steps issued on the current stream,
+    _scored_rows(*chunk) -> the rows whose score / length are the boards', and _place_trace(full, trace, *chunk)."""
+
+    rows_per_board = 1
+
+    def __init__(self, hip_ops, count, noops, seed, greedy, steps_per_launch, record, use_graph):
+        self.count = check_count(count)
+        if isinstance(noops, bool) or int(noops) != noops or int(noops) < 0:
+            raise ValueError("noops %r: expected an integer >= 0" % (noops,))
+        if int(steps_per_launch) < 1:
+            raise ValueError("steps_per_launch %r: expected a positive integer" % (steps_per_launch,))
+        self.hip_ops = hip_ops
+        self.noops, self.greedy, self.seed, self.record = int(noops), bool(greedy), int(seed), bool(record)
+        self.block = (int(steps_per_launch) + 1) // 2 * 2
+        self.use_graph = bool(use_graph) and not self.record
+        self.graphs = {}                                   # chunk -> the captured block
+        self.launches = 0                                  # blocks issued by the last run()
+
+    def _allocate(self, chunk, words, num_actions, dev, stream):
+        """The buffers of chunks of up to `chunk` boards: ping-pong stacks and state records, one block of actions, the accounts."""
+        import torch
+        self.chunk = chunk
+        rows = chunk * self.rows_per_board
+        self.stacks = [torch.zeros((rows, 84, 84, 4), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.states = [torch.zeros((rows, words), dtype=torch.int32, device=dev) for _ in range(2)]
+        self.probs = torch.zeros((rows, num_actions), dtype=torch.float32, device=dev)
+        self.actions = torch.zeros((self.block, rows), dtype=torch.int32, device=dev)
+        self.score = torch.zeros(rows, dtype=torch.float32, device=dev)
+        self.length = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.done = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.alive = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
+
+    def _captured(self, chunk):
+        if chunk not in self.graphs:
+            g = self.hip_ops.Graph()
+            g.begin()
+            try:
+                self._block(*chunk)
+            except Exception:
+                g.abort()
+                raise
+            g.end()
+            self.graphs[chunk] = g
+        return self.graphs[chunk]
+
+    def run(self):
+        """-> (scores float32 [count], lengths int32 [count]) in board order; with record=True also the action trace int32
+        [steps, rows_per_board * count] (zero where a chunk had stopped earlier) and the per-board no-op counts int32 [count]."""
+        import torch
+        scores, lengths = np.zeros(self.count, dtype=np.float32), np.zeros(self.count, dtype=np.int32)
+        traces = []
+        self.launches = 0
+        with torch.cuda.stream(self.stream):
+            for chunk in self._chunks():
+                n, env_offset = chunk[:2]
+                rows = n * self.rows_per_board
+                self._reset(*chunk)
+                for t in (self.score, self.length, self.done, self.step):
+                    t.zero_()
+                self.alive.fill_(rows)
+                trace, steps = [], 0
+                while steps < self.max_steps:
+                    if self.use_graph:
+                        self._captured(chunk).launch()
+                    else:
+                        self._block(*chunk)
+                    steps += self.block
+                    self.launches += 1
+                    if self.record:
+                        trace.append(self.actions[:, :rows].cpu().numpy().copy())
+                    if int(self.alive.cpu().item()) == 0:          # (synchronises the stream: the block has run)
+                        break
+                mine = self._scored_rows(*chunk)
+                scores[env_offset:env_offset + n] = self.score[mine].cpu().numpy()
+                lengths[env_offset:env_offset + n] = self.length[mine].cpu().numpy()
+                traces.append((chunk, np.concatenate(trace) if trace else None))
+        if not self.record:
+            return scores, lengths
+        full = np.zeros((max(len(t) for _, t in traces), self.rows_per_board * self.count), dtype=np.int32)
+        for chunk, t in traces:
+            self._place_trace(full, t, *chunk)
+        return scores, lengths, full, eval_noops(self.seed, np.arange(self.count), self.noops)
+
+    def timed_run(self):
+        """run() with its wall time -> (scores, lengths, seconds)."""
+        start = time.time()
+        scores, lengths = self.run()[:2]
+        return scores, lengths, time.time() - start
+
+    def close(self):
+        for g in self.graphs.values():
+            g.close()
+        self.graphs = {}
+
+
+class DeviceEvaluator(DeviceDriver):
     """Scores `count` environments of a device game, one episode each, with the policy of `network` -- nothing crosses to the
     host but one int32 per block of steps.
 
@@ -182,39 +285,24 @@ class DeviceEvaluator(object):
 
     def __init__(self, network, ctx, env_spec, count, noops=30, greedy=False, seed=0, steps_per_launch=16, record=False,
                  use_graph=True, stream=None):
-        import torch
         from . import hip_ops
         from .paac import STATEFUL_KINDS
         self.kind = check_env_spec(env_spec)
-        self.count = check_count(count)
-        if isinstance(noops, bool) or int(noops) != noops or int(noops) < 0:
-            raise ValueError("noops %r: expected an integer >= 0" % (noops,))
-        if int(steps_per_launch) < 1:
-            raise ValueError("steps_per_launch %r: expected a positive integer" % (steps_per_launch,))
+        super(DeviceEvaluator, self).__init__(hip_ops, count, noops, seed, greedy, steps_per_launch, record, use_graph)
         if ctx.num_actions != network.num_actions or ctx.arch != network.arch_id:
             raise ValueError("the context was not made for this network")
-        self.network, self.ctx, self.hip_ops = network, ctx, hip_ops
+        self.network, self.ctx = network, ctx
         self.game = STATEFUL_KINDS[self.kind]
         self.env_seed = int(env_spec["seed"])
-        self.noops, self.greedy, self.seed, self.record = int(noops), bool(greedy), int(seed), bool(record)
-        self.block = (int(steps_per_launch) + 1) // 2 * 2
         self.max_steps = max_steps_of(self.kind, self.noops)
-        self.use_graph = bool(use_graph) and not self.record
-        self.chunk = min(self.count, ctx.max_batch, MAX_CHUNK)
-        dev = network.torch_device
-        n, A = self.chunk, network.num_actions
-        self.stacks = [torch.zeros((n, 84, 84, 4), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.states = [torch.zeros((n, self.game["words"]), dtype=torch.int32, device=dev) for _ in range(2)]
-        self.probs = torch.zeros((n, A), dtype=torch.float32, device=dev)
-        self.actions = torch.zeros((self.block, n), dtype=torch.int32, device=dev)
-        self.score = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.length = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.done = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.alive = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.graphs = {}                                   # environments of a chunk -> the captured block
-        self.launches = 0                                  # blocks issued by the last run()
+        self._allocate(min(self.count, ctx.max_batch, MAX_CHUNK), self.game["words"], network.num_actions, network.torch_device,
+                       stream)
+
+    def _chunks(self):
+        return [(min(self.chunk, self.count - env_offset), env_offset) for env_offset in range(0, self.count, self.chunk)]
+
+    def _reset(self, n, env_offset):
+        self.game["reset"](self.env_seed, env_offset, self.states[0][:n], self.stacks[0][:n])
 
     def _block(self, n, env_offset):
         """`block` x [acting forward -> evaluation step] on the first n environments, then the step counter moves on."""
@@ -227,69 +315,14 @@ class DeviceEvaluator(object):
                           self.score[:n], self.length[:n], self.done[:n], self.alive)
         ops.counter_add(self.step, self.block)
 
-    def _captured(self, n, env_offset):
-        key = (n, env_offset)
-        if key not in self.graphs:
-            g = self.hip_ops.Graph()
-            g.begin()
-            try:
-                self._block(n, env_offset)
-            except Exception:
-                g.abort()
-                raise
-            g.end()
-            self.graphs[key] = g
-        return self.graphs[key]
+    def _scored_rows(self, n, env_offset):
+        return slice(0, n)
 
-    def run(self):
-        """-> (scores float32 [count], lengths int32 [count]); with record=True also the action trace int32 [steps, count]
-        (zero where a chunk had stopped earlier) and the per-environment no-op counts int32 [count]."""
-        import torch
-        scores, lengths = np.zeros(self.count, dtype=np.float32), np.zeros(self.count, dtype=np.int32)
-        traces = []
-        self.launches = 0
-        with torch.cuda.stream(self.stream):
-            for env_offset in range(0, self.count, self.chunk):
-                n = min(self.chunk, self.count - env_offset)
-                self.game["reset"](self.env_seed, env_offset, self.states[0][:n], self.stacks[0][:n])
-                for t in (self.score, self.length, self.done, self.step):
-                    t.zero_()
-                self.alive.fill_(n)
-                trace, steps = [], 0
-                while steps < self.max_steps:
-                    if self.use_graph:
-                        self._captured(n, env_offset).launch()
-                    else:
-                        self._block(n, env_offset)
-                    steps += self.block
-                    self.launches += 1
-                    if self.record:
-                        trace.append(self.actions[:, :n].cpu().numpy().copy())
-                    if int(self.alive.cpu().item()) == 0:          # (synchronises the stream: the block has run)
-                        break
-                scores[env_offset:env_offset + n] = self.score[:n].cpu().numpy()
-                lengths[env_offset:env_offset + n] = self.length[:n].cpu().numpy()
-                traces.append(np.concatenate(trace) if trace else None)
-        if not self.record:
-            return scores, lengths
-        full = np.zeros((max(len(t) for t in traces), self.count), dtype=np.int32)
-        for i, t in enumerate(traces):
-            full[:len(t), i * self.chunk:i * self.chunk + t.shape[1]] = t
-        return scores, lengths, full, eval_noops(self.seed, np.arange(self.count), self.noops)
+    def _place_trace(self, full, trace, n, env_offset):
+        full[:len(trace), env_offset:env_offset + n] = trace
 
     def summary(self, scores, lengths, seconds):
         """The fields of an `eval` record of metrics.jsonl (without global_step)."""
         return dict(count=self.count, greedy=self.greedy, mean=float(np.mean(scores)), min=float(np.min(scores)),
                     max=float(np.max(scores)), std=float(np.std(scores)), mean_length=float(np.mean(lengths)),
                     seconds=float(seconds))
-
-    def timed_run(self):
-        """run() with its wall time -> (scores, lengths, seconds)."""
-        start = time.time()
-        scores, lengths = self.run()[:2]
-        return scores, lengths, time.time() - start
-
-    def close(self):
-        for g in self.graphs.values():
-            g.close()
-        self.graphs = {}

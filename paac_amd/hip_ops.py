@@ -64,6 +64,47 @@ def _step_ptrs(N, stack_out=None, rewards_out=None, masks_out=None, ep_reward=No
             ctypes.c_void_p(finished.data_ptr()) if finished is not None else ctypes.c_void_p(0)]
 
 
+# The buffer checks of the device games' wrappers (game / duel / ghost steps and resets, eval_step, match_step).
+def _shaped_ptrs(shape, dtype, named, nullable):
+    """Every named tensor against `shape` -> their pointers in the order given; the names in `nullable` may be None."""
+    for nm, t in named.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError("%s must be [%s], got %s" % (nm, ",".join(str(d) for d in shape), tuple(t.shape)))
+    return [_ptr(t, dtype, int(np.prod(shape)), nm, nm in nullable) for nm, t in named.items()]
+
+
+def _state_ptrs(N, words, nullable=(), **named):
+    """int32 state records [N, words]."""
+    return _shaped_ptrs((N, words), torch.int32, named, nullable)
+
+
+def _stack_ptrs(N, nullable=(), **named):
+    """uint8 observation stacks [N, 84, 84, 4]."""
+    return _shaped_ptrs((N,) + OBS_SHAPE, torch.uint8, named, nullable)
+
+
+def _env_offset(fn, env_offset, N):
+    """The first global environment of N: they all have 32-bit keys."""
+    if not 0 <= int(env_offset) <= 0xFFFFFFFF - N:
+        raise ValueError("%s: env_offset %r" % (fn, env_offset))
+    return int(env_offset)
+
+
+def _env_records(N, records, truncs_out):
+    """paac_env_records: _step_ptrs' five record pointers and the truncation plane float32[N] (None: not written)."""
+    return _lib.EnvRecords(*records, _ptr(truncs_out, torch.float32, N, "truncs_out", True))
+
+
+def _game_step_ptrs(words, actions, state_in, state_out, state_out2, stack_in, stack_out, stack_out2, rewards_out, masks_out,
+                    ep_reward, ep_len, finished):
+    """What the game steps share -> N, [actions, state_in, state_out, state_out2, stack_in, stack_out, stack_out2] in the C
+    order, and the five record pointers."""
+    N = actions.shape[0]
+    out, out2, *records = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
+    states = _state_ptrs(N, words, ("state_out2",), state_in=state_in, state_out=state_out, state_out2=state_out2)
+    return N, [_ptr(actions, torch.int32, N, "actions"), *states, _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), out, out2], records
+
+
 # (filters, kernel size, stride) of the stock trunks' conv layers and their fc width (networks.py)
 STOCK_GEOMETRY = {_lib.ARCH_NATURE: ([(32, 8, 4), (64, 4, 2), (64, 3, 1)], 512),
                   _lib.ARCH_NIPS: ([(16, 8, 4), (32, 4, 2)], 256)}
@@ -759,9 +800,7 @@ def _stateful_reset(entry, words, seed, env_offset, state_out, stack_out):
     N = stack_out.shape[0]
     if tuple(stack_out.shape) != (N,) + OBS_SHAPE:
         raise ValueError("stack_out must be [N,84,84,4]")
-    if tuple(state_out.shape) != (N, words):
-        raise ValueError("state_out must be [%d,%d], got %s" % (N, words, tuple(state_out.shape)))
-    _lib.check(getattr(_lib.load(), entry)(int(seed), int(env_offset), N, _ptr(state_out, torch.int32, N * words, "state_out"),
+    _lib.check(getattr(_lib.load(), entry)(int(seed), int(env_offset), N, *_state_ptrs(N, words, state_out=state_out),
                                            _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _stream()), entry)
 
 
@@ -769,15 +808,10 @@ def _stateful_step(entry, words, seed, env_offset, actions, state_in, state_out,
                    ep_reward, ep_len, finished, stack_out2, state_out2, extra=()):
     """paac_<game>_step: the shape checks and the argument list the stateful games share; `extra` = the game's own integer
     arguments, which follow `finished`."""
-    N = actions.shape[0]
-    step = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
-    for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
-        if t is not None and tuple(t.shape) != (N, words):
-            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
-    args = [int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
-            _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
-            _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in")]
-    _lib.check(getattr(_lib.load(), entry)(*(args + step + [int(x) for x in extra] + [_stream()])), entry)
+    N, buffers, records = _game_step_ptrs(words, actions, state_in, state_out, state_out2, stack_in, stack_out, stack_out2,
+                                          rewards_out, masks_out, ep_reward, ep_len, finished)
+    _lib.check(getattr(_lib.load(), entry)(int(seed), int(env_offset), N, *buffers, *records, *(int(x) for x in extra), _stream()),
+               entry)
 
 
 def game_reset(kind, seed, env_offset, state_out, stack_out):
@@ -792,17 +826,11 @@ def game_step_records(kind, seed, env_offset, actions, state_in, state_out, stac
     name, words = game["step_option"], game["words"]
     if set(option) - {name}:
         raise TypeError("%s_step: unexpected keyword arguments %s" % (kind, sorted(set(option) - {name})))
-    N = actions.shape[0]
-    out, out2, *records = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
-    for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
-        if t is not None and tuple(t.shape) != (N, words):
-            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
-    rec = _lib.EnvRecords(*records, _ptr(truncs_out, torch.float32, N, "truncs_out", True))
-    _lib.check(_lib.load().paac_game_step(
-        game["eval_id"], int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
-        _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
-        _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), out, out2,
-        ctypes.byref(rec), int(bool(option.get(name, False))) if name else 0, _stream()), "paac_game_step")
+    N, buffers, records = _game_step_ptrs(words, actions, state_in, state_out, state_out2, stack_in, stack_out, stack_out2,
+                                          rewards_out, masks_out, ep_reward, ep_len, finished)
+    rec = _env_records(N, records, truncs_out)
+    _lib.check(_lib.load().paac_game_step(game["eval_id"], int(seed), int(env_offset), N, *buffers, ctypes.byref(rec),
+                                          int(bool(option.get(name, False))) if name else 0, _stream()), "paac_game_step")
 
 
 def game_step(kind, seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len,
@@ -842,34 +870,19 @@ def duel_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_ou
               finished=None, stack_out2=None, state_out2=None, truncs_out=None):
     """paac_duel_step: game_step's argument list without the kind; row e also reads actions[(e + N / 2) % N].  truncs_out
     float32[N] (None: not written) as game_step_records'.  The library refuses an odd N, N < 2 and in-place buffers."""
-    words = DUEL_STATE_WORDS
-    N = actions.shape[0]
-    out, out2, *records = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
-    for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
-        if t is not None and tuple(t.shape) != (N, words):
-            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
-    rec = _lib.EnvRecords(*records, _ptr(truncs_out, torch.float32, N, "truncs_out", True))
-    _lib.check(_lib.load().paac_duel_step(
-        int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
-        _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
-        _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), out, out2,
-        ctypes.byref(rec), _stream()), "paac_duel_step")
+    N, buffers, records = _game_step_ptrs(DUEL_STATE_WORDS, actions, state_in, state_out, state_out2, stack_in, stack_out,
+                                          stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished)
+    rec = _env_records(N, records, truncs_out)
+    _lib.check(_lib.load().paac_duel_step(int(seed), int(env_offset), N, *buffers, ctypes.byref(rec), _stream()), "paac_duel_step")
 
 
 def duel_ghost_reset(seed, env_offset, state_out, stack_out, ghost_stack_out):
     """paac_duel_ghost_reset (include/paac_hip.h; spec in paac_amd/duel_pool.py): N boards, the learner's rows and the ghosts'
     observations -- duel_reset on 2N rows, split."""
-    words = DUEL_STATE_WORDS
     N = stack_out.shape[0]
-    for nm, t in (("stack_out", stack_out), ("ghost_stack_out", ghost_stack_out)):
-        if tuple(t.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
-    if tuple(state_out.shape) != (N, words):
-        raise ValueError("state_out must be [%d,%d], got %s" % (N, words, tuple(state_out.shape)))
-    _lib.check(_lib.load().paac_duel_ghost_reset(
-        int(seed), int(env_offset), N, _ptr(state_out, torch.int32, N * words, "state_out"),
-        _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(ghost_stack_out, torch.uint8, N * 28224, "ghost_stack_out"),
-        _stream()), "paac_duel_ghost_reset")
+    stacks = _stack_ptrs(N, stack_out=stack_out, ghost_stack_out=ghost_stack_out)
+    _lib.check(_lib.load().paac_duel_ghost_reset(int(seed), int(env_offset), N, *_state_ptrs(N, DUEL_STATE_WORDS, state_out=state_out),
+                                                 *stacks, _stream()), "paac_duel_ghost_reset")
 
 
 def duel_ghost_step(seed, env_offset, actions, ghost_probs, sampler_seed, step_base_dev, step_offset, state_in, state_out,
@@ -880,31 +893,36 @@ def duel_ghost_step(seed, env_offset, actions, ghost_probs, sampler_seed, step_b
     tick *step_base_dev + step_offset (None: 0) and written to ghost_actions_out int32 [N].  Records and second outputs as
     duel_step's, for the learner's rows; the ghosts get their next observations (and ghost_stack_out2) only.  Shapes are
     checked here; the library refuses N < 1, A != 6, null pointers and in-place buffers before any launch."""
-    words = DUEL_STATE_WORDS
-    N = actions.shape[0]
-    out, out2, *records = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, stack_in=stack_in)
-    for nm, t in (("state_in", state_in), ("state_out", state_out), ("state_out2", state_out2)):
-        if t is not None and tuple(t.shape) != (N, words):
-            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
-    for nm, t in (("ghost_stack_in", ghost_stack_in), ("ghost_stack_out", ghost_stack_out), ("ghost_stack_out2", ghost_stack_out2)):
-        if t is not None and tuple(t.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
+    N, buffers, records = _game_step_ptrs(DUEL_STATE_WORDS, actions, state_in, state_out, state_out2, stack_in, stack_out,
+                                          stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished)
+    ghost_stacks = _stack_ptrs(N, ("ghost_stack_out2",), ghost_stack_in=ghost_stack_in, ghost_stack_out=ghost_stack_out,
+                               ghost_stack_out2=ghost_stack_out2)
     if ghost_probs.dim() != 2 or ghost_probs.shape[0] != N:
         raise ValueError("ghost_probs must be [%d, A], got %s" % (N, tuple(ghost_probs.shape)))
     A = ghost_probs.shape[1]
-    if not 0 <= int(env_offset) <= 0xFFFFFFFF - N:
-        raise ValueError("duel_ghost_step: env_offset %r" % (env_offset,))
-    rec = _lib.EnvRecords(*records, _ptr(truncs_out, torch.float32, N, "truncs_out", True))
+    env_offset = _env_offset("duel_ghost_step", env_offset, N)
+    rec = _env_records(N, records, truncs_out)
     _lib.check(_lib.load().paac_duel_ghost_step(
-        int(seed), int(env_offset), N, _ptr(actions, torch.int32, N, "actions"),
-        _ptr(ghost_probs, torch.float32, N * A, "ghost_probs"), A, int(sampler_seed) & 0xFFFFFFFFFFFFFFFF,
-        _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
-        _ptr(state_in, torch.int32, N * words, "state_in"), _ptr(state_out, torch.int32, N * words, "state_out"),
-        _ptr(state_out2, torch.int32, N * words, "state_out2", True), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"), out, out2,
-        _ptr(ghost_stack_in, torch.uint8, N * 28224, "ghost_stack_in"),
-        _ptr(ghost_stack_out, torch.uint8, N * 28224, "ghost_stack_out"),
-        _ptr(ghost_stack_out2, torch.uint8, N * 28224, "ghost_stack_out2", True), ctypes.byref(rec),
-        _ptr(ghost_actions_out, torch.int32, N, "ghost_actions_out"), _stream()), "paac_duel_ghost_step")
+        int(seed), env_offset, N, buffers[0], _ptr(ghost_probs, torch.float32, N * A, "ghost_probs"), A,
+        int(sampler_seed) & 0xFFFFFFFFFFFFFFFF, _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
+        *buffers[1:], *ghost_stacks, ctypes.byref(rec), _ptr(ghost_actions_out, torch.int32, N, "ghost_actions_out"), _stream()),
+        "paac_duel_ghost_step")
+
+
+def _scored_step_args(fn, words, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in,
+                      state_out, stack_in, stack_out, actions_out, score, length, done, alive):
+    """paac_eval_step's arguments behind the game id = paac_match_step's, behind the shape checks the two share."""
+    if probs.dim() != 2:
+        raise ValueError("probs must be [N, A], got %s" % (tuple(probs.shape),))
+    N, A = probs.shape
+    stacks = _stack_ptrs(N, stack_in=stack_in, stack_out=stack_out)
+    states = _state_ptrs(N, words, state_in=state_in, state_out=state_out)
+    env_offset = _env_offset(fn, env_offset, N)
+    return [_ptr(probs, torch.float32, N * A, "probs"), N, A, 1 if greedy else 0, int(eval_seed) & 0xFFFFFFFFFFFFFFFF, int(noops),
+            _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset), int(env_seed) & 0xFFFFFFFFFFFFFFFF,
+            env_offset, *states, *stacks, _ptr(actions_out, torch.int32, N, "actions_out"),
+            _ptr(score, torch.float32, N, "score"), _ptr(length, torch.int32, N, "length"), _ptr(done, torch.int32, N, "done"),
+            _ptr(alive, torch.int32, 1, "alive")]
 
 
 def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
@@ -917,25 +935,10 @@ def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset,
     if game not in EVAL_GAMES:
         raise ValueError("eval_step: game %r has no device evaluation (--emulator catch|bricks|rally)" % (game,))
     game_id, words = EVAL_GAMES[game]
-    if probs.dim() != 2:
-        raise ValueError("probs must be [N, A], got %s" % (tuple(probs.shape),))
-    N, A = probs.shape
-    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out)):
-        if tuple(t.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
-    for nm, t in (("state_in", state_in), ("state_out", state_out)):
-        if tuple(t.shape) != (N, words):
-            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
-    if not 0 <= int(env_offset) <= 0xFFFFFFFF - N:
-        raise ValueError("eval_step: env_offset %r" % (env_offset,))
-    _lib.check(_lib.load().paac_eval_step(
-        game_id, _ptr(probs, torch.float32, N * A, "probs"), N, A, 1 if greedy else 0, int(eval_seed) & 0xFFFFFFFFFFFFFFFF,
-        int(noops), _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
-        int(env_seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), _ptr(state_in, torch.int32, N * words, "state_in"),
-        _ptr(state_out, torch.int32, N * words, "state_out"), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"),
-        _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(actions_out, torch.int32, N, "actions_out"),
-        _ptr(score, torch.float32, N, "score"), _ptr(length, torch.int32, N, "length"), _ptr(done, torch.int32, N, "done"),
-        _ptr(alive, torch.int32, 1, "alive"), _stream()), "paac_eval_step")
+    _lib.check(_lib.load().paac_eval_step(game_id, *_scored_step_args("eval_step", words, probs, greedy, eval_seed, noops, step_base_dev,
+                                                                      step_offset, env_seed, env_offset, state_in, state_out,
+                                                                      stack_in, stack_out, actions_out, score, length, done, alive),
+                                          _stream()), "paac_eval_step")
 
 
 def match_step(probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
@@ -944,26 +947,10 @@ def match_step(probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_
     eval_step's argument list without the game.  probs [N, 6]: rows [0, N / 2) are the bottom players' policy's, rows
     [N / 2, N) the top players'.  Shapes are checked here; the library refuses an odd N, N < 2, A != 6, negative noops and
     in-place buffers with a PaacHipError, before any launch."""
-    words = DUEL_STATE_WORDS
-    if probs.dim() != 2:
-        raise ValueError("probs must be [N, A], got %s" % (tuple(probs.shape),))
-    N, A = probs.shape
-    for nm, t in (("stack_in", stack_in), ("stack_out", stack_out)):
-        if tuple(t.shape) != (N,) + OBS_SHAPE:
-            raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, N, tuple(t.shape)))
-    for nm, t in (("state_in", state_in), ("state_out", state_out)):
-        if tuple(t.shape) != (N, words):
-            raise ValueError("%s must be [%d,%d], got %s" % (nm, N, words, tuple(t.shape)))
-    if not 0 <= int(env_offset) <= 0xFFFFFFFF - N:
-        raise ValueError("match_step: env_offset %r" % (env_offset,))
-    _lib.check(_lib.load().paac_match_step(
-        _ptr(probs, torch.float32, N * A, "probs"), N, A, 1 if greedy else 0, int(eval_seed) & 0xFFFFFFFFFFFFFFFF,
-        int(noops), _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset),
-        int(env_seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), _ptr(state_in, torch.int32, N * words, "state_in"),
-        _ptr(state_out, torch.int32, N * words, "state_out"), _ptr(stack_in, torch.uint8, N * 28224, "stack_in"),
-        _ptr(stack_out, torch.uint8, N * 28224, "stack_out"), _ptr(actions_out, torch.int32, N, "actions_out"),
-        _ptr(score, torch.float32, N, "score"), _ptr(length, torch.int32, N, "length"), _ptr(done, torch.int32, N, "done"),
-        _ptr(alive, torch.int32, 1, "alive"), _stream()), "paac_match_step")
+    _lib.check(_lib.load().paac_match_step(*_scored_step_args("match_step", DUEL_STATE_WORDS, probs, greedy, eval_seed, noops,
+                                                              step_base_dev, step_offset, env_seed, env_offset, state_in, state_out,
+                                                              stack_in, stack_out, actions_out, score, length, done, alive),
+                                           _stream()), "paac_match_step")
 
 
 FUSED_SAMPLE_MAX_DRAWS = 2304

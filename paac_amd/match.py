@@ -3,7 +3,7 @@
 This is the SPEC of a match, as evaluation.py is the spec of an evaluation; the same numbers are produced
   * on the host by the plain-numpy functions below (`match_actions`, `replay_match`, with evaluation.eval_noops / account and
     duel.DuelBoards), and
-  * on the device by paac_match_step (csrc/misc.hip; include/paac_hip.h has the contract), one step of N rows = N / 2 boards
+  * on the device by paac_match_step (csrc/games.hip; include/paac_hip.h has the contract), one step of N rows = N / 2 boards
     per launch, driven by `DeviceMatch`.
 
 Spec
@@ -21,14 +21,12 @@ Spec
   sides        fixed by the board index, so that side and serve asymmetry cancel: X is the bottom player on boards
                [0, ceil(count / 2)) and the top player on the rest; swap_sides reverses this
 """
-import time
-
 import numpy as np
 
 from . import duel
-from .evaluation import MAX_CHUNK, account, check_count, eval_action, eval_noops, philox_word0
+from .evaluation import MAX_CHUNK, DeviceDriver, account, eval_action, eval_noops, philox_word0
 
-MATCH_STREAM_TOP = 0x45560003          # csrc/misc.hip: kMatchStreamTop
+MATCH_STREAM_TOP = 0x45560003          # csrc/games.hip: kMatchStreamTop
 MATCH_KINDS = ("rally", "duel")        # the runs whose agents play this board: 6 actions, the same planes
 MAX_EPISODE_STEPS = duel.MAX_STEPS
 
@@ -115,7 +113,7 @@ def check_train_flags(args):
     return True
 
 
-class DeviceMatch(object):
+class DeviceMatch(DeviceDriver):
     """Plays `count` duel boards, one scored episode each, between player X (params_x through ctx_x) and player Y -- nothing
     crosses to the host but one int32 per block of steps.
 
@@ -124,44 +122,32 @@ class DeviceMatch(object):
     geometries agree -- its forwards repack what they are handed.  seed: the match's own (no-ops and sampled actions);
     game_seed: the boards'.  Each leg (a side of X) is played in chunks of at most min(ctx.max_batch, MAX_CHUNK) boards,
     env_offset advancing.  steps_per_launch: steps per block (made even: the ping-pong closes), one hipGraph per (chunk size,
-    offset, leg) when use_graph; record=True runs eagerly and keeps the action trace."""
+    offset, leg) when use_graph; record=True runs eagerly and keeps the action trace.
+
+    run(): X's scores and lengths; the trace's column b is the bottom player of board b, column count + b its top player."""
+
+    rows_per_board = 2
 
     def __init__(self, params_x, ctx_x, params_y, ctx_y, count, noops=30, greedy=False, seed=0, game_seed=0, steps_per_launch=16,
                  record=False, use_graph=True, stream=None, swap_sides=False):
-        import torch
         from . import hip_ops
-        self.count = check_count(count)
-        if isinstance(noops, bool) or int(noops) != noops or int(noops) < 0:
-            raise ValueError("noops %r: expected an integer >= 0" % (noops,))
-        if int(steps_per_launch) < 1:
-            raise ValueError("steps_per_launch %r: expected a positive integer" % (steps_per_launch,))
+        super(DeviceMatch, self).__init__(hip_ops, count, noops, seed, greedy, steps_per_launch, record, use_graph)
         for who, params, ctx in (("X", params_x, ctx_x), ("Y", params_y, ctx_y)):
             if ctx.num_actions != duel.NUM_ACTIONS:
                 raise ValueError("player %s: a context of %d actions; the duel board has %d" % (who, ctx.num_actions, duel.NUM_ACTIONS))
             if params.numel() != ctx.layout["total"]:
                 raise ValueError("player %s: %d parameters; the context's geometry has %d" % (who, params.numel(), ctx.layout["total"]))
         self.players = ((params_x, ctx_x), (params_y, ctx_y))
-        self.hip_ops = hip_ops
-        self.noops, self.greedy, self.seed, self.game_seed = int(noops), bool(greedy), int(seed), int(game_seed)
-        self.record, self.swap_sides = bool(record), bool(swap_sides)
-        self.block = (int(steps_per_launch) + 1) // 2 * 2
+        self.game_seed, self.swap_sides = int(game_seed), bool(swap_sides)
         self.max_steps = self.noops + MAX_EPISODE_STEPS
-        self.use_graph = bool(use_graph) and not self.record
-        self.chunk = min(self.count, ctx_x.max_batch, ctx_y.max_batch, MAX_CHUNK)
-        dev = params_x.device
-        rows, A = 2 * self.chunk, duel.NUM_ACTIONS
-        self.stacks = [torch.zeros((rows, 84, 84, 4), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.states = [torch.zeros((rows, duel.STATE_WORDS), dtype=torch.int32, device=dev) for _ in range(2)]
-        self.probs = torch.zeros((rows, A), dtype=torch.float32, device=dev)
-        self.actions = torch.zeros((self.block, rows), dtype=torch.int32, device=dev)
-        self.score = torch.zeros(rows, dtype=torch.float32, device=dev)
-        self.length = torch.zeros(rows, dtype=torch.int32, device=dev)
-        self.done = torch.zeros(rows, dtype=torch.int32, device=dev)
-        self.alive = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.graphs = {}                                   # (boards of a chunk, offset, X is bottom) -> the captured block
-        self.launches = 0                                  # blocks issued by the last run()
+        self._allocate(min(self.count, ctx_x.max_batch, ctx_y.max_batch, MAX_CHUNK), duel.STATE_WORDS, duel.NUM_ACTIONS,
+                       params_x.device, stream)
+
+    def _chunks(self):
+        return [(n, env_offset, x_bottom) for env_offset, n, x_bottom in legs(self.count, self.chunk, self.swap_sides)]
+
+    def _reset(self, n, env_offset, x_bottom):
+        self.hip_ops.duel_reset(self.game_seed, env_offset, self.states[0][:2 * n], self.stacks[0][:2 * n])
 
     def _block(self, n, env_offset, x_bottom):
         """`block` x [the bottom player's forward, the top player's forward, one match step] on n boards, then the counter."""
@@ -176,57 +162,12 @@ class DeviceMatch(object):
                            self.actions[j][:2 * n], self.score[:2 * n], self.length[:2 * n], self.done[:2 * n], self.alive)
         ops.counter_add(self.step, self.block)
 
-    def _captured(self, n, env_offset, x_bottom):
-        key = (n, env_offset, x_bottom)
-        if key not in self.graphs:
-            g = self.hip_ops.Graph()
-            g.begin()
-            try:
-                self._block(n, env_offset, x_bottom)
-            except Exception:
-                g.abort()
-                raise
-            g.end()
-            self.graphs[key] = g
-        return self.graphs[key]
+    def _scored_rows(self, n, env_offset, x_bottom):
+        return slice(0, n) if x_bottom else slice(n, 2 * n)
 
-    def run(self):
-        """-> (X's scores float32 [count], lengths int32 [count]) in board order; with record=True also the action trace int32
-        [steps, 2 count] (column b: the bottom player of board b, column count + b: its top player; zero where a chunk had
-        stopped earlier) and the per-board no-op counts int32 [count]."""
-        import torch
-        scores, lengths = np.zeros(self.count, dtype=np.float32), np.zeros(self.count, dtype=np.int32)
-        traces = []
-        self.launches = 0
-        with torch.cuda.stream(self.stream):
-            for env_offset, n, x_bottom in legs(self.count, self.chunk, self.swap_sides):
-                self.hip_ops.duel_reset(self.game_seed, env_offset, self.states[0][:2 * n], self.stacks[0][:2 * n])
-                for t in (self.score, self.length, self.done, self.step):
-                    t.zero_()
-                self.alive.fill_(2 * n)
-                trace, steps = [], 0
-                while steps < self.max_steps:
-                    if self.use_graph:
-                        self._captured(n, env_offset, x_bottom).launch()
-                    else:
-                        self._block(n, env_offset, x_bottom)
-                    steps += self.block
-                    self.launches += 1
-                    if self.record:
-                        trace.append(self.actions[:, :2 * n].cpu().numpy().copy())
-                    if int(self.alive.cpu().item()) == 0:          # (synchronises the stream: the block has run)
-                        break
-                mine = slice(0, n) if x_bottom else slice(n, 2 * n)
-                scores[env_offset:env_offset + n] = self.score[mine].cpu().numpy()
-                lengths[env_offset:env_offset + n] = self.length[mine].cpu().numpy()
-                traces.append((env_offset, n, np.concatenate(trace) if trace else None))
-        if not self.record:
-            return scores, lengths
-        full = np.zeros((max(len(t) for _, _, t in traces), 2 * self.count), dtype=np.int32)
-        for off, n, t in traces:
-            full[:len(t), off:off + n] = t[:, :n]
-            full[:len(t), self.count + off:self.count + off + n] = t[:, n:]
-        return scores, lengths, full, eval_noops(self.seed, np.arange(self.count), self.noops)
+    def _place_trace(self, full, trace, n, env_offset, x_bottom):
+        full[:len(trace), env_offset:env_offset + n] = trace[:, :n]
+        full[:len(trace), self.count + env_offset:self.count + env_offset + n] = trace[:, n:]
 
     def summary(self, scores, lengths, seconds):
         """evaluator.summary's fields, of X's scores, plus the fractions of boards X won, drew and lost."""
@@ -235,14 +176,3 @@ class DeviceMatch(object):
                     max=float(np.max(scores)), std=float(np.std(scores)), mean_length=float(np.mean(lengths)),
                     seconds=float(seconds), wins=float(np.mean(scores > 0)), draws=float(np.mean(scores == 0)),
                     losses=float(np.mean(scores < 0)))
-
-    def timed_run(self):
-        """run() with its wall time -> (scores, lengths, seconds)."""
-        start = time.time()
-        scores, lengths = self.run()[:2]
-        return scores, lengths, time.time() - start
-
-    def close(self):
-        for g in self.graphs.values():
-            g.close()
-        self.graphs = {}

@@ -3,7 +3,7 @@ a scripted opponent's in the top row; a ball that passes a paddle is a point for
 
 This is the SPEC of the rally environment family; the same numbers are produced
   * on the host by `RallyEnvironment` (a BaseEnvironment plugin, numpy and pure Python), and
-  * on the device by paac_rally_reset / paac_rally_step (csrc/rally_dev.h, csrc/misc.hip), N envs per launch.
+  * on the device by paac_rally_reset / paac_rally_step (csrc/rally_dev.h, csrc/games.hip), N envs per launch.
 Catch (catch.py) is a 13-step bandit and bricks (bricks.py) a long game with lives; both have three actions, no adversary and no
 negative reward.  This game has an opponent that plays back, rewards of both signs, the six actions of ALE Pong's minimal set
 (aliases included) and episodes of up to 1000 steps.  Call pattern as BricksEnvironment's: get_initial_state() /

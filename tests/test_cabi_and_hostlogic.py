@@ -26,6 +26,17 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().paac_version() >= 100
 
 
+def test_every_exported_symbol_is_defined_in_exactly_one_source():
+    """The sources are cut by subsystem ("Where the code around the network lives"): an entry point that fell out
+    of a cut, or was left in two files, shows here without a library."""
+    from paac_amd import _lib, build
+    sources = {src: open(os.path.join(build.CSRC, src)).read() for src in build.SOURCES}
+    for name in _lib.EXPORTED_SYMBOLS:
+        definition = re.compile(r"^(int|int64_t|void|const char\*) %s\(" % re.escape(name), re.M)
+        found = [src for src, text in sources.items() for _ in definition.findall(text)]
+        assert len(found) == 1, "%s is defined in %s" % (name, found or "no source")
+
+
 def test_cfg_query_needs_no_device_and_follows_the_table_sizes():
     """paac_debug_cfg_known / paac_debug_cfg_body (what paac_debug_set_tuning and PAAC_TUNE_OVERRIDE validate with): the
     plain band of every op has the number of entries csrc/net_common.h states; the exhaustive walk is tests/test_tuning_table_gpu.py."""

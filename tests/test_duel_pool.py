@@ -110,7 +110,7 @@ def test_the_ghost_action_rule_and_its_stream():
 
 
 def test_the_stream_is_the_kernels_constant():
-    source = open(os.path.join(ROOT, "paac_amd", "csrc", "misc.hip")).read()
+    source = open(os.path.join(ROOT, "paac_amd", "csrc", "games.hip")).read()
     assert int(re.search(r"constexpr uint32_t kGhostStream = (0x[0-9A-Fa-f]+)u;", source).group(1), 16) == duel_pool.GHOST_STREAM
     assert (duel_pool.GHOST_STREAM, duel_pool.POOL_STREAM_LATEST, duel_pool.POOL_STREAM_SLOT) == (0x44500001, 0x44500002, 0x44500003)
 
@@ -263,5 +263,5 @@ def test_the_entries_are_declared_and_exported_and_no_kind_was_added():
     assert callable(hip_ops.duel_ghost_reset) and callable(hip_ops.duel_ghost_step)
     # a flag on --emulator duel, not a new emulator kind
     assert set(hip_ops.PAIRED_GAMES) == set(paac.PAIRED_KINDS) == set(environment_creator.PAIRED_GAMES) == {"duel"}
-    source = open(os.path.join(ROOT, "paac_amd", "csrc", "misc.hip")).read()
+    source = open(os.path.join(ROOT, "paac_amd", "csrc", "games.hip")).read()
     assert "void ghost_step_kernel(" in source and "dim3(2 * N, PRE_BANDS)" in source

@@ -22,7 +22,7 @@ def test_stream_constants():
     for c in (EVAL_STREAM_ACTION, EVAL_STREAM_NOOP):
         assert 0 < c < 2 ** 32 and not 0x504D0000 <= c < 0x504D0040
     # ... and the kernel source holds the same two numbers
-    src = open(os.path.join(os.path.dirname(evaluation.__file__), "csrc", "misc.hip")).read()
+    src = open(os.path.join(os.path.dirname(evaluation.__file__), "csrc", "games.hip")).read()
     assert "kEvalStreamAction = 0x%08Xu" % EVAL_STREAM_ACTION in src and "kEvalStreamNoop = 0x%08Xu" % EVAL_STREAM_NOOP in src
 
 

@@ -256,7 +256,7 @@ def test_the_c_entry_is_declared_and_exported():
 
 
 def test_the_top_stream_is_the_kernels_constant():
-    source = open(os.path.join(ROOT, "paac_amd", "csrc", "misc.hip")).read()
+    source = open(os.path.join(ROOT, "paac_amd", "csrc", "games.hip")).read()
     top = re.search(r"constexpr uint32_t kMatchStreamTop = (0x[0-9A-Fa-f]+)u;", source).group(1)
     assert int(top, 16) == match.MATCH_STREAM_TOP
     for name, value in (("kEvalStreamAction", evaluation.EVAL_STREAM_ACTION), ("kEvalStreamNoop", evaluation.EVAL_STREAM_NOOP)):

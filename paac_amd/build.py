@@ -21,6 +21,13 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def library_is_current(lib):
+    """True where `lib` exists and is newer than every source, every header and this file: nothing it was built from has
+    changed since, whether or not its object files are still there."""
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    return not _stale(lib, deps)
+
+
 def build(force=False, verbose=True, extra_flags=(), lib_path=None, obj_suffix=""):
     """extra_flags / lib_path / obj_suffix: diagnostic variants (e.g. -DPAAC_DMM_STAMPS into libpaac_hip_stamps.so).
     Safe to call from several processes at once (every torchrun rank calls it for a user architecture): the build runs
@@ -96,20 +103,22 @@ def parse_user_arch(spec):
 FAMILY = [(8, 4), (4, 2), (3, 1)]      # (kernel size, stride) of the reference trunks' layers (networks.py:145-149, :161-167)
 
 
-def user_arch_library(convs, fc):
-    """In-tree path of the library compiled for a user architecture (convs: [(filters, size, stride), ...])."""
+def user_arch_library(convs, fc, variant=""):
+    """In-tree path of the library compiled for a user architecture (convs: [(filters, size, stride), ...]); variant: the tag
+    of a diagnostic build of it ("_rowdiv")."""
     convs = [tuple(int(v) for v in c) for c in convs]
     tag = "_".join(str(f) for f, _, _ in convs) + "_%d" % fc
     if any((k, s) != FAMILY[i] for i, (_, k, s) in enumerate(convs)):      # other layer shapes: they are part of the name
         tag += "_k" + "_".join("%dx%d" % (k, s) for _, k, s in convs)
+    tag += variant
     return os.path.join(HERE, "libpaac_hip_user_%s.so" % tag), "_user_" + tag
 
 
-def build_user_arch(convs, fc, verbose=False):
+def build_user_arch(convs, fc, verbose=False, variant="", variant_flags=()):
     """Compile libpaac_hip for a user architecture (include/paac_hip.h: PAAC_ARCH_USER; reference networks.py:117-120): two or
     three VALID conv layers (filters, size, stride) over the 84 x 84 x 4 input, then an fc layer.  The geometry is a
     compile-time template argument of every kernel, so a new architecture is a new build (about a minute of hipcc), cached
-    in-tree by its shape.  The reference trunks' layer shapes -- conv 8x8 / 4, conv 4x4 / 2 [, conv 3x3 / 1] -- run on the MFMA
+    in-tree by its shape (variant / variant_flags: a diagnostic build of it, under its own name).  The reference trunks' layer shapes -- conv 8x8 / 4, conv 4x4 / 2 [, conv 3x3 / 1] -- run on the MFMA
     data-gradient forms; any other kernel size / stride runs its forward and weight gradient on the same generic MFMA
     contraction (dmm.h) and its data gradient on a direct kernel.  Returns the library path."""
     convs = [tuple(int(v) for v in c) for c in convs]
@@ -128,8 +137,8 @@ def build_user_arch(convs, fc, verbose=False):
         if size < k:
             raise ValueError("layer shapes %r leave no output (VALID convolutions over 84 x 84)" % (convs,))
         size = (size - k) // s + 1
-    lib, suffix = user_arch_library(convs, fc)
-    flags = ["-DPAAC_USER_ARCH", "-DPAAC_USER_NCONV=%d" % len(convs), "-DPAAC_USER_C1=%d" % convs[0][0],
+    lib, suffix = user_arch_library(convs, fc, variant)
+    flags = list(variant_flags) + ["-DPAAC_USER_ARCH", "-DPAAC_USER_NCONV=%d" % len(convs), "-DPAAC_USER_C1=%d" % convs[0][0],
              "-DPAAC_USER_C2=%d" % convs[1][0], "-DPAAC_USER_C3=%d" % (convs[2][0] if len(convs) == 3 else 0),
              "-DPAAC_USER_H=%d" % fc]
     layers = convs + [(0, 3, 1)] * (3 - len(convs))
@@ -141,15 +150,36 @@ def build_user_arch(convs, fc, verbose=False):
         raise RuntimeError("building the user architecture %s (fc %d) failed: %s" % (convs, fc, exc)) from exc
 
 
+ROWDIV_FLAGS = ["-DPAAC_WGRAD_ROW_WALK=0"]
+
+
+def rowdiv_library(spec=None):
+    """In-tree path of the build whose weight gradients decompose their patch rows by division per load (csrc/dmm.h:
+    PAAC_WGRAD_ROW_WALK=0) instead of walking them: the stock library, or the one of user architecture `spec`."""
+    if spec is None:
+        return os.path.join(HERE, "libpaac_hip_rowdiv.so")
+    return user_arch_library(*parse_user_arch(spec), variant="_rowdiv")[0]
+
+
+def build_rowdiv(spec=None, verbose=False):
+    if spec is None:
+        return build(verbose=verbose, extra_flags=ROWDIV_FLAGS, lib_path=rowdiv_library(), obj_suffix="_rowdiv")
+    return build_user_arch(*parse_user_arch(spec), verbose=verbose, variant="_rowdiv", variant_flags=ROWDIV_FLAGS)
+
+
 if __name__ == "__main__":
     if "--user-arch" in sys.argv:        # e.g. --user-arch 32,64,64,1024 (filter counts, then the fc width), or
         spec = sys.argv[sys.argv.index("--user-arch") + 1]          # 32:8:4,64:5:2,64:3:1,512 (filters:size:stride per layer)
         print(build_user_arch(*parse_user_arch(spec), verbose=True))
-    elif "--stamps" in sys.argv or "--ksplit" in sys.argv:
+    elif "--stamps" in sys.argv or "--ksplit" in sys.argv or "--rowdiv" in sys.argv:
         # --stamps: cycle stamps inside the kernels (tools/probe_*stamps.py); --ksplit: the conv tower's small regions on the K
-        # split over wave pairs instead of GEMM / helper wave roles (csrc/tower.h: PAAC_T_ROLES), for A/B runs.  They combine.
-        tag = ("_stamps" if "--stamps" in sys.argv else "") + ("_ksplit" if "--ksplit" in sys.argv else "")
-        flags = (["-DPAAC_DMM_STAMPS"] if "--stamps" in sys.argv else []) + (["-DPAAC_T_ROLES=0"] if "--ksplit" in sys.argv else [])
+        # split over wave pairs instead of GEMM / helper wave roles (csrc/tower.h: PAAC_T_ROLES), for A/B runs; --rowdiv: the
+        # weight gradients' patch rows decomposed by division per load instead of walked (csrc/dmm.h: PAAC_WGRAD_ROW_WALK),
+        # for A/B runs and tests/test_wgrad_row_walk_gpu.py.  They combine.
+        variants = [("--stamps", "_stamps", "-DPAAC_DMM_STAMPS"), ("--ksplit", "_ksplit", "-DPAAC_T_ROLES=0"),
+                    ("--rowdiv", "_rowdiv", "-DPAAC_WGRAD_ROW_WALK=0")]
+        tag = "".join(t for a, t, _ in variants if a in sys.argv)
+        flags = [f for a, _, f in variants if a in sys.argv]
         print(build(extra_flags=flags, lib_path=os.path.join(HERE, "libpaac_hip%s.so" % tag), obj_suffix=tag))
     else:
         print(build(force="--force" in sys.argv))

@@ -39,6 +39,78 @@ struct Geom {
   static constexpr bool PADDED = (PH_ != 0) || (PW_ != 0);
 };
 
+// Weight gradients: the patch row of every FRAG_MN A load comes from a walk over (sample, oy, ox) instead of being
+// decomposed from its row index with two divisions per load.  0 keeps the division form (`python -m paac_amd.build
+// --rowdiv`), for A/B runs and the equality test; both request the same addresses, load for load.
+#ifndef PAAC_WGRAD_ROW_WALK
+#define PAAC_WGRAD_ROW_WALK 1
+#endif
+
+// Patch row r = (b * OH + oy) * OW + ox of geometry G as a running state: `off` is the byte offset of the lane's load
+// (element size ES; the lane's kernel row / column folded in), `oy`, `ox` carry the wraps.  step<N> moves N rows
+// ahead without a division: N = QB samples + QY lines + QX pixels at compile time, then at most one carry out of ox
+// (ox < OW and QX < OW) and one out of oy (oy < OH, QY <= OH - 1, carry <= 1).
+template <class G, unsigned ES>
+struct RowWalk {
+  static constexpr unsigned SX = (unsigned)(G::S * G::C) * ES;             // one pixel to the right
+  static constexpr unsigned SY = (unsigned)(G::S * G::IW * G::C) * ES;     // one line down
+  static constexpr unsigned SB = (unsigned)(G::IH * G::IW * G::C) * ES;    // one sample on
+  unsigned off;
+  int oy, ox;
+  __device__ __forceinline__ void start(int r, int f_kh, int f_kwc) {
+    const int b = r / G::OPIX;
+    const int rem = r - b * G::OPIX;
+    oy = rem / G::OW;
+    ox = rem - oy * G::OW;
+    off = (unsigned)(((b * G::IH + oy * G::S - G::PH + f_kh) * G::IW + ox * G::S - G::PW) * G::C + f_kwc) * ES;
+  }
+  template <int N>
+  __device__ __forceinline__ void step() {
+    constexpr int QB = N / G::OPIX, R = N % G::OPIX, QY = R / G::OW, QX = R % G::OW;
+    off += (unsigned)QB * SB + (unsigned)QY * SY + (unsigned)QX * SX;
+    if constexpr (R != 0) {
+      if constexpr (QX != 0) {
+        ox += QX;
+        const bool cx = ox >= G::OW;
+        ox = cx ? ox - G::OW : ox;
+        oy += cx ? QY + 1 : QY;
+        off += cx ? SY - (unsigned)G::OW * SX : 0u;
+      } else {
+        oy += QY;
+      }
+      const bool cy = oy >= G::OH;
+      oy = cy ? oy - G::OH : oy;
+      off += cy ? SB - (unsigned)G::OH * SY : 0u;
+    }
+  }
+  // The row s (0..3, a constant once the caller's loop is unrolled) ahead of this one, this one left where it is.  On a
+  // line of more than s pixels at most one carry leaves ox, and with it at most one leaves oy: a compare, a select and an
+  // add, the line-end correction chosen once per row walked from (the compiler shares it among the s).  Zero padding needs
+  // (oy, ox) too and short lines can carry twice: those take single steps.
+  __device__ __forceinline__ RowWalk ahead(int s) const {
+    RowWalk r = *this;
+    if (s == 0) return r;
+    if (!G::PADDED && G::OW > s) {
+      const unsigned wrap = (oy == G::OH - 1) ? SY - (unsigned)G::OW * SX + SB - (unsigned)G::OH * SY : SY - (unsigned)G::OW * SX;
+      r.off = off + (unsigned)s * SX + ((ox >= G::OW - s) ? wrap : 0u);
+    } else {
+      for (int i = 0; i < s; ++i) r.template step<1>();
+    }
+    return r;
+  }
+};
+
+// The type of a lane's walk state: RowWalk for a FRAG_MN A operand, an empty struct where ON is false (FRAG_K bodies --
+// forward, data gradient -- which walk nothing).
+template <class G, unsigned ES, bool ON>
+struct LaneRows {
+  struct Walk {};
+};
+template <class G, unsigned ES>
+struct LaneRows<G, ES, true> {
+  using Walk = RowWalk<G, ES>;
+};
+
 enum { FRAG_K = 0, FRAG_MN = 1 };
 enum { EPI_BIAS_RELU = 0, EPI_SLAB = 1, EPI_MASK = 2, EPI_MASK_PARITY = 3 };
 
@@ -346,6 +418,16 @@ struct Dmm {
   // no branch around its loads and the compiler's s_waitcnt placement keeps the full prefetch distance.
   f32x4 fa[RING][GS][NA], fb[RING][GS][NB];
   unsigned ua[RING][GS][NA];                    // XB: the raw bytes of the A operand (4 per lane and load)
+#if PAAC_WGRAD_ROW_WALK
+  // FRAG_MN A: the lane's rows 16 (GS g + gs) + 4 kq + s are walked, not decomposed.  load_group is called for
+  // g = g_begin, g_begin + 1, ... in order (prologue, then the loop, dead groups included), which is what the walk
+  // follows; the division happens once, here, for the lane's first row.
+  // A FRAG_K body (forward, data gradient) walks nothing: its `walk` is an empty struct.
+  typename LaneRows<G, ES, AP == FRAG_MN>::Walk walk;
+  if constexpr (AP == FRAG_MN) walk.start(KSTAGE * g_begin + 4 * kq, f_kh, f_kwc);
+  // row r = k16 + 4 kq + s is live while k16 + s < walk_end (never, for a lane whose features are out of range)
+  const int walk_end = f_ok ? k_end - 4 * kq : -(1 << 30);
+#endif
   auto load_group = [&](int slot, int g, bool live) {
     const unsigned kill = live ? 0u : kOob;     // wave-uniform
 #pragma unroll
@@ -383,8 +465,24 @@ struct Dmm {
     } else {
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const int r = k16 + 4 * kq + s;
+        // (read by the division form only.  It stays in front of both forms: declared inside the #else, the walk form's
+        // kernels come out with another instruction schedule than the one that was measured)
+        [[maybe_unused]] const int r = k16 + 4 * kq + s;
         unsigned off = kOob;
+#if PAAC_WGRAD_ROW_WALK
+        // `walk` stands on the group's first row 4 kq + k16; row s is read off it, then it moves 16 rows on
+        {
+          const RowWalk<G, ES> row = walk.ahead(s);
+          bool ok = k16 + s < walk_end;
+          if constexpr (G::PADDED) {
+            const int iy = row.oy * G::S - G::PH + f_kh;
+            const int ix = row.ox * G::S - G::PW + f_kw;
+            ok = ok && (iy >= 0) && (iy < G::IH) && (ix >= 0) && (ix < G::IW);
+          }
+          off = ok ? row.off : kOob;
+          if (s == 3) walk.template step<16>();
+        }
+#else
         if (f_ok && r < k_end) {
           const int b = r / G::OPIX;
           const int rem = r - b * G::OPIX;
@@ -396,6 +494,7 @@ struct Dmm {
           if constexpr (G::PADDED) ok = (iy >= 0) && (iy < G::IH) && (ix0 + f_kw >= 0) && (ix0 + f_kw < G::IW);
           if (ok) off = (unsigned)(((b * G::IH + iy) * G::IW + ix0) * G::C + f_kwc) * ES;
         }
+#endif
         if constexpr (U8) {
           static_assert(!U8 || TM == 4, "u8 FRAG_MN loads are uchar4");
           if constexpr (XB == 1) ua[slot][gs][s] = __builtin_amdgcn_raw_buffer_load_b32(rsA, off, 0, 0);

@@ -559,7 +559,7 @@ static int backward_impl(paac_ctx* ctx, const float* params, const uint8_t* stat
     }
     int splits = 0;
     // The conv2 and conv1 weight gradients wait on the data-gradient tower only, and a workgroup of each fits a CU
-    // together (two 4-wave bodies, 133 registers, 66.5 KB of LDS: 2 per CU = the 256 + 256 workgroups of the pair): one
+    // together (two 4-wave bodies, 139 registers, 66.5 KB of LDS: 2 per CU = the 256 + 256 workgroups of the pair): one
     // launch.  conv1 runs its 4-wave configuration here (alone its 8-wave one is faster; in the pair it is not).
     if constexpr (NT::FAMILY) {       // (the stock NIPS geometry too: its heuristics land on the pair's configurations)
       static const bool pair_on = env_int("PAAC_WGRAD_PAIR", 1) != 0;

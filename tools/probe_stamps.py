@@ -1,4 +1,7 @@
-"""Diagnostic (stamped build only): where one dmm wave spends its cycles.  PAAC_HIP_LIB=.../libpaac_hip_stamps.so"""
+"""Diagnostic (stamped build only): where one dmm wave spends its cycles.  PAAC_HIP_LIB=.../libpaac_hip_stamps.so
+PROBE_MODE=fwd (default) stamps the forward bodies, PROBE_MODE=bwd those of one loss_backward too, in the launches the
+update really makes: a body of a paired launch is stamped with its partner running beside it.  PROBE_B: batch rows (32).
+profiles/r07_wgrad_stamps.txt is PROBE_MODE=bwd PROBE_B=160 on the --stamps and the --stamps --rowdiv builds."""
 import sys, os, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -40,3 +43,8 @@ for which in range(4 if mode == "fwd" else 11):
         (w7.max() - w0.min()) / 100))
     seg = np.diff(st[:, 1:7].astype(np.float64), axis=1)
     print("    " + " | ".join("%s %d" % (n, np.median(seg[:, i])) for i, n in enumerate(names)) + "  (median cycles)")
+    # the K loop (prologue loads + main loop, stamp slots 2 -> 4) against the wave's lifetime (slots 1 -> 6), in cycles
+    kloop, life = seg[:, 1] + seg[:, 2], seg.sum(axis=1)
+    live = kloop > 0
+    print("    K loop %d of %d cycles (medians) = %.2f of the lifetime (median share over the %d waves with a K range)" % (
+        np.median(kloop), np.median(life), np.median(kloop[live] / life[live]), live.sum()))

@@ -653,9 +653,26 @@ int paac_duel_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_ou
 int paac_duel_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
                    int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out, uint8_t* stack_out2,
                    const paac_env_records* rec, paac_stream_t stream);
+/* A user's device game (--emulator user --device_game; plugin contract in paac_amd/user_game.py and csrc/game_dev.h): one
+ * non-paired game trait from a header outside the package, compiled into a library of its own (-DPAAC_USER_GAME,
+ * -DPAAC_USER_GAME_HEADER, -DPAAC_USER_GAME_TRAIT) and run by the same step and evaluation kernels as the built-in games.
+ * paac_user_game_info: returns 1 and fills the trait's kWords, kActions and kMaxSteps where a user game is compiled in;
+ *   returns 0 (and zeros) in the stock library.
+ * paac_user_game_reset: paac_catch_reset's argument list, outputs and refusals, state i32 [N, kWords].
+ * paac_user_game_step: paac_duel_step's argument list (the records as one block, rec->truncs nullable) with the game's one
+ *   integer option before the stream (0 where the game has none); outputs and refusals as paac_game_step's.  One launch.
+ * The game's id for paac_game_step / paac_eval_step is PAAC_EVAL_USER.  In the stock library reset and step fail with a
+ * message, without a launch, and PAAC_EVAL_USER is refused as any unknown id is. */
+int paac_user_game_info(int* words, int* actions, int* max_steps);
+int paac_user_game_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                         paac_stream_t stream);
+int paac_user_game_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                        int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                        uint8_t* stack_out2, const paac_env_records* rec, int option, paac_stream_t stream);
 #define PAAC_EVAL_CATCH 0
 #define PAAC_EVAL_BRICKS 1
 #define PAAC_EVAL_RALLY 2
+#define PAAC_EVAL_USER 3 /* the user's game: only in a library built with one (paac_user_game_info below) */
 int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
                    const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
                    const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out,

@@ -21,6 +21,7 @@ PPO_MINIBATCHES_MAX = 16       # PAAC_PPO_MINIBATCHES_MAX
 PPO_STEPS_MAX = 64             # PAAC_PPO_STEPS_MAX: optimizer steps (epochs x minibatches) of one cycle
 MINIBATCH_MAX_ROWS = 8192      # PAAC_MINIBATCH_MAX_ROWS
 EVAL_CATCH, EVAL_BRICKS, EVAL_RALLY = 0, 1, 2          # PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS, PAAC_EVAL_RALLY
+EVAL_USER = 3                  # PAAC_EVAL_USER: the user's game, in a library built with one (paac_amd/user_game.py)
 
 
 class Layout(ctypes.Structure):
@@ -185,6 +186,11 @@ _SIGNATURES["paac_duel_step"] = (c_int, [c_uint64, c_uint32, c_int] + [c_void_p]
 _SIGNATURES["paac_duel_ghost_reset"] = (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p])
 _SIGNATURES["paac_duel_ghost_step"] = (c_int, [c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_uint64] +
                                        [c_void_p] * 9 + [POINTER(EnvRecords), c_void_p, c_void_p])
+# the user's game (hip_ops.USER_GAMES; paac_amd/user_game.py): what is compiled in, catch's reset list, and duel's step list with
+# the game's one integer option before the stream
+_SIGNATURES["paac_user_game_info"] = (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)])
+_SIGNATURES["paac_user_game_reset"] = _SIGNATURES["paac_catch_reset"]
+_SIGNATURES["paac_user_game_step"] = (c_int, [c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p])
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 
@@ -209,6 +215,14 @@ def user_arch():
     sizes, strides = (c_int32 * 3)(), (c_int32 * 3)()
     load().paac_user_arch_layers(sizes, strides)
     return [(int(filters[i]), int(sizes[i]), int(strides[i])) for i in range(nconv.value)], int(fc.value)
+
+
+def user_game():
+    """-> (state words, actions, max episode steps) of the user game compiled into the loaded library, or None (no user game)."""
+    words, actions, max_steps = c_int(), c_int(), c_int()
+    if not load().paac_user_game_info(ctypes.byref(words), ctypes.byref(actions), ctypes.byref(max_steps)):
+        return None
+    return int(words.value), int(actions.value), int(max_steps.value)
 
 
 def load():

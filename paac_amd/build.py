@@ -1,6 +1,8 @@
 """In-tree build of libpaac_hip.so (gfx950 only).  Used by __graft_entry__.build() and `python -m paac_amd.build`."""
 import fcntl
+import hashlib
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -21,15 +23,18 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def library_is_current(lib):
-    """True where `lib` exists and is newer than every source, every header and this file: nothing it was built from has
-    changed since, whether or not its object files are still there."""
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+def library_is_current(lib, extra_deps=()):
+    """True where `lib` exists and is newer than every source, every header and this file (and extra_deps: a user game's
+    header): nothing it was built from has changed since, whether or not its object files are still there."""
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.abspath(__file__)] + list(extra_deps)
     return not _stale(lib, deps)
 
 
-def build(force=False, verbose=True, extra_flags=(), lib_path=None, obj_suffix=""):
+def build(force=False, verbose=True, extra_flags=(), lib_path=None, obj_suffix="", extra_deps=(), only=None):
     """extra_flags / lib_path / obj_suffix: diagnostic variants (e.g. -DPAAC_DMM_STAMPS into libpaac_hip_stamps.so).
+    extra_deps: files outside csrc/ the variant's objects are built from as well (a user game's header).  only: the sources
+    the variant compiles for itself; the others are linked from the stock build's objects, which the caller has made current
+    and keeps from being rewritten (build_user_game).
     Safe to call from several processes at once (every torchrun rank calls it for a user architecture): the build runs
     under an exclusive file lock next to the library, objects and library are written to temporary names and renamed into
     place, so a rank that has already loaded the library never sees it rewritten under it."""
@@ -37,17 +42,20 @@ def build(force=False, verbose=True, extra_flags=(), lib_path=None, obj_suffix="
     with open(lib + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            return _build_locked(force, verbose, extra_flags, lib, obj_suffix)
+            return _build_locked(force, verbose, extra_flags, lib, obj_suffix, extra_deps, only)
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(force, verbose, extra_flags, lib, obj_suffix):
+def _build_locked(force, verbose, extra_flags, lib, obj_suffix, extra_deps=(), only=None):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
+    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)] + list(extra_deps)
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
+        if only is not None and src not in only:
+            objs.append(os.path.join(CSRC, src.replace(".hip", ".o")))      # the stock build's object
+            continue
         o = os.path.join(CSRC, src.replace(".hip", obj_suffix + ".o"))
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
@@ -148,6 +156,76 @@ def build_user_arch(convs, fc, verbose=False, variant="", variant_flags=()):
         return build(verbose=verbose, extra_flags=flags, lib_path=lib, obj_suffix=suffix)
     except RuntimeError as exc:
         raise RuntimeError("building the user architecture %s (fc %d) failed: %s" % (convs, fc, exc)) from exc
+
+
+USER_GAME_SOURCES = ("games.hip",)      # the only source that reads PAAC_USER_GAME
+
+
+def user_game_library(tag):
+    """In-tree path of the library compiled for the user game `tag` (the specification module's file stem), and the suffix of
+    its objects."""
+    if not re.fullmatch(r"[A-Za-z0-9_]+", str(tag)):
+        raise ValueError("device game tag %r (the specification module's file stem) must match [A-Za-z0-9_]+: it becomes part "
+                         "of a library's file name" % (tag,))
+    return os.path.join(HERE, "libpaac_hip_game_%s.so" % tag), "_game_" + tag
+
+
+def _write_sidecar(sidecar, header, trait, digest):
+    tmp = "%s.tmp.%d" % (sidecar, os.getpid())
+    with open(tmp, "w") as f:
+        f.write("%s\n%s\n%s\n" % (header, trait, digest))
+    os.replace(tmp, sidecar)
+
+
+def build_user_game(header, trait, tag, verbose=False):
+    """Compile libpaac_hip with a user's device game in it (include/paac_hip.h: paac_user_game_info; the plugin contract is
+    paac_amd/user_game.py's and csrc/game_dev.h's): `header` holds the trait struct `trait`, `tag` names the library.  Only
+    games.hip reads the game, so only it is compiled again (a few seconds of hipcc); the other five objects are the stock
+    build's, brought up to date first and held under the stock build's lock until the library is linked.  The header is among
+    the dependencies: editing it rebuilds the library; a library newer than everything it was built from is
+    returned as it is, whether or not the objects are still there.  Two different headers under one tag are refused -- the header's path, the
+    trait and a digest of the header's text are kept in <library>.header; a recorded path that no longer exists or names the same file (the
+    tree was moved, copied or is reached through a link) does not refuse, and the library stands if the text and the trait are the same.  Safe to call from several processes at once, like build().  Returns the library path."""
+    lib, suffix = user_game_library(tag)
+    header = os.path.abspath(header)
+    if not os.path.isfile(header):
+        raise FileNotFoundError("device game header %s not found" % header)
+    if not re.fullmatch(r"[A-Za-z_][A-Za-z0-9_]*(::[A-Za-z_][A-Za-z0-9_]*)*", str(trait)):
+        raise ValueError("device game trait %r is not the (qualified) name of a struct" % (trait,))
+    sidecar = lib + ".header"
+    flags = ["-DPAAC_USER_GAME", '-DPAAC_USER_GAME_HEADER="%s"' % header, "-DPAAC_USER_GAME_TRAIT=%s" % trait, "-I" + CSRC]
+    with open(lib + ".lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            digest = hashlib.sha256(open(header, "rb").read()).hexdigest()
+            force = False
+            if os.path.exists(sidecar):
+                was = open(sidecar).read().split("\n")
+                was_header, was_trait, was_digest = (was + ["", "", ""])[:3]
+                if was_header != header and os.path.isfile(was_header) and not os.path.samefile(was_header, header):
+                    raise ValueError("device game tag %r is taken: %s was built from %s, not from %s -- two games need two file "
+                                     "stems (or remove that library)" % (tag, os.path.basename(lib), was_header, header))
+                # the same path -- or the recorded header is gone: a tree that was moved or copied.  The same text and trait:
+                # the same game, and its library stands if it is newer than everything it was built from, objects kept or not
+                same = was_trait == trait and was_digest == digest
+                if same and library_is_current(lib, [header]):
+                    if was_header != header:
+                        _write_sidecar(sidecar, header, trait, digest)
+                    return lib
+                force = not same
+            with open(LIB + ".lock", "w") as stock:          # lock order: the game's, then the stock build's
+                fcntl.flock(stock, fcntl.LOCK_EX)
+                try:
+                    _build_locked(False, verbose, (), LIB, "")
+                    _build_locked(force, verbose, flags, lib, suffix, extra_deps=[header], only=USER_GAME_SOURCES)
+                finally:
+                    fcntl.flock(stock, fcntl.LOCK_UN)
+            _write_sidecar(sidecar, header, trait, digest)
+            return lib
+        except RuntimeError as exc:
+            raise RuntimeError("building the device game %s (%s in %s) failed: %s" % (tag, trait, header, exc)) from exc
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
 
 
 ROWDIV_FLAGS = ["-DPAAC_WGRAD_ROW_WALK=0"]

@@ -1,13 +1,38 @@
 // The device games (catch, bricks, rally, duel: one trait each, csrc/game_dev.h and the game's header): the step kernel,
-// GPU-resident evaluation, head-to-head matches and the duel against a pool of past selves.
+// GPU-resident evaluation, head-to-head matches and the duel against a pool of past selves; and, in a library built for one,
+// a user's game (-DPAAC_USER_GAME): the same two kernel templates instantiated for a trait from outside the package.
 #include "common.h"
 #include "game_dev.h"
 #include "catch_dev.h"
 #include "bricks_dev.h"
 #include "rally_dev.h"
 #include "duel_dev.h"
+// A user's game (--emulator user --device_game; paac_amd/user_game.py): one more trait, from a header outside the package,
+// in a library of its own (paac_amd/build.py: build_user_game).  It obeys game_dev.h's contract for a non-paired game and
+// states two numbers more: kActions (the policy's width) and kMaxSteps (the longest episode, evaluation's step budget).
+#ifdef PAAC_USER_GAME
+#if !defined(PAAC_USER_GAME_HEADER) || !defined(PAAC_USER_GAME_TRAIT)
+#error "PAAC_USER_GAME needs PAAC_USER_GAME_HEADER (the header to include) and PAAC_USER_GAME_TRAIT (the trait struct in it)"
+#endif
+#include PAAC_USER_GAME_HEADER
+#endif
 
 namespace paac {
+
+#ifdef PAAC_USER_GAME
+typedef PAAC_USER_GAME_TRAIT UserGame;
+template <class G, class = void>
+struct declares_paired : std::false_type {};
+template <class G>
+struct declares_paired<G, std::void_t<decltype(G::kPaired)>> : std::true_type {};
+static_assert(!declares_paired<UserGame>::value,
+              "a user game must not declare kPaired: paired games (two rows per board) are not supported as user games");
+static_assert(UserGame::kWords > 0 && UserGame::kWords % 4 == 0,
+              "a user game's kWords must be positive and a multiple of 4 (the record is loaded in 16-byte parts)");
+static_assert(UserGame::kActions >= 2 && UserGame::kActions <= 32,
+              "a user game's kActions must be within [2, 32] (what paac_eval_step accepts)");
+static_assert(UserGame::kMaxSteps > 0, "a user game's kMaxSteps must be positive");
+#endif
 
 // The device games (catch, bricks, rally: one trait G each, csrc/game_dev.h and the game's header).  The shape of
 // synth_step_a_kernel: grid (N, 7), 256 threads, 252 of them own one quad of four pixels -- one 16-byte load of the old stack,
@@ -371,6 +396,13 @@ static EnvRecords env_records_of(const paac_env_records* rec) {
 // (its single_life), the others 0.  Any other id is refused in the name of the entry `fn`.
 template <class F>
 static int with_game(const char* fn, int game, int option, F&& f) {
+#ifdef PAAC_USER_GAME
+  // a user-game library: the user's game (its option passed through, as bricks') beside the three
+  PAAC_REQUIRE(game == PAAC_EVAL_CATCH || game == PAAC_EVAL_BRICKS || game == PAAC_EVAL_RALLY || game == PAAC_EVAL_USER,
+               "%s: game %d is none of catch (%d), bricks (%d), rally (%d), the user game (%d)", fn, game, PAAC_EVAL_CATCH,
+               PAAC_EVAL_BRICKS, PAAC_EVAL_RALLY, PAAC_EVAL_USER);
+  if (game == PAAC_EVAL_USER) return f(UserGame{}, option);
+#endif
   PAAC_REQUIRE(game == PAAC_EVAL_CATCH || game == PAAC_EVAL_BRICKS || game == PAAC_EVAL_RALLY,
                "%s: game %d is none of catch (%d), bricks (%d), rally (%d)", fn, game, PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS,
                PAAC_EVAL_RALLY);
@@ -440,6 +472,44 @@ int paac_duel_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* act
   PAAC_REQUIRE(rec, "paac_duel_step: null records");
   return game_step<DuelGame>("paac_duel_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in, stack_out,
                              stack_out2, env_records_of(rec), 0, stream);
+}
+
+// The user's game (--emulator user --device_game): the same launchers on the user's trait; the stock library has none.
+int paac_user_game_info(int* words, int* actions, int* max_steps) {
+#ifdef PAAC_USER_GAME
+  if (words) *words = UserGame::kWords;
+  if (actions) *actions = UserGame::kActions;
+  if (max_steps) *max_steps = UserGame::kMaxSteps;
+  return 1;
+#else
+  if (words) *words = 0;
+  if (actions) *actions = 0;
+  if (max_steps) *max_steps = 0;
+  return 0;
+#endif
+}
+
+int paac_user_game_reset(uint64_t seed, uint32_t env_offset, int N, int32_t* state_out, uint8_t* stack_out,
+                         paac_stream_t stream) {
+#ifdef PAAC_USER_GAME
+  return game_reset<UserGame>("paac_user_game_reset", seed, env_offset, N, state_out, stack_out, stream);
+#else
+  PAAC_REQUIRE(false, "paac_user_game_reset: this library was built without a user game (--device_game builds one)");
+  return -1;
+#endif
+}
+
+int paac_user_game_step(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                        int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                        uint8_t* stack_out2, const paac_env_records* rec, int option, paac_stream_t stream) {
+#ifdef PAAC_USER_GAME
+  PAAC_REQUIRE(rec, "paac_user_game_step: null records");
+  return game_step<UserGame>("paac_user_game_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
+                             stack_out, stack_out2, env_records_of(rec), option, stream);
+#else
+  PAAC_REQUIRE(false, "paac_user_game_step: this library was built without a user game (--device_game builds one)");
+  return -1;
+#endif
 }
 
 // paac_<game>_step by the game's id, with the records as one block -- the truncation plane among them.

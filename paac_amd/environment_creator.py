@@ -7,11 +7,13 @@ breakout/qbert/seaquest by the reference's pretrained/*/checkpoints/*.index acto
 `--emulator catch` creates the catch game of paac_amd/catch.py instead (3 actions, whatever `-g` says), `--emulator bricks`
 the brick-wall game of paac_amd/bricks.py (3 actions, lives: `--single_life_episodes` applies), `--emulator rally` the
 two-paddle game of paac_amd/rally.py (6 actions, ALE Pong's minimal set; no lives), `--emulator duel` rally played against the
-learner itself (paac_amd/duel.py: device loop only, an even `-ec`; the host environment created is rally's).
+learner itself (paac_amd/duel.py: device loop only, an even `-ec`; the host environment created is rally's), `--emulator user
+--device_game PATH` a user's own device game (paac_amd/user_game.py: the action count, the host twin and the device trait come
+from the specification module at PATH).
 A user environment plugs in exactly as in the reference: subclass BaseEnvironment and return it from
 create_environment(i).
 """
-from . import bricks, catch, duel, rally
+from . import bricks, catch, duel, rally, user_game
 from .synthetic import SyntheticEnvironment, terminal_threshold
 
 # ALE minimal action set sizes.
@@ -50,8 +52,17 @@ class EnvironmentCreator(object):
             self.create_environment = lambda i: atari_emulator.AtariEmulator(i, args)
             self._device_twin = False
             return
+        user_game.check_flags(args)               # --device_game without --emulator user and the reverse, --user_arch beside it
         self._device_twin = True
         self._game = getattr(args, "emulator", "synthetic")
+        if self._game == user_game.KIND:
+            # a user's device game (paac_amd/user_game.py): the module is validated, its library built or found and made the
+            # process's, the game registered under the kind "user"; -g is ignored
+            module = user_game.load(args.device_game)
+            self._user_options = user_game.option_keys(module)
+            self.num_actions = module.NUM_ACTIONS
+            self.create_environment = lambda i: module.Environment(i, seed=self._seed(), **self._game_options())
+            return
         if self._game in DEVICE_GAMES:
             # games of their own (-g is ignored), with their own action counts; no raw-screen form
             if self._raw():
@@ -94,7 +105,8 @@ class EnvironmentCreator(object):
 
     def _game_options(self):
         """The options of the game (DEVICE_GAMES): keywords of the host environment and keys of the device spec alike."""
-        return {key: getattr(self, "_" + key)() for key in DEVICE_GAMES[self._game][2]}
+        keys = self._user_options if self._game == user_game.KIND else DEVICE_GAMES[self._game][2]
+        return {key: getattr(self, "_" + key)() for key in keys}
 
     def _raw(self):
         return bool(getattr(self.args, "synthetic_raw_frames", False))
@@ -104,7 +116,7 @@ class EnvironmentCreator(object):
         """Device-batched twin of the same environments (PAACLearner uses it when present)."""
         if not self._device_twin:
             return None
-        if self._game in DEVICE_GAMES:
+        if self._game in DEVICE_GAMES or self._game == user_game.KIND:
             return dict(kind=self._game, seed=self._seed(), **self._game_options())
         if self._game in PAIRED_GAMES:
             # --duel_pool K (paac_amd/duel_pool.py): the rows are boards played against a pool of frozen opponents; the key

@@ -125,9 +125,9 @@ def replay_on_twins(env_creator, actions_trace, noops, env_offset=0):
 
 
 def max_steps_of(kind, noops):
-    """noops + the longest episode of game `kind` (paac.STATEFUL_KINDS)."""
-    from .paac import STATEFUL_KINDS
-    return int(noops) + int(STATEFUL_KINDS[kind]["max_episode_steps"])
+    """noops + the longest episode of game `kind` (paac.STATEFUL_KINDS, then the user's game: paac.USER_KINDS)."""
+    from .paac import stateful_kind
+    return int(noops) + int(stateful_kind(kind)["max_episode_steps"])
 
 
 def check_count(count, what="count"):
@@ -138,9 +138,9 @@ def check_count(count, what="count"):
 
 def check_env_spec(env_spec):
     """The device games an evaluation can play, or a ValueError naming them."""
-    from .paac import STATEFUL_KINDS
+    from .paac import stateful_kind
     kind = None if env_spec is None else env_spec.get("kind", "synthetic")
-    if kind not in STATEFUL_KINDS:
+    if stateful_kind(kind) is None:
         raise ValueError("device evaluation plays the games resident on the GPU only: --emulator catch|bricks|rally (got %s; the "
                          "synthetic reward is a hash, and ALE or user plugins are stepped on the host)"
                          % ("a host-only environment" if kind is None else "'%s'" % kind))
@@ -158,7 +158,8 @@ def check_train_flags(args, world_size=1):
     if getattr(args, "host_environments", False):
         raise ValueError("--eval_every evaluates on the device games: it cannot be combined with --host_environments true")
     # (duel: a paired game, evaluated as rally against the scripted opponent -- paac.eval_env_spec)
-    if getattr(args, "emulator", "synthetic") not in ("catch", "bricks", "rally", "duel"):
+    # (user: a game compiled in through --device_game, paac_amd/user_game.py)
+    if getattr(args, "emulator", "synthetic") not in ("catch", "bricks", "rally", "duel", "user"):
         raise ValueError("--eval_every needs a game resident on the GPU: --emulator catch|bricks|rally (got '%s')"
                          % getattr(args, "emulator", "synthetic"))
     if int(world_size) > 1:
@@ -286,13 +287,13 @@ class DeviceEvaluator(DeviceDriver):
     def __init__(self, network, ctx, env_spec, count, noops=30, greedy=False, seed=0, steps_per_launch=16, record=False,
                  use_graph=True, stream=None):
         from . import hip_ops
-        from .paac import STATEFUL_KINDS
+        from .paac import stateful_kind
         self.kind = check_env_spec(env_spec)
         super(DeviceEvaluator, self).__init__(hip_ops, count, noops, seed, greedy, steps_per_launch, record, use_graph)
         if ctx.num_actions != network.num_actions or ctx.arch != network.arch_id:
             raise ValueError("the context was not made for this network")
         self.network, self.ctx = network, ctx
-        self.game = STATEFUL_KINDS[self.kind]
+        self.game = stateful_kind(self.kind)
         self.env_seed = int(env_spec["seed"])
         self.max_steps = max_steps_of(self.kind, self.noops)
         self._allocate(min(self.count, ctx.max_batch, MAX_CHUNK), self.game["words"], network.num_actions, network.torch_device,

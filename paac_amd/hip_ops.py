@@ -876,6 +876,52 @@ def duel_step(seed, env_offset, actions, state_in, state_out, stack_in, stack_ou
     _lib.check(_lib.load().paac_duel_step(int(seed), int(env_offset), N, *buffers, ctypes.byref(rec), _stream()), "paac_duel_step")
 
 
+# The user's game (paac_amd/user_game.py: --emulator user --device_game): DEVICE_GAMES' fields under the kind "user", filled by
+# user_game.load() from the specification module once the process holds the library built with the game in it.  A table of its
+# own: the games above are the package's, this one is whatever the loaded library was built with.  Entry points
+# paac_user_game_reset / paac_user_game_step; paac_game_step and paac_eval_step know the game as _lib.EVAL_USER.
+USER_GAMES = {}
+
+
+def register_user_game(words, step_option=None):
+    """-> the USER_GAMES entry of the game compiled into the loaded library (user_game.load checks the numbers against it)."""
+    if step_option not in (None, "single_life"):
+        raise ValueError("a user game's STEP_OPTION is None or 'single_life', got %r" % (step_option,))
+    USER_GAMES["user"] = dict(words=int(words), eval_id=_lib.EVAL_USER, step_option=step_option)
+    return USER_GAMES["user"]
+
+
+def _user_game():
+    if "user" not in USER_GAMES:
+        raise ValueError("no user game is registered: --emulator user --device_game PATH (paac_amd.user_game.load) does that")
+    return USER_GAMES["user"]
+
+
+def user_game_reset(seed, env_offset, state_out, stack_out):
+    """paac_user_game_reset (include/paac_hip.h): game_reset of the user's game."""
+    _stateful_reset("paac_user_game_reset", _user_game()["words"], seed, env_offset, state_out, stack_out)
+
+
+def user_game_step_records(seed, env_offset, actions, state_in, state_out, stack_in, stack_out, rewards_out, masks_out, ep_reward,
+                           ep_len, finished=None, stack_out2=None, state_out2=None, truncs_out=None, **option):
+    """paac_user_game_step: game_step_records' argument list without the kind -- the records go as one block, truncs_out
+    float32[N] (None: not written) among them; `option`: the game's step option by its keyword (False if not given)."""
+    game = _user_game()
+    name = game["step_option"]
+    if set(option) - {name}:
+        raise TypeError("user_game_step: unexpected keyword arguments %s" % sorted(set(option) - {name}))
+    N, buffers, records = _game_step_ptrs(game["words"], actions, state_in, state_out, state_out2, stack_in, stack_out, stack_out2,
+                                          rewards_out, masks_out, ep_reward, ep_len, finished)
+    rec = _env_records(N, records, truncs_out)
+    _lib.check(_lib.load().paac_user_game_step(int(seed), int(env_offset), N, *buffers, ctypes.byref(rec),
+                                               int(bool(option.get(name, False))) if name else 0, _stream()),
+               "paac_user_game_step")
+
+
+# one entry serves both: the records always go as a block, with or without the truncation plane
+user_game_step = user_game_step_records
+
+
 def duel_ghost_reset(seed, env_offset, state_out, stack_out, ghost_stack_out):
     """paac_duel_ghost_reset (include/paac_hip.h; spec in paac_amd/duel_pool.py): N boards, the learner's rows and the ghosts'
     observations -- duel_reset on 2N rows, split."""
@@ -932,9 +978,9 @@ def eval_step(game, probs, greedy, eval_seed, noops, step_base_dev, step_offset,
     actions_out, the game stepped from state_in / stack_in into state_out / stack_out, the first scored episode accounted in
     score / length / done [N] and alive [1].  Shapes are checked here; the library refuses in-place buffers, A outside [2, 32]
     and negative noops with a PaacHipError, before any launch."""
-    if game not in EVAL_GAMES:
+    if game not in EVAL_GAMES and game not in USER_GAMES:
         raise ValueError("eval_step: game %r has no device evaluation (--emulator catch|bricks|rally)" % (game,))
-    game_id, words = EVAL_GAMES[game]
+    game_id, words = EVAL_GAMES[game] if game in EVAL_GAMES else (USER_GAMES[game]["eval_id"], USER_GAMES[game]["words"])
     _lib.check(_lib.load().paac_eval_step(game_id, *_scored_step_args("eval_step", words, probs, greedy, eval_seed, noops, step_base_dev,
                                                                       step_offset, env_seed, env_offset, state_in, state_out,
                                                                       stack_in, stack_out, actions_out, score, length, done, alive),

@@ -50,10 +50,28 @@ PAIRED_KINDS = {
 }
 
 
+# The user's game (paac_amd/user_game.py: --emulator user --device_game): _stateful_kind's fields under the kind "user", filled by
+# user_game.load() from the specification module.  A table of its own, consulted after the two above.
+USER_KINDS = {}
+
+
+def register_user_kind(spec_kwargs, max_episode_steps, truncates):
+    """-> the USER_KINDS entry of the user game hip_ops.USER_GAMES holds."""
+    USER_KINDS["user"] = dict(words=hip_ops.USER_GAMES["user"]["words"], reset=hip_ops.user_game_reset, step=hip_ops.user_game_step,
+                              spec_kwargs=tuple(spec_kwargs), max_episode_steps=int(max_episode_steps), truncates=bool(truncates))
+    return USER_KINDS["user"]
+
+
+def stateful_kind(kind):
+    """The entry of a non-paired game that carries a state record: STATEFUL_KINDS, then USER_KINDS; None for any other kind."""
+    return STATEFUL_KINDS.get(kind) or USER_KINDS.get(kind)
+
+
 def device_kind(env_spec):
-    """The STATEFUL_KINDS or PAIRED_KINDS entry of a device env spec; None for the synthetic environments (or no spec)."""
+    """The STATEFUL_KINDS, PAIRED_KINDS or USER_KINDS entry of a device env spec; None for the synthetic environments (or no
+    spec)."""
     kind = (env_spec or {}).get("kind", "synthetic")
-    return STATEFUL_KINDS.get(kind) or PAIRED_KINDS.get(kind)
+    return STATEFUL_KINDS.get(kind) or PAIRED_KINDS.get(kind) or USER_KINDS.get(kind)
 
 
 def eval_env_spec(env_spec, **changes):

@@ -26,6 +26,11 @@ def bool_arg(string):
         raise argparse.ArgumentTypeError("Expected True or False, but got {}".format(string))
 
 
+def _game_path(string):
+    """--device_game: the path made absolute (args.json records it so: paac_amd.test -f FOLDER finds the game again)."""
+    return os.path.abspath(string) if string else ""
+
+
 # (option strings, dest, default, type, help)
 REFERENCE_FLAGS = (
     (("-g",), "game", "pong", None, "game to play"),
@@ -74,8 +79,14 @@ BUILD_FLAGS = (
      "network plays both paddles, each row seeing the board from its own side; device loop only, -ec must be even, the logged "
      "returns average 0 by construction: use --eval_every, which scores the policy against rally's scripted opponent; "
      "--host_environments true is refused, --single_life_episodes, -g, --synthetic_terminal_p, --synthetic_raw_frames and "
-     "--random_start do not apply) or 'ale' (Atari through an installed Arcade "
-     "Learning Environment)"),
+     "--random_start do not apply), 'user' (with --device_game PATH: a user's own game compiled into the device loop, "
+     "paac_amd/user_game.py; -g, --synthetic_terminal_p, --synthetic_raw_frames and --random_start do not apply, --duel_pool and "
+     "--eval_match stay duel's) or 'ale' (Atari through an installed Arcade Learning Environment)"),
+    (("--device_game",), "device_game", "", _game_path,
+     "--emulator user: the game's specification module, a Python file (examples/patrol/patrol.py is one) that names the "
+     "game's numbers, its host twin and the header with its device trait; the trait is compiled into a library of its own on "
+     "first use (paac_amd/libpaac_hip_game_<file stem>.so) and the process loads that library; cannot be combined with "
+     "--user_arch; args.json records the absolute path"),
     (("--device_preprocess",), "device_preprocess", False, bool_arg,
      "host environments hand out raw screen pairs; max + resize + frame history run on the GPU"),
     (("--user_arch",), "user_arch", "", None,
@@ -153,7 +164,7 @@ def get_arg_parser():
         if kind is not None:
             kwargs["type"] = kind
         if dest in ("sampler", "emulator", "checkpoint_format", "optimizer"):
-            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "rally", "duel", "ale"],
+            kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "rally", "duel", "user", "ale"],
                                  "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"]}[dest]
         parser.add_argument(*options, **kwargs)
     return parser

@@ -158,6 +158,41 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
                      void* finished, uint8_t* raw_scratch, void* walk_scratch, int64_t walk_scratch_bytes,
                      paac_stream_t stream);
 
+/* paac_act_step_mt's small route with the sampler OFF the dependent chain: two launches per step, the same bits.
+ * In the path-A synthetic environments the new frame and the terminal flag are functions of (seed, environment, step id)
+ * alone -- only the reward bookkeeping reads the action; the fused step launch of paac_act_step_mt already shifts the stacks
+ * beside the sampler on that ground.  So the shift of step t needs nothing step t computes, the conv tower of step t + 1 needs
+ * only that shift, and nobody reads step t's sample before the update.  (Device games, whose frame depends on the action, have
+ * no such entry.)
+ * paac_act_step_pipe (paac_act_step_mt's arguments): launches the conv tower of step t, then its fc + head-partials launch,
+ * which also carries (a) the frame shift of step t, states -> stack_out [/ stack_out2], dealt over the fc workgroups, and (b)
+ * one extra workgroup, first in the grid, that finishes the heads, samples and does the bookkeeping of the PREVIOUS pipelined
+ * step, if one is owed.  No workgroup waits for another: every rider reads only what an earlier launch wrote (the head
+ * partials alternate between two regions of the acting fc slab buffer).  On return step t's stacks are enqueued, and its
+ * actions, probs_out, values_out, mt_state advance, rewards, masks, episode totals and finished ring are OWED: the ctx
+ * remembers the step's arguments (host-side state, like paac_keep_next_forward's; under graph capture it is resolved at
+ * capture time, so a captured sequence must pay what it owes inside the capture).  The debt is paid by
+ *   - the next paac_act_step_pipe (its fc launch),
+ *   - paac_bootstrap_forward_trunk on the same ctx (its fc launch carries the owed sample, nothing else changes), or
+ *   - paac_act_step_flush: a one-workgroup launch of the same routine (nothing owed: nothing launched).
+ * All three give the bits of paac_act_step_mt.  *step_base_dev is read when the debt is paid: it must not change in between
+ * (the rollout advances it once per cycle, behind the bootstrap forward).
+ * Refused (nothing launched, no state changed): stack_out == NULL or stacks shifted in place; raw_scratch (path B: its
+ * preprocess launch follows the step, it keeps paac_act_step_mt); shapes outside paac_act_step_mt's three-launch route
+ * (batch <= PAAC_ACT_STEP_MAX_ENVS, N*(A-1) <= 1024, a geometry with the fc + head-partials kernel, and two regions of partials
+ * that fit: A <= 31 at batch == max_batch).  While a sample is owed, every other acting forward on the ctx (paac_act_step_mt,
+ * paac_forward*) and every entry that reads what the sample writes (paac_loss_backward*, paac_returns_norm_tick,
+ * paac_record_policy) is refused with a message that names the flush.  walk_scratch is accepted and unused.
+ * paac_act_step_pending: 1 while a sample is owed. */
+int paac_act_step_pipe(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, uint32_t* mt_state,
+                       int32_t* actions, float* probs_out, float* values_out, uint64_t env_seed, uint32_t env_offset,
+                       uint32_t terminal_threshold, const uint64_t* step_base_dev, uint64_t step_offset, uint8_t* stack_out,
+                       uint8_t* stack_out2, float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len,
+                       void* finished, uint8_t* raw_scratch, void* walk_scratch, int64_t walk_scratch_bytes,
+                       paac_stream_t stream);
+int paac_act_step_flush(paac_ctx* ctx, paac_stream_t stream);
+int paac_act_step_pending(const paac_ctx* ctx);
+
 /* Conv-weight packing.  The Nature conv layers run as one fused launch that reads the conv weights pre-split into bf16
  * planes (an internal copy owned by the ctx).  By default every paac_forward* / paac_train_forward / paac_loss_backward
  * call refreshes that copy from `params` first (one small extra launch), so a caller may change `params` at any time.

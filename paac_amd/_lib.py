@@ -145,6 +145,11 @@ _SIGNATURES = {
     "paac_act_step_mt": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
                                  c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "paac_act_step_pipe": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
+                                   c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "paac_act_step_flush": (c_int, [c_void_p, c_void_p]),
+    "paac_act_step_pending": (c_int, [c_void_p]),
     "paac_walk_scratch_bytes": (c_int64, [c_int, c_int]),
     "paac_debug_report_zero": (c_int, [c_int]),
     "paac_sample_mt_synth_step": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_uint64, c_uint32, c_int, c_uint32, c_void_p,

@@ -85,6 +85,13 @@ static const char* kFamilyNames[PAAC_PROF_FAMILIES] = {
 
 using namespace paac;
 
+// The entries that read what an acting step's sampler writes (actions, values, rewards, masks) refuse to run while the last
+// paac_act_step_pipe's sample is still owed.
+#define PAAC_NO_PENDING_SAMPLE(ctx, fn)                                                                                  \
+  PAAC_REQUIRE(!(ctx)->act_owed->partial, "%s: the last paac_act_step_pipe's sample is still pending (that step's actions, "  \
+               "values and records are not written yet): pay it with paac_bootstrap_forward_trunk, another "                \
+               "paac_act_step_pipe or paac_act_step_flush first", fn)
+
 struct paac_graph {
   hipGraph_t graph;
   hipGraphExec_t exec;
@@ -233,6 +240,10 @@ int paac_create(const paac_cfg* cfg, paac_ctx** out) {
   PAAC_CHECK_HIP(hipMemset(c->mt_ahead, 0, mt_ahead_bytes()));
   c->ahead_state = nullptr;
   c->ahead_D = 0;
+  c->act_owed = new (std::nothrow) ActSample{};
+  PAAC_REQUIRE(c->act_owed, "paac_create: out of host memory");
+  c->fc_rider = nullptr;
+  c->act_region = 0;
   {
     const char* v = getenv("PAAC_TOWER");
     c->tower_on = (cfg->arch == PAAC_ARCH_NATURE) && !(v && *v && atoi(v) == 0);
@@ -286,6 +297,7 @@ int paac_destroy(paac_ctx* c) {
   delete[] c->ev_family;
   delete[] c->ev_batch;
   delete[] c->ev_mix;
+  delete c->act_owed;
   delete c;
   return 0;
 }
@@ -349,7 +361,20 @@ int paac_bootstrap_forward_trunk(paac_ctx* ctx, const float* params, const uint8
   PAAC_REQUIRE(ctx && params && states, "paac_bootstrap_forward_trunk: null argument");
   PAAC_REQUIRE(batch > 0 && train_row >= 0 && train_row + batch <= ctx->max_batch,
                "paac_bootstrap_forward_trunk: rows [%d, %d) outside max_batch=%d", train_row, train_row + batch, ctx->max_batch);
+  // a pipelined acting step's sample is owed: this forward's fc launch carries it (no frame shift: nothing steps here)
+  ActRider rider{};
+  rider.owed = *ctx->act_owed;
+  if (rider.owed.partial) {
+    PAAC_REQUIRE(batch <= PAAC_ACT_STEP_MAX_ENVS && forward_has_fc_heads(ctx) &&
+                 (size_t)(ctx->spec.fc / 8) * batch * (ctx->cfg.num_actions + 1) <= act_region_floats(ctx),
+                 "paac_bootstrap_forward_trunk: a forward of %d rows cannot carry the pending sample of paac_act_step_pipe "
+                 "(paac_act_step_flush pays it)", batch);
+    ctx->fc_rider = &rider;
+  }
   const int rc = launch_bootstrap_trunk(ctx, params, states, batch, train_row, (hipStream_t)stream);
+  const bool carried = rider.owed.partial && ctx->fc_rider == nullptr;      // (the fc launch takes the riders: one shot)
+  ctx->fc_rider = nullptr;
+  if (carried) ctx->act_owed->partial = nullptr;
   if (rc) return rc;
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
@@ -498,6 +523,59 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
   return 0;
 }
 
+int paac_act_step_pipe(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, uint32_t* mt_state,
+                       int32_t* actions, float* probs_out, float* values_out, uint64_t env_seed, uint32_t env_offset,
+                       uint32_t terminal_threshold, const uint64_t* step_base_dev, uint64_t step_offset, uint8_t* stack_out,
+                       uint8_t* stack_out2, float* rewards_out, float* masks_out, float* ep_reward, int32_t* ep_len,
+                       void* finished, uint8_t* raw_scratch, void* walk_scratch, int64_t walk_scratch_bytes,
+                       paac_stream_t stream) {
+  (void)walk_scratch;
+  (void)walk_scratch_bytes;
+  PAAC_REQUIRE(ctx && params && states && mt_state && actions && probs_out && values_out, "paac_act_step_pipe: null argument");
+  PAAC_REQUIRE(!raw_scratch, "paac_act_step_pipe: path B (raw_scratch) keeps paac_act_step_mt's route -- its preprocess launch "
+               "follows the step");
+  SynthStep st;
+  if (synth_step_of("paac_act_step_pipe", "null argument (the pipelined step always steps the environments)", false, &st, env_seed,
+                    env_offset, batch, terminal_threshold, step_base_dev, step_offset, states, stack_out, stack_out2, rewards_out,
+                    masks_out, ep_reward, ep_len, finished, nullptr))
+    return -1;
+  const int A = ctx->cfg.num_actions;
+  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch && batch <= PAAC_ACT_STEP_MAX_ENVS && (int64_t)batch * (A - 1) <= 1024 &&
+               forward_has_fc_heads(ctx),
+               "paac_act_step_pipe: up to min(max_batch=%d, %d) environments and 1024 draws on a geometry with the fc + head "
+               "partials kernel (use paac_act_step_mt); got %d x %d actions", ctx->max_batch, PAAC_ACT_STEP_MAX_ENVS, batch, A);
+  // two alternating regions of head partials, [tiles <= H / 8][batch][A + 1] each, in the acting fc slab buffer
+  PAAC_REQUIRE((size_t)(ctx->spec.fc / 8) * batch * (A + 1) <= act_region_floats(ctx),
+               "paac_act_step_pipe: two regions of head partials for %d x %d actions do not fit the fc slab buffer of "
+               "max_batch=%d (use paac_act_step_mt)", batch, A, ctx->max_batch);
+  ActRider rider{};
+  rider.owed = *ctx->act_owed;
+  rider.shift = st;
+  HeadsPartials hp{nullptr, 0, nullptr, nullptr, values_out};
+  ctx->fc_rider = &rider;
+  const int rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
+  const bool launched = ctx->fc_rider == nullptr;      // (the fc launch takes the riders: one shot)
+  ctx->fc_rider = nullptr;
+  if (launched)      // the earlier debt rode that launch; this step's takes its place
+    *ctx->act_owed = ActSample{hp.partial, hp.ntiles, hp.ba, hp.bc, probs_out, values_out, A, mt_state, actions, env_seed,
+                               env_offset, batch, terminal_threshold, step_base_dev, step_offset, st.rec};
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_act_step_flush(paac_ctx* ctx, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx, "paac_act_step_flush: null ctx");
+  if (!ctx->act_owed->partial) return 0;
+  const int rc = launch_act_sample_flush(*ctx->act_owed, (hipStream_t)stream);
+  if (rc) return rc;
+  ctx->act_owed->partial = nullptr;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_act_step_pending(const paac_ctx* ctx) { return (ctx && ctx->act_owed->partial) ? 1 : 0; }
+
 // The fields of a paac_returns that do not depend on the entry: the rollout records, estimator, lambda, the schedule pointers.
 static int check_returns(const char* fn, const paac_returns* ret) {
   PAAC_REQUIRE(ret->rewards && ret->masks && ret->values && ret->y_out && ret->adv_out, "%s: null rollout record", fn);
@@ -518,6 +596,7 @@ static int loss_backward_entry(const char* fn, paac_ctx* ctx, const float* param
   PAAC_REQUIRE(ctx && params && states && actions && grad && (call.ret || (call.y && call.adv)), "%s: null argument", fn);
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "%s: batch %d outside (0, max_batch=%d]", fn, batch, ctx->max_batch);
   PAAC_REQUIRE(phase >= 0 && phase <= 3, "%s: phase %d", fn, phase);
+  PAAC_NO_PENDING_SAMPLE(ctx, fn);
   if (const paac_returns* ret = call.ret) {
     PAAC_REQUIRE(ret->T > 0 && ret->N > 0 && ret->T * ret->N == batch, "%s: T*N = %d*%d != batch %d", fn, ret->T, ret->N, batch);
     if (const int rc = check_returns(fn, ret)) return rc;
@@ -603,6 +682,7 @@ int paac_returns_norm_tick(paac_ctx* ctx, const float* params, const paac_return
   PAAC_REQUIRE(ret && adv_n_out, "paac_returns_norm_tick: null argument");
   PAAC_REQUIRE(ret->T > 0 && ret->N > 0, "paac_returns_norm_tick: T=%d N=%d", ret->T, ret->N);
   if (const int rc = check_returns("paac_returns_norm_tick", ret)) return rc;
+  if (ctx) PAAC_NO_PENDING_SAMPLE(ctx, "paac_returns_norm_tick");
   const float* v_boot = ret->v_boot;
   if (!v_boot) {
     const int64_t batch = (int64_t)ret->T * ret->N;
@@ -624,6 +704,7 @@ int paac_record_policy(paac_ctx* ctx, const float* params, const int32_t* action
   PAAC_REQUIRE(ctx && params, "paac_record_policy: null argument");
   PAAC_REQUIRE(p_old_out || v_out, "paac_record_policy: nothing to record (p_old_out and v_out are both NULL)");
   PAAC_REQUIRE(!p_old_out || actions, "paac_record_policy: p_old_out needs the actions");
+  PAAC_NO_PENDING_SAMPLE(ctx, "paac_record_policy");
   if (!p_old_out) batch = 0;
   if (!v_out) value_rows = 0;
   const int rows = batch > value_rows ? batch : value_rows;

@@ -112,6 +112,11 @@ struct FinalizeArgs {
 
 }  // namespace paac
 
+namespace paac {
+struct ActSample;      // csrc/synth_dev.h: what an acting step's sampler still owes; the riders of an acting fc launch
+struct ActRider;
+}  // namespace paac
+
 struct paac_ctx {
   paac_cfg cfg;
   paac::Tune tune[paac::OP_COUNT][3];   // [op][batch class: 0 = batch <= 64, 1 = batch <= 512, 2 = larger]
@@ -151,6 +156,12 @@ struct paac_ctx {
   void* mt_ahead;                  // MtAhead, owned by the ctx
   const uint32_t* ahead_state;     // one shot, set by paac_act_step_mt: the MT19937 state to work ahead from (nullptr: off)
   int ahead_D;                     // doubles the step can consume at most: N * (A - 1)
+  // paac_act_step_pipe: the sample of the last pipelined step, owed until the next acting fc launch (or the flush) pays it --
+  // host-side state like keep_row / ahead_state: under graph capture it is resolved at capture time
+  paac::ActSample* act_owed;       // owned by the ctx; ->partial == nullptr: nothing pending
+  const paac::ActRider* fc_rider;  // one shot: the next acting fc launch carries these riders (csrc/fc_heads.h: RIDER)
+  int act_region;                  // the half of ws[0].fc_slab the next ridden fc launch writes its head partials to (they
+                                   // alternate: the rider beside it is still reading the other half)
   float* dl_buf;                   // [max_batch][kDlStride] per-row head gradients + loss terms (heads.h)
   float* ppo_rows;                 // [max_batch][2] per-row clip / KL terms of paac_loss_backward_ppo (heads.h: ppo_stats_kernel)
   float* vclip_rows;               // [max_batch] per-row vclipped of paac_loss_backward_ppo_vclip
@@ -160,6 +171,7 @@ struct paac_ctx {
   void* fc_pack;         // fc weights in fc_heads_kernel's fragment order (flat * H floats)
   int tower_on;          // PAAC_TOWER (default 1)
   int heads_ntiles;      // column groups of the last fc + head-partials launch (fc_heads.h: 16- or 8-wide tiles)
+  float* heads_partial;  // ... and where it left the partials
   int no_quarter_tiles;  // PAAC_FC_QUARTER=0: always whole 16 x 16 tiles (A/B measurements)
   int tower2_on;         // the two-conv tower of the stock NIPS geometry (csrc/tower2.h), same knob
   int managed_weights;   // paac_set_managed_weights: 1 = the caller keeps tower_pack current (paac_clip_rmsprop / paac_pack_weights
@@ -251,6 +263,13 @@ struct HeadsPartials {
   const float *ba, *bc;
   float* values_out;
 };
+// floats of one of the two head-partial regions ridden fc launches alternate between: half of ws[0].fc_slab
+inline size_t act_region_floats(const paac_ctx* c) { return (size_t)c->fc_splits_max * c->max_batch * c->spec.fc / 2; }
+// the acting fc launch with riders and the flush launch of an owed sample (csrc/misc.hip, where the sampler lives)
+int launch_fc_heads_rider(bool nature, bool quarter, bool packed, unsigned fc_wgs, const float* act, const void* wfp,
+                          const float* bf, const float* wa, const float* wc, int A, int batch, float* partial, float* h_out,
+                          const ActRider& r, hipStream_t s);
+int launch_act_sample_flush(const ActSample& owed, hipStream_t s);
 size_t mt_ahead_bytes();
 bool sampler_folds_heads(int N, int A, const void* walk_scratch);
 bool tower2_available();

@@ -13,6 +13,8 @@
 //                        by workgroup 0 of the fused sampler + environment-step launch (csrc/misc.hip), which leaves the
 //                        probabilities in LDS for the sampler: the acting step is three launches (conv tower, fc + head
 //                        partials, heads finish + sampler + env step).  Both callers run the same code: same bits.
+//                        (The pipelined acting step is two: a ridden instantiation of the fc kernels -- RIDER, below -- also
+//                        shifts the step's frames and carries the sampler workgroup of the step before.)
 // fp32 MFMA (v_mfma_f32_16x16x4_f32): at 32 rows the layer is 0.1 GFLOP against 6.4 MB of weights; each workgroup
 // streams its 16 columns (200 KB) once, direct to registers in the MFMA layout (K order permuted inside each 16-wide
 // group, identically for both operands, like dmm.h).
@@ -51,30 +53,52 @@ __global__ __launch_bounds__(256) void pack_fc_kernel(const float* __restrict__ 
   out[i] = v;
 }
 
+// RIDER (the pipelined acting step, paac_act_step_pipe): work that rides the acting fc launch beside the fc workgroups,
+// none of it waited for by them and all of it reading only what earlier launches wrote.  NoRider: the instantiations every
+// other caller uses -- their code is what it was (the empty struct is one byte at the end of the kernel arguments, which no
+// instruction reads).  A rider (csrc/misc.hip: ActRiderDev) has
+//   front(bid, nfc)       true in the workgroups that are the rider's alone (they come FIRST in the grid: the sampler workgroup
+//                         of the previous step, whose chain is the longest thing in the launch) after running them on `lds`;
+//                         otherwise bid / nfc become the workgroup's index among / the count of the fc workgroups
+//   shift_load / _store   the frame shift of this step, dealt over the fc workgroups' first four waves: the 16-byte load of the
+//                         old stack is issued before the K loop and the store after it
+// Every workgroup of the launch reserves the kernel's whole LDS and register allocation: the rider's workgroup shares `red`.
+struct NoRider {};
+constexpr int kRiderLdsVecs = kFcHeadsMaxRows * 33 / 4;      // f32x4s of LDS a rider's own workgroup wants of `red`
+
 // NW waves split K evenly (NW divides K / 16: 7 x 28 groups for Nature's 3136, 9 x 18 for NIPS' 2592), so the K loop of a
 // wave has a compile-time trip count and is fully unrolled: straight-line loads PF groups ahead of their MFMAs, exact
 // s_waitcnt vmcnt(N) counts (a loop with clamped tails made the compiler sink the prefetch loads behind vmcnt(0)).
 // A_PACKED: `act` is in fragment order [row tile][K group][lane][4] (written that way by the conv tower's epilogue): the A
 // fragment of a group is one coalesced 16-byte load per lane too; otherwise plain rows [B, K].
-template <int K, int H, int NW, bool A_PACKED>
+template <int K, int H, int NW, bool A_PACKED, class RIDER = NoRider>
 __global__ __launch_bounds__(64 * NW) void fc_heads_kernel(const float* __restrict__ act, const f32x4* __restrict__ wfp,
                                                            const float* __restrict__ bf, const float* __restrict__ Wa,
                                                            const float* __restrict__ Wc, const int A, const int B,
                                                            float* __restrict__ partial, float* __restrict__ h_out,
-                                                           const MtAheadArgs ahead) {
+                                                           const MtAheadArgs ahead, const RIDER rider) {
   constexpr int NTILES = H / 16, G = K / 16, GPW = G / NW, PF = 8;
+  constexpr bool RIDDEN = !__is_same(RIDER, NoRider);
   static_assert(K % 16 == 0 && H % 16 == 0 && G % NW == 0 && GPW > PF, "fc geometry");
-  if (ahead.out != nullptr && blockIdx.x == gridDim.x - 1) {
-    // the spare workgroup (csrc/mt_ahead.h): the doubles of the sampling step that follows this forward
-    __shared__ uint32_t ahead_blocks[MT_AHEAD_BLK * 624];
-    mt_produce_ahead<64 * NW>(ahead, ahead_blocks);
-    return;
+  if constexpr (!RIDDEN) {
+    if (ahead.out != nullptr && blockIdx.x == gridDim.x - 1) {
+      // the spare workgroup (csrc/mt_ahead.h): the doubles of the sampling step that follows this forward
+      __shared__ uint32_t ahead_blocks[MT_AHEAD_BLK * 624];
+      mt_produce_ahead<64 * NW>(ahead, ahead_blocks);
+      return;
+    }
   }
-  __shared__ f32x4 red[NW * 64];
+  __shared__ f32x4 red[RIDDEN && kRiderLdsVecs > NW * 64 ? kRiderLdsVecs : NW * 64];
+  int bid = blockIdx.x, nfc = gridDim.x;
+  uint4 shift_old = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (RIDDEN) {
+    if (rider.front(bid, nfc, reinterpret_cast<float*>(red))) return;
+    shift_old = rider.shift_load(bid);
+  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, kq = lane >> 4;
-  const int nt = blockIdx.x % NTILES, mt = blockIdx.x / NTILES;
+  const int nt = bid % NTILES, mt = bid / NTILES;
   const int row_a = mt * 16 + li;                       // A operand: this lane's row
   const bool row_ok = row_a < B;
   const int col = nt * 16 + li;                         // D: this lane's column
@@ -114,6 +138,7 @@ __global__ __launch_bounds__(64 * NW) void fc_heads_kernel(const float* __restri
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(row_ok ? fa[i % RING][e] : 0.f, fb[i % RING][e], acc, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
+  if constexpr (RIDDEN) rider.shift_store(bid, nfc, shift_old);
   red[wave * 64 + lane] = acc;
   __syncthreads();
   // every wave rebuilds the complete tile (fixed order), applies bias + ReLU, then folds its share of the head outputs
@@ -161,19 +186,27 @@ __global__ __launch_bounds__(64 * NW) void fc_heads_kernel(const float* __restri
 // half of the matrix pipe's work is thrown away, in a layer that keeps it 8 % busy.  (Masking the upper lanes instead --
 // zeros, no loads -- was measured SLOWER than whole tiles, 9.45 against 8.1 us: a load instruction occupies the L1 for
 // the same time whatever its lane mask.)
-template <int K, int H, int NW, bool A_PACKED>
+template <int K, int H, int NW, bool A_PACKED, class RIDER = NoRider>
 __global__ __launch_bounds__(64 * NW) void fc_heads_q_kernel(const float* __restrict__ act, const f32x4* __restrict__ wfp,
                                                              const float* __restrict__ bf, const float* __restrict__ Wa,
                                                              const float* __restrict__ Wc, const int A, const int B,
-                                                             float* __restrict__ partial, float* __restrict__ h_out) {
+                                                             float* __restrict__ partial, float* __restrict__ h_out,
+                                                             const RIDER rider) {
   constexpr int NTILES = H / 8, G = K / 16, GPW = G / NW, NS = GPW / 2, PF = 6;
+  constexpr bool RIDDEN = !__is_same(RIDER, NoRider);
   static_assert(K % 16 == 0 && H % 16 == 0 && G % NW == 0 && GPW % 2 == 0 && NS > PF, "fc geometry");
-  __shared__ f32x4 red[NW * 64];
+  __shared__ f32x4 red[RIDDEN && kRiderLdsVecs > NW * 64 ? kRiderLdsVecs : NW * 64];
+  int bid = blockIdx.x, nfc = gridDim.x;
+  uint4 shift_old = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (RIDDEN) {
+    if (rider.front(bid, nfc, reinterpret_cast<float*>(red))) return;
+    shift_old = rider.shift_load(bid);
+  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, kq = lane >> 4;
   const int l8 = li & 7, odd = li >> 3;                 // position inside the 8-wide tile; which K group of a pair this lane feeds
-  const int nt = blockIdx.x % NTILES, mt = blockIdx.x / NTILES;
+  const int nt = bid % NTILES, mt = bid / NTILES;
   const int row_a = mt * 8 + l8;                        // A operand: this lane's row
   const bool row_ok = row_a < B;
   const int col = nt * 8 + l8;                          // B operand / D: this lane's column
@@ -213,6 +246,7 @@ __global__ __launch_bounds__(64 * NW) void fc_heads_q_kernel(const float* __rest
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(row_ok ? fa[i % RING][e] : 0.f, fb[i % RING][e], acc, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
+  if constexpr (RIDDEN) rider.shift_store(bid, nfc, shift_old);
   red[wave * 64 + lane] = acc;
   __syncthreads();
   // D layout: lane (li, kq) holds rows 4 kq + r of column li.  The tile's sums: even groups at (li < 8, kq < 2), odd groups at

@@ -2,6 +2,7 @@
 // frame preprocessing / stacking, device-resident synthetic environments.  (Device games: games.hip; optimizer: optim.hip.)
 #include "common.h"
 #include "synth_dev.h"
+#include "net_common.h"
 #include "fc_heads.h"
 #include "heads.h"
 
@@ -727,9 +728,30 @@ struct FusedHeadsHook {
     }
   }
 };
+// The LDS arrays of sample_mt_body, one set per size class: a kernel that holds the body twice (two hooks: act_sample_body)
+// reserves them once.  (Function-local arrays of the body itself are per instantiation, and the compiler does not overlay them.)
+template <int LDSC>
+struct MtLds {
+  double pj[mt_lds_d(LDSC)];
+  double u[mt_lds_d(LDSC)];
+  uint32_t blocks[mt_lds_blk(LDSC) * 624];
+  __attribute__((aligned(16))) unsigned char jh_tab[mt_tab_max(LDSC)];
+  unsigned short skip_tab[mt_skip_max(LDSC)];
+  int entry[33];
+  uint32_t pos;
+  int any_zero;
+};
+// (SET: a kernel that wants the two bodies on arrays of their own asks for set 1 -- synth_step_a_mth_kernel, which thereby
+// reserves more than half of a CU's LDS and keeps the other workgroups of its launch off the sampler workgroup's CU: with
+// one set, --raw-frames measured 0.2345 against 0.2317 ms per cycle, profiles/r08_secondary.txt)
+template <int LDSC, int SET>
+__device__ __forceinline__ MtLds<LDSC>& mt_lds() {
+  __shared__ MtLds<LDSC> lds;
+  return lds;
+}
 template <class H> struct HookFused { static constexpr bool value = false; };
 template <> struct HookFused<FusedHeadsHook> { static constexpr bool value = true; };
-template <int LDSC, class HOOK = NoProbsHook>
+template <int LDSC, class HOOK = NoProbsHook, int SET = 0>
 __device__ __forceinline__ bool sample_mt_body(const float* __restrict__ probs, int N, int A,
                                                uint32_t* __restrict__ mt_state, double* __restrict__ pj_g,
                                                double* __restrict__ u_g, uint32_t* __restrict__ blocks_g,
@@ -743,9 +765,10 @@ __device__ __forceinline__ bool sample_mt_body(const float* __restrict__ probs, 
   MISC_STAMP(0);
   constexpr bool LDSPATH = LDSC > 0;
   constexpr int PRW = LDSC == 2 ? 18 : 8;             // probability floats per thread of the one-round-trip load
-  __shared__ double pj_s[mt_lds_d(LDSC)];
-  __shared__ double u_s[mt_lds_d(LDSC)];
-  __shared__ uint32_t blocks_s[mt_lds_blk(LDSC) * 624];
+  MtLds<LDSC>& lds = mt_lds<LDSC, SET>();
+  double* const pj_s = lds.pj;
+  double* const u_s = lds.u;
+  uint32_t* const blocks_s = lds.blocks;
   double* pj_buf = LDSPATH ? pj_s : pj_g;
   double* u_buf = LDSPATH ? u_s : u_g;
   uint32_t* blocks = LDSPATH ? blocks_s : blocks_g;
@@ -753,8 +776,8 @@ __device__ __forceinline__ bool sample_mt_body(const float* __restrict__ probs, 
   const int J = A - 1;
   const int D = N * J;
   __shared__ float probs_s[LDSPATH ? 2 * mt_lds_d(LDSC) : 1];   // N*A = D*A/(A-1) <= 2*D floats
-  __shared__ uint32_t pos_s;
-  __shared__ int any_zero;       // some conditional probability is exactly 0 (the table chase needs none); later
+  uint32_t& pos_s = lds.pos;
+  int& any_zero = lds.any_zero;  // some conditional probability is exactly 0 (the table chase needs none); later
                                  // reused for the consumed-draw count
   uint32_t pos;
   // csrc/mt_ahead.h (class 2 only): the step's doubles, made one launch ahead, travel with the state words and the
@@ -809,7 +832,7 @@ __device__ __forceinline__ bool sample_mt_body(const float* __restrict__ probs, 
   const float* pr = LDSPATH ? (probs_lds ? probs_lds : probs_s) : probs;
   const int nblk = (int)((pos + 2u * (uint32_t)D) / 624u) + 1;
   // the walks of the small shards (mt_group_walks) want thresholds: phase 1 leaves them behind too
-  __shared__ __attribute__((aligned(16))) unsigned char jh_tab[mt_tab_max(LDSC)];
+  unsigned char* const jh_tab = lds.jh_tab;
   const bool multi = LDSC == 2 && mw.W > 0;          // group walks spread over mw.W workgroups of the launch
   const bool walk_ok = (LDSC == 1 && N <= 32 && 4 + 48 * (J - 1) <= 256) || multi;
   double* thr_s = reinterpret_cast<double*>(jh_tab);           // [D <= 1024]   (the first-hit table is not built then)
@@ -910,8 +933,8 @@ __device__ __forceinline__ bool sample_mt_body(const float* __restrict__ probs, 
   // o + min(jh+1, J) with jh = first category hit when env e starts drawing at offset o.  jh is tabulated for
   // every reachable (e, o) in parallel (o <= e*J), then one lane chases the table: N dependent LDS byte reads
   // instead of N ballot/popcount/compare rounds.
-  __shared__ unsigned short skip_tab[mt_skip_max(LDSC)];
-  __shared__ int entry_s[33];
+  unsigned short* const skip_tab = lds.skip_tab;
+  int* const entry_s = lds.entry;
   bool chased = false;
   if constexpr (LDSPATH) {
     // env e can only start at offsets e .. e J (every earlier env drew between 1 and J doubles)
@@ -1321,9 +1344,61 @@ __global__ __launch_bounds__(256) void synth_step_a_mt_kernel(const float* __res
   }
 }
 
-// The same launch with the heads finish in front of the sampler: workgroup 0 sums the fc kernel's per-tile head partials
-// (csrc/fc_heads.h), adds the biases, takes the softmax -- probabilities straight into LDS for the sampler (and to HBM for
-// the learner's records) -- then samples and does the bookkeeping.  One launch per step for heads + sampler + env step.
+// Heads finish + sampler + bookkeeping of one acting step, by one workgroup's first 256 threads: sums the fc kernel's per-tile
+// head partials (csrc/fc_heads.h), adds the biases, takes the softmax -- probabilities straight into LDS for the sampler (and
+// to HBM for the learner's records) -- then samples and does the environments' bookkeeping (rewards_out == nullptr: none, the
+// host environments' policy + sampler).  Called by workgroup 0 of the step launch below and by the workgroup that rides the
+// NEXT fc launch in the pipelined step (ActRiderDev) or the flush launch: one routine, the same bits.
+// id: the step's id; lg_s: kFcHeadsMaxRows * 33 floats of LDS.  ONE_SET: the two sampler bodies share one set of LDS arrays
+// (the riders, which must leave room for an fc workgroup on their CU); otherwise each has its own (mt_lds).
+template <bool ONE_SET>
+__device__ __forceinline__ void act_sample_body(const float* __restrict__ partial, int ntiles, const float* __restrict__ ba,
+                                                const float* __restrict__ bc, float* __restrict__ probs_out,
+                                                float* __restrict__ values_out, int A, uint32_t* __restrict__ mt_state,
+                                                int32_t* __restrict__ actions, uint64_t seed, uint32_t env_offset, int N,
+                                                uint32_t thresh, uint64_t id, float* rewards_out, float* masks_out,
+                                                float* ep_reward, int32_t* ep_len, FinishedRing* fin,
+                                                const MtAhead* __restrict__ ahead, float* lg_s) {
+  __shared__ int16_t act_s[kFcHeadsMaxRows];
+  __shared__ float probs_sh[kFcHeadsMaxRows * 32];
+  // nothing below depends on these: request them before the head sums
+  uint32_t stw[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) stw[k] = mt_state[min((int)threadIdx.x + k * 256, 624)];
+  const int e0 = threadIdx.x < N ? threadIdx.x : 0;
+  const bool env_step = rewards_out != nullptr;          // SynthStep::active(); false: policy + sampler only (host environments)
+  const float ep_reward0 = env_step ? ep_reward[e0] : 0.f;
+  const int32_t ep_len0 = env_step ? ep_len[e0] : 0;
+  // ... and the action-independent half of environment e0's bookkeeping
+  const uint32_t key0 = synth_key(seed, env_offset + (uint32_t)e0, id);
+  const uint32_t hr5 = synth_reward_slot(key0);
+  const bool term0 = synth_terminal(key0, thresh);
+  if (N <= 32 && A <= 7 && ntiles <= 64) {
+    // (row = tid >> 3, output = tid & 7): the partials are requested now; summed, turned into probabilities and into
+    // conditional probabilities in registers after the sampler's state blocks and doubles (FusedHeadsHook)
+    float pv[64];
+    const int row = (int)threadIdx.x >> 3, a = (int)threadIdx.x & 7;
+    const int n = N * (A + 1);
+    const int idx = (row < N && a <= A) ? row * (A + 1) + a : 0;
+    const float bias = (a < A) ? ba[a] : bc[0];
+#pragma unroll
+    for (int t = 0; t < 64; ++t) pv[t] = partial[(size_t)(t < ntiles ? t : 0) * n + idx];
+    sample_mt_body<1, FusedHeadsHook, ONE_SET ? 0 : 1>(nullptr, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, probs_sh, stw,
+                      FusedHeadsHook{pv, bias, ntiles, N, A, probs_sh, probs_out, values_out},
+                      MultiWalk{nullptr, nullptr, nullptr, 0}, ahead);
+  } else {
+    heads_from_partials(partial, ntiles, N, A, ba, bc, lg_s, probs_sh, nullptr, probs_out, values_out, nullptr, nullptr,
+                        nullptr);
+    sample_mt_body<1>(nullptr, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, probs_sh, stw, NoProbsHook(),
+                      MultiWalk{nullptr, nullptr, nullptr, 0}, ahead);
+  }
+  // (the sampler body ends past a barrier; its last wave is still writing the stream position back)
+  if (env_step && (int)threadIdx.x < N)       // N <= 64 here: one environment per thread
+    synth_bookkeep_hashed(hr5, term0, e0, act_s[e0], ep_reward0, ep_len0, StepRecords{rewards_out, masks_out, ep_reward, ep_len, fin});
+}
+
+// The step launch with the heads finish in front of the sampler: workgroup 0 is act_sample_body, the other N * 7 shift the
+// observation stacks meanwhile.  One launch per step for heads + sampler + env step.
 // (The step's arguments one by one, not a SynthStep by value like the other step kernels: with the block by value the compiler
 // fetches all of it in the entry block, the values the bookkeeping needs after the sampler then sit in SGPRs through the sampler
 // instead of being loaded behind it, and the launch measured 7.16 us against 6.84 us at 32 x 4.  DESIGN.md.)
@@ -1342,47 +1417,65 @@ __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __re
                                                                const MtAhead* __restrict__ ahead) {
   const uint64_t id = (step_base ? *step_base : 0ull) + step_off + 1ull;
   if (blockIdx.x == 0) {
-    __shared__ int16_t act_s[kFcHeadsMaxRows];
     __shared__ float lg_s[kFcHeadsMaxRows * 33];
-    __shared__ float probs_sh[kFcHeadsMaxRows * 32];
-    // nothing below depends on these: request them before the head sums
-    uint32_t stw[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) stw[k] = mt_state[min((int)threadIdx.x + k * 256, 624)];
-    const int e0 = threadIdx.x < N ? threadIdx.x : 0;
-    const bool env_step = rewards_out != nullptr;          // SynthStep::active(); false: policy + sampler only (host environments)
-    const float ep_reward0 = env_step ? ep_reward[e0] : 0.f;
-    const int32_t ep_len0 = env_step ? ep_len[e0] : 0;
-    // ... and the action-independent half of environment e0's bookkeeping
-    const uint32_t key0 = synth_key(seed, env_offset + (uint32_t)e0, id);
-    const uint32_t hr5 = synth_reward_slot(key0);
-    const bool term0 = synth_terminal(key0, thresh);
-    if (N <= 32 && A <= 7 && ntiles <= 64) {
-      // (row = tid >> 3, output = tid & 7): the partials are requested now; summed, turned into probabilities and into
-      // conditional probabilities in registers after the sampler's state blocks and doubles (FusedHeadsHook)
-      float pv[64];
-      const int row = (int)threadIdx.x >> 3, a = (int)threadIdx.x & 7;
-      const int n = N * (A + 1);
-      const int idx = (row < N && a <= A) ? row * (A + 1) + a : 0;
-      const float bias = (a < A) ? ba[a] : bc[0];
-#pragma unroll
-      for (int t = 0; t < 64; ++t) pv[t] = partial[(size_t)(t < ntiles ? t : 0) * n + idx];
-      sample_mt_body<1>(nullptr, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, probs_sh, stw,
-                        FusedHeadsHook{pv, bias, ntiles, N, A, probs_sh, probs_out, values_out},
-                        MultiWalk{nullptr, nullptr, nullptr, 0}, ahead);
-    } else {
-      heads_from_partials(partial, ntiles, N, A, ba, bc, lg_s, probs_sh, nullptr, probs_out, values_out, nullptr, nullptr,
-                          nullptr);
-      sample_mt_body<1>(nullptr, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, probs_sh, stw, NoProbsHook(),
-                        MultiWalk{nullptr, nullptr, nullptr, 0}, ahead);
-    }
-    // (the sampler body ends past a barrier; its last wave is still writing the stream position back)
-    if (env_step && (int)threadIdx.x < N)       // N <= 64 here: one environment per thread
-      synth_bookkeep_hashed(hr5, term0, e0, act_s[e0], ep_reward0, ep_len0, StepRecords{rewards_out, masks_out, ep_reward, ep_len, fin});
+    act_sample_body<false>(partial, ntiles, ba, bc, probs_out, values_out, A, mt_state, actions, seed, env_offset, N, thresh, id,
+                    rewards_out, masks_out, ep_reward, ep_len, fin, ahead, lg_s);
     return;
   }
   if (raw) synth_raw_unit(seed, env_offset, id, (int)blockIdx.x - 1, raw);     // path B: the preprocess launch follows
   else synth_shift_band(seed, env_offset, id, thresh, (int)blockIdx.x - 1, stack_in, stack_out, stack_out2);
+}
+
+// The pipelined acting step (csrc/api.hip: paac_act_step_pipe): the sampler leaves the dependent chain tower -> fc -> sampler.
+// In the path-A synthetic environments the new frame and the terminal flag depend on (seed, env, step id) only -- what the
+// step launch above already relies on to shift beside the sampler -- so the shift of step t needs nothing step t computes,
+// tower(t + 1) needs only that shift, and nobody reads step t's sample before the update.  fc(t)'s launch therefore carries
+// (fc_heads.h: RIDER) the shift of step t, dealt over the fc workgroups, and one extra workgroup, first in the grid, that is
+// act_sample_body of step t - 1 on the partial region fc(t - 1) wrote (fc(t) writes the other one).  No workgroup waits for
+// another: every rider reads only what an earlier launch wrote.  (Device games, whose frame depends on the action, keep their
+// routes.)  The fc kernels run 448 or 576 threads, the sampler body and the shift are written for 256: a rider workgroup's
+// surplus waves return before the first barrier, an fc workgroup's take no part in the shift.
+struct ActRiderDev {
+  ActRider r;
+  __device__ __forceinline__ bool front(int& bid, int& nfc, float* lds) const {
+    const int ns = r.owed.partial ? 1 : 0;
+    if (bid < ns) {
+      if (threadIdx.x >= 256) return true;
+      const ActSample& o = r.owed;
+      const uint64_t id = (o.step_base ? *o.step_base : 0ull) + o.step_off + 1ull;
+      act_sample_body<true>(o.partial, o.ntiles, o.ba, o.bc, o.probs_out, o.values_out, o.A, o.mt_state, o.actions, o.seed,
+                      o.env_offset, o.N, o.thresh, id, o.rec.rewards, o.rec.masks, o.rec.ep_reward, o.rec.ep_len, o.rec.fin,
+                      nullptr, lds);
+      return true;
+    }
+    bid -= ns;
+    nfc -= ns;
+    return false;
+  }
+  // fc workgroup `bid` of nfc shifts units bid, bid + nfc, ...: the first one around its K loop, the others behind it
+  __device__ __forceinline__ uint4 shift_load(const int bid) const {
+    const SynthStep& st = r.shift;
+    if (st.stack_in == nullptr || threadIdx.x >= 256 || bid >= st.N * PRE_BANDS) return make_uint4(0u, 0u, 0u, 0u);
+    return synth_shift_load(bid, st.stack_in);
+  }
+  __device__ __forceinline__ void shift_store(const int bid, const int nfc, const uint4 old) const {
+    const SynthStep& st = r.shift;
+    if (st.stack_in == nullptr || threadIdx.x >= 256) return;
+    const uint64_t id = st.id();
+    const int units = st.N * PRE_BANDS;
+    if (bid < units) synth_shift_store(st.seed, st.env_offset, id, st.thresh, bid, old, st.stack_out, st.stack_out2);
+    for (int u = bid + nfc; u < units; u += nfc)
+      synth_shift_band(st.seed, st.env_offset, id, st.thresh, u, st.stack_in, st.stack_out, st.stack_out2);
+  }
+};
+
+// The flush: the owed sample as a launch of its own (one workgroup), for a caller that ends a run of pipelined steps without
+// a forward behind it.
+__global__ __launch_bounds__(256) void act_sample_flush_kernel(const ActSample o) {
+  __shared__ float lg_s[kFcHeadsMaxRows * 33];
+  const uint64_t id = (o.step_base ? *o.step_base : 0ull) + o.step_off + 1ull;
+  act_sample_body<true>(o.partial, o.ntiles, o.ba, o.bc, o.probs_out, o.values_out, o.A, o.mt_state, o.actions, o.seed, o.env_offset,
+                  o.N, o.thresh, id, o.rec.rewards, o.rec.masks, o.rec.ep_reward, o.rec.ep_len, o.rec.fin, nullptr, lg_s);
 }
 
 // Path B, stage 1: generate the two raw 210x160 gray frames of this step + bookkeeping.
@@ -1439,6 +1532,51 @@ int launch_sample_env_step_heads(const HeadsPartials& hp, float* probs_out, int 
   }
   if (st.raw) launch_preprocess_after_step(st, s);
   return 0;
+}
+
+int launch_act_sample_flush(const ActSample& owed, hipStream_t s) {
+  ProfScope ps(g_prof_ctx, F_SAMPLE_ENV_STEP, owed.N, s);
+  launch_k(act_sample_flush_kernel, dim3(1), dim3(256), s, PROF_WHOLE, owed);
+  return 0;
+}
+
+// The acting fc launch with its riders (the caller holds the fc family's ProfScope): fc_wgs fc workgroups behind the owed
+// sample's one, if any.  quarter / packed: which fc kernel, as csrc/net_fwd.hip chose it.
+template <class NT>
+static int launch_fc_rider_of(bool quarter, bool packed, unsigned fc_wgs, const float* act, const void* wfp, const float* bf,
+                              const float* wa, const float* wc, int A, int batch, float* partial, float* h_out,
+                              const ActRider& r, hipStream_t s) {
+  constexpr int NW = fc_heads_waves(NT::FLAT);
+  if constexpr (NW > 0) {
+    const ActRiderDev rd{r};
+    const dim3 grid(fc_wgs + (r.owed.partial ? 1u : 0u)), block(64 * NW);
+    const f32x4* w = reinterpret_cast<const f32x4*>(wfp);
+    if constexpr (fc_heads_quarter_ok(NT::FLAT)) if (quarter) {
+      if (packed) launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, true, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc,
+                           A, batch, partial, h_out, rd);
+      else launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, false, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc, A,
+                    batch, partial, h_out, rd);
+      return 0;
+    }
+    if (quarter) {
+      set_error("fc rider: no quarter-tile kernel for this geometry");
+      return -1;
+    }
+    const MtAheadArgs none{nullptr, nullptr, 0};
+    if (packed) launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, true, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc, A,
+                         batch, partial, h_out, none, rd);
+    else launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, false, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc, A, batch,
+                  partial, h_out, none, rd);
+    return 0;
+  }
+  set_error("fc rider: this geometry has no fc + head partials kernel");
+  return -1;
+}
+int launch_fc_heads_rider(bool nature, bool quarter, bool packed, unsigned fc_wgs, const float* act, const void* wfp,
+                          const float* bf, const float* wa, const float* wc, int A, int batch, float* partial, float* h_out,
+                          const ActRider& r, hipStream_t s) {
+  if (nature) return launch_fc_rider_of<NatureNet>(quarter, packed, fc_wgs, act, wfp, bf, wa, wc, A, batch, partial, h_out, r, s);
+  return launch_fc_rider_of<OtherNet>(quarter, packed, fc_wgs, act, wfp, bf, wa, wc, A, batch, partial, h_out, r, s);
 }
 
 // (arguments validated by paac_returns_norm_tick, csrc/api.hip)

@@ -271,6 +271,13 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
                         bool defer_heads = false, bool trunk_only = false) {
   const paac_layout& L = ctx->layout;
   Workspace& W = ctx->ws[wsi];
+  // the head partials a pending sample will be finished from live in the acting set's fc slab buffer, which every acting
+  // forward writes: only a forward whose fc launch carries that sample (fc_rider) may run
+  if (wsi == 0 && ctx->act_owed->partial && !ctx->fc_rider) {
+    set_error("forward: the last paac_act_step_pipe's sample is still pending: pay it with paac_bootstrap_forward_trunk, another "
+              "paac_act_step_pipe or paac_act_step_flush before another acting forward (paac_act_step_mt, paac_forward*)");
+    return -1;
+  }
   ctx->last_ws = wsi;
   const int cls = batch_class(batch);
   const int A = ctx->cfg.num_actions;
@@ -314,6 +321,12 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
   // few workgroups (heads_finish_rows_kernel) instead of split-K slabs + a per-row heads launch
   const bool mid_tail = !small_tail && (tower || tower2) && !keep_acts && wsi == 0 && batch <= kFcHeadsMidRows && !ph.enabled &&
                         !st.active() && !trunk_only;
+  // riders (one shot: paac_act_step_pipe, paac_bootstrap_forward_trunk) go with the fc + head partials launch of the small
+  // acting route alone: refused here, before anything is launched
+  if (wsi == 0 && ctx->fc_rider && (!small_tail || ctx->ahead_state)) {
+    set_error("forward: the fc launch's riders need the small acting route without the spare MT19937 workgroup");
+    return -1;
+  }
   Workspace* keepW = nullptr;
   if (keep_row >= 0) {
     // (the fc + head partials routes, or -- the counter-based sampler's forwards -- the split-K fc with its per-row heads
@@ -377,6 +390,13 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
     const int NTILES = quarter ? NT::H / 8 : NT::H / 16;
     ctx->heads_ntiles = NTILES;
     float* partial = W.fc_slab;      // [NTILES][batch][A + 1]: fits the split-K slab buffer
+    // one shot (paac_act_step_pipe, paac_bootstrap_forward_trunk): this launch carries riders, and its partials go to the
+    // half of the buffer the rider workgroup is NOT reading
+    // (taken -- fc_rider cleared, the regions swapped -- only once the launch has been issued, below: that is what tells the
+    // caller its riders rode)
+    const ActRider* rider = wsi == 0 ? ctx->fc_rider : nullptr;
+    if (rider) partial += (size_t)ctx->act_region * act_region_floats(ctx);
+    ctx->heads_partial = partial;
     const bool keep_h = keep_acts;
     // kept rows: the finished fc activations (bias + ReLU applied) go where the training forward's fc slabs would be
     float* h_keep = keepW ? keepW->fc_slab + (size_t)keep_row * NT::H : nullptr;
@@ -387,23 +407,32 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
       MtAheadArgs ah{ctx->ahead_state, ctx->ahead_state ? reinterpret_cast<MtAhead*>(ctx->mt_ahead) : nullptr, ctx->ahead_D};
       ctx->ahead_state = nullptr;
       const unsigned grid = NTILES * ((batch + 15) / 16) + (ah.out ? 1 : 0);
+      if (rider) {
+        const unsigned fc_wgs = quarter ? NTILES * ((batch + 7) / 8) : NTILES * ((batch + 15) / 16);
+        if (launch_fc_heads_rider(ctx->cfg.arch == PAAC_ARCH_NATURE, quarter, packed3, fc_wgs, last,
+                                  ctx->fc_pack, bf, wa, wc, A, batch, partial, packed3 ? h_keep : (keep_h ? W.h : (float*)nullptr),
+                                  *rider, s))
+          return -1;
+        ctx->fc_rider = nullptr;
+        ctx->act_region ^= 1;
+      } else
       if constexpr (fc_heads_quarter_ok(NT::FLAT)) if (quarter) {
         if (packed3)
           launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, true>, dim3(NTILES * ((batch + 7) / 8)), dim3(64 * NW), s, PROF_WHOLE,
-                   last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial, h_keep);
+                   last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial, h_keep, NoRider{});
         else
           launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, false>, dim3(NTILES * ((batch + 7) / 8)), dim3(64 * NW), s, PROF_WHOLE,
                    last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial,
-                   keep_h ? W.h : (float*)nullptr);
+                   keep_h ? W.h : (float*)nullptr, NoRider{});
       }
-      if (quarter) {
+      if (quarter || rider) {
       } else if (packed3)
         launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, true>, dim3(grid), dim3(64 * NW), s, PROF_WHOLE,
-                 last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial, h_keep, ah);
+                 last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial, h_keep, ah, NoRider{});
       else
         launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, false>, dim3(grid), dim3(64 * NW), s, PROF_WHOLE,
                  last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial,
-                 keep_h ? W.h : (float*)nullptr, ah);
+                 keep_h ? W.h : (float*)nullptr, ah, NoRider{});
     }
     if (defer_heads) return 0;       // the caller's launch finishes the heads (or, for bootstrap rows, the backward's)
     if (mid_tail) {
@@ -542,11 +571,11 @@ int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* stat
   const int nt = L.num_tensors;
   hp->ba = params + L.offset[nt - 3];
   hp->bc = params + L.offset[nt - 1];
-  hp->partial = ctx->ws[0].fc_slab;
   const int rc = (ctx->cfg.arch == PAAC_ARCH_NATURE)
                      ? forward_impl<NatureNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true)
                      : forward_impl<OtherNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true);
-  hp->ntiles = ctx->heads_ntiles;       // (this launch's: whole or quarter tiles, fc_heads.h)
+  hp->partial = ctx->heads_partial;     // (this launch's: ws[0].fc_slab, or the half of it a ridden launch took)
+  hp->ntiles = ctx->heads_ntiles;       // (whole or quarter tiles, fc_heads.h)
   return rc;
 }
 

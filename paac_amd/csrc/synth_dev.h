@@ -100,21 +100,25 @@ __device__ __forceinline__ bool synth_bookkeep(uint32_t key, int e, const int32_
 // Frame shift of one (env, band) unit of path A: push the step's new 84x84 plane into the 4-deep history
 // (one dword = the 4 channels of a pixel).  unit = env * PRE_BANDS + band; 256 threads, 252 of them own one quad of four
 // pixels each: ONE generator word is the quad's four new bytes, one 16-byte load and one 16-byte store per thread.
-__device__ __forceinline__ void synth_shift_band(uint64_t seed, uint32_t env_offset, uint64_t id, uint32_t thresh, int unit,
-                                                 const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
-                                                 uint32_t* __restrict__ stack_out2 = nullptr,
-                                                 const bool force_reset = false) {
+// In two halves, so that a caller with work of its own (the acting fc launch's workgroups, csrc/fc_heads.h) can put it between
+// the load of the old stack and the store of the new one: synth_shift_load requests the thread's 16 bytes, synth_shift_store
+// pushes the new bytes and writes.  Threads 252.. of the 256 own nothing in either half.
+constexpr int SHIFT_QUADS = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
+__device__ __forceinline__ uint4 synth_shift_load(int unit, const uint32_t* __restrict__ stack_in) {
+  const int i = threadIdx.x;
+  if (i >= SHIFT_QUADS) return make_uint4(0u, 0u, 0u, 0u);
+  const long quad = (long)(unit / PRE_BANDS) * (OBS_PIX / 4) + (unit % PRE_BANDS) * SHIFT_QUADS + i;
+  return reinterpret_cast<const uint4*>(stack_in)[quad];
+}
+__device__ __forceinline__ void synth_shift_store(uint64_t seed, uint32_t env_offset, uint64_t id, uint32_t thresh, int unit,
+                                                  uint4 old, uint32_t* __restrict__ stack_out,
+                                                  uint32_t* __restrict__ stack_out2, const bool force_reset = false) {
   const int e = unit / PRE_BANDS;
   const int band = unit % PRE_BANDS;
-  constexpr int QUADS_PER_BAND = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
   const int i = threadIdx.x;
-  if (i >= QUADS_PER_BAND) return;
-  const int q = band * QUADS_PER_BAND + i;                 // = y * 21 + (x >> 2): the generator's word index
+  if (i >= SHIFT_QUADS) return;
+  const int q = band * SHIFT_QUADS + i;                 // = y * 21 + (x >> 2): the generator's word index
   const long quad = (long)e * (OBS_PIX / 4) + q;
-  // the old stack is requested whether or not this step resets the environment (1 step in 100 reads 16 bytes for nothing):
-  // the reset flag hangs on the step id, which the caller has just LOADED -- asked for only when needed, the two round
-  // trips to memory ran one after the other in every workgroup of the launch
-  uint4 old = force_reset ? make_uint4(0u, 0u, 0u, 0u) : reinterpret_cast<const uint4*>(stack_in)[quad];
   const uint32_t key = synth_key(seed, env_offset + (uint32_t)e, id);
   const bool reset = force_reset || lowbias32(key ^ 0x3C6EF372u) < thresh;
   if (reset) old = make_uint4(0u, 0u, 0u, 0u);
@@ -124,6 +128,41 @@ __device__ __forceinline__ void synth_shift_band(uint64_t seed, uint32_t env_off
   reinterpret_cast<uint4*>(stack_out)[quad] = outv;
   if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
 }
+__device__ __forceinline__ void synth_shift_band(uint64_t seed, uint32_t env_offset, uint64_t id, uint32_t thresh, int unit,
+                                                 const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
+                                                 uint32_t* __restrict__ stack_out2 = nullptr,
+                                                 const bool force_reset = false) {
+  // the old stack is requested whether or not this step resets the environment (1 step in 100 reads 16 bytes for nothing):
+  // the reset flag hangs on the step id, which the caller has just LOADED -- asked for only when needed, the two round
+  // trips to memory ran one after the other in every workgroup of the launch
+  const uint4 old = force_reset ? make_uint4(0u, 0u, 0u, 0u) : synth_shift_load(unit, stack_in);
+  synth_shift_store(seed, env_offset, id, thresh, unit, old, stack_out, stack_out2, force_reset);
+}
+
+// The pipelined acting step (paac_act_step_pipe, csrc/api.hip): what the sampler of one acting step still owes after the
+// step's fc launch -- the heads finish, the MT19937 sampler and the bookkeeping of `N` environments, read from the head
+// partials the fc launch left -- and what the NEXT fc launch carries beside its own work: that debt and the frame shift of
+// its own step (shift.stack_in == nullptr: none, the bootstrap forward's launch).
+struct ActSample {
+  const float* partial;            // nullptr: nothing owed
+  int ntiles;
+  const float *ba, *bc;
+  float *probs_out, *values_out;
+  int A;
+  uint32_t* mt_state;
+  int32_t* actions;
+  uint64_t seed;
+  uint32_t env_offset;
+  int N;
+  uint32_t thresh;
+  const uint64_t* step_base;
+  uint64_t step_off;
+  StepRecords rec;
+};
+struct ActRider {
+  ActSample owed;
+  SynthStep shift;
+};
 
 // Path B: one of PRE_BANDS parts of environment e's raw 2 x 210 x 160 gray screen pair for step `id` (16,800 generator
 // words = 4,200 16-byte stores per environment, 600 per unit).  unit = env * PRE_BANDS + part; 256 threads.

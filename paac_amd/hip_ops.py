@@ -421,6 +421,28 @@ class Context(object):
         self._act(N, params, states, mt_state, actions, probs_out, values_out, step, env_seed, env_offset, terminal_threshold,
                   step_base_dev, step_offset, raw_scratch, walk_scratch)
 
+    def act_step_pipe(self, params, states, mt_state, actions, probs_out, values_out, env_seed, env_offset,
+                      terminal_threshold, step_base_dev, step_offset, stack_out, rewards_out, masks_out, ep_reward, ep_len,
+                      finished=None, stack_out2=None):
+        """act_step_mt with the sampler off the dependent chain, two launches per step (include/paac_hip.h:
+        paac_act_step_pipe): conv tower, then the fc launch, which also shifts this step's frames and finishes, samples and
+        records the PREVIOUS pipelined step.  This step's actions, probabilities, values and records are owed until the next
+        act_step_pipe, bootstrap_forward_trunk or act_step_flush.  Path A, N <= ACT_STEP_MAX_ENVS, N*(A-1) <= 1024."""
+        N = self._check_states(states)
+        if stack_out is None:
+            raise ValueError("stack_out is required")
+        step = _step_ptrs(N, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished, stack_out2, states=states)
+        self._act(N, params, states, mt_state, actions, probs_out, values_out, step, env_seed, env_offset, terminal_threshold,
+                  step_base_dev, step_offset, entry="paac_act_step_pipe")
+
+    def act_step_flush(self):
+        """Pay the sample the last act_step_pipe owes, as a launch of its own; nothing pending: nothing launched."""
+        _lib.check(self.lib.paac_act_step_flush(self.handle, _stream()), "paac_act_step_flush")
+
+    def act_step_pending(self):
+        """True while the last act_step_pipe's sample is owed (host-side state of the context)."""
+        return bool(self.lib.paac_act_step_pending(self.handle))
+
     def act_mt(self, params, states, mt_state, actions, probs_out, values_out):
         """Policy forward + numpy-parity sampler in three launches, no environment step (paac_act_step_mt with stack_out =
         NULL): what the host-plugin loop runs per step (paac.py:104-110).  N <= ACT_STEP_MAX_ENVS, N*(A-1) <= 1024."""
@@ -428,17 +450,18 @@ class Context(object):
         self._act(N, params, states, mt_state, actions, probs_out, values_out, _step_ptrs(N))
 
     def _act(self, N, params, states, mt_state, actions, probs_out, values_out, step, env_seed=0, env_offset=0,
-             terminal_threshold=0, step_base_dev=None, step_offset=0, raw_scratch=None, walk_scratch=None):
-        """paac_act_step_mt; step: _step_ptrs' list."""
+             terminal_threshold=0, step_base_dev=None, step_offset=0, raw_scratch=None, walk_scratch=None,
+             entry="paac_act_step_mt"):
+        """paac_act_step_mt (or paac_act_step_pipe: the same arguments); step: _step_ptrs' list."""
         A = self.num_actions
-        _lib.check(self.lib.paac_act_step_mt(
+        _lib.check(getattr(self.lib, entry)(
             self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
             _ptr(states, torch.uint8, N * 28224, "states"), N, _ptr(mt_state, torch.int32, 625, "mt_state"),
             _ptr(actions, torch.int32, N, "actions"), _ptr(probs_out, torch.float32, N * A, "probs_out"),
             _ptr(values_out, torch.float32, N, "values_out"), int(env_seed), int(env_offset), int(terminal_threshold),
             _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset), *step,
             _ptr(raw_scratch, torch.uint8, N * 2 * RAW_H * RAW_W, "raw_scratch", True),
-            *_lent(walk_scratch), _stream()), "paac_act_step_mt")
+            *_lent(walk_scratch), _stream()), entry)
 
     def pack_weights(self, params):
         """Refresh the ctx's pre-split copy of the conv weights (include/paac_hip.h: paac_pack_weights)."""
@@ -1002,6 +1025,7 @@ def match_step(probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_
 FUSED_SAMPLE_MAX_DRAWS = 2304
 ACT_STEP_MAX_DRAWS = 1024
 ACT_STEP_MAX_ENVS = 64
+ACT_PIPE_MAX_ACTIONS = 31        # paac_act_step_pipe: two regions of head partials in the acting fc slab buffer
 ACT_STEP_MAX_ENVS_LARGE = 256    # paac_act_step_mt's four-launch form (large shards)
 KEEP_FORWARD_MAX_ROWS = 256      # paac_keep_next_forward: acting forwards of up to this many rows (csrc/fc_heads.h)
 

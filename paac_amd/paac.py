@@ -87,6 +87,7 @@ class DeviceRollout(object):
     """Device-resident rollout/update cycle for N local environments x T steps."""
     truncs = None      # --bootstrap_truncated: the [T, N] truncation plane, allocated by __init__ only where it applies
     pool = None        # --duel_pool: the duel_pool.DevicePool, created by __init__ only with the pool on
+    act_pipeline = False   # the small act_step route as two launches per step (act_step_pipe), set by __init__ only where it applies
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
                  total_envs=None):
@@ -216,6 +217,13 @@ class DeviceRollout(object):
         self.act_step_large = os.environ.get("PAAC_MT_AHEAD", "1") != "0" and N <= hip_ops.ACT_STEP_MAX_ENVS_LARGE and towered
         self.reuse_acting = os.environ.get("PAAC_REUSE_ACTING", "1") != "0" and towered and N <= hip_ops.KEEP_FORWARD_MAX_ROWS
         self.route = self._route()
+        # The small act_step route runs pipelined (hip_ops.act_step_pipe): two launches per step, the sampler and the bookkeeping
+        # of step t riding the fc launch of step t + 1 and those of the last step the bootstrap forward's -- which is why it
+        # needs the kept acting rows (reuse_acting).  It rests on the path-A synthetic environments' frames not depending on
+        # the action.  PAAC_ACT_PIPELINE=0, read here, restores the three-launch step.
+        self.act_pipeline = (os.environ.get("PAAC_ACT_PIPELINE", "1") != "0" and self.route == "act_step" and self.raw is None
+                             and self.reuse_acting and N <= hip_ops.ACT_STEP_MAX_ENVS
+                             and N * (A - 1) <= hip_ops.ACT_STEP_MAX_DRAWS and A <= hip_ops.ACT_PIPE_MAX_ACTIONS)
         # what step t records, as every route's step call takes it (the per-cycle counterpart: cycle_tick above)
         self.records = [(self.rewards[t], self.masks[t], self.ep_reward, self.ep_len, self.finished) for t in range(T)]
         if self.pool is not None:
@@ -262,7 +270,10 @@ class DeviceRollout(object):
         seed = self.env_spec["seed"]
         if self.reuse_acting:
             L.ctx.keep_next_forward(t * self.N)
-        if route == "act_step":
+        if route == "act_step" and self.act_pipeline:
+            L.ctx.act_step_pipe(params, obs, self.mt_state, self.actions[t], self.probs, self.values[t], seed, self.env_offset,
+                                self.env_spec["terminal_threshold"], self.tick, t, nxt, *records, stack_out2=wrap)
+        elif route == "act_step":
             L.ctx.act_step_mt(params, obs, self.mt_state, self.actions[t], self.probs, self.values[t], seed, self.env_offset,
                               self.env_spec["terminal_threshold"], self.tick, t, nxt, *records, stack_out2=wrap,
                               raw_scratch=self.raw, walk_scratch=self.walk_scratch)
@@ -313,7 +324,7 @@ class DeviceRollout(object):
         # training forward over the T*N rollout rows with the N bootstrap observations appended (paac.py:140-142)
         # (the forward stops after the fc layer: the heads of the rollout rows AND the value head of the bootstrap rows are
         # finished inside the backward's first launch)
-        if keep:
+        if keep:      # (its fc launch also pays what the last pipelined step owes: act_pipeline)
             L.ctx.bootstrap_forward_trunk(params, self.states[self._slot(parity, T)], T * N)
         else:
             L.ctx.train_forward_trunk(params, self.states[parity * T:(parity + 1) * T + 1].view((T + 1) * N, 84, 84, 4))

@@ -234,15 +234,11 @@ int paac_create(const paac_cfg* cfg, paac_ctx** out) {
   PAAC_CHECK_HIP(hipMalloc(&c->zeros, (size_t)(c->spec.fc > 1024 ? c->spec.fc : 1024) * sizeof(float)));
   PAAC_CHECK_HIP(hipMemset(c->zeros, 0, (size_t)(c->spec.fc > 1024 ? c->spec.fc : 1024) * sizeof(float)));
   c->keep_row = -1;
-  c->keep_h_only = 0;
   c->heads_pending_h = 0;
   PAAC_CHECK_HIP(hipMalloc(&c->mt_ahead, mt_ahead_bytes()));
   PAAC_CHECK_HIP(hipMemset(c->mt_ahead, 0, mt_ahead_bytes()));
-  c->ahead_state = nullptr;
-  c->ahead_D = 0;
   c->act_owed = new (std::nothrow) ActSample{};
   PAAC_REQUIRE(c->act_owed, "paac_create: out of host memory");
-  c->fc_rider = nullptr;
   c->act_region = 0;
   {
     const char* v = getenv("PAAC_TOWER");
@@ -302,15 +298,27 @@ int paac_destroy(paac_ctx* c) {
   return 0;
 }
 
+// The tail of the forward and acting entries: the status of the entry's last launcher, then what HIP has recorded meanwhile.
+static int launched(int rc) {
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// The head partials a kHeadsDefer forward left, as the launch that finishes the heads takes them.
+static HeadsPartials partials_of(const paac_ctx* ctx, const float* params, const ForwardCall& call, float* values_out) {
+  const paac_layout& L = ctx->layout;
+  const int nt = L.num_tensors;
+  return HeadsPartials{call.partial, call.ntiles, params + L.offset[nt - 3], params + L.offset[nt - 1], values_out};
+}
+
 int paac_forward(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* logits, float* probs,
                  float* values, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && states, "paac_forward: null argument");
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_forward: batch %d outside (0, max_batch=%d]", batch,
                ctx->max_batch);
-  const int rc = launch_forward(ctx, 0, params, states, batch, logits, probs, values, (hipStream_t)stream);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  ForwardCall call{.ws = 0, .logits = logits, .probs = probs, .values = values};
+  return launched(launch_forward(ctx, params, states, batch, call, (hipStream_t)stream));
 }
 
 int paac_pack_weights(paac_ctx* ctx, const float* params, paac_stream_t stream) {
@@ -332,20 +340,16 @@ int paac_train_forward(paac_ctx* ctx, const float* params, const uint8_t* states
   PAAC_REQUIRE(ctx && params && states, "paac_train_forward: null argument");
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_train_forward: batch %d outside (0, max_batch=%d]", batch,
                ctx->max_batch);
-  const int rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, values, (hipStream_t)stream);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  ForwardCall call{.ws = 1, .values = values};
+  return launched(launch_forward(ctx, params, states, batch, call, (hipStream_t)stream));
 }
 
 int paac_train_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && states, "paac_train_forward_trunk: null argument");
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_train_forward_trunk: batch %d outside (0, max_batch=%d]", batch,
                ctx->max_batch);
-  const int rc = launch_forward_trunk_train(ctx, params, states, batch, (hipStream_t)stream);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  ForwardCall call{.ws = 1, .heads = kHeadsTrunkOnly};
+  return launched(launch_forward(ctx, params, states, batch, call, (hipStream_t)stream));
 }
 
 int paac_keep_next_forward(paac_ctx* ctx, int train_row) {
@@ -369,15 +373,20 @@ int paac_bootstrap_forward_trunk(paac_ctx* ctx, const float* params, const uint8
                  (size_t)(ctx->spec.fc / 8) * batch * (ctx->cfg.num_actions + 1) <= act_region_floats(ctx),
                  "paac_bootstrap_forward_trunk: a forward of %d rows cannot carry the pending sample of paac_act_step_pipe "
                  "(paac_act_step_flush pays it)", batch);
-    ctx->fc_rider = &rider;
   }
-  const int rc = launch_bootstrap_trunk(ctx, params, states, batch, train_row, (hipStream_t)stream);
-  const bool carried = rider.owed.partial && ctx->fc_rider == nullptr;      // (the fc launch takes the riders: one shot)
-  ctx->fc_rider = nullptr;
-  if (carried) ctx->act_owed->partial = nullptr;
+  // Acting-shaped forward of the N bootstrap observations whose rows complete a training set the acting steps have kept
+  // (paac_keep_next_forward): conv tower + fc, rows kept at [train_row, train_row + batch) -- of the bootstrap rows the update
+  // reads the fc activations only, the backward covers the rollout rows; no heads -- the backward's first launch takes the
+  // bootstrap values from the kept fc activations like it does after a trunk-only training forward.
+  ForwardCall call{.ws = 0, .heads = kHeadsDefer, .keep_row = train_row, .keep_h_only = true,
+                   .rider = rider.owed.partial ? &rider : nullptr};
+  const int rc = launch_forward(ctx, params, states, batch, call, (hipStream_t)stream);
+  if (call.rode) ctx->act_owed->partial = nullptr;
   if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  ctx->heads_pending_rows = train_row + batch;
+  ctx->heads_pending_splits = 1;
+  ctx->heads_pending_h = 1;
+  return launched(0);
 }
 
 int paac_forward_sample(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
@@ -386,11 +395,8 @@ int paac_forward_sample(paac_ctx* ctx, const float* params, const uint8_t* state
   PAAC_REQUIRE(ctx && params && states && actions, "paac_forward_sample: null argument");
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_forward_sample: batch %d outside (0, max_batch=%d]", batch,
                ctx->max_batch);
-  const int rc = launch_forward_sample(ctx, params, states, batch, probs, values, seed, step_base_dev, step_offset,
-                                       env_offset, actions, nullptr, (hipStream_t)stream);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launched(launch_forward_sample(ctx, params, states, batch, probs, values, seed, step_base_dev, step_offset, env_offset,
+                                        actions, nullptr, (hipStream_t)stream));
 }
 
 int paac_forward_sample_synth_step(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
@@ -406,11 +412,8 @@ int paac_forward_sample_synth_step(paac_ctx* ctx, const float* params, const uin
     return -1;
   PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_forward_sample_synth_step: batch %d outside (0, max_batch=%d]",
                batch, ctx->max_batch);
-  const int rc = launch_forward_sample(ctx, params, states, batch, probs, values, seed, step_base_dev, step_offset, env_offset,
-                                       actions, &st, (hipStream_t)stream);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launched(launch_forward_sample(ctx, params, states, batch, probs, values, seed, step_base_dev, step_offset, env_offset,
+                                        actions, &st, (hipStream_t)stream));
 }
 
 int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, uint32_t* mt_state,
@@ -420,8 +423,10 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
                      void* finished, uint8_t* raw_scratch, void* walk_scratch, int64_t walk_scratch_bytes,
                      paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && states && mt_state && actions && probs_out && values_out, "paac_act_step_mt: null argument");
-  // the fc kernel's head partials, where a launch leaves them for the sampler launch to finish (launch_forward_trunk fills it)
-  HeadsPartials hp{nullptr, 0, nullptr, nullptr, values_out};
+  // the acting forward that finishes its heads into the caller's arrays, and the one that leaves the fc kernel's head partials
+  // for the sampler launch to finish (partials_of)
+  const ForwardCall finish{.ws = 0, .probs = probs_out, .values = values_out}, defer{.ws = 0, .heads = kHeadsDefer};
+  const hipStream_t s = (hipStream_t)stream;
   if (stack_out == nullptr) {
     // policy forward + sampler only (the environments live on the host: paac.py:104-110 without :115-116): three launches up
     // to PAAC_ACT_STEP_MAX_ENVS environments, paac_forward + paac_sample_mt beyond
@@ -433,21 +438,16 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
                  "paac_forward + paac_sample_mt); got %d x %d actions", PAAC_ACT_STEP_MAX_ENVS, batch, ctx->cfg.num_actions);
     if (!forward_has_fc_heads(ctx)) {
       // no head partials on this geometry: the plain forward finishes the heads, the sampler reads its probabilities
-      int rc = launch_forward(ctx, 0, params, states, batch, nullptr, probs_out, values_out, (hipStream_t)stream);
-      if (rc) return rc;
-      rc = launch_sample_mt_probs(probs_out, ctx->cfg.num_actions, mt_state, actions, batch, (hipStream_t)stream);
-      if (rc) return rc;
-      PAAC_CHECK_HIP(hipGetLastError());
-      return 0;
+      ForwardCall call = finish;
+      if (const int rc = launch_forward(ctx, params, states, batch, call, s)) return rc;
+      return launched(launch_sample_mt_probs(probs_out, ctx->cfg.num_actions, mt_state, actions, batch, s));
     }
     SynthStep none{};            // no environment step: heads finish + sampler over `batch` rows
     none.N = batch;
-    int rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
-    if (rc) return rc;
-    rc = launch_sample_env_step_heads(hp, probs_out, ctx->cfg.num_actions, mt_state, actions, none, nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-    PAAC_CHECK_HIP(hipGetLastError());
-    return 0;
+    ForwardCall call = defer;
+    if (const int rc = launch_forward(ctx, params, states, batch, call, s)) return rc;
+    return launched(launch_sample_env_step_heads(partials_of(ctx, params, call, values_out), probs_out, ctx->cfg.num_actions,
+                                                 mt_state, actions, none, nullptr, s));
   }
   SynthStep st;
   if (synth_step_of("paac_act_step_mt", "null argument", false, &st, env_seed, env_offset, batch, terminal_threshold, step_base_dev,
@@ -461,22 +461,20 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
                (long)batch * (ctx->cfg.num_actions - 1), PAAC_FUSED_SAMPLE_MAX_DRAWS);
   if (!forward_has_fc_heads(ctx)) {
     // no head partials on this geometry (fc_heads_waves == 0): paac_forward + paac_sample_mt_synth_step's launch
-    int rc = launch_forward(ctx, 0, params, states, batch, nullptr, probs_out, values_out, (hipStream_t)stream);
-    if (rc) return rc;
-    rc = launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, st, walk_scratch, walk_scratch_bytes,
-                                     nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-    PAAC_CHECK_HIP(hipGetLastError());
-    return 0;
+    ForwardCall call = finish;
+    if (const int rc = launch_forward(ctx, params, states, batch, call, s)) return rc;
+    return launched(launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, st, walk_scratch,
+                                                walk_scratch_bytes, nullptr, s));
   }
   if (batch > PAAC_ACT_STEP_MAX_ENVS || (int64_t)batch * (ctx->cfg.num_actions - 1) > 1024) {
     // the large shards (128 x 18, 256 x 4): policy forward with its heads finish, then the sampler + environment-step launch
     // with the walks spread over several workgroups -- whose MT19937 doubles a spare workgroup of the fc launch makes
     // meanwhile (csrc/mt_ahead.h)
     const bool tail = (ctx->tower_on || ctx->tower2_on) && ctx->managed_weights && batch <= PAAC_ACT_STEP_MAX_ENVS_LARGE;
+    ForwardCall call = finish;
     if (tail) {
-      ctx->ahead_state = mt_state;
-      ctx->ahead_D = batch * (ctx->cfg.num_actions - 1);
+      call.ahead_state = mt_state;
+      call.ahead_D = batch * (ctx->cfg.num_actions - 1);
     }
     // (three launches when the walks can be spread -- walk_scratch lent -- and the action set is small: the sampler workgroups
     // then also finish the heads of the environments they visit, from the fc kernel's per-tile partials.  Measured: 256 x 4
@@ -488,18 +486,13 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
       return (v && *v) ? (atoi(v) != 0 ? 1 : 0) : -1;
     }();
     const bool fold = fold_knob >= 0 ? fold_knob == 1 : ctx->cfg.num_actions <= 8;
-    int rc;
     if (tail && fold && sampler_folds_heads(batch, ctx->cfg.num_actions, walk_scratch))
-      rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
-    else
-      rc = launch_forward(ctx, 0, params, states, batch, nullptr, probs_out, values_out, (hipStream_t)stream);
-    ctx->ahead_state = nullptr;
-    if (rc) return rc;
-    rc = launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, st, walk_scratch, walk_scratch_bytes,
-                                     tail ? ctx->mt_ahead : nullptr, (hipStream_t)stream, hp.partial ? &hp : nullptr);
-    if (rc) return rc;
-    PAAC_CHECK_HIP(hipGetLastError());
-    return 0;
+      call.heads = kHeadsDefer;      // (the outputs are then the sampler launch's to write)
+    if (const int rc = launch_forward(ctx, params, states, batch, call, s)) return rc;
+    const HeadsPartials hp = partials_of(ctx, params, call, values_out);
+    return launched(launch_sample_mt_synth_step(probs_out, ctx->cfg.num_actions, mt_state, actions, st, walk_scratch,
+                                                walk_scratch_bytes, tail ? ctx->mt_ahead : nullptr, s,
+                                                call.heads == kHeadsDefer ? &hp : nullptr));
   }
   // Up to 64 environments the sampler's state blocks and doubles already hide behind the loads of the head partials
   // (misc.hip: synth_step_a_mth_kernel): making them one launch ahead (csrc/mt_ahead.h) measured SLOWER here -- 658 k against
@@ -509,18 +502,14 @@ int paac_act_step_mt(paac_ctx* ctx, const float* params, const uint8_t* states, 
     const char* v = getenv("PAAC_MT_AHEAD_SMALL");
     return v && *v && atoi(v) != 0;
   }();
+  ForwardCall call = defer;
   if (ahead_on) {
-    ctx->ahead_state = mt_state;
-    ctx->ahead_D = batch * (ctx->cfg.num_actions - 1);
+    call.ahead_state = mt_state;
+    call.ahead_D = batch * (ctx->cfg.num_actions - 1);
   }
-  int rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
-  ctx->ahead_state = nullptr;
-  if (rc) return rc;
-  rc = launch_sample_env_step_heads(hp, probs_out, ctx->cfg.num_actions, mt_state, actions, st, ahead_on ? ctx->mt_ahead : nullptr,
-                                    (hipStream_t)stream);
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  if (const int rc = launch_forward(ctx, params, states, batch, call, s)) return rc;
+  return launched(launch_sample_env_step_heads(partials_of(ctx, params, call, values_out), probs_out, ctx->cfg.num_actions,
+                                               mt_state, actions, st, ahead_on ? ctx->mt_ahead : nullptr, s));
 }
 
 int paac_act_step_pipe(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, uint32_t* mt_state,
@@ -551,17 +540,14 @@ int paac_act_step_pipe(paac_ctx* ctx, const float* params, const uint8_t* states
   ActRider rider{};
   rider.owed = *ctx->act_owed;
   rider.shift = st;
-  HeadsPartials hp{nullptr, 0, nullptr, nullptr, values_out};
-  ctx->fc_rider = &rider;
-  const int rc = launch_forward_trunk(ctx, params, states, batch, &hp, (hipStream_t)stream);
-  const bool launched = ctx->fc_rider == nullptr;      // (the fc launch takes the riders: one shot)
-  ctx->fc_rider = nullptr;
-  if (launched)      // the earlier debt rode that launch; this step's takes its place
+  ForwardCall call{.ws = 0, .heads = kHeadsDefer, .rider = &rider};
+  const int rc = launch_forward(ctx, params, states, batch, call, (hipStream_t)stream);
+  if (call.rode) {   // the earlier debt rode that launch; this step's takes its place
+    const HeadsPartials hp = partials_of(ctx, params, call, values_out);
     *ctx->act_owed = ActSample{hp.partial, hp.ntiles, hp.ba, hp.bc, probs_out, values_out, A, mt_state, actions, env_seed,
                                env_offset, batch, terminal_threshold, step_base_dev, step_offset, st.rec};
-  if (rc) return rc;
-  PAAC_CHECK_HIP(hipGetLastError());
-  return 0;
+  }
+  return launched(rc);
 }
 
 int paac_act_step_flush(paac_ctx* ctx, paac_stream_t stream) {
@@ -606,7 +592,8 @@ static int loss_backward_entry(const char* fn, paac_ctx* ctx, const float* param
   }
   int rc = 0;
   if (!forward_done && phase != 2) {
-    rc = launch_forward(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    ForwardCall fwd{.ws = 1};
+    rc = launch_forward(ctx, params, states, batch, fwd, (hipStream_t)stream);
     if (rc) return rc;
   }
   ctx->last_ws = 1;

@@ -147,19 +147,16 @@ struct paac_ctx {
   // paac_keep_next_forward: the next acting forward (ws[0] routes of the conv tower + fc_heads_kernel) also leaves its rows'
   // activations -- conv1 / conv2 / conv3 outputs and the fc activations -- at rows [keep_row, keep_row + batch) of the
   // TRAINING activation set, so that an update over rows the acting steps have already computed needs no training forward
-  // (weights are frozen inside a cycle).  -1 = off (one shot: the forward that honours it resets it).
+  // (weights are frozen inside a cycle).  -1 = off.  One shot, and the only thing a forward takes from the context instead
+  // of from its ForwardCall (below): launch_forward alone reads it, into the call's keep_row, and resets it.
   int keep_row;
-  int keep_h_only;                 // with keep_row: only the fc activations are kept (bootstrap rows: the update reads nothing else of them)
   int heads_pending_h;             // 1: the pending "slab" holds finished fc activations (bias + ReLU applied), one split
   float* zeros;                    // max(H) zero floats (the bias of heads that read finished activations)
   // csrc/mt_ahead.h: the record a spare workgroup of the acting forward's fc launch leaves for the sampling step behind it
   void* mt_ahead;                  // MtAhead, owned by the ctx
-  const uint32_t* ahead_state;     // one shot, set by paac_act_step_mt: the MT19937 state to work ahead from (nullptr: off)
-  int ahead_D;                     // doubles the step can consume at most: N * (A - 1)
   // paac_act_step_pipe: the sample of the last pipelined step, owed until the next acting fc launch (or the flush) pays it --
-  // host-side state like keep_row / ahead_state: under graph capture it is resolved at capture time
+  // host-side state that lives from one entry to the next: under graph capture it is resolved at capture time
   paac::ActSample* act_owed;       // owned by the ctx; ->partial == nullptr: nothing pending
-  const paac::ActRider* fc_rider;  // one shot: the next acting fc launch carries these riders (csrc/fc_heads.h: RIDER)
   int act_region;                  // the half of ws[0].fc_slab the next ridden fc launch writes its head partials to (they
                                    // alternate: the rider beside it is still reading the other half)
   float* dl_buf;                   // [max_batch][kDlStride] per-row head gradients + loss terms (heads.h)
@@ -170,8 +167,6 @@ struct paac_ctx {
   void* tower_pack;      // kTowerPackVecs x 16 bytes, nullptr when the tower is off
   void* fc_pack;         // fc weights in fc_heads_kernel's fragment order (flat * H floats)
   int tower_on;          // PAAC_TOWER (default 1)
-  int heads_ntiles;      // column groups of the last fc + head-partials launch (fc_heads.h: 16- or 8-wide tiles)
-  float* heads_partial;  // ... and where it left the partials
   int no_quarter_tiles;  // PAAC_FC_QUARTER=0: always whole 16 x 16 tiles (A/B measurements)
   int tower2_on;         // the two-conv tower of the stock NIPS geometry (csrc/tower2.h), same knob
   int managed_weights;   // paac_set_managed_weights: 1 = the caller keeps tower_pack current (paac_clip_rmsprop / paac_pack_weights
@@ -240,7 +235,6 @@ inline void launch_k(K kernel, dim3 grid, dim3 block, hipStream_t s, int part, A
 }
 
 // launchers implemented in the kernel translation units
-int launch_forward_trunk_train(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, hipStream_t s);
 int launch_deferred_heads(paac_ctx* ctx, const float* params, hipStream_t s);
 // --adv_norm: the heads of the N bootstrap rows [batch, batch + N) of a pending trunk-only training forward alone (the
 // rollout rows stay pending for the backward's first launch); the returns + normalisation launch (csrc/misc.hip)
@@ -248,9 +242,8 @@ int launch_bootstrap_heads(paac_ctx* ctx, const float* params, int batch, int N,
 int launch_returns_norm(const paac_returns* ret, const float* v_boot, float* adv_n, double* stats, hipStream_t s);
 // --ppo_minibatches' record pass: p_old / values out of the finished training-side heads (csrc/misc.hip)
 int launch_record_policy(paac_ctx* ctx, const int32_t* actions, int batch, int vrows, float* p_old, float* v_out, hipStream_t s);
-int launch_forward(paac_ctx* ctx, int ws, const float* params, const uint8_t* states, int batch, float* logits,
-                   float* probs, float* values, hipStream_t s);
 struct SynthStep;      // one environment step's arguments (synth_dev.h); step == nullptr / an inactive one: no environment step
+// the acting forward with the counter-based sampler (and the step) inside its heads launch: fills a ForwardCall (below)
 int launch_forward_sample(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
                           float* values, uint64_t seed, const uint64_t* step_base, uint64_t step_off,
                           uint32_t env_offset, int32_t* actions, const SynthStep* step, hipStream_t s);
@@ -266,9 +259,8 @@ struct HeadsPartials {
 // floats of one of the two head-partial regions ridden fc launches alternate between: half of ws[0].fc_slab
 inline size_t act_region_floats(const paac_ctx* c) { return (size_t)c->fc_splits_max * c->max_batch * c->spec.fc / 2; }
 // the acting fc launch with riders and the flush launch of an owed sample (csrc/misc.hip, where the sampler lives)
-int launch_fc_heads_rider(bool nature, bool quarter, bool packed, unsigned fc_wgs, const float* act, const void* wfp,
-                          const float* bf, const float* wa, const float* wc, int A, int batch, float* partial, float* h_out,
-                          const ActRider& r, hipStream_t s);
+struct FcHeadsArgs;    // fc_heads.h
+int launch_fc_heads_rider(bool nature, const FcHeadsArgs& a, const ActRider& r, hipStream_t s);
 int launch_act_sample_flush(const ActSample& owed, hipStream_t s);
 size_t mt_ahead_bytes();
 bool sampler_folds_heads(int N, int A, const void* walk_scratch);
@@ -283,7 +275,7 @@ int launch_sample_mt_synth_step(const float* probs, int A, uint32_t* mt_state, i
 // sampler only, from finished probabilities (no environment step): N <= 64 environments, N * (A - 1) <= 1024 draws
 int launch_sample_mt_probs(const float* probs, int A, uint32_t* mt_state, int32_t* actions, int N, hipStream_t stream);
 // false: the geometry of ctx's arch has no fc + head partials kernel (fc_heads.h: fc_heads_waves == 0), so no acting
-// forward leaves head partials for a later launch (launch_forward_trunk)
+// forward leaves head partials for a later launch (kHeadsDefer)
 bool forward_has_fc_heads(const paac_ctx* ctx);
 // the conv weight gradients fit the head blocks of paac_clip_rmsprop's norm pass, which can then finish their slab
 // reduction (paac_loss_backward phase 3); false for user architectures with large conv layers
@@ -358,8 +350,34 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
 }
 
 bool norm_head_fits(const paac_ctx* ctx);
-int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row, hipStream_t s);
-int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, HeadsPartials* hp, hipStream_t s);
+// What one call of the forward varies in, and what the forward reports back -- everything but paac_keep_next_forward's pending
+// row arrives here, nothing through the context.  The fields a call does not name are null / zero / off.
+enum HeadsMode {
+  kHeadsFinish = 0,        // logits, probabilities and values come out of this call
+  kHeadsDefer,             // the caller's next launch finishes the heads from the fc kernel's per-tile partials (fc_heads.h):
+                           // acting batches of the fc + head partials routes only
+  kHeadsTrunkOnly          // training set: up to the fc layer's split-K slabs (batches above the small-batch tail only; smaller
+                           // ones run the whole forward); the backward's first launch or launch_deferred_heads finishes the heads
+};
+struct PhiloxArgs;         // heads.h
+struct ForwardCall {
+  int ws;                          // activation set: 0 acting, 1 training
+  float *logits, *probs, *values;  // outputs beside the set's own copies; nullable
+  const PhiloxArgs* philox;        // the counter-based sampler inside the heads launch; nullable
+  const SynthStep* step;           // ... and an environment step inside it too; nullable
+  HeadsMode heads;
+  int keep_row = -1;               // the rows are also kept at [keep_row, keep_row + batch) of the training set; -1: the pending
+                                   // row of paac_keep_next_forward, if any (set 0)
+  bool keep_h_only;                // with keep_row: only the fc activations are kept (bootstrap rows: the update reads nothing else)
+  const uint32_t* ahead_state;     // MT19937 state a spare workgroup of the fc launch works ahead from (mt_ahead.h); nullptr: off
+  int ahead_D;                     // doubles the sampling step can consume at most: N * (A - 1)
+  const ActRider* rider;           // riders of the fc launch (fc_heads.h: RIDER); the caller's stack object
+  // results
+  float* partial;                  // where the fc + head partials launch left the partials: ws[0].fc_slab, or the half of it a
+  int ntiles;                      // ridden launch took; in how many column groups (16- or 8-wide tiles)
+  bool rode;                       // the fc launch that carries the riders was issued
+};
+int launch_forward(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, ForwardCall& call, hipStream_t s);
 int launch_sample_env_step_heads(const HeadsPartials& hp, float* probs_out, int A, uint32_t* mt_state, int32_t* actions,
                                  const SynthStep& st, const void* mt_ahead, hipStream_t s);
 // What the heads of one backward compute (heads.h has the arithmetic of each loss): the arrays a loss reads or writes, the

@@ -62,8 +62,11 @@ __global__ __launch_bounds__(256) void pack_fc_kernel(const float* __restrict__ 
 //                         otherwise bid / nfc become the workgroup's index among / the count of the fc workgroups
 //   shift_load / _store   the frame shift of this step, dealt over the fc workgroups' first four waves: the 16-byte load of the
 //                         old stack is issued before the K loop and the store after it
+//   front_wgs()           host side: how many such workgroups the launch gets in front of the fc ones
 // Every workgroup of the launch reserves the kernel's whole LDS and register allocation: the rider's workgroup shares `red`.
-struct NoRider {};
+struct NoRider {
+  unsigned front_wgs() const { return 0u; }
+};
 constexpr int kRiderLdsVecs = kFcHeadsMaxRows * 33 / 4;      // f32x4s of LDS a rider's own workgroup wants of `red`
 
 // NW waves split K evenly (NW divides K / 16: 7 x 28 groups for Nature's 3136, 9 x 18 for NIPS' 2592), so the K loop of a
@@ -291,6 +294,48 @@ __global__ __launch_bounds__(64 * NW) void fc_heads_q_kernel(const float* __rest
 constexpr bool fc_heads_quarter_ok(const int flat) {
   const int w = fc_heads_waves(flat);
   return w > 0 && (flat / 16 / w) % 2 == 0 && (flat / 16 / w) / 2 > 6;
+}
+
+// One fc + head partials launch, as the host asks for it; the one place either kernel is launched from.
+struct FcHeadsArgs {
+  const float* act;        // packed: the conv tower's fragment-order output, else plain rows [batch, K]
+  const f32x4* wfp;        // pack_fc_kernel's
+  const float *bf, *wa, *wc;
+  int A, batch;
+  float* partial;          // [tiles][batch][A + 1]
+  float* h_out;            // the finished fc activations as plain rows too; nullable
+  bool quarter, packed;    // quarter tiles (fc_heads_q_kernel) / whole tiles; A_PACKED
+  MtAheadArgs ahead;       // whole tiles without riders: out != nullptr adds the spare MT19937 workgroup (mt_ahead.h) at the end
+};
+// NT: the net (FLAT, H).  The grid: the rider's own workgroups in front, the tiles' (H / 8 column groups x 8-row groups, or
+// H / 16 x 16-row groups), the spare workgroup.  (The caller holds the fc family's ProfScope.)
+template <class NT, class RIDER>
+int launch_fc_heads(const FcHeadsArgs& a, const RIDER& rider, hipStream_t s) {
+  constexpr int NW = fc_heads_waves(NT::FLAT);
+  if constexpr (NW > 0) {
+    const dim3 block(64 * NW);
+    if (a.quarter) {
+      if constexpr (fc_heads_quarter_ok(NT::FLAT)) {
+        const dim3 grid(rider.front_wgs() + (NT::H / 8) * ((a.batch + 7) / 8));
+        if (a.packed) launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, true, RIDER>, grid, block, s, PROF_WHOLE, a.act, a.wfp, a.bf,
+                               a.wa, a.wc, a.A, a.batch, a.partial, a.h_out, rider);
+        else launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, false, RIDER>, grid, block, s, PROF_WHOLE, a.act, a.wfp, a.bf, a.wa,
+                      a.wc, a.A, a.batch, a.partial, a.h_out, rider);
+        return 0;
+      }
+      set_error("fc + head partials: no quarter-tile kernel for this geometry");
+      return -1;
+    }
+    const bool spare = __is_same(RIDER, NoRider) && a.ahead.out != nullptr;      // (the kernels' own condition)
+    const dim3 grid(rider.front_wgs() + (NT::H / 16) * ((a.batch + 15) / 16) + (spare ? 1 : 0));
+    if (a.packed) launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, true, RIDER>, grid, block, s, PROF_WHOLE, a.act, a.wfp, a.bf, a.wa,
+                           a.wc, a.A, a.batch, a.partial, a.h_out, a.ahead, rider);
+    else launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, false, RIDER>, grid, block, s, PROF_WHOLE, a.act, a.wfp, a.bf, a.wa, a.wc,
+                  a.A, a.batch, a.partial, a.h_out, a.ahead, rider);
+    return 0;
+  }
+  set_error("fc + head partials: this geometry has no such kernel");
+  return -1;
 }
 
 // Second half of the heads finish: logits of all B rows in lg_s -> softmax, stores.  Ends with a barrier.

@@ -1437,6 +1437,7 @@ __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __re
 // surplus waves return before the first barrier, an fc workgroup's take no part in the shift.
 struct ActRiderDev {
   ActRider r;
+  unsigned front_wgs() const { return r.owed.partial ? 1u : 0u; }      // the owed sample's workgroup
   __device__ __forceinline__ bool front(int& bid, int& nfc, float* lds) const {
     const int ns = r.owed.partial ? 1 : 0;
     if (bid < ns) {
@@ -1540,43 +1541,11 @@ int launch_act_sample_flush(const ActSample& owed, hipStream_t s) {
   return 0;
 }
 
-// The acting fc launch with its riders (the caller holds the fc family's ProfScope): fc_wgs fc workgroups behind the owed
-// sample's one, if any.  quarter / packed: which fc kernel, as csrc/net_fwd.hip chose it.
-template <class NT>
-static int launch_fc_rider_of(bool quarter, bool packed, unsigned fc_wgs, const float* act, const void* wfp, const float* bf,
-                              const float* wa, const float* wc, int A, int batch, float* partial, float* h_out,
-                              const ActRider& r, hipStream_t s) {
-  constexpr int NW = fc_heads_waves(NT::FLAT);
-  if constexpr (NW > 0) {
-    const ActRiderDev rd{r};
-    const dim3 grid(fc_wgs + (r.owed.partial ? 1u : 0u)), block(64 * NW);
-    const f32x4* w = reinterpret_cast<const f32x4*>(wfp);
-    if constexpr (fc_heads_quarter_ok(NT::FLAT)) if (quarter) {
-      if (packed) launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, true, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc,
-                           A, batch, partial, h_out, rd);
-      else launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, false, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc, A,
-                    batch, partial, h_out, rd);
-      return 0;
-    }
-    if (quarter) {
-      set_error("fc rider: no quarter-tile kernel for this geometry");
-      return -1;
-    }
-    const MtAheadArgs none{nullptr, nullptr, 0};
-    if (packed) launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, true, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc, A,
-                         batch, partial, h_out, none, rd);
-    else launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, false, ActRiderDev>, grid, block, s, PROF_WHOLE, act, w, bf, wa, wc, A, batch,
-                  partial, h_out, none, rd);
-    return 0;
-  }
-  set_error("fc rider: this geometry has no fc + head partials kernel");
-  return -1;
-}
-int launch_fc_heads_rider(bool nature, bool quarter, bool packed, unsigned fc_wgs, const float* act, const void* wfp,
-                          const float* bf, const float* wa, const float* wc, int A, int batch, float* partial, float* h_out,
-                          const ActRider& r, hipStream_t s) {
-  if (nature) return launch_fc_rider_of<NatureNet>(quarter, packed, fc_wgs, act, wfp, bf, wa, wc, A, batch, partial, h_out, r, s);
-  return launch_fc_rider_of<OtherNet>(quarter, packed, fc_wgs, act, wfp, bf, wa, wc, A, batch, partial, h_out, r, s);
+// The acting fc launch with its riders, as csrc/net_fwd.hip asks for it (fc_heads.h: launch_fc_heads; the ridden instantiations
+// are compiled here, beside the sampler they carry).
+int launch_fc_heads_rider(bool nature, const FcHeadsArgs& a, const ActRider& r, hipStream_t s) {
+  if (nature) return launch_fc_heads<NatureNet>(a, ActRiderDev{r}, s);
+  return launch_fc_heads<OtherNet>(a, ActRiderDev{r}, s);
 }
 
 // (arguments validated by paac_returns_norm_tick, csrc/api.hip)

@@ -265,19 +265,18 @@ static void launch_tower2(paac_ctx* ctx, Workspace& W, const float* params, cons
   }
 }
 
+// One forward as its ForwardCall (common.h) describes it; what varies per call is read from the block alone.
 template <class NT>
-static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8_t* states, int batch, float* logits,
-                        float* probs, float* values, const PhiloxArgs& ph, const SynthStep& st, hipStream_t s,
-                        bool defer_heads = false, bool trunk_only = false) {
+static int forward_impl(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, ForwardCall& call, hipStream_t s) {
   const paac_layout& L = ctx->layout;
+  const int wsi = call.ws;
   Workspace& W = ctx->ws[wsi];
-  // the head partials a pending sample will be finished from live in the acting set's fc slab buffer, which every acting
-  // forward writes: only a forward whose fc launch carries that sample (fc_rider) may run
-  if (wsi == 0 && ctx->act_owed->partial && !ctx->fc_rider) {
-    set_error("forward: the last paac_act_step_pipe's sample is still pending: pay it with paac_bootstrap_forward_trunk, another "
-              "paac_act_step_pipe or paac_act_step_flush before another acting forward (paac_act_step_mt, paac_forward*)");
-    return -1;
-  }
+  float *const logits = call.logits, *const probs = call.probs, *const values = call.values;
+  PhiloxArgs ph;
+  memset(&ph, 0, sizeof(ph));
+  if (call.philox) ph = *call.philox;
+  const SynthStep st = call.step ? *call.step : SynthStep{};
+  const bool defer_heads = call.heads == kHeadsDefer, trunk_only = call.heads == kHeadsTrunkOnly;
   ctx->last_ws = wsi;
   const int cls = batch_class(batch);
   const int A = ctx->cfg.num_actions;
@@ -303,15 +302,9 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
   if constexpr (NT::NCONV == 3) tower = ctx->tower_on != 0;
   bool tower2 = false;                       // the two-conv network's tower (tower2.h)
   if constexpr (NT::NCONV == 2 && kTower2) tower2 = ctx->tower2_on != 0;
-  // paac_keep_next_forward (one shot): this acting forward's rows are also kept in the training activation set
-  int keep_row = -1;
-  bool keep_h_only = false;
-  if (wsi == 0) {
-    keep_row = ctx->keep_row;
-    keep_h_only = ctx->keep_h_only != 0;
-    ctx->keep_row = -1;
-    ctx->keep_h_only = 0;
-  }
+  // this forward's rows are also kept in the training activation set (paac_keep_next_forward, paac_bootstrap_forward_trunk)
+  const int keep_row = call.keep_row;
+  const bool keep_h_only = call.keep_h_only;
   const bool keep_acts = wsi == 1 || !ctx->managed_weights;          // fp32 conv activations / h kept for backward and read-back
   constexpr int NW = fc_heads_waves(NT::FLAT);      // 0: this fc geometry has no fc + head partials kernel
   const bool small_tail = NW > 0 && batch <= kFcHeadsMaxRows && !ph.enabled && !st.active();   // fc + head partials kernel (fc_heads.h)
@@ -321,9 +314,10 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
   // few workgroups (heads_finish_rows_kernel) instead of split-K slabs + a per-row heads launch
   const bool mid_tail = !small_tail && (tower || tower2) && !keep_acts && wsi == 0 && batch <= kFcHeadsMidRows && !ph.enabled &&
                         !st.active() && !trunk_only;
-  // riders (one shot: paac_act_step_pipe, paac_bootstrap_forward_trunk) go with the fc + head partials launch of the small
-  // acting route alone: refused here, before anything is launched
-  if (wsi == 0 && ctx->fc_rider && (!small_tail || ctx->ahead_state)) {
+  // riders (paac_act_step_pipe, paac_bootstrap_forward_trunk) go with the fc + head partials launch of the small acting route
+  // alone: refused here, before anything is launched
+  const ActRider* rider = wsi == 0 ? call.rider : nullptr;
+  if (rider && (!small_tail || call.ahead_state)) {
     set_error("forward: the fc launch's riders need the small acting route without the spare MT19937 workgroup");
     return -1;
   }
@@ -385,54 +379,31 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
   if constexpr (NW > 0) if (small_tail || mid_tail) {
     if (wsi == 1) ctx->heads_pending_rows = 0;
     // quarter tiles (fc_heads.h) while they fit one workgroup per CU: 32 rows of the stock fc width = 256 workgroups
+    // (the spare MT19937 workgroup is the whole-tile kernel's)
     const bool quarter = fc_heads_quarter_ok(NT::FLAT) && ((batch + 7) / 8) * (NT::H / 8) <= 256 && !ctx->no_quarter_tiles &&
-                         ctx->ahead_state == nullptr;
+                         call.ahead_state == nullptr;
     const int NTILES = quarter ? NT::H / 8 : NT::H / 16;
-    ctx->heads_ntiles = NTILES;
     float* partial = W.fc_slab;      // [NTILES][batch][A + 1]: fits the split-K slab buffer
-    // one shot (paac_act_step_pipe, paac_bootstrap_forward_trunk): this launch carries riders, and its partials go to the
-    // half of the buffer the rider workgroup is NOT reading
-    // (taken -- fc_rider cleared, the regions swapped -- only once the launch has been issued, below: that is what tells the
-    // caller its riders rode)
-    const ActRider* rider = wsi == 0 ? ctx->fc_rider : nullptr;
+    // a launch that carries riders leaves its partials in the half of the buffer the rider workgroup is NOT reading
     if (rider) partial += (size_t)ctx->act_region * act_region_floats(ctx);
-    ctx->heads_partial = partial;
-    const bool keep_h = keep_acts;
+    call.partial = partial;
+    call.ntiles = NTILES;
     // kept rows: the finished fc activations (bias + ReLU applied) go where the training forward's fc slabs would be
     float* h_keep = keepW ? keepW->fc_slab + (size_t)keep_row * NT::H : nullptr;
     {
       ProfScope ps(ctx, F_FC_FWD, batch, s);
       prof_mix(1);     // fp32 MFMA
-      // one-shot (paac_act_step_mt): a spare workgroup makes the next sampling step's MT19937 doubles meanwhile (mt_ahead.h)
-      MtAheadArgs ah{ctx->ahead_state, ctx->ahead_state ? reinterpret_cast<MtAhead*>(ctx->mt_ahead) : nullptr, ctx->ahead_D};
-      ctx->ahead_state = nullptr;
-      const unsigned grid = NTILES * ((batch + 15) / 16) + (ah.out ? 1 : 0);
-      if (rider) {
-        const unsigned fc_wgs = quarter ? NTILES * ((batch + 7) / 8) : NTILES * ((batch + 15) / 16);
-        if (launch_fc_heads_rider(ctx->cfg.arch == PAAC_ARCH_NATURE, quarter, packed3, fc_wgs, last,
-                                  ctx->fc_pack, bf, wa, wc, A, batch, partial, packed3 ? h_keep : (keep_h ? W.h : (float*)nullptr),
-                                  *rider, s))
-          return -1;
-        ctx->fc_rider = nullptr;
+      // paac_act_step_mt: a spare workgroup makes the next sampling step's MT19937 doubles meanwhile (mt_ahead.h)
+      const MtAheadArgs ah{call.ahead_state, call.ahead_state ? reinterpret_cast<MtAhead*>(ctx->mt_ahead) : nullptr, call.ahead_D};
+      const FcHeadsArgs fa{last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial,
+                           packed3 ? h_keep : (keep_acts ? W.h : (float*)nullptr), quarter, packed3, ah};
+      if (rider) {     // (the ridden instantiations are csrc/misc.hip's, where the sampler lives)
+        if (launch_fc_heads_rider(ctx->cfg.arch == PAAC_ARCH_NATURE, fa, *rider, s)) return -1;
+        call.rode = true;          // the regions swap only once the launch has been issued
         ctx->act_region ^= 1;
-      } else
-      if constexpr (fc_heads_quarter_ok(NT::FLAT)) if (quarter) {
-        if (packed3)
-          launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, true>, dim3(NTILES * ((batch + 7) / 8)), dim3(64 * NW), s, PROF_WHOLE,
-                   last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial, h_keep, NoRider{});
-        else
-          launch_k(fc_heads_q_kernel<NT::FLAT, NT::H, NW, false>, dim3(NTILES * ((batch + 7) / 8)), dim3(64 * NW), s, PROF_WHOLE,
-                   last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial,
-                   keep_h ? W.h : (float*)nullptr, NoRider{});
+      } else if (launch_fc_heads<NT>(fa, NoRider{}, s)) {
+        return -1;
       }
-      if (quarter || rider) {
-      } else if (packed3)
-        launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, true>, dim3(grid), dim3(64 * NW), s, PROF_WHOLE,
-                 last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial, h_keep, ah, NoRider{});
-      else
-        launch_k(fc_heads_kernel<NT::FLAT, NT::H, NW, false>, dim3(grid), dim3(64 * NW), s, PROF_WHOLE,
-                 last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial,
-                 keep_h ? W.h : (float*)nullptr, ah, NoRider{});
     }
     if (defer_heads) return 0;       // the caller's launch finishes the heads (or, for bootstrap rows, the backward's)
     if (mid_tail) {
@@ -477,25 +448,25 @@ static int forward_impl(paac_ctx* ctx, int wsi, const float* params, const uint8
   return 0;
 }
 
-int launch_forward(paac_ctx* ctx, int ws, const float* params, const uint8_t* states, int batch, float* logits,
-                   float* probs, float* values, hipStream_t s) {
-  PhiloxArgs ph;
-  memset(&ph, 0, sizeof(ph));
-  const SynthStep st{};
-  if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    return forward_impl<NatureNet>(ctx, ws, params, states, batch, logits, probs, values, ph, st, s);
-  return forward_impl<OtherNet>(ctx, ws, params, states, batch, logits, probs, values, ph, st, s);
-}
-
-// Training forward up to the fc layer's split-K slabs (batches above the small-batch tail only; smaller ones run the
-// whole forward): the heads are finished by the backward's first launch, or by launch_deferred_heads.
-int launch_forward_trunk_train(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, hipStream_t s) {
-  PhiloxArgs ph;
-  memset(&ph, 0, sizeof(ph));
-  const SynthStep st{};
-  if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    return forward_impl<NatureNet>(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, false, true);
-  return forward_impl<OtherNet>(ctx, 1, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, false, true);
+int launch_forward(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, ForwardCall& call, hipStream_t s) {
+  call.partial = nullptr;
+  call.ntiles = 0;
+  call.rode = false;
+  if (call.ws == 0) {
+    // the head partials a pending sample will be finished from live in the acting set's fc slab buffer, which every acting
+    // forward writes: only a forward whose fc launch carries that sample (call.rider) may run
+    if (ctx->act_owed->partial && !call.rider) {
+      set_error("forward: the last paac_act_step_pipe's sample is still pending: pay it with paac_bootstrap_forward_trunk, another "
+                "paac_act_step_pipe or paac_act_step_flush before another acting forward (paac_act_step_mt, paac_forward*)");
+      return -1;
+    }
+    // paac_keep_next_forward's pending row, read here and nowhere else: any acting forward that gets this far consumes it,
+    // one that brings rows of its own (paac_bootstrap_forward_trunk) too
+    if (call.keep_row < 0) call.keep_row = ctx->keep_row;
+    ctx->keep_row = -1;
+  }
+  if (ctx->cfg.arch == PAAC_ARCH_NATURE) return forward_impl<NatureNet>(ctx, params, states, batch, call, s);
+  return forward_impl<OtherNet>(ctx, params, states, batch, call, s);
 }
 
 // The heads launch a trunk-only training forward left out (a backward that cannot fuse it runs it first).
@@ -562,60 +533,12 @@ bool forward_has_fc_heads(const paac_ctx* ctx) {
   return fc_heads_waves(ctx->cfg.arch == PAAC_ARCH_NATURE ? NatureNet::FLAT : OtherNet::FLAT) > 0;
 }
 
-// Acting trunk up to the per-tile head partials (fc_heads.h); the caller's sampler launch finishes the heads.
-int launch_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, HeadsPartials* hp, hipStream_t s) {
-  PhiloxArgs ph;
-  memset(&ph, 0, sizeof(ph));
-  const SynthStep st{};
-  const paac_layout& L = ctx->layout;
-  const int nt = L.num_tensors;
-  hp->ba = params + L.offset[nt - 3];
-  hp->bc = params + L.offset[nt - 1];
-  const int rc = (ctx->cfg.arch == PAAC_ARCH_NATURE)
-                     ? forward_impl<NatureNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true)
-                     : forward_impl<OtherNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true);
-  hp->partial = ctx->heads_partial;     // (this launch's: ws[0].fc_slab, or the half of it a ridden launch took)
-  hp->ntiles = ctx->heads_ntiles;       // (whole or quarter tiles, fc_heads.h)
-  return rc;
-}
-
-// Acting-shaped forward of the N bootstrap observations whose rows complete a training set the acting steps have kept
-// (paac_keep_next_forward): conv tower + fc, rows kept at [train_row, train_row + batch); no heads -- the backward's first
-// launch takes the bootstrap values from the kept fc activations like it does after a trunk-only training forward.
-int launch_bootstrap_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row, hipStream_t s) {
-  PhiloxArgs ph;
-  memset(&ph, 0, sizeof(ph));
-  const SynthStep st{};
-  ctx->keep_row = train_row;
-  ctx->keep_h_only = 1;          // the backward covers the rollout rows only: of the bootstrap rows it reads the fc activations
-  int rc;
-  if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    rc = forward_impl<NatureNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true);
-  else
-    rc = forward_impl<OtherNet>(ctx, 0, params, states, batch, nullptr, nullptr, nullptr, ph, st, s, true);
-  ctx->keep_row = -1;
-  ctx->keep_h_only = 0;
-  if (rc) return rc;
-  ctx->heads_pending_rows = train_row + batch;
-  ctx->heads_pending_splits = 1;
-  ctx->heads_pending_h = 1;
-  return 0;
-}
-
 int launch_forward_sample(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, float* probs,
                           float* values, uint64_t seed, const uint64_t* step_base, uint64_t step_off,
                           uint32_t env_offset, int32_t* actions, const SynthStep* step, hipStream_t s) {
-  const SynthStep st = step ? *step : SynthStep{};
-  PhiloxArgs ph;
-  ph.enabled = 1;
-  ph.seed = seed;
-  ph.step_base = step_base;
-  ph.step_off = step_off;
-  ph.env_offset = env_offset;
-  ph.actions = actions;
-  if (ctx->cfg.arch == PAAC_ARCH_NATURE)
-    return forward_impl<NatureNet>(ctx, 0, params, states, batch, nullptr, probs, values, ph, st, s);
-  return forward_impl<OtherNet>(ctx, 0, params, states, batch, nullptr, probs, values, ph, st, s);
+  const PhiloxArgs ph{1, seed, step_base, step_off, env_offset, actions};
+  ForwardCall call{.ws = 0, .probs = probs, .values = values, .philox = &ph, .step = step};
+  return launch_forward(ctx, params, states, batch, call, s);
 }
 
 #ifdef PAAC_DMM_STAMPS

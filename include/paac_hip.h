@@ -192,6 +192,18 @@ int paac_act_step_pipe(paac_ctx* ctx, const float* params, const uint8_t* states
                        paac_stream_t stream);
 int paac_act_step_flush(paac_ctx* ctx, paac_stream_t stream);
 int paac_act_step_pending(const paac_ctx* ctx);
+/* PAAC_ACT_TOWER_RIDER (read at paac_create; default 1): on the Nature network, at up to 32 environments, the conv tower launch
+ * of a pipelined step has four idle waves per workgroup, and carries on them -- 1: the heads finish of the owed sample (up to 7
+ * actions), which leaves the sampler's inputs in a record owned by the ctx, so that the workgroup riding the next fc launch
+ * only parks them; 2: also the frame shift of its own step, so that the first fc launch of a run carries nothing (measured level
+ * with 1, hence not the default); 0: neither
+ * (the route described above).  The same bits every way.  paac_act_finish_layout: that record's size, the byte offsets of its
+ * conditional probabilities / packed thresholds / probabilities / exact-zero words and the limits it is sized for (environments,
+ * actions, column groups of head partials) -- eight words.  paac_act_tower_rode: what the conv tower of the last
+ * paac_act_step_pipe / paac_bootstrap_forward_trunk whose fc launch was issued with riders did carry -- 1: a heads finish,
+ * 2: the frame shift (host-side state, for tests and probes). */
+int paac_act_finish_layout(int64_t* out, int n);
+int paac_act_tower_rode(const paac_ctx* ctx);
 
 /* Conv-weight packing.  The Nature conv layers run as one fused launch that reads the conv weights pre-split into bf16
  * planes (an internal copy owned by the ctx).  By default every paac_forward* / paac_train_forward / paac_loss_backward

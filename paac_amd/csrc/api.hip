@@ -240,6 +240,11 @@ int paac_create(const paac_cfg* cfg, paac_ctx** out) {
   c->act_owed = new (std::nothrow) ActSample{};
   PAAC_REQUIRE(c->act_owed, "paac_create: out of host memory");
   c->act_region = 0;
+  { const char* v = getenv("PAAC_ACT_TOWER_RIDER"); c->act_tower_rider = (v && *v) ? atoi(v) : 1; }
+  PAAC_REQUIRE(c->act_tower_rider >= 0 && c->act_tower_rider <= 2, "paac_create: PAAC_ACT_TOWER_RIDER=%d (0, 1 or 2)",
+               c->act_tower_rider);
+  PAAC_CHECK_HIP(hipMalloc(&c->act_fin_rec, sizeof(ActFinishRecord)));
+  PAAC_CHECK_HIP(hipMemset(c->act_fin_rec, 0, sizeof(ActFinishRecord)));
   {
     const char* v = getenv("PAAC_TOWER");
     c->tower_on = (cfg->arch == PAAC_ARCH_NATURE) && !(v && *v && atoi(v) == 0);
@@ -281,6 +286,7 @@ int paac_destroy(paac_ctx* c) {
   for (float* b : bufs)
     if (b) (void)hipFree(b);
   if (c->mt_ahead) (void)hipFree(c->mt_ahead);
+  if (c->act_fin_rec) (void)hipFree(c->act_fin_rec);
   if (c->dh_planes) (void)hipFree(c->dh_planes);
   if (c->tower_pack) (void)hipFree(c->tower_pack);
   if (c->fc_pack) (void)hipFree(c->fc_pack);
@@ -360,6 +366,29 @@ int paac_keep_next_forward(paac_ctx* ctx, int train_row) {
   return 0;
 }
 
+// What the conv tower launch of an acting forward is offered to carry (csrc/tower.h: RIDER; the forward settles what it does
+// carry): the heads finish of the owed sample, at the limits of heads_finish_fused, and -- step: the forward's own environment
+// step -- its frame shift, where the stacks written are not the ones the tower reads.
+static TowerRider tower_rider_of(const paac_ctx* ctx, const ActSample& owed, const SynthStep* step) {
+  TowerRider tr{};
+  if (ctx->act_tower_rider >= 1 && owed.partial && owed.N <= kActFinMaxN && owed.A <= kActFinMaxA && owed.ntiles <= kActFinMaxTiles)
+    tr.fin = ActFinish{owed.partial, owed.ntiles, owed.ba, owed.bc, owed.probs_out, owed.values_out, owed.A, owed.N,
+                       ctx->act_fin_rec};
+  if (ctx->act_tower_rider >= 2 && step && step->stack_out != step->stack_in && step->stack_out2 != step->stack_in) tr.shift = *step;
+  return tr;
+}
+
+int paac_act_tower_rode(const paac_ctx* ctx) { return ctx ? ctx->act_tower_rode : 0; }
+
+int paac_act_finish_layout(int64_t* out, int n) {
+  PAAC_REQUIRE(out && n >= 8, "paac_act_finish_layout: eight words");
+  const int64_t v[8] = {(int64_t)sizeof(ActFinishRecord), (int64_t)offsetof(ActFinishRecord, pj), (int64_t)offsetof(ActFinishRecord, thr),
+                        (int64_t)offsetof(ActFinishRecord, probs), (int64_t)offsetof(ActFinishRecord, any_zero), kActFinMaxN,
+                        kActFinMaxA, kActFinMaxTiles};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return 0;
+}
+
 int paac_bootstrap_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int train_row,
                                  paac_stream_t stream) {
   PAAC_REQUIRE(ctx && params && states, "paac_bootstrap_forward_trunk: null argument");
@@ -378,8 +407,9 @@ int paac_bootstrap_forward_trunk(paac_ctx* ctx, const float* params, const uint8
   // (paac_keep_next_forward): conv tower + fc, rows kept at [train_row, train_row + batch) -- of the bootstrap rows the update
   // reads the fc activations only, the backward covers the rollout rows; no heads -- the backward's first launch takes the
   // bootstrap values from the kept fc activations like it does after a trunk-only training forward.
+  const TowerRider trider = tower_rider_of(ctx, rider.owed, nullptr);      // (the heads finish of step T - 1 rides its tower)
   ForwardCall call{.ws = 0, .heads = kHeadsDefer, .keep_row = train_row, .keep_h_only = true,
-                   .rider = rider.owed.partial ? &rider : nullptr};
+                   .rider = rider.owed.partial ? &rider : nullptr, .tower_rider = &trider};
   const int rc = launch_forward(ctx, params, states, batch, call, (hipStream_t)stream);
   if (call.rode) ctx->act_owed->partial = nullptr;
   if (rc) return rc;
@@ -540,7 +570,8 @@ int paac_act_step_pipe(paac_ctx* ctx, const float* params, const uint8_t* states
   ActRider rider{};
   rider.owed = *ctx->act_owed;
   rider.shift = st;
-  ForwardCall call{.ws = 0, .heads = kHeadsDefer, .rider = &rider};
+  const TowerRider trider = tower_rider_of(ctx, rider.owed, &st);
+  ForwardCall call{.ws = 0, .heads = kHeadsDefer, .rider = &rider, .tower_rider = &trider};
   const int rc = launch_forward(ctx, params, states, batch, call, (hipStream_t)stream);
   if (call.rode) {   // the earlier debt rode that launch; this step's takes its place
     const HeadsPartials hp = partials_of(ctx, params, call, values_out);

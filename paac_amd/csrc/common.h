@@ -115,6 +115,8 @@ struct FinalizeArgs {
 namespace paac {
 struct ActSample;      // csrc/synth_dev.h: what an acting step's sampler still owes; the riders of an acting fc launch
 struct ActRider;
+struct TowerRider;     // ... and those of the conv tower launch in front of it
+struct ActFinishRecord;
 }  // namespace paac
 
 struct paac_ctx {
@@ -159,6 +161,12 @@ struct paac_ctx {
   paac::ActSample* act_owed;       // owned by the ctx; ->partial == nullptr: nothing pending
   int act_region;                  // the half of ws[0].fc_slab the next ridden fc launch writes its head partials to (they
                                    // alternate: the rider beside it is still reading the other half)
+  // PAAC_ACT_TOWER_RIDER (default 1; read at paac_create): what the conv tower launch of a pipelined acting step carries on its
+  // helper waves -- 1: the heads finish of the owed sample, 2: also the step's frame shift (measured level with 1:
+  // profiles/r10_bench.txt), 0: nothing
+  int act_tower_rider;
+  int act_tower_rode;              // what the tower of the last forward with riders did carry: 1 heads finish | 2 frame shift
+  paac::ActFinishRecord* act_fin_rec;      // what that heads finish leaves for the sampler riding the next fc launch; owned
   float* dl_buf;                   // [max_batch][kDlStride] per-row head gradients + loss terms (heads.h)
   float* ppo_rows;                 // [max_batch][2] per-row clip / KL terms of paac_loss_backward_ppo (heads.h: ppo_stats_kernel)
   float* vclip_rows;               // [max_batch] per-row vclipped of paac_loss_backward_ppo_vclip
@@ -372,6 +380,7 @@ struct ForwardCall {
   const uint32_t* ahead_state;     // MT19937 state a spare workgroup of the fc launch works ahead from (mt_ahead.h); nullptr: off
   int ahead_D;                     // doubles the sampling step can consume at most: N * (A - 1)
   const ActRider* rider;           // riders of the fc launch (fc_heads.h: RIDER); the caller's stack object
+  const TowerRider* tower_rider;   // with rider: what the conv tower launch in front may carry instead (tower.h: RIDER)
   // results
   float* partial;                  // where the fc + head partials launch left the partials: ws[0].fc_slab, or the half of it a
   int ntiles;                      // ridden launch took; in how many column groups (16- or 8-wide tiles)

@@ -393,6 +393,82 @@ __device__ __forceinline__ void heads_from_partials(const float* __restrict__ pa
   heads_softmax_store(B, A, lg_s, probs_lds, logits_out, probs_out, values_out, logits_out2, probs_out2, values_out2);
 }
 
+// Walk thresholds carry their sense in the sign bit: hit(U) == ((U > |t|) != signbit(t)) -- thresholds lie in [0, 1], so one
+// 8-byte LDS read per (environment, category) instead of a threshold and a flag (the walks are bound by the LDS instructions
+// they issue: 2 x J per hop instead of 3 x J).
+__device__ __forceinline__ double mt_pack_threshold(const double cond) {
+  const bool inv = !(cond <= 0.5);
+  const double thr = inv ? 1.0 - (1.0 - cond) : 1.0 - cond;
+  return inv ? __longlong_as_double(__double_as_longlong(thr) | (long long)0x8000000000000000ull) : thr;
+}
+
+// The small shards' heads finish (up to 32 environments x 7 actions, at most 64 column groups: the headline shape) without
+// leaving the registers, in two halves for a caller with something to do while the partials travel.  Thread tid of 256 (row =
+// tid >> 3, a = tid & 7) owns output a of environment row (a < A: a logit, a == A: the value).
+//   heads_partials_request   asks for the thread's partial of every column group, and its bias
+//   heads_finish_fused       sums them in tile order, gathers its row's logits from the seven neighbouring lanes, takes the
+//                            softmax exactly as heads_softmax_store does (same operations in the same order: same bits), gathers
+//                            the row's probabilities the same way and forms its conditional probability exactly as phase 1 of
+//                            the sampler does (csrc/misc.hip) -- no LDS round trip and no barrier, only shuffles inside 8-lane
+//                            groups.  Leaves the probabilities in probs_dst (and probs_out), the values in values_out, the
+//                            conditional probabilities in pj_buf and their packed thresholds in thr_s (nullable), as phase 1
+//                            would; returns whether this thread's conditional probability is exactly zero.
+// Both callers -- the sampler workgroup (csrc/misc.hip: FusedHeadsHook, destinations in LDS) and the helper waves of a conv tower
+// workgroup (csrc/tower.h: RIDER, destinations in the context's ActFinishRecord) -- run this one routine: the same bits.
+__device__ __forceinline__ void heads_partials_request(const float* __restrict__ partial, const int ntiles,
+                                                       const float* __restrict__ ba, const float* __restrict__ bc, const int N,
+                                                       const int A, const int tid, float (&pv)[64], float& bias) {
+  const int row = tid >> 3, a = tid & 7;
+  const int n = N * (A + 1);
+  const int idx = (row < N && a <= A) ? row * (A + 1) + a : 0;
+  bias = (a < A) ? ba[a] : bc[0];
+#pragma unroll
+  for (int t = 0; t < 64; ++t) pv[t] = partial[(size_t)(t < ntiles ? t : 0) * n + idx];
+}
+__device__ __forceinline__ bool heads_finish_fused(const float (&pv)[64], const float bias, const int ntiles, const int N,
+                                                   const int A, const int tid, float* probs_dst, float* probs_out,
+                                                   float* values_out, double* pj_buf, double* thr_s) {
+  const int lane = tid & 63;
+  const int row = tid >> 3, a = tid & 7, J = A - 1;
+  const bool rv = row < N;
+  float acc = bias;
+#pragma unroll
+  for (int t = 0; t < 64; ++t) acc += (t < ntiles) ? pv[t] : 0.f;
+  float lg[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) lg[j] = __shfl(acc, (lane & ~7) | j, 64);
+  float m = lg[0];
+#pragma unroll
+  for (int j = 1; j < 7; ++j)
+    if (j < A) m = fmaxf(m, lg[j]);
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < 7; ++j)
+    if (j < A) sum += expf(lg[j] - m);
+  const float pa = expf(acc - m) / sum;               // (meaningful in the lanes a < A)
+  if (rv && a < A) {
+    probs_dst[row * A + a] = pa;
+    probs_out[row * A + a] = pa;
+  }
+  if (rv && a == A) values_out[row] = acc;
+  float pr[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pr[j] = __shfl(pa, (lane & ~7) | j, 64);
+  bool zero = false;
+  if (rv && a < J) {
+    double remaining = 1.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+      if (i < a) remaining -= (double)(pr[i] - 5.9604644775390625e-08f);
+    const double p = (double)(pa - 5.9604644775390625e-08f);
+    const double cond = p / remaining;
+    pj_buf[row * J + a] = cond;
+    zero = cond == 0.0;
+    if (thr_s) thr_s[row * J + a] = mt_pack_threshold(cond);
+  }
+  return zero;
+}
+
 static __global__ __launch_bounds__(256) void heads_finish_kernel(const float* __restrict__ partial, int ntiles, int B, int A,
                                                            const float* __restrict__ ba, const float* __restrict__ bc,
                                                            float* __restrict__ logits_ws, float* __restrict__ probs_ws,

@@ -387,14 +387,8 @@ __device__ __forceinline__ void mt_fill_table(const double* pj_buf, const double
   }
 }
 
-// Walk thresholds carry their sense in the sign bit: hit(U) == ((U > |t|) != signbit(t)) -- thresholds lie in [0, 1], so one
-// 8-byte LDS read per (environment, category) instead of a threshold and a flag (the walks are bound by the LDS instructions
-// they issue: 2 x J per hop instead of 3 x J).
-__device__ __forceinline__ double mt_pack_threshold(const double cond) {
-  const bool inv = !(cond <= 0.5);
-  const double thr = inv ? 1.0 - (1.0 - cond) : 1.0 - cond;
-  return inv ? __longlong_as_double(__double_as_longlong(thr) | (long long)0x8000000000000000ull) : thr;
-}
+// (mt_pack_threshold -- walk thresholds carry their sense in the sign bit: hit(U) == ((U > |t|) != signbit(t)) -- is
+// csrc/fc_heads.h's, beside the heads finish that leaves them)
 __device__ __forceinline__ bool mt_hit(const double U, const double t) {
   return (U > fabs(t)) != (__double_as_longlong(t) < 0);
 }
@@ -675,11 +669,8 @@ struct RowsHeadsHook {
 template <class H> struct HookOwnRows { static constexpr bool value = false; };
 template <> struct HookOwnRows<RowsHeadsHook> { static constexpr bool value = true; };
 // The small shards' hook (up to 32 environments x 7 actions, the headline shape): heads finish AND phase 1 without leaving
-// the registers.  Thread (row = tid >> 3, a = tid & 7) owns output a of environment row (a < A: a logit, a == A: the value):
-// it sums its partials (requested by the caller before the sampler's own phases), gathers its row's logits from the seven
-// neighbouring lanes, takes the softmax exactly as heads_softmax_store does (same operations in the same order: same bits),
-// gathers the row's probabilities the same way and forms its conditional probability exactly as phase 1 does -- no LDS
-// round trip and no barrier between the partial sums and the thresholds (the separate hook + phase 1 take three).
+// the registers -- heads_finish_fused (csrc/fc_heads.h) on the partials the caller requested before the sampler's own phases: no
+// LDS round trip and no barrier between the partial sums and the thresholds (the separate hook + phase 1 take three).
 // Leaves probs in probs_lds / probs_out, values in values_out, pj_buf / thr_s / *any_zero as phase 1 would; NO barrier.
 struct FusedHeadsHook {
   const float (&pv)[64];
@@ -689,43 +680,26 @@ struct FusedHeadsHook {
   float* probs_out;
   float* values_out;
   __device__ __forceinline__ void operator()(double* pj_buf, double* thr_s, int* any_zero) const {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int row = tid >> 3, a = tid & 7, J = A - 1;
-    const bool rv = row < N;
-    float acc = bias;
-#pragma unroll
-    for (int t = 0; t < 64; ++t) acc += (t < ntiles) ? pv[t] : 0.f;
-    float lg[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lg[j] = __shfl(acc, (lane & ~7) | j, 64);
-    float m = lg[0];
-#pragma unroll
-    for (int j = 1; j < 7; ++j)
-      if (j < A) m = fmaxf(m, lg[j]);
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 7; ++j)
-      if (j < A) sum += expf(lg[j] - m);
-    const float pa = expf(acc - m) / sum;               // (meaningful in the lanes a < A)
-    if (rv && a < A) {
-      probs_lds[row * A + a] = pa;
-      probs_out[row * A + a] = pa;
+    if (heads_finish_fused(pv, bias, ntiles, N, A, (int)threadIdx.x, probs_lds, probs_out, values_out, pj_buf, thr_s)) *any_zero = 1;
+  }
+};
+// The same place in the body for a debt whose heads the conv tower launch in front of this one has finished (csrc/tower.h:
+// RIDER; synth_dev.h: ActFinishRecord): the record's words, requested by the caller together with the state words -- one round
+// trip --, are parked where the hook above leaves its results.  D = N (A - 1) <= 192 and NA = N A <= 224: one of each per thread.
+struct ParkedRecordHook {
+  double pj, thr;
+  float pr;
+  bool zero;
+  int D, NA;
+  float* probs_lds;
+  __device__ __forceinline__ void operator()(double* pj_buf, double* thr_s, int* any_zero) const {
+    const int tid = threadIdx.x;
+    if (tid < D) {
+      pj_buf[tid] = pj;
+      if (thr_s) thr_s[tid] = thr;
     }
-    if (rv && a == A) values_out[row] = acc;
-    float pr[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pr[j] = __shfl(pa, (lane & ~7) | j, 64);
-    if (rv && a < J) {
-      double remaining = 1.0;
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-        if (i < a) remaining -= (double)(pr[i] - 5.9604644775390625e-08f);
-      const double p = (double)(pa - 5.9604644775390625e-08f);
-      const double cond = p / remaining;
-      pj_buf[row * J + a] = cond;
-      if (cond == 0.0) *any_zero = 1;
-      if (thr_s) thr_s[row * J + a] = mt_pack_threshold(cond);
-    }
+    if (tid < NA) probs_lds[tid] = pr;
+    if (zero && tid == 0) *any_zero = 1;
   }
 };
 // The LDS arrays of sample_mt_body, one set per size class: a kernel that holds the body twice (two hooks: act_sample_body)
@@ -751,6 +725,7 @@ __device__ __forceinline__ MtLds<LDSC>& mt_lds() {
 }
 template <class H> struct HookFused { static constexpr bool value = false; };
 template <> struct HookFused<FusedHeadsHook> { static constexpr bool value = true; };
+template <> struct HookFused<ParkedRecordHook> { static constexpr bool value = true; };
 template <int LDSC, class HOOK = NoProbsHook, int SET = 0>
 __device__ __forceinline__ bool sample_mt_body(const float* __restrict__ probs, int N, int A,
                                                uint32_t* __restrict__ mt_state, double* __restrict__ pj_g,
@@ -775,7 +750,8 @@ __device__ __forceinline__ bool sample_mt_body(const float* __restrict__ probs, 
   const int tid = threadIdx.x;
   const int J = A - 1;
   const int D = N * J;
-  __shared__ float probs_s[LDSPATH ? 2 * mt_lds_d(LDSC) : 1];   // N*A = D*A/(A-1) <= 2*D floats
+  // N*A = D*A/(A-1) <= 2*D floats (a parked record's probabilities come in the caller's array: none of its own)
+  __shared__ float probs_s[LDSPATH && !__is_same(HOOK, ParkedRecordHook) ? 2 * mt_lds_d(LDSC) : 1];
   uint32_t& pos_s = lds.pos;
   int& any_zero = lds.any_zero;  // some conditional probability is exactly 0 (the table chase needs none); later
                                  // reused for the consumed-draw count
@@ -1351,16 +1327,22 @@ __global__ __launch_bounds__(256) void synth_step_a_mt_kernel(const float* __res
 // NEXT fc launch in the pipelined step (ActRiderDev) or the flush launch: one routine, the same bits.
 // id: the step's id; lg_s: kFcHeadsMaxRows * 33 floats of LDS.  ONE_SET: the two sampler bodies share one set of LDS arrays
 // (the riders, which must leave room for an fc workgroup on their CU); otherwise each has its own (mt_lds).
-template <bool ONE_SET>
+// FIN (a second front end, the ridden fc launch behind a conv tower that carried the heads finish: `finished` holds what the
+// hook would compute): the record's words are requested with the state words in one round trip and parked where the hook leaves
+// its results (ParkedRecordHook); everything behind that point -- walks, the exact-zero fallback, bookkeeping -- is the same
+// code.  Such a kernel holds neither the hook nor its 64 partials per thread.
+template <bool ONE_SET, bool FIN = false>
 __device__ __forceinline__ void act_sample_body(const float* __restrict__ partial, int ntiles, const float* __restrict__ ba,
                                                 const float* __restrict__ bc, float* __restrict__ probs_out,
                                                 float* __restrict__ values_out, int A, uint32_t* __restrict__ mt_state,
                                                 int32_t* __restrict__ actions, uint64_t seed, uint32_t env_offset, int N,
                                                 uint32_t thresh, uint64_t id, float* rewards_out, float* masks_out,
                                                 float* ep_reward, int32_t* ep_len, FinishedRing* fin,
-                                                const MtAhead* __restrict__ ahead, float* lg_s) {
+                                                const MtAhead* __restrict__ ahead, float* lg_s,
+                                                const ActFinishRecord* __restrict__ finished = nullptr) {
   __shared__ int16_t act_s[kFcHeadsMaxRows];
   __shared__ float probs_sh[kFcHeadsMaxRows * 32];
+  MISC_STAMP(14);
   // nothing below depends on these: request them before the head sums
   uint32_t stw[3];
 #pragma unroll
@@ -1373,16 +1355,21 @@ __device__ __forceinline__ void act_sample_body(const float* __restrict__ partia
   const uint32_t key0 = synth_key(seed, env_offset + (uint32_t)e0, id);
   const uint32_t hr5 = synth_reward_slot(key0);
   const bool term0 = synth_terminal(key0, thresh);
-  if (N <= 32 && A <= 7 && ntiles <= 64) {
+  if constexpr (FIN) {
+    static_assert(ONE_SET, "the finished front end is the riders'");
+    const int tid = threadIdx.x, D = N * (A - 1), NA = N * A;      // D <= 192, NA <= 224 (kActFinMaxN, kActFinMaxA)
+    const double pj = finished->pj[tid < D ? tid : 0], thr = finished->thr[tid < D ? tid : 0];
+    const float pr = finished->probs[tid < NA ? tid : 0];
+    const bool zero = (finished->any_zero[0] | finished->any_zero[1] | finished->any_zero[2] | finished->any_zero[3]) != 0;
+    sample_mt_body<1, ParkedRecordHook, 0>(nullptr, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, probs_sh, stw,
+                                           ParkedRecordHook{pj, thr, pr, zero, D, NA, probs_sh},
+                                           MultiWalk{nullptr, nullptr, nullptr, 0}, ahead);
+  } else if (N <= kActFinMaxN && A <= kActFinMaxA && ntiles <= kActFinMaxTiles) {
     // (row = tid >> 3, output = tid & 7): the partials are requested now; summed, turned into probabilities and into
     // conditional probabilities in registers after the sampler's state blocks and doubles (FusedHeadsHook)
     float pv[64];
-    const int row = (int)threadIdx.x >> 3, a = (int)threadIdx.x & 7;
-    const int n = N * (A + 1);
-    const int idx = (row < N && a <= A) ? row * (A + 1) + a : 0;
-    const float bias = (a < A) ? ba[a] : bc[0];
-#pragma unroll
-    for (int t = 0; t < 64; ++t) pv[t] = partial[(size_t)(t < ntiles ? t : 0) * n + idx];
+    float bias;
+    heads_partials_request(partial, ntiles, ba, bc, N, A, (int)threadIdx.x, pv, bias);
     sample_mt_body<1, FusedHeadsHook, ONE_SET ? 0 : 1>(nullptr, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, probs_sh, stw,
                       FusedHeadsHook{pv, bias, ntiles, N, A, probs_sh, probs_out, values_out},
                       MultiWalk{nullptr, nullptr, nullptr, 0}, ahead);
@@ -1392,9 +1379,11 @@ __device__ __forceinline__ void act_sample_body(const float* __restrict__ partia
     sample_mt_body<1>(nullptr, N, A, mt_state, nullptr, nullptr, nullptr, actions, act_s, probs_sh, stw, NoProbsHook(),
                       MultiWalk{nullptr, nullptr, nullptr, 0}, ahead);
   }
+  MISC_STAMP(7);
   // (the sampler body ends past a barrier; its last wave is still writing the stream position back)
   if (env_step && (int)threadIdx.x < N)       // N <= 64 here: one environment per thread
     synth_bookkeep_hashed(hr5, term0, e0, act_s[e0], ep_reward0, ep_len0, StepRecords{rewards_out, masks_out, ep_reward, ep_len, fin});
+  MISC_STAMP(8);
 }
 
 // The step launch with the heads finish in front of the sampler: workgroup 0 is act_sample_body, the other N * 7 shift the
@@ -1435,6 +1424,7 @@ __global__ __launch_bounds__(256) void synth_step_a_mth_kernel(const float* __re
 // another: every rider reads only what an earlier launch wrote.  (Device games, whose frame depends on the action, keep their
 // routes.)  The fc kernels run 448 or 576 threads, the sampler body and the shift are written for 256: a rider workgroup's
 // surplus waves return before the first barrier, an fc workgroup's take no part in the shift.
+template <bool FIN>
 struct ActRiderDev {
   ActRider r;
   unsigned front_wgs() const { return r.owed.partial ? 1u : 0u; }      // the owed sample's workgroup
@@ -1444,9 +1434,9 @@ struct ActRiderDev {
       if (threadIdx.x >= 256) return true;
       const ActSample& o = r.owed;
       const uint64_t id = (o.step_base ? *o.step_base : 0ull) + o.step_off + 1ull;
-      act_sample_body<true>(o.partial, o.ntiles, o.ba, o.bc, o.probs_out, o.values_out, o.A, o.mt_state, o.actions, o.seed,
-                      o.env_offset, o.N, o.thresh, id, o.rec.rewards, o.rec.masks, o.rec.ep_reward, o.rec.ep_len, o.rec.fin,
-                      nullptr, lds);
+      act_sample_body<true, FIN>(o.partial, o.ntiles, o.ba, o.bc, o.probs_out, o.values_out, o.A, o.mt_state, o.actions, o.seed,
+                                 o.env_offset, o.N, o.thresh, id, o.rec.rewards, o.rec.masks, o.rec.ep_reward, o.rec.ep_len,
+                                 o.rec.fin, nullptr, lds, o.finished);
       return true;
     }
     bid -= ns;
@@ -1543,9 +1533,17 @@ int launch_act_sample_flush(const ActSample& owed, hipStream_t s) {
 
 // The acting fc launch with its riders, as csrc/net_fwd.hip asks for it (fc_heads.h: launch_fc_heads; the ridden instantiations
 // are compiled here, beside the sampler they carry).
+// Two forms: a debt whose heads the conv tower in front has finished -- the instantiation with the record front end alone
+// (Nature: the tower that carries the finish is its) --, otherwise the sampler with the heads finish of its own.  (A launch with
+// nothing to carry -- that tower shifted the frames and no sample is owed -- is the forward's plain one.)
 int launch_fc_heads_rider(bool nature, const FcHeadsArgs& a, const ActRider& r, hipStream_t s) {
-  if (nature) return launch_fc_heads<NatureNet>(a, ActRiderDev{r}, s);
-  return launch_fc_heads<OtherNet>(a, ActRiderDev{r}, s);
+  if (r.owed.partial && r.owed.finished) {
+    if (nature) return launch_fc_heads<NatureNet>(a, ActRiderDev<true>{r}, s);
+    set_error("fc launch riders: a finished debt needs the Nature conv tower in front");
+    return -1;
+  }
+  if (nature) return launch_fc_heads<NatureNet>(a, ActRiderDev<false>{r}, s);
+  return launch_fc_heads<OtherNet>(a, ActRiderDev<false>{r}, s);
 }
 
 // (arguments validated by paac_returns_norm_tick, csrc/api.hip)

@@ -160,17 +160,21 @@ int launch_pack_weights(paac_ctx* ctx, const float* params, hipStream_t s) {
   return launch_pack_dgrad(ctx, params, s);
 }
 
-template <class G, bool KEEP>
-static void launch_tower_variant(const TowerArgs& a, hipStream_t s) {
-  launch_k(tower_kernel<G, KEEP>, dim3((unsigned)(a.batch * G::NR)), dim3(512), s, PROF_WHOLE, a);
+template <class G, bool KEEP, class RIDER = NoTowerRider>
+static void launch_tower_variant(const TowerArgs& a, hipStream_t s, const RIDER& rider = RIDER()) {
+  launch_k(tower_kernel<G, KEEP, RIDER>, dim3((unsigned)(a.batch * G::NR)), dim3(512), s, PROF_WHOLE, a, rider);
 }
 
 // keep = also write the fp32 conv1 / conv2 activations (the backward pass and the debug read-back need them)
 // packed3: conv3's output goes out in fc_heads_kernel's A-fragment order (acting rows that nothing else reads)
 // keepW / keep_row: the rows are ALSO kept in another activation set (the training set) at row offset keep_row -- fp32 conv1
 // / conv2 outputs and a plain-row copy of conv3's -- while the fragment-order conv3 output for the fc kernel goes to W
-static void launch_tower(paac_ctx* ctx, Workspace& W, const float* params, const uint8_t* states, int batch, bool keep,
-                         bool packed3, hipStream_t s, Workspace* keepW = nullptr, int keep_row = 0) {
+// trider (nullable): what the launch is asked to carry on its helper waves (tower.h: RIDER) -- taken by the eight-region
+// geometry alone; returns what it did carry: kTowerRodeFinish | kTowerRodeShift
+constexpr int kTowerRodeFinish = 1, kTowerRodeShift = 2;
+static int launch_tower(paac_ctx* ctx, Workspace& W, const float* params, const uint8_t* states, int batch, bool keep,
+                        bool packed3, hipStream_t s, Workspace* keepW = nullptr, int keep_row = 0,
+                        const TowerRider* trider = nullptr) {
   const paac_layout& L = ctx->layout;
   TowerArgs a;
   a.states = states;
@@ -207,6 +211,11 @@ static void launch_tower(paac_ctx* ctx, Workspace& W, const float* params, const
   int regions = (8 * batch <= 256) ? 8 : (4 * batch <= 256) ? 4 : (2 * batch <= 256) ? 2 : 1;
   if (force == 1 || force == 2 || force == 4 || force == 8) regions = force;
   if (regions == 8) {
+    if (trider && (trider->fin.partial || trider->shift.stack_in)) {
+      if (keep) launch_tower_variant<TowerGeom<4, 2>, true>(a, s, TowerRiderDev{*trider});
+      else launch_tower_variant<TowerGeom<4, 2>, false>(a, s, TowerRiderDev{*trider});
+      return (trider->fin.partial ? kTowerRodeFinish : 0) | (trider->shift.stack_in ? kTowerRodeShift : 0);
+    }
     if (keep) launch_tower_variant<TowerGeom<4, 2>, true>(a, s);
     else launch_tower_variant<TowerGeom<4, 2>, false>(a, s);
   } else if (regions == 4) {
@@ -219,6 +228,7 @@ static void launch_tower(paac_ctx* ctx, Workspace& W, const float* params, const
     if (keep) launch_tower_variant<TowerGeom<7, 7>, true>(a, s);
     else launch_tower_variant<TowerGeom<7, 7>, false>(a, s);
   }
+  return 0;
 }
 
 template <class G, bool KEEP>
@@ -321,6 +331,10 @@ static int forward_impl(paac_ctx* ctx, const float* params, const uint8_t* state
     set_error("forward: the fc launch's riders need the small acting route without the spare MT19937 workgroup");
     return -1;
   }
+  // ... and the conv tower launch in front of it may take the heads finish of the owed sample and the step's frame shift off
+  // that fc launch (tower.h: RIDER): what the tower carried is settled once it has been launched
+  const TowerRider* trider = rider ? call.tower_rider : nullptr;
+  int tower_rode = 0;
   Workspace* keepW = nullptr;
   if (keep_row >= 0) {
     // (the fc + head partials routes, or -- the counter-based sampler's forwards -- the split-K fc with its per-row heads
@@ -341,7 +355,8 @@ static int forward_impl(paac_ctx* ctx, const float* params, const uint8_t* state
     ProfScope ps(ctx, F_CONV_TOWER, batch, s);
     prof_mix(3);       // conv1: u8 pixels x weights split into 3 bf16 terms
     prof_mix(6);       // conv2, conv3: six-product split-bf16
-    launch_tower(ctx, W, params, states, batch, keep_acts, packed3, s, keep_h_only ? nullptr : keepW, keep_row < 0 ? 0 : keep_row);
+    tower_rode = launch_tower(ctx, W, params, states, batch, keep_acts, packed3, s, keep_h_only ? nullptr : keepW,
+                              keep_row < 0 ? 0 : keep_row, trider);
   }
   if (tower2) {
     ProfScope ps(ctx, F_CONV_TOWER, batch, s);
@@ -398,9 +413,17 @@ static int forward_impl(paac_ctx* ctx, const float* params, const uint8_t* state
       const FcHeadsArgs fa{last, reinterpret_cast<const f32x4*>(ctx->fc_pack), bf, wa, wc, A, batch, partial,
                            packed3 ? h_keep : (keep_acts ? W.h : (float*)nullptr), quarter, packed3, ah};
       if (rider) {     // (the ridden instantiations are csrc/misc.hip's, where the sampler lives)
-        if (launch_fc_heads_rider(ctx->cfg.arch == PAAC_ARCH_NATURE, fa, *rider, s)) return -1;
+        ActRider fc_rider = *rider;
+        fc_rider.owed.finished = (tower_rode & kTowerRodeFinish) ? trider->fin.rec : nullptr;
+        if (tower_rode & kTowerRodeShift) fc_rider.shift = SynthStep{};
+        // nothing left to carry (the tower shifted the frames, no sample is owed): the plain instantiation
+        const bool plain = !fc_rider.owed.partial && !fc_rider.shift.stack_in;
+        if (plain ? launch_fc_heads<NT>(fa, NoRider{}, s)
+                  : launch_fc_heads_rider(ctx->cfg.arch == PAAC_ARCH_NATURE, fa, fc_rider, s))
+          return -1;
         call.rode = true;          // the regions swap only once the launch has been issued
         ctx->act_region ^= 1;
+        ctx->act_tower_rode = tower_rode;
       } else if (launch_fc_heads<NT>(fa, NoRider{}, s)) {
         return -1;
       }

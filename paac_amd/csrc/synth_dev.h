@@ -104,18 +104,20 @@ __device__ __forceinline__ bool synth_bookkeep(uint32_t key, int e, const int32_
 // the load of the old stack and the store of the new one: synth_shift_load requests the thread's 16 bytes, synth_shift_store
 // pushes the new bytes and writes.  Threads 252.. of the 256 own nothing in either half.
 constexpr int SHIFT_QUADS = OBS_PIX / PRE_BANDS / 4;  // 252: 12 rows of 21 quads
-__device__ __forceinline__ uint4 synth_shift_load(int unit, const uint32_t* __restrict__ stack_in) {
-  const int i = threadIdx.x;
+// (The _at forms take the thread's index among the unit's 256 instead of threadIdx.x: the conv tower's helper waves, csrc/tower.h.)
+__device__ __forceinline__ uint4 synth_shift_load_at(const int i, int unit, const uint32_t* __restrict__ stack_in) {
   if (i >= SHIFT_QUADS) return make_uint4(0u, 0u, 0u, 0u);
   const long quad = (long)(unit / PRE_BANDS) * (OBS_PIX / 4) + (unit % PRE_BANDS) * SHIFT_QUADS + i;
   return reinterpret_cast<const uint4*>(stack_in)[quad];
 }
-__device__ __forceinline__ void synth_shift_store(uint64_t seed, uint32_t env_offset, uint64_t id, uint32_t thresh, int unit,
-                                                  uint4 old, uint32_t* __restrict__ stack_out,
-                                                  uint32_t* __restrict__ stack_out2, const bool force_reset = false) {
+__device__ __forceinline__ uint4 synth_shift_load(int unit, const uint32_t* __restrict__ stack_in) {
+  return synth_shift_load_at((int)threadIdx.x, unit, stack_in);
+}
+__device__ __forceinline__ void synth_shift_store_at(const int i, uint64_t seed, uint32_t env_offset, uint64_t id, uint32_t thresh,
+                                                     int unit, uint4 old, uint32_t* __restrict__ stack_out,
+                                                     uint32_t* __restrict__ stack_out2, const bool force_reset = false) {
   const int e = unit / PRE_BANDS;
   const int band = unit % PRE_BANDS;
-  const int i = threadIdx.x;
   if (i >= SHIFT_QUADS) return;
   const int q = band * SHIFT_QUADS + i;                 // = y * 21 + (x >> 2): the generator's word index
   const long quad = (long)e * (OBS_PIX / 4) + q;
@@ -127,6 +129,11 @@ __device__ __forceinline__ void synth_shift_store(uint64_t seed, uint32_t env_of
                                 (old.z >> 8) | (((w >> 16) & 255u) << 24), (old.w >> 8) | ((w >> 24) << 24));
   reinterpret_cast<uint4*>(stack_out)[quad] = outv;
   if (stack_out2) reinterpret_cast<uint4*>(stack_out2)[quad] = outv;   // second copy (the observation ring's wrap-around slot)
+}
+__device__ __forceinline__ void synth_shift_store(uint64_t seed, uint32_t env_offset, uint64_t id, uint32_t thresh, int unit,
+                                                  uint4 old, uint32_t* __restrict__ stack_out,
+                                                  uint32_t* __restrict__ stack_out2, const bool force_reset = false) {
+  synth_shift_store_at((int)threadIdx.x, seed, env_offset, id, thresh, unit, old, stack_out, stack_out2, force_reset);
 }
 __device__ __forceinline__ void synth_shift_band(uint64_t seed, uint32_t env_offset, uint64_t id, uint32_t thresh, int unit,
                                                  const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
@@ -143,6 +150,18 @@ __device__ __forceinline__ void synth_shift_band(uint64_t seed, uint32_t env_off
 // step's fc launch -- the heads finish, the MT19937 sampler and the bookkeeping of `N` environments, read from the head
 // partials the fc launch left -- and what the NEXT fc launch carries beside its own work: that debt and the frame shift of
 // its own step (shift.stack_in == nullptr: none, the bootstrap forward's launch).
+// The heads finish of an owed sample done ahead of its sampler, by the conv tower launch that lies between the fc launch that
+// left the partials and the fc launch that carries the sampler (csrc/tower.h: RIDER): what heads_finish_fused (fc_heads.h)
+// leaves for the sampler's walks, at the limits of that routine -- one record per context, since fc(t) completes before
+// tower(t + 1) starts.  any_zero: one word per helper wave of the tower workgroup (no barrier there: the reader ORs the four).
+constexpr int kActFinMaxN = 32, kActFinMaxA = 7, kActFinMaxTiles = 64;
+struct ActFinishRecord {
+  double pj[kActFinMaxN * (kActFinMaxA - 1)];      // conditional probabilities [N][A - 1]
+  double thr[kActFinMaxN * (kActFinMaxA - 1)];     // packed walk thresholds, same order
+  float probs[kActFinMaxN * kActFinMaxA];          // probabilities [N][A]
+  int32_t any_zero[4];                             // != 0: some conditional probability is exactly zero
+};
+static_assert(sizeof(ActFinishRecord) <= 4096, "the finish record is a few KB");
 struct ActSample {
   const float* partial;            // nullptr: nothing owed
   int ntiles;
@@ -158,9 +177,26 @@ struct ActSample {
   const uint64_t* step_base;
   uint64_t step_off;
   StepRecords rec;
+  const ActFinishRecord* finished; // the heads of this debt are finished and the record holds them (set by the forward for the fc
+                                   // launch behind a tower that carried the finish; nullptr: the sampler finishes them itself)
 };
 struct ActRider {
   ActSample owed;
+  SynthStep shift;
+};
+// ... and what the conv tower launch in front of that fc launch carries on its helper waves (PAAC_ACT_TOWER_RIDER): the heads
+// finish of the owed sample (fin.partial == nullptr: none) and the frame shift of its own step (shift.stack_in == nullptr: none;
+// the fc launch then shifts nothing).
+struct ActFinish {
+  const float* partial;
+  int ntiles;
+  const float *ba, *bc;
+  float *probs_out, *values_out;
+  int A, N;
+  ActFinishRecord* rec;
+};
+struct TowerRider {
+  ActFinish fin;
   SynthStep shift;
 };
 

@@ -28,6 +28,8 @@
 //     services together fall on 64 distinct banks for the stride-2 / stride-1 walks of conv2 / conv3.
 #pragma once
 #include "dmm.h"
+#include "synth_dev.h"
+#include "fc_heads.h"
 
 namespace paac {
 
@@ -346,8 +348,26 @@ struct Koff3Full {   // conv3, all of K: k-step i = (tap i / 2, channel half i %
   __device__ static constexpr int at(int i) { return (((i / 2) / 3) * G::R2W + ((i / 2) % 3)) * G::S2 + (i % 2) * 64; }
 };
 
-template <class G, bool WRITE_ALL>
-__global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
+// RIDER (the pipelined acting step, paac_act_step_pipe; TowerGeom<4, 2> -- the 32-row acting tower -- only): work that rides the
+// helper waves (TowerGeom::ROLES: waves 4-7, idle after conv1 but for the kept rows) of the tower launch that lies between two
+// acting fc launches, none of it waited for by another workgroup and all of it reading only what earlier launches wrote:
+//   * workgroup 0: the heads finish of the step before (heads_finish_fused, fc_heads.h: the four helper waves are the 256
+//     threads it is written for, htid = tid - 256), from the partials fc(t - 1) left, into the context's ActFinishRecord, which
+//     the sampler workgroup riding fc(t) parks instead of finishing the heads itself;
+//   * workgroups w < 7 N: the frame shift of this step's (environment, band) unit w -- it reads the stacks the tower reads and
+//     writes other ones --, so that fc(t) carries no shift.
+// Both in the helper branch of phase 2, where the helper waves' registers are free: the requests first, the kept rows while they
+// travel.  NoTowerRider: the instantiations every other caller uses -- their code is what it was (the empty struct is one byte
+// at the end of the kernel arguments, which no instruction reads).
+struct NoTowerRider {};
+struct TowerRiderDev {
+  TowerRider r;
+};
+
+template <class G, bool WRITE_ALL, class RIDER = NoTowerRider>
+__global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p, const RIDER rider) {
+  constexpr bool RIDDEN = !__is_same(RIDER, NoTowerRider);
+  static_assert(!RIDDEN || G::ROLES, "the riders are the helper waves'");
   // WRITE_ALL with several regions per sample: pixels in the overlap are written by more than one workgroup, with identical values
   __shared__ __attribute__((aligned(16))) char lds[G::LDS_BYTES];
   char* const lds_in = lds;                       // bf16 input image [RIH][RIW][4]            (phase 0-1)
@@ -483,6 +503,11 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
 
   WaveGemm<9, G::NT3, 4, 3, G::PL2, G::PF3, Koff3Half<G>> g3h;     // only the one matching KSPLIT3 is used
   WaveGemm<18, G::NT3, 4, 3, G::PL2, G::PF3, Koff3Full<G>, true, G::ROLES ? 1 : 0> g3f;
+  // what the helper waves carry for a rider (RIDDEN; tower.h: RIDER): requested in phase 2, the heads finished in phase 3
+  bool shifts = false, finishes = false;
+  uint4 shift_old = make_uint4(0u, 0u, 0u, 0u);
+  float pv[64];
+  float hbias = 0.f;
   // ---- phase 2: conv2 (K = 512 = 16 taps x 32 channels) ---------------------------------------------------------------
   if (gemm_wave) {
     const int ct = wave & 3, half = wave >> 2;      // ROLES: half == 0, every pixel tile over all of K
@@ -548,8 +573,27 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
       store_split4<G::PL2>(lds_a2 + pix[j] * G::S2 + (16 * ct + 4 * kq) * 2, v);
     }
   } else {
+    // (RIDDEN: both tests are wave-uniform -- kernel arguments and blockIdx.x; the requests go out first, the kept rows are
+    // stored while they travel.  The shift is stored here; the heads are finished in the helper branch of phase 3, where no
+    // barrier follows: finished here, workgroup 0's GEMM waves waited at the next barrier for 12 k cycles of helper waves
+    // against their own 4.6 k, and every tower of the cycle took 12.9 us instead of 10.4 -- profiles/r10_rider_stamps.txt)
+    if constexpr (RIDDEN) {
+      const int htid = tid - 256;
+      const SynthStep& st = rider.r.shift;
+      const ActFinish& fn = rider.r.fin;
+      shifts = st.stack_in != nullptr && (int)blockIdx.x < st.N * PRE_BANDS;
+      finishes = blockIdx.x == 0 && fn.partial != nullptr;
+      if (shifts) shift_old = synth_shift_load_at(htid, (int)blockIdx.x, st.stack_in);
+      if (finishes) heads_partials_request(fn.partial, fn.ntiles, fn.ba, fn.bc, fn.N, fn.A, htid, pv, hbias);
+    }
     if constexpr (WRITE_ALL)      // helper waves: the kept conv1 rows, from the planes conv2's GEMM is reading
       store_kept_rows<G::P1, G::R1W, G::S1, G::PL1, 32>(lds_a1, p.act1 + ((size_t)(b * 20 + y1a) * 20 + x1a) * 32, 20, tid - 256);
+    if constexpr (RIDDEN) {
+      const SynthStep& st = rider.r.shift;
+      if (shifts)
+        synth_shift_store_at(tid - 256, st.seed, st.env_offset, st.id(), st.thresh, (int)blockIdx.x, shift_old, st.stack_out,
+                             st.stack_out2);
+    }
     TOWER_STAMP(7);
   }
   __syncthreads();
@@ -612,6 +656,15 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p) {
   } else {
     if constexpr (WRITE_ALL)      // helper waves: the kept conv2 rows
       store_kept_rows<G::P2, G::R2W, G::S2, G::PL2, 64>(lds_a2, p.act2 + ((size_t)(b * 9 + y3a) * 9 + x3a) * 64, 9, tid - 256);
+    if constexpr (RIDDEN) {
+      if (finishes) {             // workgroup 0: the heads finish of the step before, from the partials requested in phase 2
+        const ActFinish& fn = rider.r.fin;
+        const bool zero = heads_finish_fused(pv, hbias, fn.ntiles, fn.N, fn.A, tid - 256, fn.rec->probs, fn.probs_out, fn.values_out,
+                                             fn.rec->pj, fn.rec->thr);
+        const unsigned long long any = __ballot(zero);
+        if (lane == 0) fn.rec->any_zero[wave - 4] = any != 0ull ? 1 : 0;
+      }
+    }
     TOWER_STAMP(9);
   }
   TOWER_STAMP(10);

@@ -195,8 +195,8 @@ int paac_act_step_pending(const paac_ctx* ctx);
 /* PAAC_ACT_TOWER_RIDER (read at paac_create; default 1): on the Nature network, at up to 32 environments, the conv tower launch
  * of a pipelined step has four idle waves per workgroup, and carries on them -- 1: the heads finish of the owed sample (up to 7
  * actions), which leaves the sampler's inputs in a record owned by the ctx, so that the workgroup riding the next fc launch
- * only parks them; 2: also the frame shift of its own step, so that the first fc launch of a run carries nothing (measured level
- * with 1, hence not the default); 0: neither
+ * only parks them; 2: also the frame shift of its own step, so that the first fc launch of a run carries nothing (measured
+ * 0.6 % ahead of 1 in two sessions, beyond three times the run-to-run spread in one of them only: not the default); 0: neither
  * (the route described above).  The same bits every way.  paac_act_finish_layout: that record's size, the byte offsets of its
  * conditional probabilities / packed thresholds / probabilities / exact-zero words and the limits it is sized for (environments,
  * actions, column groups of head partials) -- eight words.  paac_act_tower_rode: what the conv tower of the last
@@ -204,6 +204,11 @@ int paac_act_step_pending(const paac_ctx* ctx);
  * 2: the frame shift (host-side state, for tests and probes). */
 int paac_act_finish_layout(int64_t* out, int n);
 int paac_act_tower_rode(const paac_ctx* ctx);
+/* paac_tower_kept_layout (host only): the eight-region conv tower (up to 32 rows) stores every kept conv1 / conv2 pixel from ONE
+ * of the regions that compute it.  out[0] = the number of regions of a sample; then per region, for conv1 (20 x 20) and then
+ * conv2 (9 x 9), eight words: the rectangle it computes (y, x, height, width) and the rectangle it owns, in image
+ * coordinates -- 1 + 16 * regions words.  regions: 8 (the other region counts store from their GEMM epilogues: refused). */
+int paac_tower_kept_layout(int regions, int64_t* out, int n);
 
 /* Conv-weight packing.  The Nature conv layers run as one fused launch that reads the conv weights pre-split into bf16
  * planes (an internal copy owned by the ctx).  By default every paac_forward* / paac_train_forward / paac_loss_backward

@@ -152,6 +152,7 @@ _SIGNATURES = {
     "paac_act_step_pending": (c_int, [c_void_p]),
     "paac_act_finish_layout": (c_int, [POINTER(c_int64), c_int]),
     "paac_act_tower_rode": (c_int, [c_void_p]),
+    "paac_tower_kept_layout": (c_int, [c_int, POINTER(c_int64), c_int]),
     "paac_walk_scratch_bytes": (c_int64, [c_int, c_int]),
     "paac_debug_report_zero": (c_int, [c_int]),
     "paac_sample_mt_synth_step": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_uint64, c_uint32, c_int, c_uint32, c_void_p,

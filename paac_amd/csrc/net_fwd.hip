@@ -573,3 +573,25 @@ extern "C" void paac_debug_set_heads_stamps(unsigned long long* p) {
 int fc_splits_max() { return FC_SPLITS_MAX; }
 
 }  // namespace paac
+
+// Host only (include/paac_hip.h): what each region of the eight-region tower computes and what it owns of the kept conv1 / conv2
+// images, from the constants the kernel reads (tower.h: TowerGeom::cut).
+int paac_tower_kept_layout(int regions, int64_t* out, int n) {
+  using G = paac::TowerGeom<4, 2>;
+  PAAC_REQUIRE(G::ROLES, "paac_tower_kept_layout: this build has no helper waves (PAAC_T_ROLES=0)");
+  PAAC_REQUIRE(regions == G::NR, "paac_tower_kept_layout: %d regions -- only the %d-region tower stores kept rows by owner", regions, G::NR);
+  PAAC_REQUIRE(out && n >= 1 + 16 * G::NR, "paac_tower_kept_layout: %d words", 1 + 16 * G::NR);
+  out[0] = G::NR;
+  for (int reg = 0; reg < G::NR; ++reg) {
+    const int ry = reg / G::NRX, rx = reg % G::NRX;
+    const int y3a = G::origin3(ry, G::R3H), x3a = G::origin3(rx, G::R3W);
+    const int64_t v[16] = {2 * y3a, 2 * x3a, G::R1H, G::R1W,
+                           G::cut(ry, 20, G::NRY), G::cut(rx, 20, G::NRX), G::cut(ry + 1, 20, G::NRY) - G::cut(ry, 20, G::NRY),
+                           G::cut(rx + 1, 20, G::NRX) - G::cut(rx, 20, G::NRX),
+                           y3a, x3a, G::R2H, G::R2W,
+                           G::cut(ry, 9, G::NRY), G::cut(rx, 9, G::NRX), G::cut(ry + 1, 9, G::NRY) - G::cut(ry, 9, G::NRY),
+                           G::cut(rx + 1, 9, G::NRX) - G::cut(rx, 9, G::NRX)};
+    for (int i = 0; i < 16; ++i) out[1 + 16 * reg + i] = v[i];
+  }
+  return 0;
+}

@@ -153,7 +153,7 @@ __device__ __forceinline__ void synth_shift_band(uint64_t seed, uint32_t env_off
 // The heads finish of an owed sample done ahead of its sampler, by the conv tower launch that lies between the fc launch that
 // left the partials and the fc launch that carries the sampler (csrc/tower.h: RIDER): what heads_finish_fused (fc_heads.h)
 // leaves for the sampler's walks, at the limits of that routine -- one record per context, since fc(t) completes before
-// tower(t + 1) starts.  any_zero: one word per helper wave of the tower workgroup (no barrier there: the reader ORs the four).
+// tower(t + 1) starts.  any_zero: one word per finishing wave -- tower workgroups 0 .. 3, one helper wave each -- (the reader ORs the four).
 constexpr int kActFinMaxN = 32, kActFinMaxA = 7, kActFinMaxTiles = 64;
 struct ActFinishRecord {
   double pj[kActFinMaxN * (kActFinMaxA - 1)];      // conditional probabilities [N][A - 1]

@@ -158,6 +158,26 @@ struct TowerGeom {
   // conv2's weight fragments at kernel start)
   static constexpr bool W1_LDS = FRONT_AL + 3 * PL1 + W1_BYTES <= 160 * 1024;
   static constexpr int LDS_BYTES = FRONT_AL + 3 * PL1 + (W1_LDS ? W1_BYTES : 0);
+  // Kept rows (WRITE_ALL) with several regions per sample: the regions' conv1 / conv2 footprints overlap, and every kept pixel
+  // has ONE owner -- along an axis of L pixels cut into n regions, region r owns [cut(r, L, n), cut(r + 1, L, n)), cuts that
+  // lie inside the overlap of the neighbours' computed ranges (asserted below) and balance the owners (<4, 2>: conv1 columns
+  // 5 / 10 / 15 and rows 10, conv2 columns 2 / 5 / 7 and rows 5).  The helper waves (ROLES) store the owned rectangle alone.
+  static constexpr int cut(int r, int L, int n) { return (r * L + n / 2) / n; }
+  static constexpr int origin3(int r, int R3) { return r * R3 < 7 - R3 ? r * R3 : 7 - R3; }   // region origin in conv3 / conv2 coordinates
+  static constexpr int own_max(int L, int n) {
+    int m = 0;
+    for (int r = 0; r < n; ++r) m = cut(r + 1, L, n) - cut(r, L, n) > m ? cut(r + 1, L, n) - cut(r, L, n) : m;
+    return m;
+  }
+  // every region's owned range [cut(r), cut(r + 1)) lies inside what it computes: [mul * origin3(r), ... + R)
+  static constexpr bool own_inside(int L, int n, int R3, int R, int mul) {
+    for (int r = 0; r < n; ++r)
+      if (cut(r, L, n) < mul * origin3(r, R3) || cut(r + 1, L, n) > mul * origin3(r, R3) + R) return false;
+    return cut(0, L, n) == 0 && cut(n, L, n) == L;
+  }
+  static constexpr int OWN1H = own_max(20, NRY), OWN1W = own_max(20, NRX), OWN2H = own_max(9, NRY), OWN2W = own_max(9, NRX);
+  static_assert(own_inside(20, NRY, R3H, R1H, 2) && own_inside(20, NRX, R3W, R1W, 2), "owned conv1 rectangles inside the computed ones");
+  static_assert(own_inside(9, NRY, R3H, R2H, 1) && own_inside(9, NRX, R3W, R2W, 1), "owned conv2 rectangles inside the computed ones");
   static_assert(RIW % 4 == 0, "input rows are staged 4 pixels (16 bytes) at a time");
   static_assert(!KSPLIT3 || 4 * NT3 * 1024 <= 3 * PL1, "conv3 K-split partials reuse the conv1 planes");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
@@ -306,17 +326,22 @@ __device__ __forceinline__ void store_split4(char* dst, const f32x4 v) {
 // x = hi + mid + lo holds exactly (split3_bf16; for x = 0 and x >= 2^-103 -- below that the remainders are subnormal and
 // their truncation drops bits: a conv output that small and not 0 does not come out of a sum of fp32 terms), and
 // (lo + mid) + hi rounds nowhere: lo + mid is the 16-bit remainder r1, r1 + hi is x -- and stored as the region's rows of
-// the [B, H, W, C] image.  htid = 0 .. 255 over the four helper waves.
-template <int P, int RW, int S, int PL, int C>
-__device__ __forceinline__ void store_kept_rows(const char* __restrict__ planes, float* __restrict__ img /* region origin */,
-                                                const int img_w, const int htid) {
-  constexpr int V = C / 4, N = P * V;     // f32x4 per pixel, per region
+// the [B, H, W, C] image: the oh x ow pixels the region OWNS (TowerGeom::cut; at most OH x OW, whose slots the threads walk --
+// no division by a run-time width), every kept pixel stored once per launch.  htid = 0 .. nthr - 1 over the helper waves that
+// store, nthr wave-uniform and at least kKeptMinThreads (three waves, where the fourth finishes the heads: tower_kernel).
+constexpr int kKeptMinThreads = 192;
+template <int OH, int OW, int RW, int S, int PL, int C>
+__device__ __forceinline__ void store_kept_rows(const char* __restrict__ planes /* owned origin */, float* __restrict__ img /* owned origin */,
+                                                const int img_w, const int oh, const int ow, const int htid, const int nthr) {
+  constexpr int V = C / 4, N = OH * OW * V;     // f32x4 per pixel, per owned rectangle
 #pragma unroll
-  for (int i0 = 0; i0 < N; i0 += 256) {
-    const int i = i0 + htid;
-    if (i0 + 256 > N && i >= N) break;
+  for (int it = 0; it < (N + kKeptMinThreads - 1) / kKeptMinThreads; ++it) {
+    const int i = it * nthr + htid;
+    if (i >= N) break;
     const int pi = i / V, c4 = i - pi * V;
-    const char* src = planes + pi * S + c4 * 8;
+    const int y = pi / OW, x = pi - y * OW;
+    if (y >= oh || x >= ow) continue;
+    const char* src = planes + (y * RW + x) * S + c4 * 8;
     const u32x2 h = *reinterpret_cast<const u32x2*>(src), m = *reinterpret_cast<const u32x2*>(src + PL),
                 l = *reinterpret_cast<const u32x2*>(src + 2 * PL);
     f32x4 v;
@@ -326,7 +351,6 @@ __device__ __forceinline__ void store_kept_rows(const char* __restrict__ planes,
       v[2 * q + 1] = (__builtin_bit_cast(float, l[q] & 0xFFFF0000u) + __builtin_bit_cast(float, m[q] & 0xFFFF0000u)) +
                      __builtin_bit_cast(float, h[q] & 0xFFFF0000u);
     }
-    const int y = pi / RW, x = pi - y * RW;
     *reinterpret_cast<f32x4*>(img + ((size_t)y * img_w + x) * C + 4 * c4) = v;
   }
 }
@@ -351,9 +375,15 @@ struct Koff3Full {   // conv3, all of K: k-step i = (tap i / 2, channel half i %
 // RIDER (the pipelined acting step, paac_act_step_pipe; TowerGeom<4, 2> -- the 32-row acting tower -- only): work that rides the
 // helper waves (TowerGeom::ROLES: waves 4-7, idle after conv1 but for the kept rows) of the tower launch that lies between two
 // acting fc launches, none of it waited for by another workgroup and all of it reading only what earlier launches wrote:
-//   * workgroup 0: the heads finish of the step before (heads_finish_fused, fc_heads.h: the four helper waves are the 256
-//     threads it is written for, htid = tid - 256), from the partials fc(t - 1) left, into the context's ActFinishRecord, which
-//     the sampler workgroup riding fc(t) parks instead of finishing the heads itself;
+//   * workgroups q = 0 .. 3 (the grid has at least eight): the heads finish of the step before for rows 8 q .. 8 q + 7, on ONE
+//     helper wave each (wave 4, as threads 64 q + lane of the 256 heads_finish_fused, fc_heads.h, is written for -- the routine
+//     works inside 8-lane groups and one wave's ballot, so nothing crosses a wave), from the partials fc(t - 1) left, into the
+//     context's ActFinishRecord (any_zero[q] on every step), which the sampler workgroup riding fc(t) parks instead of finishing
+//     the heads itself.  One wave's 64 one-dword requests per lane fill its memory counter: that wave stores no kept rows (the
+//     other three helper waves cover the owned rectangle, in phase 3 as well: the finishing wave is that phase's longest as it
+//     is, 3.7 k cycles against the GEMM waves' 3.1 k), and a CU carries a quarter of what workgroup 0 alone carried, whose GEMM
+//     waves' weight fragments queued behind all 256 load instructions (phase 2 of its GEMM waves 7.0 k cycles against 4.7 k
+//     elsewhere; now 5.1-5.3 k on four CUs: profiles/r11_rider_stamps.txt);
 //   * workgroups w < 7 N: the frame shift of this step's (environment, band) unit w -- it reads the stacks the tower reads and
 //     writes other ones --, so that fc(t) carries no shift.
 // Both in the helper branch of phase 2, where the helper waves' registers are free: the requests first, the kept rows while they
@@ -368,7 +398,9 @@ template <class G, bool WRITE_ALL, class RIDER = NoTowerRider>
 __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p, const RIDER rider) {
   constexpr bool RIDDEN = !__is_same(RIDER, NoTowerRider);
   static_assert(!RIDDEN || G::ROLES, "the riders are the helper waves'");
-  // WRITE_ALL with several regions per sample: pixels in the overlap are written by more than one workgroup, with identical values
+  // WRITE_ALL with several regions per sample: the helper waves (ROLES) store each kept conv1 / conv2 pixel from its one owner
+  // (TowerGeom::cut); the geometries that store from the GEMM epilogues write pixels in the overlap from more than one
+  // workgroup, with identical values
   __shared__ __attribute__((aligned(16))) char lds[G::LDS_BYTES];
   char* const lds_in = lds;                       // bf16 input image [RIH][RIW][4]            (phase 0-1)
   char* const lds_a2 = lds;                       // conv2 planes [3][P2][S2]                  (phase 2-3), then
@@ -504,7 +536,8 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p, const RID
   WaveGemm<9, G::NT3, 4, 3, G::PL2, G::PF3, Koff3Half<G>> g3h;     // only the one matching KSPLIT3 is used
   WaveGemm<18, G::NT3, 4, 3, G::PL2, G::PF3, Koff3Full<G>, true, G::ROLES ? 1 : 0> g3f;
   // what the helper waves carry for a rider (RIDDEN; tower.h: RIDER): requested in phase 2, the heads finished in phase 3
-  bool shifts = false, finishes = false;
+  // finish_wg: a workgroup one of whose helper waves (wave 4: finishes) finishes heads -- its kept rows are the other three's
+  bool shifts = false, finish_wg = false, finishes = false;
   uint4 shift_old = make_uint4(0u, 0u, 0u, 0u);
   float pv[64];
   float hbias = 0.f;
@@ -582,12 +615,19 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p, const RID
       const SynthStep& st = rider.r.shift;
       const ActFinish& fn = rider.r.fin;
       shifts = st.stack_in != nullptr && (int)blockIdx.x < st.N * PRE_BANDS;
-      finishes = blockIdx.x == 0 && fn.partial != nullptr;
+      finish_wg = blockIdx.x < 4 && fn.partial != nullptr;
+      finishes = finish_wg && wave == 4;
       if (shifts) shift_old = synth_shift_load_at(htid, (int)blockIdx.x, st.stack_in);
-      if (finishes) heads_partials_request(fn.partial, fn.ntiles, fn.ba, fn.bc, fn.N, fn.A, htid, pv, hbias);
+      if (finishes) heads_partials_request(fn.partial, fn.ntiles, fn.ba, fn.bc, fn.N, fn.A, 64 * (int)blockIdx.x + lane, pv, hbias);
     }
-    if constexpr (WRITE_ALL)      // helper waves: the kept conv1 rows, from the planes conv2's GEMM is reading
-      store_kept_rows<G::P1, G::R1W, G::S1, G::PL1, 32>(lds_a1, p.act1 + ((size_t)(b * 20 + y1a) * 20 + x1a) * 32, 20, tid - 256);
+    if constexpr (WRITE_ALL) {    // helper waves: the kept conv1 rows this region owns, from the planes conv2's GEMM is reading
+      const int oy = G::cut(ry, 20, G::NRY), ox = G::cut(rx, 20, G::NRX);
+      const int t0 = finish_wg ? 512 - kKeptMinThreads : 256;      // the first thread that stores: wave 5 beside a finishing wave, else wave 4
+      if (!finishes)
+        store_kept_rows<G::OWN1H, G::OWN1W, G::R1W, G::S1, G::PL1, 32>(
+            lds_a1 + ((oy - y1a) * G::R1W + ox - x1a) * G::S1, p.act1 + ((size_t)(b * 20 + oy) * 20 + ox) * 32, 20,
+            G::cut(ry + 1, 20, G::NRY) - oy, G::cut(rx + 1, 20, G::NRX) - ox, tid - t0, 512 - t0);
+    }
     if constexpr (RIDDEN) {
       const SynthStep& st = rider.r.shift;
       if (shifts)
@@ -654,15 +694,21 @@ __global__ __launch_bounds__(512) void tower_kernel(const TowerArgs p, const RID
       }
     }
   } else {
-    if constexpr (WRITE_ALL)      // helper waves: the kept conv2 rows
-      store_kept_rows<G::P2, G::R2W, G::S2, G::PL2, 64>(lds_a2, p.act2 + ((size_t)(b * 9 + y3a) * 9 + x3a) * 64, 9, tid - 256);
+    if constexpr (WRITE_ALL) {    // helper waves: the kept conv2 rows this region owns
+      const int oy = G::cut(ry, 9, G::NRY), ox = G::cut(rx, 9, G::NRX);
+      const int t0 = finish_wg ? 512 - kKeptMinThreads : 256;
+      if (!finishes)
+        store_kept_rows<G::OWN2H, G::OWN2W, G::R2W, G::S2, G::PL2, 64>(
+            lds_a2 + ((oy - y3a) * G::R2W + ox - x3a) * G::S2, p.act2 + ((size_t)(b * 9 + oy) * 9 + ox) * 64, 9,
+            G::cut(ry + 1, 9, G::NRY) - oy, G::cut(rx + 1, 9, G::NRX) - ox, tid - t0, 512 - t0);
+    }
     if constexpr (RIDDEN) {
-      if (finishes) {             // workgroup 0: the heads finish of the step before, from the partials requested in phase 2
-        const ActFinish& fn = rider.r.fin;
-        const bool zero = heads_finish_fused(pv, hbias, fn.ntiles, fn.N, fn.A, tid - 256, fn.rec->probs, fn.probs_out, fn.values_out,
-                                             fn.rec->pj, fn.rec->thr);
+      if (finishes) {             // workgroup q < 4, wave 4: the heads finish of the step before, rows 8 q .. 8 q + 7, from the
+        const ActFinish& fn = rider.r.fin;      // partials requested in phase 2
+        const bool zero = heads_finish_fused(pv, hbias, fn.ntiles, fn.N, fn.A, 64 * (int)blockIdx.x + lane, fn.rec->probs, fn.probs_out,
+                                             fn.values_out, fn.rec->pj, fn.rec->thr);
         const unsigned long long any = __ballot(zero);
-        if (lane == 0) fn.rec->any_zero[wave - 4] = any != 0ull ? 1 : 0;
+        if (lane == 0) fn.rec->any_zero[blockIdx.x] = any != 0ull ? 1 : 0;
       }
     }
     TOWER_STAMP(9);

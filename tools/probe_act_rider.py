@@ -1,7 +1,7 @@
 """Diagnostic (stamped build only): the sampler workgroup INSIDE a ridden acting fc launch (paac_act_step_pipe), beside the fc
 workgroups it shares the CUs with -- tools/probe_sampler.py stamps it with a CU to itself.  Wall-clock stamps (10 ns ticks) of the
 last ridden launch of each run of T pipelined steps, and the launches' durations from the events on their dispatches.
-PAAC_HIP_LIB=.../libpaac_hip_stamps.so [PAAC_ACT_TOWER_RIDER=0|1|2] python tools/probe_act_rider.py
+PAAC_HIP_LIB=.../libpaac_hip_stamps.so [PAAC_ACT_TOWER_RIDER=0|1|2] [PROBE_KEEP=1] python tools/probe_act_rider.py
 profiles/r10_rider_stamps.txt is this at 32 x 4 on the parent and on the build."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,9 +22,10 @@ tstamps = torch.zeros(12 * 8 * 8 * N, dtype=torch.int64, device=dev)
 lib.paac_debug_set_tower_stamps(ctypes.c_void_p(tstamps.data_ptr()))
 ctx = hip_ops.Context(1, A, max_batch=N)
 params = torch.randn(ctx.layout["total"], device=dev) * 0.02
-ctx.set_managed_weights(True)
-ctx.pack_weights(params)
-mt = hip_ops.mt_state_from_numpy(np.random.RandomState(1).get_state(), dev)
+if os.environ.get("PROBE_KEEP", "0") != "1":      # PROBE_KEEP=1: unmanaged weights -- the acting tower is the kept-rows variant
+    ctx.set_managed_weights(True)
+    ctx.pack_weights(params)
+mt =hip_ops.mt_state_from_numpy(np.random.RandomState(1).get_state(), dev)
 stacks = torch.zeros((T + 1, N, 84, 84, 4), dtype=torch.uint8, device=dev)
 hip_ops.synth_reset(3, 0, stacks[0], None)
 act = torch.zeros((T, N), dtype=torch.int32, device=dev)
@@ -42,7 +43,7 @@ names = ["entry: requests issued", "loads landed, state words parked", "phase-1 
 reps = 40
 acc = np.zeros(len(order) - 1)
 tower, fc_first, fc_ridden = [], [], []
-phase2 = []
+phase2, phase3 = [], []
 ctx.prof_enable(True)
 for r in range(reps + 5):
     torch.cuda.synchronize()
@@ -60,6 +61,7 @@ for r in range(reps + 5):
     acc += np.diff(st[order])
     ts = tstamps.cpu().numpy().reshape(-1, 8, 12).astype(np.float64)
     phase2.append(ts[:, :, 7] - ts[:, :, 6])
+    phase3.append(ts[:, :, 9] - ts[:, :, 8])
     tw = [ms * 1000.0 for name, _, ms in events if name == "conv_tower"]
     fc = [ms * 1000.0 for name, _, ms in events if name == "fc_fwd"]
     tower += tw[1:]
@@ -76,5 +78,13 @@ print("tower phase 2 (stamps 6 -> 7), median cycles: workgroup 0 GEMM waves %s |
       "all other workgroups: GEMM waves %.0f, helper waves %.0f" % (p2[0, :4].astype(int).tolist(), p2[0, 4:].astype(int).tolist(),
                                                                   p2[1 % len(p2), 4:].astype(int).tolist(), np.median(p2[1:, :4]),
                                                                   np.median(p2[1:, 4:])))
+# the workgroups that finish heads (csrc/tower.h: RIDER -- 0 .. 3, wave 4 each) beside one that does not, phase 2 and phase 3
+# (stamps 8 -> 9: conv3's GEMM on waves 0-3; the kept conv2 rows and the heads finish on waves 4-7)
+p3 = np.median(np.stack(phase3), axis=0)
+for w in range(min(5, len(p2))):
+    print("workgroup %d: phase 2 GEMM waves %s helper waves %s | phase 3 GEMM waves %s helper waves %s" % (
+        w, p2[w, :4].astype(int).tolist(), p2[w, 4:].astype(int).tolist(), p3[w, :4].astype(int).tolist(), p3[w, 4:].astype(int).tolist()))
+print("workgroups 4 and up, medians: phase 2 GEMM waves %.0f helper waves %.0f | phase 3 GEMM waves %.0f helper waves %.0f" % (
+    np.median(p2[4:, :4]), np.median(p2[4:, 4:]), np.median(p3[4:, :4]), np.median(p3[4:, 4:])))
 if hasattr(lib, "paac_act_tower_rode"):
     print("the last tower carried (1 heads finish | 2 frame shift):", lib.paac_act_tower_rode(ctx.handle))

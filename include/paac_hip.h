@@ -557,6 +557,47 @@ int paac_returns_scan(const paac_returns* ret, paac_stream_t stream);
 int paac_returns_norm_tick(paac_ctx* ctx, const float* params, const paac_returns* ret, float* adv_n_out, double* stats_out,
                            paac_stream_t stream);
 
+/* --window_stats (spec and numpy twin: paac_amd/window_stats.py): one finished cycle folded into the running accumulators of
+ * the log window, acc_f device double[n_f] and acc_i device int64[n_i] (paac_window_fields reports the two lengths; the field
+ * offsets are window_stats.FIELDS_F / FIELDS_I; all zero bytes = an empty window).  ONE launch of one workgroup of 256 threads,
+ * no atomics, capturable; it only reads its inputs and reads and writes the block.
+ *   planes    values, rewards, masks, y, adv float[T*N] and actions int32[T*N], row t * N + n; truncs float[T*N], nullable (the
+ *             plane of --bootstrap_truncated): sums of v, v^2, y, y^2, y - v, (y - v)^2, adv, adv^2 and the clipped reward, max
+ *             |adv|, counts of masks == 0, truncs != 0, rewards != 0 and of every action in [0, A).  Thread i takes rows i,
+ *             i + 256, ... in order, in fp64, every product and sum a separate round-to-nearest operation; the 256 partials are
+ *             added in index order
+ *   update    loss float[steps, 4], one row per optimizer step of the cycle (loss0, nullable float[4]: read in place of row 0);
+ *             ppo_stats, nullable float[steps, stats_cols], stats_cols 2 or 3 (column 2, value_clip_fraction, is live only with
+ *             3), summed over the steps >= stats_first; applied, nullable int32[steps] (--ppo_target_kl: steps with a non-zero
+ *             entry count as applied; NULL: all do); gnorm float[1], summed and maximised once per cycle
+ *   finished  nullable: the finished-episode ring (paac_synth_step).  Entries [acc_i[ring_cursor], count) are new; at most the
+ *             newest 4096 of them survive in the ring and are folded (sum and sum of squares of return and length, min and max,
+ *             which the fold that sees the window's first episode sets), the rest are counted as dropped; ring_cursor = count
+ * Refused with a message naming the argument, without a launch: a null pointer among in, acc_f, acc_i, the six planes, loss and
+ * gnorm; T * N < 1; A outside [2, 32]; steps outside [1, PAAC_PPO_STEPS_MAX]; with ppo_stats, stats_cols other than 2 or 3 and
+ * stats_first outside [0, steps]. */
+typedef struct {
+  int32_t T, N, A;
+  const float* values;
+  const float* rewards;
+  const float* masks;
+  const int32_t* actions;
+  const float* y;
+  const float* adv;
+  const float* truncs;
+  const float* loss;
+  const float* loss0;
+  int32_t steps;
+  const float* ppo_stats;
+  int32_t stats_cols;
+  int32_t stats_first;
+  const int32_t* applied;
+  const float* gnorm;
+  const void* finished;
+} paac_window_inputs;
+int paac_window_fields(int* n_f, int* n_i);
+int paac_window_fold(const paac_window_inputs* in, double* acc_f, int64_t* acc_i, paac_stream_t stream);
+
 /* paac.py:34-45 bit-exact: probs - float32.epsneg, then numpy legacy multinomial(1, p) per env in
  * index order on ONE MT19937 stream.  mt_state: device uint32[625] = numpy key[624] + pos, advanced
  * in place (import/export with np.random.get_state()/set_state()).  scratch: device, >=

@@ -60,6 +60,14 @@ class EnvRecords(ctypes.Structure):
                 ("finished", c_void_p), ("truncs", c_void_p)]
 
 
+class WindowInputs(ctypes.Structure):
+    """paac_window_inputs (include/paac_hip.h): what one cycle hands to the --window_stats fold."""
+    _fields_ = [("T", c_int32), ("N", c_int32), ("A", c_int32), ("values", c_void_p), ("rewards", c_void_p), ("masks", c_void_p),
+                ("actions", c_void_p), ("y", c_void_p), ("adv", c_void_p), ("truncs", c_void_p), ("loss", c_void_p),
+                ("loss0", c_void_p), ("steps", c_int32), ("ppo_stats", c_void_p), ("stats_cols", c_int32),
+                ("stats_first", c_int32), ("applied", c_void_p), ("gnorm", c_void_p), ("finished", c_void_p)]
+
+
 class KlGate(ctypes.Structure):
     """paac_kl_gate (include/paac_hip.h): the gate of a --ppo_target_kl optimizer step, every pointer in device memory."""
     _fields_ = [("kl", c_void_p), ("scale", c_float), ("thr", c_float), ("first", c_int), ("stop", c_void_p),
@@ -105,6 +113,8 @@ _SIGNATURES = {
     "paac_adv_normalize": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "paac_returns_norm_tick": (c_int, [c_void_p, c_void_p, POINTER(Returns), c_void_p, c_void_p, c_void_p]),
     "paac_returns_scan": (c_int, [POINTER(Returns), c_void_p]),
+    "paac_window_fields": (c_int, [POINTER(c_int), POINTER(c_int)]),
+    "paac_window_fold": (c_int, [POINTER(WindowInputs), c_void_p, c_void_p, c_void_p]),
     "paac_game_step": (c_int, [c_int, c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),

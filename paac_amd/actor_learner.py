@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, hip_ops, parallel
+from . import _lib, hip_ops, parallel, window_stats
 from .networks import Placeholder
 from .session import Saver, Session, checkpoint_key, tensor_of_key
 
@@ -78,6 +78,8 @@ class ActorLearner(object):
         if not isinstance(self.bootstrap_truncated, (bool, np.bool_)):
             raise ValueError("bootstrap_truncated %r: expected True or False" % (self.bootstrap_truncated,))
         self.bootstrap_truncated = bool(self.bootstrap_truncated)
+        # --window_stats (paac_amd/window_stats.py): Namespaces / args.json files without the field mean off
+        self.window_stats = window_stats.check_flags(args)
         self.ppo_vclip = float(getattr(args, "ppo_vclip", 0.0))
         if not (0.0 <= self.ppo_vclip and math.isfinite(self.ppo_vclip)):          # (NaN fails the comparison)
             raise ValueError("ppo_vclip %r: expected a finite value >= 0 (0 = off)" % (self.ppo_vclip,))

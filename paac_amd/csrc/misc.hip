@@ -144,6 +144,192 @@ __global__ __launch_bounds__(kNormThreads) void returns_norm_kernel(const RT r, 
   adv_normalize_block(r.adv_out, B, adv_n, stats, lds);
 }
 
+// --window_stats (spec and twin: paac_amd/window_stats.py; include/paac_hip.h has the contract): one cycle folded into the
+// window's accumulator block.  ONE workgroup of kWinThreads threads and no atomics, so the order of every float64 sum is fixed:
+// thread i takes rows i, i + 256, ... (and surviving ring entries i, i + 256, ...) in order, every product and sum a separate
+// round-to-nearest operation, and one finishing thread per field adds the 256 partials in index order out of LDS and stores
+// the field.  The four waves finish one part each -- row sums, counts, episodes, the update's scalars -- beside one another.
+// The block's offsets (window_stats.FIELDS_F / FIELDS_I; paac_window_fields reports the two lengths):
+constexpr int kWinThreads = 256;
+enum : int { kWfRowSums = 0 /* v v2 y y2 d d2 adv adv2, max|adv|, reward */, kWfMaxAbsAdv = 8, kWfSumLoss = 10, kWfSumStats = 14,
+             kWfSumGnorm = 17, kWfMaxGnorm = 18, kWfEpSums = 19 /* return, return2, length, length2 */,
+             kWfEpRetMin = 23 /* return min, return max, length min, length max */, kWinFieldsF = 27 };
+enum : int { kWiCycles = 0, kWiRows = 1, kWiTerminals = 2 /* terminals, truncated, nonzero rewards */, kWiOptSteps = 5,
+             kWiOptApplied = 6, kWiStatSteps = 7, kWiEpisodes = 8, kWiDropped = 9, kWiActionCount = 10, kWiRingCursor = 42,
+             kWinFieldsI = 43 };
+constexpr int kWinRowFields = 10, kWinActions = 32, kWinRing = 4096;
+static_assert(kWfEpRetMin == kWfEpSums + 4 && kWfMaxAbsAdv < kWinRowFields, "the finishing lanes index consecutive fields");
+// One finishing thread's walk over the 256 partials of its field, in index order: kWinOpAdd from 0.0, or the min / max of the
+// first `holders` partials.  16 partials are requested from LDS at a time and then combined one after the other -- the
+// order is the contract, the loads need not wait for one another.
+enum : int { kWinOpAdd = 0, kWinOpMin = 1, kWinOpMax = 2 };
+__device__ __forceinline__ double window_partials(const double* src, const int op, const int holders) {
+  double t = op == kWinOpAdd ? 0.0 : src[0];
+  for (int i0 = 0; i0 < kWinThreads; i0 += 16) {
+    double x[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) x[u] = src[i0 + u];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const double lo = fmin(t, x[u]), hi = fmax(t, x[u]);
+      t = op == kWinOpAdd ? __dadd_rn(t, x[u]) : (i0 + u < holders ? (op == kWinOpMin ? lo : hi) : t);
+    }
+  }
+  return t;
+}
+__device__ __forceinline__ int64_t window_counts(const int32_t* src) {
+  int64_t t = 0;
+  for (int i0 = 0; i0 < kWinThreads; i0 += 16) {
+    int32_t x[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) x[u] = src[i0 + u];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) t += x[u];
+  }
+  return t;
+}
+__global__ __launch_bounds__(kWinThreads) void window_fold_kernel(const paac_window_inputs w, double* __restrict__ acc_f,
+                                                                  int64_t* __restrict__ acc_i) {
+  __shared__ double row_p[kWinRowFields][kWinThreads];
+  __shared__ double ep_p[8][kWinThreads];
+  __shared__ int32_t cnt_p[3][kWinThreads];
+  __shared__ int32_t hist[kWinActions][kWinThreads];      // a column per thread: private, so plain read-modify-write
+  const int tid = threadIdx.x, B = w.T * w.N;
+  const FinishedRing* fin = (const FinishedRing*)w.finished;
+  // what the block and the ring say as the fold starts (each read once, before anything is stored)
+  const int64_t cursor = acc_i[kWiRingCursor], episodes0 = acc_i[kWiEpisodes];
+  const int64_t count = fin ? (int64_t)fin->count : cursor;
+#pragma unroll
+  for (int a = 0; a < kWinActions; ++a) hist[a][tid] = 0;
+  // ---- rows ----
+  double s[kWinRowFields];
+#pragma unroll
+  for (int q = 0; q < kWinRowFields; ++q) s[q] = 0.0;
+  int terminals = 0, truncated = 0, nonzero = 0;
+  constexpr int U = 4;      // passes requested at once: one memory round trip per U passes
+  for (int i0 = tid; i0 < B; i0 += U * kWinThreads) {
+    float v[U], y[U], ad[U], r[U], m[U], tr[U];
+    int32_t a[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = i0 + u * kWinThreads, j = i < B ? i : i0;
+      v[u] = w.values[j];
+      y[u] = w.y[j];
+      ad[u] = w.adv[j];
+      r[u] = w.rewards[j];
+      m[u] = w.masks[j];
+      a[u] = w.actions[j];
+      tr[u] = w.truncs ? w.truncs[j] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (i0 + u * kWinThreads < B) {
+        const double V = (double)v[u], Y = (double)y[u], D = __dsub_rn(Y, V), A = (double)ad[u];
+        s[0] = __dadd_rn(s[0], V);
+        s[1] = __dadd_rn(s[1], __dmul_rn(V, V));
+        s[2] = __dadd_rn(s[2], Y);
+        s[3] = __dadd_rn(s[3], __dmul_rn(Y, Y));
+        s[4] = __dadd_rn(s[4], D);
+        s[5] = __dadd_rn(s[5], __dmul_rn(D, D));
+        s[6] = __dadd_rn(s[6], A);
+        s[7] = __dadd_rn(s[7], __dmul_rn(A, A));
+        s[8] = fmax(s[8], fabs(A));
+        s[9] = __dadd_rn(s[9], (double)r[u]);
+        terminals += m[u] == 0.f;
+        truncated += tr[u] != 0.f;
+        nonzero += r[u] != 0.f;
+        if ((uint32_t)a[u] < (uint32_t)w.A) hist[a[u]][tid] += 1;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kWinRowFields; ++q) row_p[q][tid] = s[q];
+  cnt_p[0][tid] = terminals;
+  cnt_p[1][tid] = truncated;
+  cnt_p[2][tid] = nonzero;
+  // ---- the ring's new entries: [count - kept, count), slot = entry & 4095 ----
+  const int64_t fresh = count > cursor ? count - cursor : 0;
+  const int64_t dropped = fresh > kWinRing ? fresh - kWinRing : 0;
+  const int kept = (int)(fresh - dropped);
+  double e[4] = {0.0, 0.0, 0.0, 0.0}, lo_r = 0.0, hi_r = 0.0, lo_l = 0.0, hi_l = 0.0;
+  for (int k = tid; k < kept; k += kWinThreads) {
+    const int slot = (int)((count - kept + k) & (kWinRing - 1));
+    const double R = (double)fin->reward[slot], L = (double)fin->len[slot];
+    e[0] = __dadd_rn(e[0], R);
+    e[1] = __dadd_rn(e[1], __dmul_rn(R, R));
+    e[2] = __dadd_rn(e[2], L);
+    e[3] = __dadd_rn(e[3], __dmul_rn(L, L));
+    const bool first = k == tid;
+    lo_r = first ? R : fmin(lo_r, R);
+    hi_r = first ? R : fmax(hi_r, R);
+    lo_l = first ? L : fmin(lo_l, L);
+    hi_l = first ? L : fmax(hi_l, L);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) ep_p[q][tid] = e[q];
+  ep_p[4][tid] = lo_r;
+  ep_p[5][tid] = hi_r;
+  ep_p[6][tid] = lo_l;
+  ep_p[7][tid] = hi_l;
+  __syncthreads();
+  // ---- finish: one thread per field, the partials in index order ----
+  const int wave = tid >> 6, j = tid & 63;
+  if (wave == 0) {
+    if (j < kWinRowFields) {
+      const bool is_max = j == kWfMaxAbsAdv;
+      const double t = window_partials(row_p[j], is_max ? kWinOpMax : kWinOpAdd, kWinThreads);
+      acc_f[kWfRowSums + j] = is_max ? fmax(acc_f[kWfRowSums + j], t) : __dadd_rn(acc_f[kWfRowSums + j], t);
+    }
+  } else if (wave == 1) {
+    const bool is_action = j >= 8 && j < 8 + w.A;
+    if (j < 3 || is_action) {      // (one walk for both kinds of count: the lanes differ in where they read and write)
+      const int64_t t = window_counts(is_action ? hist[j - 8] : cnt_p[j]);
+      acc_i[is_action ? kWiActionCount + j - 8 : kWiTerminals + j] += t;
+    } else if (j == 48) {
+      acc_i[kWiCycles] += 1;
+      acc_i[kWiRows] += B;
+    }
+  } else if (wave == 2) {
+    if (fin && j < 8 && kept > 0) {
+      // j < 4: the four sums; above: min (j even) or max (j odd) over the threads that saw an entry, and the window's first
+      // episode sets the field.  One walk for all eight lanes
+      const bool is_sum = j < 4, is_max = j & 1;
+      const double t = window_partials(ep_p[j], is_sum ? kWinOpAdd : (is_max ? kWinOpMax : kWinOpMin),
+                                       kept < kWinThreads ? kept : kWinThreads);
+      const double old = acc_f[kWfEpSums + j];      // (kWfEpRetMin == kWfEpSums + 4: the eight fields are consecutive)
+      acc_f[kWfEpSums + j] = is_sum ? __dadd_rn(old, t) : (episodes0 == 0 ? t : (is_max ? fmax(old, t) : fmin(old, t)));
+    } else if (fin && j == 8) {
+      acc_i[kWiEpisodes] = episodes0 + kept;
+      acc_i[kWiDropped] += dropped;
+      acc_i[kWiRingCursor] = count;
+    }
+  } else {
+    if (j < 4) {
+      double t = 0.0;
+      for (int k = 0; k < w.steps; ++k) t = __dadd_rn(t, (double)((k == 0 && w.loss0) ? w.loss0[j] : w.loss[k * 4 + j]));
+      acc_f[kWfSumLoss + j] = __dadd_rn(acc_f[kWfSumLoss + j], t);
+    } else if (j < 7) {
+      if (w.ppo_stats && j - 4 < w.stats_cols) {
+        double t = 0.0;
+        for (int k = w.stats_first; k < w.steps; ++k) t = __dadd_rn(t, (double)w.ppo_stats[k * w.stats_cols + j - 4]);
+        acc_f[kWfSumStats + j - 4] = __dadd_rn(acc_f[kWfSumStats + j - 4], t);
+      }
+    } else if (j == 7) {
+      const double g = (double)w.gnorm[0];
+      acc_f[kWfSumGnorm] = __dadd_rn(acc_f[kWfSumGnorm], g);
+      acc_f[kWfMaxGnorm] = fmax(acc_f[kWfMaxGnorm], g);
+      int applied = w.steps;
+      if (w.applied) {
+        applied = 0;
+        for (int k = 0; k < w.steps; ++k) applied += w.applied[k] != 0;
+      }
+      acc_i[kWiOptSteps] += w.steps;
+      acc_i[kWiOptApplied] += applied;
+      if (w.ppo_stats) acc_i[kWiStatSteps] += w.steps - w.stats_first;
+    }
+  }
+}
+
 // actor_learner.py:119-123 evaluated after the cycle's increments (paac.py:127,156).
 __global__ void lr_step_kernel(int64_t* global_step, int64_t inc, double lr0, int64_t anneal, float* lr_out) {
   cycle_tick(CycleTick{global_step, inc, lr0, anneal, lr_out, nullptr, 0});
@@ -1651,6 +1837,38 @@ int paac_adv_normalize(const float* adv, int B, float* adv_n_out, double* stats_
   PAAC_REQUIRE(adv && adv_n_out, "paac_adv_normalize: null argument");
   PAAC_REQUIRE(B > 0, "paac_adv_normalize: B=%d", B);
   launch_k(adv_normalize_kernel, dim3(1), dim3(kNormThreads), (hipStream_t)stream, PROF_WHOLE, adv, B, adv_n_out, stats_out);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_window_fields(int* n_f, int* n_i) {
+  if (n_f) *n_f = kWinFieldsF;
+  if (n_i) *n_i = kWinFieldsI;
+  return 0;
+}
+
+int paac_window_fold(const paac_window_inputs* in, double* acc_f, int64_t* acc_i, paac_stream_t stream) {
+  PAAC_REQUIRE(in, "paac_window_fold: in is null");
+  PAAC_REQUIRE(acc_f, "paac_window_fold: acc_f is null");
+  PAAC_REQUIRE(acc_i, "paac_window_fold: acc_i is null");
+  PAAC_REQUIRE(in->values, "paac_window_fold: values is null");
+  PAAC_REQUIRE(in->rewards, "paac_window_fold: rewards is null");
+  PAAC_REQUIRE(in->masks, "paac_window_fold: masks is null");
+  PAAC_REQUIRE(in->actions, "paac_window_fold: actions is null");
+  PAAC_REQUIRE(in->y, "paac_window_fold: y is null");
+  PAAC_REQUIRE(in->adv, "paac_window_fold: adv is null");
+  PAAC_REQUIRE(in->loss, "paac_window_fold: loss is null");
+  PAAC_REQUIRE(in->gnorm, "paac_window_fold: gnorm is null");
+  PAAC_REQUIRE(in->T >= 1 && in->N >= 1 && (int64_t)in->T * in->N <= INT32_MAX, "paac_window_fold: T=%d N=%d (T * N < 1)", in->T,
+               in->N);
+  PAAC_REQUIRE(in->A >= 2 && in->A <= kWinActions, "paac_window_fold: A=%d outside [2, %d]", in->A, kWinActions);
+  PAAC_REQUIRE(in->steps >= 1 && in->steps <= PAAC_PPO_STEPS_MAX, "paac_window_fold: steps=%d outside [1, %d]", in->steps,
+               PAAC_PPO_STEPS_MAX);
+  PAAC_REQUIRE(!in->ppo_stats || in->stats_cols == 2 || in->stats_cols == 3, "paac_window_fold: stats_cols=%d (2, or 3 with "
+               "value_clip_fraction live)", in->stats_cols);
+  PAAC_REQUIRE(!in->ppo_stats || (in->stats_first >= 0 && in->stats_first <= in->steps),
+               "paac_window_fold: stats_first=%d outside [0, steps]", in->stats_first);
+  launch_k(window_fold_kernel, dim3(1), dim3(kWinThreads), (hipStream_t)stream, PROF_WHOLE, *in, acc_f, acc_i);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

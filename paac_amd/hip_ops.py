@@ -603,6 +603,58 @@ def returns_norm_tick(v_boot, rewards, masks, values, gamma, y_out, adv_out, adv
                "paac_returns_norm_tick")
 
 
+def window_fields():
+    """-> (n_f, n_i): the lengths of the --window_stats block the library was compiled for."""
+    n_f, n_i = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().paac_window_fields(ctypes.byref(n_f), ctypes.byref(n_i)), "paac_window_fields")
+    return int(n_f.value), int(n_i.value)
+
+
+def window_block(device):
+    """An empty --window_stats block on `device`: (acc_f float64[N_F], acc_i int64[N_I]), the spec's tables checked against
+    the compiled layout."""
+    from . import window_stats
+    if window_fields() != (window_stats.N_F, window_stats.N_I):
+        raise _lib.PaacHipError("window_stats.FIELDS_F / FIELDS_I hold %d / %d fields, the library was compiled for %d / %d"
+                                % ((window_stats.N_F, window_stats.N_I) + window_fields()))
+    return (torch.zeros(window_stats.N_F, dtype=torch.float64, device=device),
+            torch.zeros(window_stats.N_I, dtype=torch.int64, device=device))
+
+
+def window_fold(acc_f, acc_i, values, rewards, masks, actions, y, adv, num_actions, loss, gnorm, truncs=None, loss0=None,
+                ppo_stats=None, stats_first=0, applied=None, finished=None):
+    """--window_stats: one cycle folded into the block (include/paac_hip.h: paac_window_fold; spec: paac_amd/window_stats.py).
+    values / rewards / masks / actions (and truncs, or None) [T, N]; y / adv [T*N]; loss [steps, 4] (loss0 [4]: in place of its
+    row 0); ppo_stats [steps, 2 or 3] or None; applied int32 [steps] or None; gnorm [1]; finished: the episode ring or None."""
+    from . import window_stats
+    if values.dim() != 2:
+        raise ValueError("values must be [T,N], got %s" % (tuple(values.shape),))
+    T, N = values.shape
+    for nm, t in (("rewards", rewards), ("masks", masks), ("actions", actions), ("truncs", truncs)):
+        if t is not None and tuple(t.shape) != (T, N):
+            raise ValueError("%s must be [%d,%d] like the values, got %s" % (nm, T, N, tuple(t.shape)))
+    if loss.dim() != 2 or loss.shape[1] != 4:
+        raise ValueError("loss must be [steps,4], got %s" % (tuple(loss.shape),))
+    steps = loss.shape[0]
+    cols = 0
+    if ppo_stats is not None:
+        if ppo_stats.dim() != 2 or ppo_stats.shape[0] != steps or ppo_stats.shape[1] not in (2, 3):
+            raise ValueError("ppo_stats must be [%d,2] or [%d,3], got %s" % (steps, steps, tuple(ppo_stats.shape)))
+        cols = ppo_stats.shape[1]
+    if finished is not None and finished.numel() * finished.element_size() < FINISHED_RING_BYTES:
+        raise ValueError("finished ring too small")
+    f32 = torch.float32
+    block = _lib.WindowInputs(
+        T, N, int(num_actions), _ptr(values, f32, T * N, "values"), _ptr(rewards, f32, T * N, "rewards"),
+        _ptr(masks, f32, T * N, "masks"), _ptr(actions, torch.int32, T * N, "actions"), _ptr(y, f32, T * N, "y"),
+        _ptr(adv, f32, T * N, "adv"), _ptr(truncs, f32, T * N, "truncs", True), _ptr(loss, f32, steps * 4, "loss"),
+        _ptr(loss0, f32, 4, "loss0", True), steps, _ptr(ppo_stats, f32, steps * cols, "ppo_stats", True), cols, int(stats_first),
+        _ptr(applied, torch.int32, steps, "applied", True), _ptr(gnorm, f32, 1, "gnorm"),
+        _ptr(finished, torch.int32, FINISHED_RING_BYTES // 4, "finished", True))
+    _lib.check(_lib.load().paac_window_fold(ctypes.byref(block), _ptr(acc_f, torch.float64, window_stats.N_F, "acc_f"),
+                                            _ptr(acc_i, torch.int64, window_stats.N_I, "acc_i"), _stream()), "paac_window_fold")
+
+
 def uses_gae(gae_lambda):
     """THE routing rule of --gae_lambda: None (not given) and exactly 1.0 mean the reference's n-step return through the
     n-step kernels -- GAE(1) is the same quantity only up to the last place -- and every other value the GAE kernels."""

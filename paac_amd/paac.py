@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from . import hip_ops, logger_utils, parallel
+from . import hip_ops, logger_utils, parallel, window_stats
 from .actor_learner import ActorLearner
 from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Runners
 
@@ -88,6 +88,7 @@ class DeviceRollout(object):
     truncs = None      # --bootstrap_truncated: the [T, N] truncation plane, allocated by __init__ only where it applies
     pool = None        # --duel_pool: the duel_pool.DevicePool, created by __init__ only with the pool on
     act_pipeline = False   # the small act_step route as two launches per step (act_step_pipe), set by __init__ only where it applies
+    window_f = window_i = None   # --window_stats: the accumulator block (paac_amd/window_stats.py), allocated by __init__ only with the flag on
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
                  total_envs=None):
@@ -157,6 +158,12 @@ class DeviceRollout(object):
                                              float(getattr(largs, "duel_pool_latest_p", 0.5)),
                                              int(getattr(largs, "random_seed", env_spec["seed"])), int(L.global_step),
                                              device_index=dev.index or 0)
+        # --window_stats: the block one fold per cycle adds to, behind the cycle's last optimizer step (_update).  Off: no block,
+        # no launch, the same graphs
+        if getattr(L, "window_stats", False):
+            if parallel.collectives_active():
+                raise ValueError(window_stats.DATA_PARALLEL_REFUSAL)
+            self.window_f, self.window_i = hip_ops.window_block(dev)
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
         if env_spec.get("raw_frames"):
@@ -398,8 +405,12 @@ class DeviceRollout(object):
                             L.entropy_beta, L.grad, L.loss_dev, forward_done=True, phase=2)
 
     def _update(self, step):
-        """Optimizer step `step` of the cycle (--ppo_target_kl gates by it)."""
+        """Optimizer step `step` of the cycle (--ppo_target_kl gates by it); --window_stats: the cycle's fold behind its last one,
+        inside the captured cycle."""
         self.L.apply_gradients(step)
+        if self.window_f is not None and step == self.K - 1:
+            self.L.window_fold(self.window_f, self.window_i, self.values, self.rewards, self.masks, self.actions, self.y, self.adv,
+                               truncs=self.truncs, finished=self.finished)
 
     def capture(self):
         """Capture the cycle into hipGraphs: one per observation-ring parity (and a separate update graph when a
@@ -685,6 +696,8 @@ class PAACLearner(ActorLearner):
         self.metrics = None
         self.stop_requested = False      # set by the signal handler (train.py); honoured at the next cycle boundary
         self.host_truncated_steps = None   # host loop under --bootstrap_truncated: ones in the last rollout's truncation plane
+        self.host_window = None            # host loop under --window_stats: its (acc_f, acc_i) block
+        self.host_window_episodes = ([], [])   # ... and the (returns, lengths) of the episodes finished since the last record
 
     def _open_metrics(self):
         """metrics.jsonl in the debugging folder (rank 0 only): what the reference sends to TensorBoard."""
@@ -748,6 +761,48 @@ class PAACLearner(ActorLearner):
             mean, std = self.adv_stats.cpu().numpy()
             self.metrics.write("adv_norm", global_step=int(self.global_step), mean=float(mean), std=float(std))
         self.metrics.flush()
+
+    def window_fold(self, acc_f, acc_i, values, rewards, masks, actions, y, adv, truncs=None, finished=None):
+        """--window_stats: the cycle that has just had its last optimizer step, folded into the block -- the rollout's planes as
+        given, the update's scalars from where this learner's update options leave them."""
+        ppo = self.ppo_epochs > 1
+        hip_ops.window_fold(acc_f, acc_i, values, rewards, masks, actions, y, adv, self.num_actions,
+                            loss=self.ppo_loss if ppo else self.loss_dev.view(1, 4), gnorm=self.gnorm_dev, truncs=truncs,
+                            # (a full-batch PPO cycle reports epoch 1 through loss_dev, and its ppo_stats row 0 stays zero)
+                            loss0=self.loss_dev if ppo and not self.minibatch_on else None,
+                            ppo_stats=self.ppo_stats if ppo else None, stats_first=0 if self.minibatch_on else 1,
+                            applied=self.ppo_applied, finished=finished)
+
+    def _window_loss_rows(self):
+        """The loss scalars a cycle's fold read, one row per optimizer step (what window_fold hands over, on the host)."""
+        if self.ppo_epochs == 1:
+            return self.loss_dev.cpu().numpy().reshape(1, 4)
+        rows = self.ppo_loss.cpu().numpy().copy()
+        if not self.minibatch_on:
+            rows[0] = self.loss_dev.cpu().numpy()
+        return rows
+
+    def _window_read(self, acc_f, acc_i, episodes=None):
+        """--window_stats at a progress record: the block copied out (the caller has synchronised) and emptied on the current
+        stream -- ring_cursor stays with the ring -> (the `window` record's fields, what the log line gains).  episodes: the
+        host loop's (returns, lengths) of the window, folded on the host."""
+        acc = window_stats.Block(acc_f.cpu().numpy(), acc_i.cpu().numpy())
+        if episodes is not None:
+            window_stats.fold_episodes(acc, *episodes)
+        acc_f.zero_()
+        acc_i[:window_stats.FIELDS_I["ring_cursor"][0]].zero_()
+        truncation = self.rollout.truncs is not None if self.rollout is not None else bool(getattr(self, "truncation_on", False))
+        record = window_stats.summary(acc, num_actions=self.num_actions, truncation=truncation,
+                                      ppo=self.ppo_epochs > 1, vclip=self.vclip_on)
+        ev, ret = record["explained_variance"], record["episode_return_mean"]
+        return record, ", explained variance {}, {} episodes of mean return {} in the window".format(
+            "n/a" if ev is None else "%.4f" % ev, record["episodes"], "n/a" if ret is None else "%.4f" % ret)
+
+    def _window_record(self, record):
+        """The `window` record behind the `progress` record."""
+        if self.metrics is not None:
+            self.metrics.write("window", global_step=int(self.global_step), **record)
+            self.metrics.flush()
 
     @staticmethod
     def choose_next_actions(network, num_actions, states, session):
@@ -888,15 +943,21 @@ class PAACLearner(ActorLearner):
                 curr_time = time.time()
                 count, eps = self.rollout.finished_episodes()
                 last_ten = 0.0 if len(eps) < 1 else np.mean([r for r, _ in eps[-10:]])
-                logging.info("Ran {} steps, at {} steps/s ({} steps/s avg), last 10 rewards avg {}"
+                window, window_text = None, ""
+                if self.rollout.window_f is not None:
+                    with torch.cuda.stream(self.rollout.stream):
+                        window, window_text = self._window_read(self.rollout.window_f, self.rollout.window_i)
+                logging.info("Ran {} steps, at {} steps/s ({} steps/s avg), last 10 rewards avg {}{}"
                              .format(self.global_step, chunk * steps_per_cycle / (curr_time - loop_start_time),
-                                     (self.global_step - global_step_start) / (curr_time - start_time), last_ten))
+                                     (self.global_step - global_step_start) / (curr_time - start_time), last_ten, window_text))
                 if metrics is not None:
                     for r, l in eps[max(0, len(eps) - (count - episodes_seen)):]:     # new since the last drain
                         metrics.write("episode", global_step=int(self.global_step), reward=float(r), length=int(l))
                     episodes_seen = count
                     self._progress_record(chunk * steps_per_cycle / (curr_time - loop_start_time),
                                           (self.global_step - global_step_start) / (curr_time - start_time), last_ten)
+                if window is not None:
+                    self._window_record(window)
             if pool is not None and pool.schedule.due(self.global_step):
                 # a pool event, between two run_cycles calls and on the rollout's stream: two device-to-device copies and the
                 # repack, queued behind the cycles already issued -- nothing here waits for the GPU
@@ -1009,6 +1070,10 @@ class PAACLearner(ActorLearner):
         mt_state = hip_ops.mt_state_from_numpy(np.random.get_state(), dev)
         mt_scratch = hip_ops.sample_mt_scratch(N, A, dev)
         mb_step = torch.zeros((1,), dtype=torch.int64, device=dev)      # --ppo_minibatches: the shuffles' step counter
+        # --window_stats: the block (folded eagerly once per cycle, behind the update) and the window's episodes so far
+        if self.window_stats and parallel.collectives_active():
+            raise ValueError(window_stats.DATA_PARALLEL_REFUSAL)
+        self.host_window = hip_ops.window_block(dev) if self.window_stats else None
         rewards = np.zeros((T, N), dtype=np.float32)
         masks = np.zeros((T, N), dtype=np.float32)
         # the sampled action indices come back through a page-locked buffer: an asynchronous copy + an event instead of a
@@ -1043,6 +1108,9 @@ class PAACLearner(ActorLearner):
             self.global_step += N * world
             for e in np.nonzero(step_overs)[0]:
                 total_rewards.append(total_episode_rewards[e])
+                if self.host_window is not None:
+                    self.host_window_episodes[0].append(total_episode_rewards[e])
+                    self.host_window_episodes[1].append(emulator_steps[e])
                 if metrics is not None:                      # paac.py:130-135
                     metrics.write("episode", global_step=int(before + (e + 1) * world),
                                   reward=float(total_episode_rewards[e]), length=int(emulator_steps[e]))
@@ -1148,13 +1216,18 @@ class PAACLearner(ActorLearner):
                     self.ppo_epoch_backward(k, d_states.view(T * N, 84, 84, 4), d_actions.view(-1), d_y, d_actor_adv, phase=0)
                     self._allreduce_grad()
                     self.apply_gradients(k)
+            if self.host_window is not None:
+                self.window_fold(*self.host_window, d_values, d_rewards, d_masks, d_actions, d_y, d_adv, truncs=d_truncs)
             if getattr(self.args, "record_feeds", False):
                 self.last_feed = dict(states=d_states.view(T * N, 84, 84, 4).cpu().numpy(), y=d_y.cpu().numpy(),
                                       adv=d_adv.cpu().numpy(), actions=d_actions.view(-1).cpu().numpy(), lr=lr,
                                       values=d_values.cpu().numpy(), global_step=self.global_step,
                                       rewards=d_rewards.cpu().numpy(), masks=d_masks.cpu().numpy(),
                                       v_boot=d_vboot.cpu().numpy(),
-                                      **(dict(truncs=d_truncs.cpu().numpy()) if truncation_on else {}))
+                                      **(dict(truncs=d_truncs.cpu().numpy()) if truncation_on else {}),
+                                      # --window_stats: the update's scalars the cycle's fold read (one row per optimizer step)
+                                      **(dict(window_loss=self._window_loss_rows(), window_gnorm=self.gnorm_dev.cpu().numpy())
+                                         if self.host_window is not None else {}))
                 if getattr(self.args, "feed_callback", None):
                     self.args.feed_callback(self.last_feed)
             if getattr(self.args, "cycle_callback", None):      # bench hook: one call per finished cycle, nothing copied
@@ -1168,11 +1241,18 @@ class PAACLearner(ActorLearner):
             if counter % (2048 / self.emulator_counts) == 0:
                 curr_time = time.time()
                 last_ten = 0.0 if len(total_rewards) < 1 else np.mean(total_rewards[-10:])
-                logging.info("Ran {} steps, at {} steps/s ({} steps/s avg), last 10 rewards avg {}"
+                window, window_text = None, ""
+                if self.host_window is not None:
+                    host_stream.synchronize()
+                    window, window_text = self._window_read(*self.host_window, episodes=self.host_window_episodes)
+                    self.host_window_episodes = ([], [])
+                logging.info("Ran {} steps, at {} steps/s ({} steps/s avg), last 10 rewards avg {}{}"
                              .format(self.global_step, T * N * world / (curr_time - loop_start_time),
-                                     (self.global_step - global_step_start) / (curr_time - start_time), last_ten))
+                                     (self.global_step - global_step_start) / (curr_time - start_time), last_ten, window_text))
                 self._progress_record(T * N * world / (curr_time - loop_start_time),
                                       (self.global_step - global_step_start) / (curr_time - start_time), last_ten)
+                if window is not None:
+                    self._window_record(window)
             self.save_vars()
         host_stream.synchronize()
         ctx_stream.__exit__(None, None, None)

@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import duel_pool, environment_creator, evaluation, logger_utils, match, parallel
+from . import duel_pool, environment_creator, evaluation, logger_utils, match, parallel, window_stats
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -127,6 +127,12 @@ BUILD_FLAGS = (
      "bootstraps its return from the value of the last state seen, r + gamma x V, instead of counting the state as worth "
      "nothing (partial-episode bootstrapping; either estimator, every update option, device and host loops); the step is "
      "still terminal and the environment still resets; accepted and without effect for catch, synthetic and ale"),
+    (("--window_stats",), "window_stats", False, bool_arg,
+     "off by default; true = every cycle is folded on the GPU into running statistics of the log window (one small launch per "
+     "cycle behind the update, device and host loops; paac_amd/window_stats.py), and every 'progress' record is followed by a "
+     "'window' record in metrics.jsonl: explained variance of the critic, value / return / advantage moments, action "
+     "frequencies, the loss scalars and gradient norm averaged over all updates, and the statistics of all episodes finished "
+     "in the window; one GPU only (refused under data parallelism).  Training is bit-identical with it on or off"),
     (("--eval_every",), "eval_every", 0, int,
      "device loop, --emulator catch|bricks|rally: score the current policy on --eval_count held-out game instances (seed random_seed "
      "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "
@@ -234,6 +240,7 @@ def main(args):
     check_eval_flags(args, world)                 # --eval_every's refusals, before a learner exists
     match.check_train_flags(args)                 # ... and --eval_match's
     duel_pool.check_train_flags(args, world)      # ... and --duel_pool's
+    window_stats.check_flags(args, world)         # ... and --window_stats'
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)
     setup_kill_signal_handler(learner)

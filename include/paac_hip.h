@@ -770,6 +770,44 @@ int paac_eval_step(int game, const float* probs, int N, int A, int greedy, uint6
                    const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
                    const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out, int32_t* actions_out,
                    float* score, int32_t* length, int32_t* done, int32_t* alive, paac_stream_t stream);
+/* Sticky actions (--sticky_action_p; spec and numpy twin: paac_amd/sticky.py; Machado et al., arXiv 1709.06009): at every
+ * step, with probability p, an environment executes the action it EXECUTED on its previous step instead of the chosen one.
+ *   draw     u = the 24 high bits of word 0 of philox4x32-10(ctr = {g, t lo, t hi, stream}; key = seed) * 2^-24 as a float32;
+ *            the step sticks iff u < p.  g = env_offset + ROW (duel: the two players of a board stick independently),
+ *            t = *step_base_dev + step_offset (base NULL = 0).  Training: stream 0x53544B01, seed = the step's `seed`;
+ *            evaluation: stream 0x45560004, seed = eval_seed, t = the evaluation step (no-op steps included).  Neither stream
+ *            is one in use (0, 0x504D0000 + epoch, 0x45560001..3, 0x44500001, 0x44500003).
+ *   executed = sticks ? prev_in[e] : chosen, where chosen = actions[e] (training) or the evaluation's own action; the game
+ *            steps on `executed` exactly as the plain entry does on its action.  A duel row also works out its partner's
+ *            executed action from actions[partner], prev_in[partner] and the partner's own draw: both rows hold the same pair.
+ *   planes   prev_in i32 [N] is read, prev_out[e] (and prev_out2[e] when given: the ring's wrap-around slot) = 0 after a
+ *            terminal step, else executed.  A run starts from a zeroed plane: 0 is every game's no-op.
+ *   records  everything else -- states, stacks, rewards, masks, truncs, the episode bookkeeping, the evaluation's accounts -- as
+ *            the plain entry's on the executed action; `actions` / actions_out keep the CHOSEN action (the agent is not told).
+ * p = 0 gives the plain entry's outputs bit for bit.  One launch, the plain entry's grid; no reset form (the plain reset and a
+ * zeroed plane).  Refused with a message, without a launch: everything the plain entry refuses, p outside [0, 1) or NaN, a
+ * null block, null prev_in / prev_out, prev_in == prev_out or prev_out2.  paac_game_step_sticky serves every PAAC_EVAL_* id,
+ * PAAC_EVAL_USER in a library built with a user game (the stock library refuses that id by name, as paac_game_step does). */
+typedef struct {
+  float p;
+  const uint64_t* step_base_dev;
+  uint64_t step_offset;
+  const int32_t* prev_in;
+  int32_t* prev_out;
+  int32_t* prev_out2;
+} paac_sticky;
+int paac_game_step_sticky(int game, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                          int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                          uint8_t* stack_out2, const paac_env_records* rec, int option, const paac_sticky* sticky,
+                          paac_stream_t stream);
+int paac_duel_step_sticky(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                          int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                          uint8_t* stack_out2, const paac_env_records* rec, const paac_sticky* sticky, paac_stream_t stream);
+int paac_eval_step_sticky(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
+                          const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
+                          const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out,
+                          int32_t* actions_out, float* score, int32_t* length, int32_t* done, int32_t* alive, float p,
+                          const int32_t* prev_in, int32_t* prev_out, paac_stream_t stream);
 /* A head-to-head match on the duel board (spec: paac_amd/match.py): one step of N rows = N / 2 boards in one launch, behind the
  * TWO acting forwards that wrote probs [N, 6] -- rows [0, N / 2) by the bottom players' policy, rows [N / 2, N) by the top
  * players'.  paac_eval_step's argument list without `game`; rows, records and the board key g = env_offset + board are

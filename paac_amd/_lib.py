@@ -60,6 +60,12 @@ class EnvRecords(ctypes.Structure):
                 ("finished", c_void_p), ("truncs", c_void_p)]
 
 
+class Sticky(ctypes.Structure):
+    """paac_sticky (include/paac_hip.h): what a sticky-action training step takes beyond the plain step's arguments."""
+    _fields_ = [("p", c_float), ("step_base_dev", c_void_p), ("step_offset", c_uint64), ("prev_in", c_void_p),
+                ("prev_out", c_void_p), ("prev_out2", c_void_p)]
+
+
 class WindowInputs(ctypes.Structure):
     """paac_window_inputs (include/paac_hip.h): what one cycle hands to the --window_stats fold."""
     _fields_ = [("T", c_int32), ("N", c_int32), ("A", c_int32), ("values", c_void_p), ("rewards", c_void_p), ("masks", c_void_p),
@@ -209,6 +215,11 @@ _SIGNATURES["paac_duel_ghost_step"] = (c_int, [c_uint64, c_uint32, c_int, c_void
 _SIGNATURES["paac_user_game_info"] = (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)])
 _SIGNATURES["paac_user_game_reset"] = _SIGNATURES["paac_catch_reset"]
 _SIGNATURES["paac_user_game_step"] = (c_int, [c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p])
+# sticky actions (paac_amd/sticky.py): paac_game_step's and paac_duel_step's lists with the paac_sticky block before the stream,
+# paac_eval_step's with p, prev_in, prev_out before it
+_SIGNATURES["paac_game_step_sticky"] = (c_int, _SIGNATURES["paac_game_step"][1][:-1] + [POINTER(Sticky), c_void_p])
+_SIGNATURES["paac_duel_step_sticky"] = (c_int, _SIGNATURES["paac_duel_step"][1][:-1] + [POINTER(Sticky), c_void_p])
+_SIGNATURES["paac_eval_step_sticky"] = (c_int, _SIGNATURES["paac_eval_step"][1][:-1] + [c_float, c_void_p, c_void_p, c_void_p])
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -30,7 +30,8 @@ KEPT = 2                 # screens of a step that reach the observation
 MAX_START_WAIT = 30
 
 # (setter, key, value) applied before the ROM is loaded: explicit action repeat means no sticky actions, no ALE-side
-# frame skip and no colour averaging (atari_emulator.py:19-24)
+# frame skip and no colour averaging (atari_emulator.py:19-24).  --sticky_action_p P takes the place of the first value: ALE's
+# own sticky actions (the default, 0.0, is the reference's)
 _ALE_OPTIONS = (("setFloat", b"repeat_action_probability", 0.0), ("setInt", b"frame_skip", 1),
                 ("setBool", b"color_averaging", False))
 
@@ -50,6 +51,8 @@ class AtariEmulator(BaseEnvironment):
         self.ale = _open_ale() if ale is None else ale
         self.ale.setInt(b"random_seed", args.random_seed * (actor_id + 1))        # per-actor seed, :18
         for setter, key, value in _ALE_OPTIONS:
+            if key == b"repeat_action_probability":
+                value = float(getattr(args, "sticky_action_p", 0.0) or 0.0)
             getattr(self.ale, setter)(key, value)
         self.ale.loadROM(("%s/%s.bin" % (args.rom_path, args.game)).encode())
         self.legal_actions = self.ale.getMinimalActionSet()

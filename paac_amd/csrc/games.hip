@@ -45,24 +45,92 @@ static_assert(UserGame::kMaxSteps > 0, "a user game's kMaxSteps must be positive
 // A paired game (duel: game_dev.h, duel_dev.h) widens that contract by one word: the new state of row e is a pure function of
 // (state_in[e], actions[e], actions[partner of e]) -- one more 4-byte load beside the own action's, of a value the launch
 // before this one wrote; N is even.  Still no row writes what another row reads, no atomics, no LDS.
-template <class G>
+//
+// Sticky actions (--sticky_action_p; spec: paac_amd/sticky.py): the compile-time form kSticky of the two step kernels.  With
+// probability p the environment executes the action it executed on its previous step instead of the one chosen: one Philox
+// block per row and step, counter {g, t lo, t hi, stream}, key the seed, g = env_offset + ROW (a paired game's two players
+// stick independently), t = *step_base + step_off.  The previous action is one more 4-byte load per row, from prev_in, asked
+// for beside the action's; every band workgroup recomputes draw and executed action in registers; thread 0 of band 0 stores
+// prev_out[e] (and prev_out2[e], the ring's wrap-around slot) = 0 after a terminal step, else the executed action.  prev_in is
+// never prev_out or prev_out2: nothing the launch reads is written by it.  The plain form (kSticky = false) takes the
+// arguments it always took and is the code it always was: the sticky form's arguments ride in the TYPE of the last one.
+// paac_amd/sticky.py: STICKY_STREAM / EVAL_STREAM_STICKY are the same numbers.
+constexpr uint32_t kStickyStream = 0x53544B01u;
+constexpr uint32_t kEvalStreamSticky = 0x45560004u;
+
+// The executed action of row g at step t: `prev` where the draw sticks, else `chosen`.  p = 0 never sticks (u >= 0).
+__device__ __forceinline__ int sticky_action(int chosen, int prev, float p, uint64_t seed, uint32_t g, uint64_t t,
+                                             uint32_t stream) {
+  uint32_t c[4] = {g, (uint32_t)t, (uint32_t)(t >> 32), stream};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const float u = (float)(c[0] >> 8) * (1.0f / 16777216.0f);
+  return u < p ? prev : chosen;
+}
+
+// What a sticky training step takes beyond the plain one's arguments (include/paac_hip.h: paac_sticky).
+struct StickyStep {
+  float p;
+  const uint64_t* step_base;
+  uint64_t step_off;
+  const int32_t* prev_in;
+  int32_t* prev_out;
+  int32_t* prev_out2;
+};
+struct StickyOpt {
+  int opt;
+  StickyStep st;
+};
+// game_step_kernel's last argument: the game's integer option, with the sticky block behind it in the sticky form.
+template <bool kSticky>
+struct step_tail {
+  typedef int type;
+};
+template <>
+struct step_tail<true> {
+  typedef StickyOpt type;
+};
+
+template <class G, bool kSticky = false>
 __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t env_offset, int N,
                                                         const int32_t* __restrict__ actions,
                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
                                                         int32_t* __restrict__ state_out2,
                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
-                                                        uint32_t* __restrict__ stack_out2, const EnvRecords rec, int opt) {
+                                                        uint32_t* __restrict__ stack_out2, const EnvRecords rec,
+                                                        const typename step_tail<kSticky>::type tail) {
   const QuadThread t = quad_thread();
   const int e = t.e;
   uint4 old = make_uint4(0u, 0u, 0u, 0u);
   typename G::State s;
   float r = 0.f;
   bool term = false, trunc = false;
+  int opt, executed = 0;
+  if constexpr (kSticky) opt = tail.opt;
+  else opt = tail;
   if (state_in) {
     // every thread loads (the four that own no quad read the band's first one): with the load under a condition the compiler
     // pulls the history's shift up behind it, and with the shift the wait -- the state record would be asked for only then
     old = reinterpret_cast<const uint4*>(stack_in)[t.load_quad];
-    if constexpr (game_is_paired<G>::value) {
+    if constexpr (kSticky) {
+      // everything the step reads is asked for here, before the draws: the actions and the previous actions of the row (and
+      // of its partner), the tick and the state record -- one round trip
+      const StickyStep& st = tail.st;
+      const uint64_t tk = (st.step_base ? *st.step_base : 0ull) + st.step_off;
+      const typename G::State s0 = G::load(state_in, e);
+      const int chosen = actions[e], prev = st.prev_in[e];
+      if constexpr (game_is_paired<G>::value) {
+        // the partner's executed action by the same device function on the partner's own row key: both rows of a board hold
+        // the same pair bit for bit (match_step_kernel's way with the partner's action)
+        const int pe = G::partner(e, N);
+        const int chosen_p = actions[pe], prev_p = st.prev_in[pe];
+        executed = sticky_action(chosen, prev, st.p, seed, env_offset + (uint32_t)e, tk, kStickyStream);
+        const int executed_p = sticky_action(chosen_p, prev_p, st.p, seed, env_offset + (uint32_t)pe, tk, kStickyStream);
+        s = G::advance(seed, env_offset + (uint32_t)G::board(e, N), s0, executed, executed_p, G::is_top(e, N), &r, &term, &trunc);
+      } else {
+        executed = sticky_action(chosen, prev, st.p, seed, env_offset + (uint32_t)e, tk, kStickyStream);
+        s = G::advance(seed, env_offset + (uint32_t)e, s0, executed, opt, &r, &term, &trunc);
+      }
+    } else if constexpr (game_is_paired<G>::value) {
       // a paired game (game_dev.h): the other player's action too -- the sampler's launch wrote both before this one started
       s = G::advance(seed, env_offset + (uint32_t)G::board(e, N), G::load(state_in, e), actions[e], actions[G::partner(e, N)],
                      G::is_top(e, N), &r, &term, &trunc);
@@ -79,6 +147,11 @@ __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t 
     if (state_in) {
       env_bookkeep(r, term, e, rec.ep_reward[e], rec.ep_len[e], rec);
       if (rec.truncs) rec.truncs[e] = trunc ? 1.f : 0.f;     // --bootstrap_truncated: why the episode ended (game_dev.h)
+      if constexpr (kSticky) {
+        const int keep = term ? 0 : executed;                // the first step of an episode has no previous action: the no-op
+        tail.st.prev_out[e] = keep;
+        if (tail.st.prev_out2) tail.st.prev_out2[e] = keep;
+      }
     }
   }
   if (!t.owner) return;
@@ -101,18 +174,45 @@ __global__ __launch_bounds__(256) void game_step_kernel(uint64_t seed, uint32_t 
 constexpr uint32_t kEvalStreamAction = 0x45560001u;
 constexpr uint32_t kEvalStreamNoop = 0x45560002u;
 
-template <class G>
+// The sticky form (kSticky, see game_step_kernel): the draw's stream is kEvalStreamSticky, its key the evaluation's seed, its
+// step the evaluation step t, no-op steps included (there the chosen action is 0 and so is the previous one).  actions_out
+// keeps the CHOSEN action: the trace replays through wrapped twins, which draw again.
+struct StickyAlive {
+  int32_t* alive;
+  float p;
+  const int32_t* prev_in;
+  int32_t* prev_out;
+};
+// eval_step_kernel's last argument: the alive counter, with the sticky arguments behind it in the sticky form.
+template <bool kSticky>
+struct eval_tail {
+  typedef int32_t* type;
+};
+template <>
+struct eval_tail<true> {
+  typedef StickyAlive type;
+};
+
+template <class G, bool kSticky = false>
 __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict__ probs, int A, int greedy, uint64_t eval_seed,
                                                         int noops, const uint64_t* __restrict__ step_base, uint64_t step_off,
                                                         uint64_t env_seed, uint32_t env_offset, int N,
                                                         const int32_t* __restrict__ state_in, int32_t* __restrict__ state_out,
                                                         const uint32_t* __restrict__ stack_in, uint32_t* __restrict__ stack_out,
                                                         int32_t* __restrict__ actions_out, float* score, int32_t* length,
-                                                        int32_t* done, int32_t* alive) {
+                                                        int32_t* done, const typename eval_tail<kSticky>::type tail) {
   const QuadThread th = quad_thread();
   const int e = th.e;
   // every thread loads (the four that own no quad read the band's first one): see game_step_kernel
   const uint4 old = reinterpret_cast<const uint4*>(stack_in)[th.load_quad];
+  int32_t* alive;
+  int prev = 0;
+  if constexpr (kSticky) {
+    alive = tail.alive;
+    prev = tail.prev_in[e];                                  // asked for up front, beside the probabilities
+  } else {
+    alive = tail;
+  }
   const uint32_t g = env_offset + (uint32_t)e;
   const uint64_t t = (step_base ? *step_base : 0ull) + step_off;
   uint32_t noops_e = 0u;
@@ -151,11 +251,14 @@ __global__ __launch_bounds__(256) void eval_step_kernel(const float* __restrict_
   }
   float r = 0.f;
   bool term = false;
+  int executed = act;
+  if constexpr (kSticky) executed = sticky_action(act, prev, tail.p, eval_seed, g, t, kEvalStreamSticky);
   // evaluation plays whole episodes: opt = 0 (bricks' single_life is off)
-  const typename G::State s = G::advance(env_seed, g, G::load(state_in, e), act, 0, &r, &term);
+  const typename G::State s = G::advance(env_seed, g, G::load(state_in, e), executed, 0, &r, &term);
   if (th.band == 0 && th.i == 0) {
     G::store(state_out, e, s);
     actions_out[e] = act;
+    if constexpr (kSticky) tail.prev_out[e] = term ? 0 : executed;
     if (playing && done[e] == 0) {                         // the first episode that starts after the no-ops, its last step included
       score[e] += r;
       length[e] += 1;
@@ -382,6 +485,39 @@ static int game_step(const char* name, uint64_t seed, uint32_t env_offset, int N
   return 0;
 }
 
+// What the sticky entries refuse about their own arguments, in the name of the entry: p outside [0, 1) (a NaN fails both
+// comparisons), a null plane, a plane read and written by one launch.
+static int sticky_check(const char* name, float p, const int32_t* prev_in, const int32_t* prev_out, const int32_t* prev_out2) {
+  PAAC_REQUIRE(p >= 0.f && p < 1.f, "%s: sticky p=%g is outside [0, 1)", name, (double)p);
+  PAAC_REQUIRE(prev_in && prev_out, "%s: null prev_in / prev_out", name);
+  PAAC_REQUIRE(prev_in != prev_out && prev_in != prev_out2,
+               "%s: prev_in is prev_out or prev_out2: the step cannot run in place (every band workgroup of an environment "
+               "reads prev_in)", name);
+  return 0;
+}
+
+// game_step with sticky actions: the same refusals, then the sticky block's, then game_step_kernel's sticky form.
+template <class G>
+static int game_step_sticky(const char* name, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions,
+                            const int32_t* state_in, int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in,
+                            uint8_t* stack_out, uint8_t* stack_out2, const EnvRecords& rec, int opt, const paac_sticky* sticky,
+                            paac_stream_t stream) {
+  PAAC_REQUIRE(N > 0 && actions && state_in && state_out && stack_in && stack_out && rec.rewards && rec.masks && rec.ep_reward &&
+               rec.ep_len, "%s: bad arguments", name);
+  PAAC_REQUIRE(state_in != state_out && state_in != state_out2 && stack_in != stack_out && stack_in != stack_out2,
+               "%s: the step cannot run in place (every band workgroup of an environment reads state_in)", name);
+  PAAC_REQUIRE(sticky, "%s: null sticky block", name);
+  if (int rc = sticky_check(name, sticky->p, sticky->prev_in, sticky->prev_out, sticky->prev_out2)) return rc;
+  const StickyOpt tail = {opt, {sticky->p, sticky->step_base_dev, sticky->step_offset, sticky->prev_in, sticky->prev_out,
+                                sticky->prev_out2}};
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+  launch_k(game_step_kernel<G, true>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, seed, env_offset, N, actions, state_in,
+           state_out, state_out2, (const uint32_t*)stack_in, (uint32_t*)stack_out, (uint32_t*)stack_out2, rec, tail);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // The records of a step as the kernels take them: from the five pointers of a per-game entry (no truncation plane), or from
 // the public block.
 static EnvRecords env_records_of(float* rewards, float* masks, float* ep_reward, int32_t* ep_len, void* finished,
@@ -520,6 +656,53 @@ int paac_game_step(int game, uint64_t seed, uint32_t env_offset, int N, const in
     PAAC_REQUIRE(rec, "paac_game_step: null records");
     return game_step<decltype(g)>("paac_game_step", seed, env_offset, N, actions, state_in, state_out, state_out2, stack_in,
                                   stack_out, stack_out2, env_records_of(rec), opt, stream);
+  });
+}
+
+// Sticky actions (spec: paac_amd/sticky.py): paac_game_step / paac_duel_step / paac_eval_step with the sticky arguments
+// behind their lists -- the plain entries' refusals, then sticky_check's, then the kernels' sticky forms.
+int paac_game_step_sticky(int game, uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                          int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                          uint8_t* stack_out2, const paac_env_records* rec, int option, const paac_sticky* sticky,
+                          paac_stream_t stream) {
+  return with_game("paac_game_step_sticky", game, option, [&](auto g, int opt) {
+    PAAC_REQUIRE(rec, "paac_game_step_sticky: null records");
+    return game_step_sticky<decltype(g)>("paac_game_step_sticky", seed, env_offset, N, actions, state_in, state_out, state_out2,
+                                         stack_in, stack_out, stack_out2, env_records_of(rec), opt, sticky, stream);
+  });
+}
+
+int paac_duel_step_sticky(uint64_t seed, uint32_t env_offset, int N, const int32_t* actions, const int32_t* state_in,
+                          int32_t* state_out, int32_t* state_out2, const uint8_t* stack_in, uint8_t* stack_out,
+                          uint8_t* stack_out2, const paac_env_records* rec, const paac_sticky* sticky, paac_stream_t stream) {
+  PAAC_REQUIRE(N >= 2 && N % 2 == 0, "paac_duel_step_sticky: N=%d is not an even number of rows >= 2 (two rows per board)", N);
+  PAAC_REQUIRE(rec, "paac_duel_step_sticky: null records");
+  return game_step_sticky<DuelGame>("paac_duel_step_sticky", seed, env_offset, N, actions, state_in, state_out, state_out2,
+                                    stack_in, stack_out, stack_out2, env_records_of(rec), 0, sticky, stream);
+}
+
+int paac_eval_step_sticky(int game, const float* probs, int N, int A, int greedy, uint64_t eval_seed, int noops,
+                          const uint64_t* step_base_dev, uint64_t step_offset, uint64_t env_seed, uint32_t env_offset,
+                          const int32_t* state_in, int32_t* state_out, const uint8_t* stack_in, uint8_t* stack_out,
+                          int32_t* actions_out, float* score, int32_t* length, int32_t* done, int32_t* alive, float p,
+                          const int32_t* prev_in, int32_t* prev_out, paac_stream_t stream) {
+  return with_game("paac_eval_step_sticky", game, 0, [&](auto g, int) {
+    PAAC_REQUIRE(N > 0, "paac_eval_step_sticky: N=%d", N);
+    PAAC_REQUIRE(A >= 2 && A <= 32, "paac_eval_step_sticky: A=%d outside [2, 32]", A);
+    PAAC_REQUIRE(noops >= 0, "paac_eval_step_sticky: noops=%d is negative", noops);
+    PAAC_REQUIRE(probs && state_in && state_out && stack_in && stack_out && actions_out && score && length && done && alive,
+                 "paac_eval_step_sticky: bad arguments");
+    PAAC_REQUIRE(state_in != state_out && stack_in != stack_out,
+                 "paac_eval_step_sticky: the step cannot run in place (every band workgroup of an environment reads state_in)");
+    if (int rc = sticky_check("paac_eval_step_sticky", p, prev_in, prev_out, nullptr)) return rc;
+    const StickyAlive tail = {alive, p, prev_in, prev_out};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(g_prof_ctx, F_ENV_STEP, N, s);
+    launch_k(eval_step_kernel<decltype(g), true>, dim3(N, PRE_BANDS), dim3(256), s, PROF_WHOLE, probs, A, greedy, eval_seed,
+             noops, step_base_dev, step_offset, env_seed, env_offset, N, state_in, state_out, (const uint32_t*)stack_in,
+             (uint32_t*)stack_out, actions_out, score, length, done, tail);
+    PAAC_CHECK_HIP(hipGetLastError());
+    return 0;
   });
 }
 

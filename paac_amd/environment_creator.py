@@ -13,7 +13,7 @@ from the specification module at PATH).
 A user environment plugs in exactly as in the reference: subclass BaseEnvironment and return it from
 create_environment(i).
 """
-from . import bricks, catch, duel, rally, user_game
+from . import bricks, catch, duel, rally, sticky, user_game
 from .synthetic import SyntheticEnvironment, terminal_threshold
 
 # ALE minimal action set sizes.
@@ -61,7 +61,7 @@ class EnvironmentCreator(object):
             module = user_game.load(args.device_game)
             self._user_options = user_game.option_keys(module)
             self.num_actions = module.NUM_ACTIONS
-            self.create_environment = lambda i: module.Environment(i, seed=self._seed(), **self._game_options())
+            self.create_environment = self._sticky(lambda i: module.Environment(i, seed=self._seed(), **self._game_options()))
             return
         if self._game in DEVICE_GAMES:
             # games of their own (-g is ignored), with their own action counts; no raw-screen form
@@ -70,7 +70,7 @@ class EnvironmentCreator(object):
                                  "synthetic only" % self._game)
             module, env_class, _ = DEVICE_GAMES[self._game]
             self.num_actions = module.NUM_ACTIONS
-            self.create_environment = lambda i: env_class(i, seed=self._seed(), **self._game_options())
+            self.create_environment = self._sticky(lambda i: env_class(i, seed=self._seed(), **self._game_options()))
             return
         if self._game in PAIRED_GAMES:
             # a paired game (paac_amd/duel.py): device loop only -- a row needs its partner's action, and the host loop steps
@@ -97,6 +97,21 @@ class EnvironmentCreator(object):
     def _seed(self):
         return int(getattr(self.args, "random_seed", 3))
 
+    # --sticky_action_p P (paac_amd/sticky.py): the host twins of catch, bricks, rally and user games come wrapped when P > 0,
+    # environment i keyed by (the game seed, i) on the training stream.  An evaluation sets sticky_stream (and sticky_seed,
+    # where its key is not the game seed) on the creator before it creates its twins.  P = 0: the twins themselves, as always.
+    sticky_stream = sticky.STICKY_STREAM
+    sticky_seed = None
+
+    def _sticky(self, create):
+        def create_environment(i):
+            p = sticky.flag_of(self.args)
+            if p <= 0.0:
+                return create(i)
+            seed = self._seed() if self.sticky_seed is None else int(self.sticky_seed)
+            return sticky.StickyEnvironment(create(i), p, seed, i, self.sticky_stream)
+        return create_environment
+
     def _terminal_p(self):
         return float(getattr(self.args, "synthetic_terminal_p", 0.01))
 
@@ -116,12 +131,15 @@ class EnvironmentCreator(object):
         """Device-batched twin of the same environments (PAACLearner uses it when present)."""
         if not self._device_twin:
             return None
+        # --sticky_action_p P: the key exists only with P > 0 (read by the rollout and the evaluators: paac.sticky_p_of)
+        p = sticky.flag_of(self.args)
+        stuck = dict(sticky_p=p) if p > 0.0 else {}
         if self._game in DEVICE_GAMES or self._game == user_game.KIND:
-            return dict(kind=self._game, seed=self._seed(), **self._game_options())
+            return dict(kind=self._game, seed=self._seed(), **self._game_options(), **stuck)
         if self._game in PAIRED_GAMES:
             # --duel_pool K (paac_amd/duel_pool.py): the rows are boards played against a pool of frozen opponents; the key
             # exists only with the pool on (read by the training rollout alone: evaluation and matches never see it)
             pool = int(getattr(self.args, "duel_pool", 0) or 0)
-            return dict(kind=self._game, seed=self._seed(), **(dict(pool=pool) if pool > 0 else {}))
+            return dict(kind=self._game, seed=self._seed(), **(dict(pool=pool) if pool > 0 else {}), **stuck)
         return dict(kind="synthetic", seed=self._seed(), terminal_threshold=terminal_threshold(self._terminal_p()),
                     raw_frames=self._raw())

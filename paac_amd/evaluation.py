@@ -282,10 +282,13 @@ class DeviceEvaluator(DeviceDriver):
     probability that differs in the last place can turn a sampled action or break a greedy tie.  seed: the evaluation's own
     (no-ops and sampled actions).  steps_per_launch: forward + evaluation steps per block (made even: the ping-pong closes),
     one hipGraph per block when use_graph; record=True runs eagerly and keeps the action trace.  stream: the torch stream
-    everything is issued on (default: one of its own)."""
+    everything is issued on (default: one of its own).  sticky_p (paac_amd/sticky.py): above 0 the games execute sticky actions
+    on the evaluation's own stream, keyed by `seed` -- a plane of previous actions ping-pongs beside the state records inside
+    the block, and the trace keeps the CHOSEN actions (replay_on_twins over wrapped twins reproduces the scores); 0: today's
+    entry and today's numbers."""
 
     def __init__(self, network, ctx, env_spec, count, noops=30, greedy=False, seed=0, steps_per_launch=16, record=False,
-                 use_graph=True, stream=None):
+                 use_graph=True, stream=None, sticky_p=0.0):
         from . import hip_ops
         from .paac import stateful_kind
         self.kind = check_env_spec(env_spec)
@@ -298,12 +301,20 @@ class DeviceEvaluator(DeviceDriver):
         self.max_steps = max_steps_of(self.kind, self.noops)
         self._allocate(min(self.count, ctx.max_batch, MAX_CHUNK), self.game["words"], network.num_actions, network.torch_device,
                        stream)
+        from . import sticky
+        self.sticky_p = sticky.check_p(sticky_p, "sticky_p")
+        self.prev = None
+        if self.sticky_p > 0.0:
+            import torch
+            self.prev = [torch.zeros(self.chunk, dtype=torch.int32, device=network.torch_device) for _ in range(2)]
 
     def _chunks(self):
         return [(min(self.chunk, self.count - env_offset), env_offset) for env_offset in range(0, self.count, self.chunk)]
 
     def _reset(self, n, env_offset):
         self.game["reset"](self.env_seed, env_offset, self.states[0][:n], self.stacks[0][:n])
+        if self.prev is not None:
+            self.prev[0].zero_()
 
     def _block(self, n, env_offset):
         """`block` x [acting forward -> evaluation step] on the first n environments, then the step counter moves on."""
@@ -311,6 +322,12 @@ class DeviceEvaluator(DeviceDriver):
         for j in range(self.block):
             a, b = j & 1, (j & 1) ^ 1
             self.ctx.forward(self.network.params, self.stacks[a][:n], probs=self.probs[:n])
+            if self.prev is not None:
+                ops.eval_step_sticky(self.kind, self.sticky_p, self.prev[a][:n], self.prev[b][:n], self.probs[:n], self.greedy,
+                                     self.seed, self.noops, self.step, j, self.env_seed, env_offset, self.states[a][:n],
+                                     self.states[b][:n], self.stacks[a][:n], self.stacks[b][:n], self.actions[j][:n],
+                                     self.score[:n], self.length[:n], self.done[:n], self.alive)
+                continue
             ops.eval_step(self.kind, self.probs[:n], self.greedy, self.seed, self.noops, self.step, j, self.env_seed, env_offset,
                           self.states[a][:n], self.states[b][:n], self.stacks[a][:n], self.stacks[b][:n], self.actions[j][:n],
                           self.score[:n], self.length[:n], self.done[:n], self.alive)
@@ -324,6 +341,9 @@ class DeviceEvaluator(DeviceDriver):
 
     def summary(self, scores, lengths, seconds):
         """The fields of an `eval` record of metrics.jsonl (without global_step)."""
-        return dict(count=self.count, greedy=self.greedy, mean=float(np.mean(scores)), min=float(np.min(scores)),
-                    max=float(np.max(scores)), std=float(np.std(scores)), mean_length=float(np.mean(lengths)),
-                    seconds=float(seconds))
+        record = dict(count=self.count, greedy=self.greedy, mean=float(np.mean(scores)), min=float(np.min(scores)),
+                      max=float(np.max(scores)), std=float(np.std(scores)), mean_length=float(np.mean(lengths)),
+                      seconds=float(seconds))
+        if self.sticky_p > 0.0:
+            record["sticky_action_p"] = self.sticky_p          # (only named when on: the records of P = 0 are today's)
+        return record

@@ -1074,6 +1074,63 @@ def match_step(probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_
                                            _stream()), "paac_match_step")
 
 
+# Sticky actions (spec and numpy twin: paac_amd/sticky.py; contract: include/paac_hip.h, paac_sticky).
+def _sticky_block(N, p, step_base_dev, step_offset, prev_in, prev_out, prev_out2):
+    """paac_sticky: the probability, the tick (pointer and offset) and the three int32 [N] planes (prev_out2: None = not
+    written).  The library refuses p outside [0, 1), null planes and prev_in == prev_out / prev_out2."""
+    planes = _shaped_ptrs((N,), torch.int32, dict(prev_in=prev_in, prev_out=prev_out, prev_out2=prev_out2), ("prev_out2",))
+    return _lib.Sticky(float(p), _ptr(step_base_dev, torch.int64, 1, "step_base", True), int(step_offset), *planes)
+
+
+def game_step_sticky(kind, p, step_base_dev, step_offset, prev_in, prev_out, seed, env_offset, actions, state_in, state_out,
+                     stack_in, stack_out, rewards_out, masks_out, ep_reward, ep_len, finished=None, stack_out2=None,
+                     state_out2=None, truncs_out=None, prev_out2=None, **option):
+    """paac_game_step_sticky: game_step_records of `kind` ('catch' / 'bricks' / 'rally', or the registered user game) where
+    every environment executes, with probability p, the action it executed on its previous step -- prev_in int32 [N] -- instead
+    of actions[e]; the draw is keyed by (seed, env_offset + e, *step_base_dev + step_offset).  prev_out (and prev_out2) get the
+    executed action, 0 after a terminal step.  Everything else as game_step_records."""
+    game = DEVICE_GAMES[kind] if kind in DEVICE_GAMES else USER_GAMES.get(kind)
+    if game is None:
+        raise ValueError("game_step_sticky: %r is no device game (catch, bricks, rally or a registered user game)" % (kind,))
+    name, words = game["step_option"], game["words"]
+    if set(option) - {name}:
+        raise TypeError("%s_step: unexpected keyword arguments %s" % (kind, sorted(set(option) - {name})))
+    N, buffers, records = _game_step_ptrs(words, actions, state_in, state_out, state_out2, stack_in, stack_out, stack_out2,
+                                          rewards_out, masks_out, ep_reward, ep_len, finished)
+    rec = _env_records(N, records, truncs_out)
+    sticky = _sticky_block(N, p, step_base_dev, step_offset, prev_in, prev_out, prev_out2)
+    _lib.check(_lib.load().paac_game_step_sticky(game["eval_id"], int(seed), _env_offset("game_step_sticky", env_offset, N), N,
+                                                 *buffers, ctypes.byref(rec), int(bool(option.get(name, False))) if name else 0,
+                                                 ctypes.byref(sticky), _stream()), "paac_game_step_sticky")
+
+
+def duel_step_sticky(p, step_base_dev, step_offset, prev_in, prev_out, seed, env_offset, actions, state_in, state_out, stack_in,
+                     stack_out, rewards_out, masks_out, ep_reward, ep_len, finished=None, stack_out2=None, state_out2=None,
+                     truncs_out=None, prev_out2=None):
+    """paac_duel_step_sticky: duel_step with sticky actions, keyed per ROW (env_offset + e): the two players of a board stick
+    independently, and both rows of a board work out the same pair of executed actions."""
+    N, buffers, records = _game_step_ptrs(DUEL_STATE_WORDS, actions, state_in, state_out, state_out2, stack_in, stack_out,
+                                          stack_out2, rewards_out, masks_out, ep_reward, ep_len, finished)
+    rec = _env_records(N, records, truncs_out)
+    sticky = _sticky_block(N, p, step_base_dev, step_offset, prev_in, prev_out, prev_out2)
+    _lib.check(_lib.load().paac_duel_step_sticky(int(seed), _env_offset("duel_step_sticky", env_offset, N), N, *buffers,
+                                                 ctypes.byref(rec), ctypes.byref(sticky), _stream()), "paac_duel_step_sticky")
+
+
+def eval_step_sticky(game, p, prev_in, prev_out, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed, env_offset,
+                     state_in, state_out, stack_in, stack_out, actions_out, score, length, done, alive):
+    """paac_eval_step_sticky: eval_step where the game executes, with probability p, the previous step's executed action
+    (prev_in int32 [N] -> prev_out) instead of the chosen one; actions_out keeps the chosen action.  The draw's key is
+    eval_seed, its stream the evaluation's own (sticky.EVAL_STREAM_STICKY)."""
+    if game not in EVAL_GAMES and game not in USER_GAMES:
+        raise ValueError("eval_step_sticky: game %r has no device evaluation (--emulator catch|bricks|rally)" % (game,))
+    game_id, words = EVAL_GAMES[game] if game in EVAL_GAMES else (USER_GAMES[game]["eval_id"], USER_GAMES[game]["words"])
+    args = _scored_step_args("eval_step_sticky", words, probs, greedy, eval_seed, noops, step_base_dev, step_offset, env_seed,
+                             env_offset, state_in, state_out, stack_in, stack_out, actions_out, score, length, done, alive)
+    planes = _shaped_ptrs((probs.shape[0],), torch.int32, dict(prev_in=prev_in, prev_out=prev_out), ())
+    _lib.check(_lib.load().paac_eval_step_sticky(game_id, *args, float(p), *planes, _stream()), "paac_eval_step_sticky")
+
+
 FUSED_SAMPLE_MAX_DRAWS = 2304
 ACT_STEP_MAX_DRAWS = 1024
 ACT_STEP_MAX_ENVS = 64

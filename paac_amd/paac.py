@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from . import hip_ops, logger_utils, parallel, window_stats
+from . import hip_ops, logger_utils, parallel, sticky, window_stats
 from .actor_learner import ActorLearner
 from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Runners
 
@@ -28,11 +28,12 @@ from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Run
 # and step wrappers (one argument list, catch's) from hip_ops.DEVICE_GAMES, the keys of the spec the step wrapper takes as
 # keyword arguments, the longest episode of the game in steps (what bounds an evaluation: paac_amd/evaluation.py), and whether
 # that length is a step cap the game can be cut off at (--bootstrap_truncated: the step then records a truncation plane) or
-# the game's own rule (catch).
+# the game's own rule (catch).  step_sticky: the step under --sticky_action_p (paac_amd/sticky.py) -- p, the tick (pointer and
+# offset) and the two planes of previous actions in front of step's list, prev_out2 among its keywords.
 def _stateful_kind(kind, spec_kwargs, max_episode_steps, truncates):
     return dict(words=hip_ops.DEVICE_GAMES[kind]["words"], reset=functools.partial(hip_ops.game_reset, kind),
                 step=functools.partial(hip_ops.game_step, kind), spec_kwargs=spec_kwargs, max_episode_steps=max_episode_steps,
-                truncates=truncates)
+                truncates=truncates, step_sticky=functools.partial(hip_ops.game_step_sticky, kind))
 
 
 STATEFUL_KINDS = {
@@ -46,7 +47,7 @@ STATEFUL_KINDS = {
 # own: its policy is scored as a rally agent, against the scripted opponent).  N must be even: two rows per board.
 PAIRED_KINDS = {
     "duel": dict(words=hip_ops.PAIRED_GAMES["duel"]["words"], reset=hip_ops.duel_reset, step=hip_ops.duel_step, spec_kwargs=(),
-                 max_episode_steps=1000, truncates=True, eval_kind="rally"),
+                 max_episode_steps=1000, truncates=True, eval_kind="rally", step_sticky=hip_ops.duel_step_sticky),
 }
 
 
@@ -58,7 +59,8 @@ USER_KINDS = {}
 def register_user_kind(spec_kwargs, max_episode_steps, truncates):
     """-> the USER_KINDS entry of the user game hip_ops.USER_GAMES holds."""
     USER_KINDS["user"] = dict(words=hip_ops.USER_GAMES["user"]["words"], reset=hip_ops.user_game_reset, step=hip_ops.user_game_step,
-                              spec_kwargs=tuple(spec_kwargs), max_episode_steps=int(max_episode_steps), truncates=bool(truncates))
+                              spec_kwargs=tuple(spec_kwargs), max_episode_steps=int(max_episode_steps), truncates=bool(truncates),
+                              step_sticky=functools.partial(hip_ops.game_step_sticky, "user"))
     return USER_KINDS["user"]
 
 
@@ -88,6 +90,8 @@ class DeviceRollout(object):
     truncs = None      # --bootstrap_truncated: the [T, N] truncation plane, allocated by __init__ only where it applies
     pool = None        # --duel_pool: the duel_pool.DevicePool, created by __init__ only with the pool on
     act_pipeline = False   # the small act_step route as two launches per step (act_step_pipe), set by __init__ only where it applies
+    prev = None        # --sticky_action_p: the ring of previously executed actions, allocated by __init__ only with P > 0 and a game
+    sticky_p = 0.0
     window_f = window_i = None   # --window_stats: the accumulator block (paac_amd/window_stats.py), allocated by __init__ only with the flag on
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
@@ -138,6 +142,15 @@ class DeviceRollout(object):
         if self.stateful:
             self.env_state = torch.zeros((2 * T + 1, N, self.stateful["words"]), dtype=torch.int32, device=dev)
             self.env_step_kwargs = {k: env_spec[k] for k in self.stateful["spec_kwargs"]}
+        # --sticky_action_p P (env_spec["sticky_p"], paac_amd/sticky.py): a ring of the actions the environments executed, beside
+        # env_state slot for slot -- a step reads slot t and writes slot t + 1, the wrap-around second output goes to slot 0 --
+        # and the step goes through the game's sticky entry with the tick the sampler gets.  Zeroed: a run starts from the
+        # no-op.  Shard-local: the draw's key carries env_offset.  P = 0 (or no game): no ring, the entries of always
+        if self.stateful and float(env_spec.get("sticky_p", 0.0) or 0.0) > 0.0:
+            if int(env_spec.get("pool", 0) or 0) > 0:
+                raise ValueError("--sticky_action_p cannot be combined with --duel_pool: the pooled (ghost) step has no sticky form")
+            self.sticky_p = float(env_spec["sticky_p"])
+            self.prev = torch.zeros((2 * T + 1, N), dtype=torch.int32, device=dev)
         # --bootstrap_truncated: the truncation plane beside rewards and masks -- step t writes row t, whatever computes the
         # cycle's returns reads it.  Only with the flag on and a game that has a step cap: otherwise no plane exists, the step
         # goes through the game's own entry and every returns launch is the one it always was.  Shard-local, like the masks.
@@ -309,6 +322,15 @@ class DeviceRollout(object):
                                         state_out2=self.env_state[0] if second else None,
                                         ghost_stack_out2=self.ghost_states[0] if second else None,
                                         truncs_out=self.truncs[t] if self.truncs is not None else None)
+            elif route == "stateful" and self.prev is not None:
+                second = wrap is not None
+                self.stateful["step_sticky"](self.sticky_p, self.tick, t, self.prev[slot], self.prev[slot + 1], seed,
+                                             self.env_offset, self.actions[t], self.env_state[slot], self.env_state[slot + 1],
+                                             obs, nxt, *records, stack_out2=wrap,
+                                             state_out2=self.env_state[0] if second else None,
+                                             prev_out2=self.prev[0] if second else None,
+                                             **(dict(truncs_out=self.truncs[t]) if self.truncs is not None else {}),
+                                             **self.env_step_kwargs)
             elif route == "stateful":
                 self.stateful["step"](seed, self.env_offset, self.actions[t], self.env_state[slot], self.env_state[slot + 1], obs,
                                       nxt, *records, stack_out2=wrap, state_out2=self.env_state[0] if wrap is not None else None,
@@ -499,7 +521,7 @@ class DeviceRollout(object):
               if t is not None]
         if L.minibatch_on:      # (the staging block of states is rewritten by every epoch's gather before anything reads it)
             ts += [L.v_rec] + [t for k, t in L.mb.items() if t is not None and k != "states"]
-        for name in ("raw", "walk_scratch", "mt_state", "env_state", "truncs", "ghost_states", "ghost_probs", "ghost_actions"):
+        for name in ("raw", "walk_scratch", "mt_state", "env_state", "prev", "truncs", "ghost_states", "ghost_probs", "ghost_actions"):
             t = getattr(self, name, None)
             if t is not None:
                 ts.append(t)
@@ -895,7 +917,8 @@ class PAACLearner(ActorLearner):
             scripted = self.environment_creator.device_env_spec.get("kind") in PAIRED_KINDS       # duel: scored on rally
             evaluator = evaluation.DeviceEvaluator(self.network, eval_ctx, spec, count, noops=30,
                                                    greedy=bool(getattr(args, "eval_greedy", True)), seed=seed,
-                                                   use_graph=getattr(args, "use_graph", True), stream=self.rollout.stream)
+                                                   use_graph=getattr(args, "use_graph", True), stream=self.rollout.stream,
+                                                   sticky_p=sticky.flag_of(args))
             next_eval = (self.global_step // eval_every + 1) * eval_every
             if match_boards:
                 with torch.cuda.stream(self.rollout.stream):
@@ -979,7 +1002,9 @@ class PAACLearner(ActorLearner):
                 next_eval = (self.global_step // eval_every + 1) * eval_every
                 logging.info("Evaluation at {} steps: {} episodes ({}), mean {:.3f}, min {:.3f}, max {:.3f}, std {:.3f}, mean "
                              "length {:.1f}, {:.3f} s".format(self.global_step, record["count"],
-                                                              "greedy" if record["greedy"] else "sampled", record["mean"],
+                                                              ("greedy" if record["greedy"] else "sampled") +
+                                                              (", sticky actions P = %g" % record["sticky_action_p"]
+                                                               if "sticky_action_p" in record else ""), record["mean"],
                                                               record["min"], record["max"], record["std"],
                                                               record["mean_length"], seconds))
                 if metrics is not None:

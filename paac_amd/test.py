@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from . import hip_ops, logger_utils
+from . import hip_ops, logger_utils, sticky
 from .paac import PAACLearner, eval_env_spec
 from .session import Session
 from .train import bool_arg, get_network_and_environment_creator
@@ -48,6 +48,11 @@ FLAGS = (
      "with --device_environments true: a second training folder; -tc duel boards are played between the two checkpoints "
      "(paac_amd/match.py; --emulator rally|duel runs only), -f's agent on the bottom of the first half of the boards and on the "
      "top of the rest"),
+    (("--sticky_action_p",), "sticky_action_p", None, float, False,
+     "sticky actions during the evaluation (paac_amd/sticky.py; runs of --emulator catch|bricks|rally|duel|user, host loop and "
+     "--device_environments true; --emulator ale: ALE's repeat_action_probability): P in [0, 1), default the training run's "
+     "own value from args.json (0 for a run from before the flag); 0 gives the numbers of a plain evaluation; refused with "
+     "--versus"),
 )
 
 
@@ -113,6 +118,8 @@ def restore_settings(cli, folder=None):
                      single_life_episodes=False, actor_id=0)
     if cli.gif_name:
         overrides["visualize"] = 1
+    if getattr(cli, "sticky_action_p", None) is not None:          # given by hand: instead of the training run's
+        overrides["sticky_action_p"] = cli.sticky_action_p
     for k, v in overrides.items():
         setattr(settings, k, v)
     return settings
@@ -137,12 +144,14 @@ def evaluate_on_device(cli, args):
     network_creator, env_creator = get_network_and_environment_creator(args, random_seed=seed)
     spec = eval_env_spec(getattr(env_creator, "device_env_spec", None))     # a duel run is scored on rally
     evaluation.check_env_spec(spec)
+    p = sticky.check_flags(args)
     network = network_creator()
     ctx = hip_ops.Context(network.arch_id, env_creator.num_actions, max_batch=min(cli.test_count, evaluation.MAX_CHUNK),
                           device_index=network.torch_device.index or 0)
     session = Session(network, ctx)
     network.init(os.path.join(cli.folder, 'checkpoints'), network.make_saver(), session)
-    evaluator = evaluation.DeviceEvaluator(network, ctx, spec, cli.test_count, noops=cli.noops, greedy=cli.greedy, seed=seed)
+    evaluator = evaluation.DeviceEvaluator(network, ctx, spec, cli.test_count, noops=cli.noops, greedy=cli.greedy, seed=seed,
+                                           sticky_p=p)
     try:
         return evaluator.run()
     finally:
@@ -184,6 +193,8 @@ def match_on_device(cli):
     from . import evaluation, match
     runs = [(folder, restore_settings(cli, folder)) for folder in (cli.folder, cli.versus)]
     check_versus_runs(runs)
+    for _, args in runs:
+        sticky.check_flags(args, versus=cli.versus)          # a match has no sticky form: refused, whichever run asks for it
     seed = cli.eval_seed if cli.eval_seed is not None else int(getattr(runs[0][1], "random_seed", 3))
     # both creators before the first network: a user architecture chooses the library the process loads
     creators = [get_network_and_environment_creator(args, random_seed=seed) for _, args in runs]
@@ -217,6 +228,8 @@ def print_match_summary(cli, record):
 
 def print_summary(args, rewards, lengths=None):
     print('Performed {} tests for {}.'.format(args.test_count, args.game))
+    if sticky.flag_of(args) > 0.0:
+        print('Sticky actions: P = {0:g}'.format(sticky.flag_of(args)))
     for label, stat in (('Mean', np.mean), ('Min', np.min), ('Max', np.max), ('Std', np.std)):
         print('{0}: {1:.2f}'.format(label, stat(rewards)))
     if lengths is not None:
@@ -237,8 +250,13 @@ def main(argv=None):
         print_summary(args, rewards, lengths)
         return rewards
     args = restore_settings(cli)
+    sticky.check_flags(args)
     seed = int(np.random.RandomState(int(time.time())).randint(1000))
     network_creator, env_creator = get_network_and_environment_creator(args, random_seed=seed)
+    # sticky actions (paac_amd/sticky.py): the twins come wrapped, on the evaluation's stream, keyed by --eval_seed (default:
+    # the seed of this evaluation's games)
+    env_creator.sticky_stream = sticky.EVAL_STREAM_STICKY
+    env_creator.sticky_seed = cli.eval_seed if cli.eval_seed is not None else seed
     network = network_creator()
     ctx = hip_ops.Context(network.arch_id, env_creator.num_actions, max_batch=max(1, args.test_count),
                           device_index=network.torch_device.index or 0)

@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import duel_pool, environment_creator, evaluation, logger_utils, match, parallel, window_stats
+from . import duel_pool, environment_creator, evaluation, logger_utils, match, parallel, sticky, window_stats
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -157,6 +157,13 @@ BUILD_FLAGS = (
     (("--duel_pool_latest_p",), "duel_pool_latest_p", 0.5, float,
      "probability in [0, 1] that the opponent of the next period is the newest frozen copy rather than a uniformly drawn pool "
      "member (a design choice, not a measured optimum); read only when --duel_pool is above 0"),
+    (("--sticky_action_p",), "sticky_action_p", 0.0, float,
+     "sticky actions (Machado et al. 2018; paac_amd/sticky.py): at every step, with probability P in [0, 1), an environment "
+     "executes the action it executed on its previous step instead of the one the agent chose (the agent is not told: the "
+     "rollout records the chosen action); 0 = off, and nothing differs.  --emulator catch|bricks|rally|duel|user: decided on "
+     "the GPU inside the game's step, by a counter-based draw keyed by the game seed, the environment and its step count "
+     "(device and host loops agree record for record; --eval_every evaluates with the same P); --emulator ale: handed to ALE's "
+     "repeat_action_probability; --emulator synthetic: accepted and without effect; refused with --duel_pool and --eval_match"),
     (("--checkpoint_format",), "checkpoint_format", "npz", None,
      "container of the checkpoints written: 'npz', or 'tf' = the reference's TensorFlow V2 tensor bundle "
      "(.index + .data-00000-of-00001); both are read"),
@@ -241,6 +248,7 @@ def main(args):
     match.check_train_flags(args)                 # ... and --eval_match's
     duel_pool.check_train_flags(args, world)      # ... and --duel_pool's
     window_stats.check_flags(args, world)         # ... and --window_stats'
+    sticky.check_flags(args)                      # ... and --sticky_action_p's
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)
     setup_kill_signal_handler(learner)

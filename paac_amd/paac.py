@@ -1062,6 +1062,7 @@ class PAACLearner(ActorLearner):
             observations = DeviceObservations(N, first.shape[1], dev)
             observations.update(shared_raw, shared_counts)
             current_states = lambda: observations.current
+            stage_states = lambda: None
         else:
             variables = [(np.asarray([emulator.get_initial_state() for emulator in self.emulators], dtype=np.uint8)),
                          (np.zeros(N, dtype=np.float32)),
@@ -1072,10 +1073,14 @@ class PAACLearner(ActorLearner):
             self.runners.start()
             shared_states, shared_rewards, shared_episode_over, shared_actions = self.runners.get_shared_variables()[:4]
             host_states = torch.from_numpy(shared_states)
-            # page-lock the shared observation array in place: the per-step H2D is then one DMA straight out of the
-            # memory the emulator workers write, instead of a staged pageable copy
-            pinned = hip_ops.pin_host_array(host_states)
-            current_states = lambda: host_states
+            # the shared observation array is pageable memory the emulator workers write (it cannot be page-locked in place
+            # everywhere: registering host memory a process already has is refused on virtual machines): the host copies it
+            # into a buffer that was allocated page-locked, and the per-step H2D is one DMA out of that.  Nothing on the
+            # device still reads the buffer when it is rewritten: the host has waited for the step that copied from it
+            # (actions_ready), and the bootstrap copy is a synchronous one
+            staged_states = torch.empty(host_states.shape, dtype=torch.uint8).pin_memory()
+            current_states = lambda: staged_states
+            stage_states = lambda: staged_states.copy_(host_states)
 
         shared_truncs = self.runners.get_shared_variables()[-1] if truncation_on else None
         truncs = np.zeros((T, N), dtype=np.float32) if truncation_on else None
@@ -1143,7 +1148,7 @@ class PAACLearner(ActorLearner):
                 emulator_steps[e] = 0
 
         # One step's GPU work -- observations H2D, policy forward, numpy-parity sampler, action indices D2H -- as ONE hipGraph
-        # launch per step where it can be captured (page-locked shared observations, up to 64 environments on a stock trunk:
+        # launch per step where it can be captured (observations staged page-locked, up to 64 environments on a stock trunk:
         # paac_act_step_mt's sampling-only form, three kernels), instead of seven API calls whose host cost is what this
         # loop is made of; PAAC_HOST_GRAPH=0, or anything that cannot be captured, keeps the eager calls
         fused_act = (N <= hip_ops.ACT_STEP_MAX_ENVS and N * (A - 1) <= hip_ops.ACT_STEP_MAX_DRAWS
@@ -1161,7 +1166,7 @@ class PAACLearner(ActorLearner):
                 hip_ops.sample_mt(d_probs, mt_state, mt_scratch, d_actions[t])
             h_actions.copy_(d_actions[t], non_blocking=True)
 
-        if (os.environ.get("PAAC_HOST_GRAPH", "1") != "0" and not raw_mode and pinned and fused_act):
+        if (os.environ.get("PAAC_HOST_GRAPH", "1") != "0" and not raw_mode and fused_act):
             with torch.cuda.stream(host_stream):
                 try:
                     for t in range(T):
@@ -1186,6 +1191,7 @@ class PAACLearner(ActorLearner):
             loop_start_time = time.time()
             pending = None
             for t in range(T):
+                stage_states()
                 if step_graphs[t] is not None:
                     step_graphs[t].launch()
                 else:
@@ -1203,6 +1209,7 @@ class PAACLearner(ActorLearner):
                 pending = (t, shared_rewards.astype(np.float32), shared_episode_over.astype(np.float32),
                            shared_truncs.astype(np.float32) if truncation_on else None)
             bookkeeping(*pending)
+            stage_states()
             d_cur.copy_(current_states())
             self.ctx.forward(params, d_cur, values=d_vboot)
             d_rewards.copy_(torch.from_numpy(rewards))
@@ -1284,8 +1291,6 @@ class PAACLearner(ActorLearner):
         for g in step_graphs:
             if g is not None:
                 g.close()
-        if not raw_mode and pinned:
-            hip_ops.unpin_host_array(host_states)      # the stream is drained and the graphs copying from it are gone
         logging.debug("Host-plugin loop: %d update cycles, global step %d", counter, self.global_step)
         np.random.set_state(hip_ops.mt_state_to_numpy(mt_state))
 

@@ -114,6 +114,35 @@ int paac_train_forward(paac_ctx* ctx, const float* params, const uint8_t* states
  * [batch, batch + N) of this forward (paac.py:140-142: the bootstrap observations appended to the rollout rows). */
 int paac_train_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, paac_stream_t stream);
 
+/* Input gradients: d(seed) / d(observation), the one layer gradient training never needs -- Jacobian saliency maps (Wang et
+ * al., arXiv 1511.06581) and L-infinity observation attacks (FGSM on the policy, Huang et al., arXiv 1702.02284).
+ * Runs, in order: the training forward of `states` (the launches of paac_train_forward, into the TRAINING activation set,
+ * heads finished); the seed kernel, dH[b, j] = relu'(h[b, j]) * (sum_a sl[b, a] Wa[j, a] + sv[b] wc[j]); the DATA gradients
+ * only, fc -> conv3 -> conv2 as the backward chooses their kernels (never the split-once fc form); conv1's data gradient
+ * (csrc/conv1_dgrad.h).  No weight-gradient launch, no slab, no finalize: no gradient buffer is written.
+ * mode selects the seeds:
+ *   PAAC_IG_SEEDS        seed_logits f32[batch, A] and seed_value f32[batch] as given; either nullable = zeros
+ *   PAAC_IG_VALUE        sv = 1, sl = 0: the gradient of V(s)
+ *   PAAC_IG_LOGP_ACTION  sl = onehot(actions[b]) - probs[b], sv = 0: the gradient of log pi(actions[b] | s); actions i32[batch]
+ *   PAAC_IG_LOGP_ARGMAX  the same with a = argmax probs[b] (lowest index on ties), taken on the device from the probabilities
+ *                        the forward of this call left: nothing from the host, so the call can sit in a captured graph
+ * dx_out: f32[batch, 84, 84, 4], the gradient wrt X = u8 * f32(1/255) (networks.py:115; no ReLU mask on the input side, 0 where
+ * no window of the first layer covers a pixel).  states_out (with fgsm_levels = E in 1..255): u8[batch, 84, 84, 4],
+ * x' = clamp(x - E * sgn(dX), 0, 255) with sgn(0) = sgn(NaN) = 0, written by the epilogue of the same kernel; it may not
+ * overlap `states`.  Either output is nullable, at least one is required; fgsm_levels = 0 writes no states_out.
+ * Refused, each with a message and before anything is launched or changed: a pending sample of paac_act_step_pipe, pending
+ * heads of the training set (a trunk-only training forward or kept acting rows no backward has consumed), a pending
+ * paac_keep_next_forward row, batch outside (0, max_batch], an unknown mode, fgsm_levels outside 0..255, fgsm_levels > 0
+ * without states_out.  Afterwards the ctx is as paac_train_forward would have left it (and dH and the activation gradients
+ * hold this call's): an ordinary paac_train_forward + paac_loss_backward behind it gives the bits it gives alone. */
+#define PAAC_IG_SEEDS 0
+#define PAAC_IG_VALUE 1
+#define PAAC_IG_LOGP_ACTION 2
+#define PAAC_IG_LOGP_ARGMAX 3
+int paac_input_grad(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int mode, const float* seed_logits,
+                    const float* seed_value, const int32_t* actions, float* dx_out, int fgsm_levels, uint8_t* states_out,
+                    paac_stream_t stream);
+
 /* An update without a training forward.  Weights are frozen inside a cycle (paac.py:99-165), so the T acting forwards of a
  * rollout have already computed the activations the update's forward (paac.py:163-165) would recompute.
  * paac_keep_next_forward(ctx, r): the NEXT acting forward on this ctx (paac_forward / paac_act_step_mt of at most 256 rows,

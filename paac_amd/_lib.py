@@ -95,6 +95,8 @@ _SIGNATURES = {
                                     c_uint32, c_void_p, c_void_p]),
     "paac_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "paac_train_forward_trunk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "paac_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                c_void_p, c_void_p]),
     "paac_keep_next_forward": (c_int, [c_void_p, c_int]),
     "paac_bootstrap_forward_trunk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "paac_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,

@@ -358,6 +358,37 @@ int paac_train_forward_trunk(paac_ctx* ctx, const float* params, const uint8_t* 
   return launched(launch_forward(ctx, params, states, batch, call, (hipStream_t)stream));
 }
 
+int paac_input_grad(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int mode, const float* seed_logits,
+                    const float* seed_value, const int32_t* actions, float* dx_out, int fgsm_levels, uint8_t* states_out,
+                    paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && states, "paac_input_grad: null argument");
+  PAAC_REQUIRE(batch > 0 && batch <= ctx->max_batch, "paac_input_grad: batch %d outside (0, max_batch=%d]", batch, ctx->max_batch);
+  PAAC_REQUIRE(mode >= PAAC_IG_SEEDS && mode <= PAAC_IG_LOGP_ARGMAX, "paac_input_grad: mode %d (PAAC_IG_SEEDS = 0, PAAC_IG_VALUE "
+               "= 1, PAAC_IG_LOGP_ACTION = 2, PAAC_IG_LOGP_ARGMAX = 3)", mode);
+  PAAC_REQUIRE(mode != PAAC_IG_LOGP_ACTION || actions, "paac_input_grad: PAAC_IG_LOGP_ACTION needs the actions");
+  PAAC_REQUIRE(fgsm_levels >= 0 && fgsm_levels <= 255, "paac_input_grad: fgsm_levels %d outside 0..255", fgsm_levels);
+  PAAC_REQUIRE(fgsm_levels == 0 || states_out, "paac_input_grad: fgsm_levels %d needs states_out", fgsm_levels);
+  PAAC_REQUIRE(dx_out || (fgsm_levels > 0 && states_out), "paac_input_grad: nothing to write (dx_out is NULL and no perturbed "
+               "frames are asked for)");
+  const size_t frame_bytes = (size_t)batch * OBS_PIX * OBS_C;
+  PAAC_REQUIRE(!states_out || states_out + frame_bytes <= states || states + frame_bytes <= states_out,
+               "paac_input_grad: states_out overlaps states");
+  PAAC_NO_PENDING_SAMPLE(ctx, "paac_input_grad");
+  PAAC_REQUIRE(ctx->heads_pending_rows == 0, "paac_input_grad: the training set holds %d rows whose heads are still pending (a "
+               "trunk-only training forward or kept acting rows): run their backward first -- this call's forward would drop them",
+               ctx->heads_pending_rows);
+  PAAC_REQUIRE(ctx->keep_row < 0, "paac_input_grad: paac_keep_next_forward row %d is pending (the next acting forward is to be "
+               "kept in the training set this call overwrites): cancel it with row -1 or run that forward first", ctx->keep_row);
+  ForwardCall fwd{.ws = 1};
+  int rc = launch_forward(ctx, params, states, batch, fwd, (hipStream_t)stream);
+  if (rc) return rc;
+  rc = launch_input_grad(ctx, params, states, batch, mode, seed_logits, seed_value, actions, dx_out, fgsm_levels, states_out,
+                         (hipStream_t)stream);
+  if (rc) return rc;
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int paac_keep_next_forward(paac_ctx* ctx, int train_row) {
   PAAC_REQUIRE(ctx, "paac_keep_next_forward: null ctx");
   PAAC_REQUIRE(train_row >= -1 && train_row < ctx->max_batch, "paac_keep_next_forward: row %d outside [-1, max_batch=%d)",

@@ -406,5 +406,9 @@ struct BackwardCall {
 };
 int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, const int32_t* actions, int batch, float beta,
                     float* grad, float* loss_out, int phase, const BackwardCall& call, hipStream_t s);
+// paac_input_grad behind its training forward (net_bwd.hip): seed kernel, data gradients, conv1's data gradient
+int launch_input_grad(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int mode, const float* seed_logits,
+                      const float* seed_value, const int32_t* actions, float* dx_out, int fgsm_levels, uint8_t* states_out,
+                      hipStream_t s);
 
 }  // namespace paac

@@ -2,6 +2,7 @@
 #include <type_traits>
 
 #include "net_common.h"
+#include "conv1_dgrad.h"
 #include "dgrad_tower.h"
 #include "fc_dgrad_once.h"
 #include "gemm3.h"
@@ -641,6 +642,135 @@ int launch_backward(paac_ctx* ctx, const float* params, const uint8_t* states, c
   if (ctx->cfg.arch == PAAC_ARCH_NATURE)
     return backward_impl<NatureNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, c.loss, ppo, vc, c.ppo_stats_out, s);
   return backward_impl<OtherNet>(ctx, params, states, actions, y, adv, batch, beta, grad, loss_out, phase, rt, estimator, c.loss, ppo, vc, c.ppo_stats_out, s);
+}
+
+// paac_input_grad behind its training forward (api.hip): seeds -> dH, then the DATA gradients only -- the fc layer on the
+// generic contraction or gemm3 as backward_impl chooses between those two (never the split-once kernel: its planes come from a
+// heads launch that does not run here), the conv tower's with no head-gradient workgroups or the separate conv3 / conv2
+// launches -- and conv1's (conv1_dgrad.h).  No weight gradient, no slab, no finalize: nothing reaches a gradient buffer.
+template <int OUT, class NT>
+static void launch_conv1_dgrad(paac_ctx* ctx, const float* w1, const InputGradOut& o, int batch, hipStream_t s) {
+  using G = typename NT::G1;
+  static const bool force_direct = env_int("PAAC_CONV1_DGRAD_DIRECT", 0) != 0;      // A/B runs against the yardstick
+  ProfScope ps(ctx, F_MISC, batch, s);
+  if constexpr (conv1_dgrad_cell_ok<G, NT::C1>()) {
+    if (!force_direct) {
+      // 64 cells per workgroup and pass: one pass (about one workgroup per CU) at 32 rows, a run of passes that keeps about
+      // a thousand workgroups in flight -- four per CU, Bw staged once each -- from there on
+      const long tiles = ((long)batch * 441 + 15) / 16;
+      long run = (tiles + kIgWaves * 1024 - 1) / (kIgWaves * 1024);
+      run = run < 1 ? 1 : run > 8 ? 8 : run;
+      const long grid = (tiles + kIgWaves * run - 1) / (kIgWaves * run);
+      prof_mix(1);
+      launch_k(conv1_dgrad_cell_kernel<G, NT::C1, OUT>, dim3((unsigned)grid), dim3(64 * kIgWaves), s, PROF_WHOLE,
+               (const float*)ctx->dact[0], w1, o, batch, (int)run);
+      return;
+    }
+  }
+  const long pixels = (long)batch * G::IH * G::IW;
+  launch_k(conv1_dgrad_direct_kernel<G, NT::C1, OUT>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), s, PROF_WHOLE,
+           (const float*)ctx->dact[0], w1, o, batch);
+}
+
+template <class NT>
+static int input_grad_impl(paac_ctx* ctx, const float* params, int batch, const InputGradSeeds& seeds, const InputGradOut& out,
+                           hipStream_t s) {
+  const paac_layout& L = ctx->layout;
+  Workspace& W = ctx->ws[1];
+  const int cls = batch_class(batch);
+  const int A = ctx->cfg.num_actions;
+  const int i_wf = (NT::NCONV == 3) ? 6 : 4;
+  const float* wf = params + L.offset[i_wf];
+  const float* w2 = params + L.offset[2];
+  const float* w3 = (NT::NCONV == 3) ? params + L.offset[4] : nullptr;
+  {
+    ProfScope ps(ctx, F_HEADS_BWD, batch, s);
+    launch_k(input_grad_seed_kernel, dim3(batch), dim3(256), s, PROF_WHOLE, (const float*)W.h, (const float*)W.probs,
+             params + L.offset[i_wf + 2], params + L.offset[i_wf + 4], seeds, A, (int)NT::H, ctx->dh);
+  }
+  const float* xf = (NT::NCONV == 3) ? W.act[2] : W.act[1];
+  float* dxf = (NT::NCONV == 3) ? ctx->dact[2] : ctx->dact[1];
+  {
+    static const int gemm3_min_rows = env_int("PAAC_GEMM3_MIN_ROWS", 513);
+    ProfScope ps(ctx, F_FC_DGRAD, batch, s);
+    if (batch >= gemm3_min_rows && (NT::H % 32) == 0) {
+      Gemm3Args a;
+      memset(&a, 0, sizeof(a));
+      a.A = ctx->dh; a.lda = NT::H;
+      a.B = wf; a.ldb = NT::H;
+      a.out = dxf; a.ldo = NT::FLAT;
+      a.mask = xf;
+      a.M = batch; a.N = NT::FLAT; a.K = NT::H;
+      using D = Gemm3<true, true, EPI_MASK>;
+      a.MB = (batch + D::TM - 1) / D::TM;
+      a.NB = (NT::FLAT + D::TN - 1) / D::TN;
+      a.S = 1;
+      a.stages_per_split = NT::H / 32;
+      prof_mix(6);
+      launch_k(gemm3_kernel<D>, dim3((unsigned)(a.MB * a.NB)), dim3(D::THREADS), s, PROF_WHOLE, a);
+    } else {
+      GemmArgs gd = make_args(ctx->dh, (size_t)batch * NT::H * 4, wf, (size_t)NT::FLAT * NT::H * 4, dxf, xf, batch, NT::FLAT, NT::H, 0, NT::FLAT);
+      if (launch_dgrad<typename NT::GFCH, NT::FLAT, NT::H, EPI_MASK>(gd, 1, ctx->tune[OP_FC_DGRAD][cls], s) < 0) return -1;
+    }
+  }
+  bool tower = false;
+  if constexpr (NT::NCONV == 3) {
+    constexpr int P2 = NT::G2::OPIX, P3 = NT::G3::OPIX;
+    tower = ctx->tower_on != 0;
+    if (tower) {
+      ProfScope ps(ctx, F_DGRAD_TOWER, batch, s);
+      prof_mix(6);
+      DgradTowerArgs da;
+      da.da3 = ctx->dact[2];
+      da.act2 = W.act[1];
+      da.act1 = W.act[0];
+      const bf16x8* base = reinterpret_cast<const bf16x8*>(ctx->tower_pack) + kTowerPackVecs;
+      da.w3d = base;
+      da.w2d = base + kDgradW3Vecs;
+      da.da2 = ctx->dact[1];
+      da.da1 = ctx->dact[0];
+      da.batch = batch;
+      HeadsGradArgs hg;
+      memset(&hg, 0, sizeof(hg));
+      launch_k(dgrad_tower_kernel, dim3((unsigned)batch), dim3(512), s, PROF_WHOLE, da, hg);
+    } else if constexpr (NT::FAMILY) {
+      GemmArgs gd = make_args(ctx->dact[2], (size_t)batch * P3 * NT::C3 * 4, w3, (size_t)NT::G3::FEATS * NT::C3 * 4, ctx->dact[1], W.act[1], batch * P2, NT::C2, 9 * NT::C3, 0, NT::C2);
+      gd.tap_base[0] = 8 * NT::C2 * NT::C3;
+      gd.tap_sh = -3 * NT::C2 * NT::C3;
+      gd.tap_sw = -NT::C2 * NT::C3;
+      ProfScope ps(ctx, F_CONV3_DGRAD, batch, s);
+      if (launch_dgrad<typename NT::G3D, NT::C2, NT::C3, EPI_MASK>(gd, 1, ctx->tune[OP_CONV3_DGRAD][cls], s) < 0) return -1;
+    } else {
+      ProfScope ps(ctx, F_CONV3_DGRAD, batch, s);
+      launch_dgrad_direct<typename NT::G3, NT::C3>(ctx->dact[2], w3, W.act[1], ctx->dact[1], batch, s);
+    }
+  }
+  if constexpr (!NT::FAMILY) {
+    ProfScope ps(ctx, F_CONV2_DGRAD, batch, s);
+    launch_dgrad_direct<typename NT::G2, NT::C2>(ctx->dact[1], w2, W.act[0], ctx->dact[0], batch, s);
+  } else if (!tower) {
+    constexpr int P1 = NT::G1::OPIX, P2 = NT::G2::OPIX;
+    GemmArgs gd = make_args(ctx->dact[1], (size_t)batch * P2 * NT::C2 * 4, w2, (size_t)NT::G2::FEATS * NT::C2 * 4, ctx->dact[0], W.act[0], batch * 100, NT::C1, 4 * NT::C2, 0, NT::C1);
+    for (int par = 0; par < 4; ++par) gd.tap_base[par] = (((par >> 1) + 2) * 4 + (par & 1) + 2) * NT::C1 * NT::C2;
+    gd.tap_sh = -8 * NT::C1 * NT::C2;
+    gd.tap_sw = -2 * NT::C1 * NT::C2;
+    ProfScope ps(ctx, F_CONV2_DGRAD, batch, s);
+    if (launch_dgrad<typename NT::G2D, NT::C1, NT::C2, EPI_MASK_PARITY>(gd, 4, ctx->tune[OP_CONV2_DGRAD][cls], s) < 0) return -1;
+  }
+  const float* w1 = params + L.offset[0];
+  if (out.dx && out.x_adv) launch_conv1_dgrad<IG_OUT_DX | IG_OUT_FGSM, NT>(ctx, w1, out, batch, s);
+  else if (out.x_adv) launch_conv1_dgrad<IG_OUT_FGSM, NT>(ctx, w1, out, batch, s);
+  else launch_conv1_dgrad<IG_OUT_DX, NT>(ctx, w1, out, batch, s);
+  return 0;
+}
+
+int launch_input_grad(paac_ctx* ctx, const float* params, const uint8_t* states, int batch, int mode, const float* seed_logits,
+                      const float* seed_value, const int32_t* actions, float* dx_out, int fgsm_levels, uint8_t* states_out,
+                      hipStream_t s) {
+  const InputGradSeeds seeds{mode, seed_logits, seed_value, actions};
+  const InputGradOut out{dx_out, states, fgsm_levels > 0 ? states_out : nullptr, fgsm_levels};
+  if (ctx->cfg.arch == PAAC_ARCH_NATURE) return input_grad_impl<NatureNet>(ctx, params, batch, seeds, out, s);
+  return input_grad_impl<OtherNet>(ctx, params, batch, seeds, out, s);
 }
 
 int64_t wslab_floats_needed(int arch) {

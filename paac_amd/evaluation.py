@@ -21,6 +21,9 @@ Spec
                terminal step at t >= noops_g, whose reward is included; then done_g = 1 and nothing of g changes again
   bound        max_steps = noops + the game's longest episode (paac.STATEFUL_KINDS: 13 for catch, 500 for bricks, 1000 for rally): every
                environment is done by then; a smaller max_steps given by hand leaves done_g = 0
+  attack       attack_eps = E > 0 (paac_amd.test --attack_eps): at every step the policy sees x' = fgsm_perturb(x, g, E) with g the
+               gradient of log pi(argmax pi | x) wrt the observation (hip_ops.Context.input_gradient, mode "logp_argmax"); the
+               game and the accounting run on the true stacks x -- the agent is attacked, the world is not
   game         the games' own specs, single_life off (test.py's restore_settings forces it off too); environment g of an
                evaluation is game environment g of the game seed, whatever the chunking
 """
@@ -94,6 +97,26 @@ def account(rewards, terminals, noops, max_steps=None):
         length[scored] += 1
         done[scored & terminals[t]] = 1
     return score, length, done
+
+
+def fgsm_perturb(x_u8, g, levels):
+    """The perturbation rule of an L-infinity observation attack of `levels` pixel levels (FGSM on the policy, Huang et al.,
+    arXiv 1702.02284): x' = clamp(x - levels * sgn(g), 0, 255) with sgn(0) = sgn(NaN) = 0 -> uint8, x's shape."""
+    g = np.asarray(g)
+    sgn = (g > 0).astype(np.int32) - (g < 0).astype(np.int32)
+    return np.clip(np.asarray(x_u8).astype(np.int32) - int(levels) * sgn, 0, 255).astype(np.uint8)
+
+
+def check_attack_eps(eps, device_environments=True, versus=None):
+    """Start-up refusals of --attack_eps (paac_amd.test) -> E as an int."""
+    if isinstance(eps, bool) or int(eps) != eps or not 0 <= int(eps) <= 255:
+        raise ValueError("attack_eps %r: expected integer pixel levels in 0..255 (0 = off)" % (eps,))
+    if int(eps) > 0 and not device_environments:
+        raise ValueError("--attack_eps perturbs the observations inside the GPU-resident evaluation: it needs "
+                         "--device_environments true")
+    if int(eps) > 0 and versus is not None:
+        raise ValueError("--attack_eps cannot be combined with --versus: a match has no attacked form")
+    return int(eps)
 
 
 def step_twins(environments, actions):
@@ -285,10 +308,12 @@ class DeviceEvaluator(DeviceDriver):
     everything is issued on (default: one of its own).  sticky_p (paac_amd/sticky.py): above 0 the games execute sticky actions
     on the evaluation's own stream, keyed by `seed` -- a plane of previous actions ping-pongs beside the state records inside
     the block, and the trace keeps the CHOSEN actions (replay_on_twins over wrapped twins reproduces the scores); 0: today's
-    entry and today's numbers."""
+    entry and today's numbers.  attack_eps = E above 0 (the spec's `attack`): every step first writes the FGSM-perturbed stacks
+    into a scratch buffer (one input_gradient call, inside the block) and the acting forward reads those; the evaluation step
+    and the game stay on the true stacks.  0: no scratch, today's calls."""
 
     def __init__(self, network, ctx, env_spec, count, noops=30, greedy=False, seed=0, steps_per_launch=16, record=False,
-                 use_graph=True, stream=None, sticky_p=0.0):
+                 use_graph=True, stream=None, sticky_p=0.0, attack_eps=0):
         from . import hip_ops
         from .paac import stateful_kind
         self.kind = check_env_spec(env_spec)
@@ -307,6 +332,11 @@ class DeviceEvaluator(DeviceDriver):
         if self.sticky_p > 0.0:
             import torch
             self.prev = [torch.zeros(self.chunk, dtype=torch.int32, device=network.torch_device) for _ in range(2)]
+        self.attack_eps = check_attack_eps(attack_eps)
+        self.scratch = None
+        if self.attack_eps > 0:
+            import torch
+            self.scratch = torch.zeros((self.chunk, 84, 84, 4), dtype=torch.uint8, device=network.torch_device)
 
     def _chunks(self):
         return [(min(self.chunk, self.count - env_offset), env_offset) for env_offset in range(0, self.count, self.chunk)]
@@ -321,7 +351,12 @@ class DeviceEvaluator(DeviceDriver):
         ops = self.hip_ops
         for j in range(self.block):
             a, b = j & 1, (j & 1) ^ 1
-            self.ctx.forward(self.network.params, self.stacks[a][:n], probs=self.probs[:n])
+            seen = self.stacks[a][:n]
+            if self.scratch is not None:          # the policy sees the attacked stacks; everything below steps the true ones
+                seen = self.scratch[:n]
+                self.ctx.input_gradient(self.network.params, self.stacks[a][:n], mode="logp_argmax", fgsm_levels=self.attack_eps,
+                                        states_out=seen)
+            self.ctx.forward(self.network.params, seen, probs=self.probs[:n])
             if self.prev is not None:
                 ops.eval_step_sticky(self.kind, self.sticky_p, self.prev[a][:n], self.prev[b][:n], self.probs[:n], self.greedy,
                                      self.seed, self.noops, self.step, j, self.env_seed, env_offset, self.states[a][:n],
@@ -346,4 +381,6 @@ class DeviceEvaluator(DeviceDriver):
                       seconds=float(seconds))
         if self.sticky_p > 0.0:
             record["sticky_action_p"] = self.sticky_p          # (only named when on: the records of P = 0 are today's)
+        if self.attack_eps > 0:
+            record["attack_eps"] = self.attack_eps
         return record

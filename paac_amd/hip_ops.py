@@ -513,6 +513,43 @@ class Context(object):
                    "paac_grad_tensor_stats")
         return out.cpu().numpy().astype(np.float64).reshape(_lib.MAX_TENSORS, 8)[:len(self.layout["tensors"])]
 
+    INPUT_GRAD_MODES = {"seeds": 0, "value": 1, "logp_action": 2, "logp_argmax": 3}      # include/paac_hip.h: PAAC_IG_*
+
+    def input_gradient(self, params, states, mode="value", seed_logits=None, seed_value=None, actions=None, out=None,
+                       fgsm_levels=0, states_out=None):
+        """d(seed) / d(observation) of the batch (include/paac_hip.h: paac_input_grad) -> `out`, float32 [B,84,84,4], the
+        gradient wrt states * float32(1/255) (allocated here unless given, or unless only the perturbed frames are asked for).
+        mode: "value" (V), "logp_action" (log pi(actions | s); actions int32 [B]), "logp_argmax" (the same of the policy's own
+        argmax, taken on the device) or "seeds" (seed_logits float32 [B, A] / seed_value float32 [B], either None = zeros).
+        fgsm_levels = E in 1..255 with states_out uint8 [B,84,84,4]: also x' = clamp(x - E * sgn(gradient), 0, 255)
+        (evaluation.fgsm_perturb), from the same kernel; `out` may then stay None (nothing is returned)."""
+        B = self._check_states(states)
+        A = self.num_actions
+        if mode not in self.INPUT_GRAD_MODES:
+            raise ValueError("input_gradient: mode %r, expected one of %s" % (mode, sorted(self.INPUT_GRAD_MODES)))
+        if mode != "seeds" and (seed_logits is not None or seed_value is not None):
+            raise ValueError("input_gradient: seed_logits / seed_value go with mode='seeds'")
+        if mode == "logp_action" and actions is None:
+            raise ValueError("input_gradient: mode='logp_action' needs the actions")
+        if isinstance(fgsm_levels, bool) or int(fgsm_levels) != fgsm_levels or not 0 <= int(fgsm_levels) <= 255:
+            raise ValueError("input_gradient: fgsm_levels %r, expected an integer in 0..255" % (fgsm_levels,))
+        if (int(fgsm_levels) > 0) != (states_out is not None):
+            raise ValueError("input_gradient: fgsm_levels above 0 and states_out go together")
+        for nm, t in (("out", out), ("states_out", states_out)):
+            if t is not None and tuple(t.shape) != (B,) + OBS_SHAPE:
+                raise ValueError("%s must be [%d,84,84,4], got %s" % (nm, B, tuple(t.shape)))
+        if states_out is not None and states_out.data_ptr() == states.data_ptr():
+            raise ValueError("input_gradient: states_out may not alias states")
+        if out is None and states_out is None:
+            out = torch.empty((B,) + OBS_SHAPE, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.paac_input_grad(
+            self.handle, _ptr(params, torch.float32, self.layout["total"], "params"), _ptr(states, torch.uint8, B * 28224, "states"),
+            B, self.INPUT_GRAD_MODES[mode], _ptr(seed_logits, torch.float32, B * A, "seed_logits", True),
+            _ptr(seed_value, torch.float32, B, "seed_value", True), _ptr(actions, torch.int32, B, "actions", True),
+            _ptr(out, torch.float32, B * 28224, "out", True), int(fgsm_levels),
+            _ptr(states_out, torch.uint8, B * 28224, "states_out", True), _stream()), "paac_input_grad")
+        return out
+
     def debug_activation(self, what, batch):
         convs, fc = arch_geometry(self.arch)
         cap = int(batch) * self.num_actions if int(what) == 26 else activation_size(convs, fc, what, batch)

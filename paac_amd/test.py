@@ -13,6 +13,9 @@ environment's score is frozen when its first episode ends.
 (paac_amd/evaluation.py: DeviceEvaluator): -tc up to 4096, --greedy true for the argmax action, --eval_seed for the game instances, the no-op counts
 and the sampled actions; the summary gains a 'Mean length' line.  --gif_name is refused there.
 
+--attack_eps E (with --device_environments true) evaluates under an FGSM observation attack of E pixel levels (evaluation.py:
+`attack`): the input gradient of log pi(argmax) is taken on the GPU at every step, inside the captured blocks.
+
 --versus FOLDER_B (with --device_environments true; runs of --emulator rally|duel) plays -tc duel boards between the two folders'
 checkpoints instead (paac_amd/match.py: DeviceMatch), -f's agent being player X: the summary is of its scores and gains a
 'Wins / Draws / Losses' line.
@@ -53,6 +56,10 @@ FLAGS = (
      "--device_environments true; --emulator ale: ALE's repeat_action_probability): P in [0, 1), default the training run's "
      "own value from args.json (0 for a run from before the flag); 0 gives the numbers of a plain evaluation; refused with "
      "--versus"),
+    (("--attack_eps",), "attack_eps", 0, int, False,
+     "with --device_environments true: an L-infinity FGSM attack on the policy's observations of E pixel levels (0..255, 0 = "
+     "off; paac_amd/evaluation.py: `attack`) -- the agent sees the perturbed stacks, the games step the true ones; refused "
+     "with --versus"),
 )
 
 
@@ -151,7 +158,7 @@ def evaluate_on_device(cli, args):
     session = Session(network, ctx)
     network.init(os.path.join(cli.folder, 'checkpoints'), network.make_saver(), session)
     evaluator = evaluation.DeviceEvaluator(network, ctx, spec, cli.test_count, noops=cli.noops, greedy=cli.greedy, seed=seed,
-                                           sticky_p=p)
+                                           sticky_p=p, attack_eps=getattr(cli, "attack_eps", 0))
     try:
         return evaluator.run()
     finally:
@@ -230,6 +237,8 @@ def print_summary(args, rewards, lengths=None):
     print('Performed {} tests for {}.'.format(args.test_count, args.game))
     if sticky.flag_of(args) > 0.0:
         print('Sticky actions: P = {0:g}'.format(sticky.flag_of(args)))
+    if getattr(args, "attack_eps", 0) > 0:
+        print('FGSM attack: E = {0:d} pixel levels'.format(args.attack_eps))
     for label, stat in (('Mean', np.mean), ('Min', np.min), ('Max', np.max), ('Std', np.std)):
         print('{0}: {1:.2f}'.format(label, stat(rewards)))
     if lengths is not None:
@@ -238,6 +247,8 @@ def print_summary(args, rewards, lengths=None):
 
 def main(argv=None):
     cli = get_arg_parser().parse_args(argv)
+    from . import evaluation
+    evaluation.check_attack_eps(cli.attack_eps, cli.device_environments, cli.versus)
     if cli.versus is not None:
         check_versus_flags(cli)
         rewards, _, record = match_on_device(cli)

@@ -627,6 +627,44 @@ typedef struct {
 int paac_window_fields(int* n_f, int* n_i);
 int paac_window_fold(const paac_window_inputs* in, double* acc_f, int64_t* acc_i, paac_stream_t stream);
 
+/* --feature_stats (spec and numpy twin: paac_amd/feature_stats.py): the activations of one cycle's training rows folded into
+ * the running accumulators of the log window, acc_f device double[n_f] and acc_i device int64[n_i].  The block is laid out by
+ * the unit counts of the four layer slots conv1, conv2, conv3, fc (feature_stats.Layout; paac_feature_fields reports the two
+ * lengths for an architecture); its live head -- per-unit sums, the fc Gram matrix; cycles, rows, samples, per-unit positive
+ * counts -- is the window's state (all zero bytes = an empty window), the scratch behind it belongs to the fold.
+ *   fold     three launches, no atomics, capturable; they only read the activations.  act[l]: fp32 conv outputs
+ *            [rows, positions[l], units[l]] (l = 0..2; NULL: the layer is not folded) and fc activations [rows, units[3]]
+ *            (l = 3, positions 1, required), 16-byte aligned.  Per unit: the sum of its activations, every term converted to
+ *            fp64 first, and the count of samples > 0.  G += H^T H over the fc activations with fp32 matrix instructions:
+ *            products and sums are fp32 inside a chunk of PAAC_FEATURE_CHUNK_ROWS rows, chunks are added in ascending
+ *            order in fp64; element (i, j), i <= j, is computed once and added to G[i][j] and G[j][i].  Two calls on the same
+ *            inputs give the same bits, eager or replayed.
+ *   fold_ctx the same launches on the TRAINING activation set of ctx (the rows paac_debug_activation(21..24) copies), rows
+ *            [0, rows).  Refused when rows exceeds max_batch and while the set's heads are pending -- a trunk-only training
+ *            forward or kept acting rows have left no finished fc activations there yet.
+ *   finish   one launch of one workgroup: out_scalars device double[PAAC_FEATURE_SCALARS] = {trace of G, squared Frobenius
+ *            norm of G, then per layer slot {units with sum * units <= tau * (the layer's sums added in index order), units
+ *            with no positive sample, positive samples}, rows, cycles, samples per layer slot}.  It only reads the block.
+ * Refused with a message, without a launch: a null pointer among in, acc_f, acc_i and the fc activations; rows < 1; an fc
+ * width that is not a multiple of 64 or above 1024; a channel count that is not a multiple of 16 or above 1024; a block that
+ * overlaps an input; tau outside [0, 1].
+ * paac_feature_constants: out[0..4] = {PAAC_FEATURE_CHUNK_ROWS, groups of chunks per tile at most, workgroups per layer of the
+ * unit statistics at most, terms of a unit sum added in fp32 before fp64 takes over (1: none), PAAC_FEATURE_SCALARS}. */
+#define PAAC_FEATURE_CHUNK_ROWS 128
+#define PAAC_FEATURE_SCALARS 20
+typedef struct {
+  const float* act[4];
+  int32_t units[4];
+  int32_t positions[4];
+  int32_t rows;
+} paac_feature_inputs;
+int paac_feature_constants(int32_t* out, int n);
+int paac_feature_fields(int arch, int64_t* n_f, int64_t* n_i);
+int paac_feature_fold(const paac_feature_inputs* in, double* acc_f, int64_t* acc_i, paac_stream_t stream);
+int paac_feature_fold_ctx(paac_ctx* ctx, int rows, double* acc_f, int64_t* acc_i, paac_stream_t stream);
+int paac_feature_finish(const int32_t* units, const double* acc_f, const int64_t* acc_i, double tau, double* out_scalars,
+                        paac_stream_t stream);
+
 /* paac.py:34-45 bit-exact: probs - float32.epsneg, then numpy legacy multinomial(1, p) per env in
  * index order on ONE MT19937 stream.  mt_state: device uint32[625] = numpy key[624] + pos, advanced
  * in place (import/export with np.random.get_state()/set_state()).  scratch: device, >=

@@ -74,6 +74,11 @@ class WindowInputs(ctypes.Structure):
                 ("stats_first", c_int32), ("applied", c_void_p), ("gnorm", c_void_p), ("finished", c_void_p)]
 
 
+class FeatureInputs(ctypes.Structure):
+    """paac_feature_inputs (include/paac_hip.h): the activations one cycle hands to the --feature_stats fold."""
+    _fields_ = [("act", c_void_p * 4), ("units", c_int32 * 4), ("positions", c_int32 * 4), ("rows", c_int32)]
+
+
 class KlGate(ctypes.Structure):
     """paac_kl_gate (include/paac_hip.h): the gate of a --ppo_target_kl optimizer step, every pointer in device memory."""
     _fields_ = [("kl", c_void_p), ("scale", c_float), ("thr", c_float), ("first", c_int), ("stop", c_void_p),
@@ -123,6 +128,11 @@ _SIGNATURES = {
     "paac_returns_scan": (c_int, [POINTER(Returns), c_void_p]),
     "paac_window_fields": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "paac_window_fold": (c_int, [POINTER(WindowInputs), c_void_p, c_void_p, c_void_p]),
+    "paac_feature_constants": (c_int, [POINTER(c_int32), c_int]),
+    "paac_feature_fields": (c_int, [c_int, POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
+    "paac_feature_fold": (c_int, [POINTER(FeatureInputs), c_void_p, c_void_p, c_void_p]),
+    "paac_feature_fold_ctx": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "paac_feature_finish": (c_int, [POINTER(c_int32), c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
     "paac_game_step": (c_int, [c_int, c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -820,7 +820,9 @@ int64_t paac_debug_activation(paac_ctx* ctx, int what, int batch, float* out, in
   if (training_set) what -= 20;
   const Workspace& W = ctx->ws[training_set ? 1 : ctx->last_ws];
   const float* src;
-  if (what >= 1 && what <= ctx->spec.nconv)
+  if (training_set)
+    src = train_activation(ctx, what - 1);
+  else if (what >= 1 && what <= ctx->spec.nconv)
     src = W.act[what - 1];
   else if (what == 4)
     src = W.h;

@@ -192,6 +192,14 @@ struct paac_ctx {
 
 namespace paac {
 
+// Where the TRAINING activation set holds layer slot `layer` (0..2: the conv outputs, plain rows [row][oh][ow][c]; 3: the fc
+// activations [row][H]); nullptr for a conv slot the geometry does not have.  THE statement of that addressing: what
+// paac_debug_activation(21..24) copies and what paac_feature_fold_ctx folds.
+inline const float* train_activation(const paac_ctx* ctx, int layer) {
+  if (layer == 3) return ctx->ws[1].h;
+  return layer >= 0 && layer < ctx->spec.nconv ? ctx->ws[1].act[layer] : nullptr;
+}
+
 // Timing hooks: while a ProfScope is alive, launch_k() attaches its start/stop events to the kernel dispatch itself
 // (hipExtLaunchKernelGGL: the events carry the dispatch's own begin/end timestamps, like rocprofv3's kernel trace),
 // so the elapsed time is the kernel's GPU duration without marker-packet overhead.  A scope with several launches

@@ -5,6 +5,7 @@
 #include "net_common.h"
 #include "fc_heads.h"
 #include "heads.h"
+#include "feature_stats.h"
 
 namespace paac {
 
@@ -1769,6 +1770,83 @@ static int launch_returns_scan(const char* name, int estimator, const float* v_b
   return 0;
 }
 
+// =============================================================================================
+// --feature_stats: dormant units and the fc features' Gram matrix folded per cycle, finished per window (kernels and their
+// design: feature_stats.h, instantiated here alone; spec and numpy twin: paac_amd/feature_stats.py; contract: include/paac_hip.h).
+static bool feat_overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const char *pa = (const char*)a, *pb = (const char*)b;
+  return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+// The checks and the three launches of one fold.
+static int feature_fold(const char* fn, const paac_feature_inputs* in, double* acc_f, int64_t* acc_i, hipStream_t s) {
+  PAAC_REQUIRE(in, "%s: in is null", fn);
+  PAAC_REQUIRE(acc_f, "%s: acc_f is null", fn);
+  PAAC_REQUIRE(acc_i, "%s: acc_i is null", fn);
+  PAAC_REQUIRE(in->rows >= 1, "%s: rows=%d (rows < 1)", fn, in->rows);
+  const int H = in->units[3];
+  PAAC_REQUIRE(in->act[3], "%s: the fc activations are null", fn);
+  PAAC_REQUIRE(H >= 64 && H % 64 == 0 && H <= 1024, "%s: fc width %d is not a multiple of 64 up to 1024", fn, H);
+  PAAC_REQUIRE(in->positions[3] == 1, "%s: the fc layer has one position per row, got %d", fn, in->positions[3]);
+  for (int l = 0; l < 3; ++l) {
+    PAAC_REQUIRE(in->units[l] >= 0 && in->units[l] % 16 == 0 && in->units[l] <= 1024,
+                 "%s: layer %d has %d channels: not a multiple of 16 up to 1024", fn, l + 1, in->units[l]);
+    PAAC_REQUIRE(!in->act[l] || (in->units[l] > 0 && in->positions[l] >= 1), "%s: layer %d is given with %d channels and %d "
+                 "positions", fn, l + 1, in->units[l], in->positions[l]);
+  }
+  FeatFold f{};
+  f.L = feat_layout(in->units);
+  f.rows = in->rows;
+  for (int l = 0; l < 4; ++l) {
+    f.act[l] = in->act[l];
+    f.positions[l] = in->positions[l];
+    if (!in->act[l]) continue;
+    const int64_t samples = (int64_t)in->rows * in->positions[l];
+    const size_t bytes = (size_t)samples * in->units[l] * sizeof(float);
+    PAAC_REQUIRE(samples * in->units[l] <= INT32_MAX, "%s: layer %d holds %ld floats (more than 2^31 - 1)", fn, l + 1,
+                 (long)(samples * in->units[l]));
+    PAAC_REQUIRE(((uintptr_t)in->act[l] & 15) == 0, "%s: the activations of layer %d are not 16-byte aligned", fn, l + 1);
+    PAAC_REQUIRE(!feat_overlaps(in->act[l], bytes, acc_f, (size_t)f.L.n_f * 8) &&
+                 !feat_overlaps(in->act[l], bytes, acc_i, (size_t)f.L.n_i * 8), "%s: the block overlaps the activations of layer %d",
+                 fn, l + 1);
+    // a workgroup of the unit statistics takes at least 8 samples per thread row
+    const int tpq = 256 / (in->units[l] / 4);
+    const int64_t want = (samples + (int64_t)tpq * 8 - 1) / ((int64_t)tpq * 8);
+    f.wgs[l] = (int)(want < kFeatUnitWgs ? want : kFeatUnitWgs);
+  }
+  PAAC_REQUIRE(!feat_overlaps(acc_f, (size_t)f.L.n_f * 8, acc_i, (size_t)f.L.n_i * 8), "%s: acc_f overlaps acc_i", fn);
+  const int chunks = (in->rows + kFeatChunkRows - 1) / kFeatChunkRows;
+  f.chunks_per_group = (chunks + kFeatSplitsMax - 1) / kFeatSplitsMax;
+  f.groups = (chunks + f.chunks_per_group - 1) / f.chunks_per_group;
+  const int n64 = H / 64;
+  int max_wgs = 1;
+  for (int l = 0; l < 4; ++l) max_wgs = f.wgs[l] > max_wgs ? f.wgs[l] : max_wgs;
+  {
+    ProfScope ps(g_prof_ctx, F_MISC, in->rows, s);
+    launch_k(feature_gram_kernel, dim3(n64 * (n64 + 1) / 2, f.groups), dim3(256), s, PROF_WHOLE, f, acc_f);
+  }
+  {
+    ProfScope ps(g_prof_ctx, F_MISC, in->rows, s);
+    launch_k(unit_stats_kernel, dim3(max_wgs, 4), dim3(256), s, PROF_WHOLE, f, acc_f, acc_i);
+  }
+  {
+    ProfScope ps(g_prof_ctx, F_MISC, in->rows, s);
+    const int64_t items = (int64_t)f.L.tiles * 1024 + f.L.U + 1;
+    launch_k(feature_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), s, PROF_WHOLE, f, acc_f, acc_i);
+  }
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+static void feat_units_of(const ArchSpec& spec, int units[4], int positions[4]) {
+  for (int l = 0; l < 3; ++l) {
+    units[l] = l < spec.nconv ? spec.conv[l].cout : 0;
+    positions[l] = l < spec.nconv ? spec.conv[l].oh * spec.conv[l].ow : 0;
+  }
+  units[3] = spec.fc;
+  positions[3] = 1;
+}
+
 }  // namespace paac
 
 using namespace paac;
@@ -1869,6 +1947,63 @@ int paac_window_fold(const paac_window_inputs* in, double* acc_f, int64_t* acc_i
   PAAC_REQUIRE(!in->ppo_stats || (in->stats_first >= 0 && in->stats_first <= in->steps),
                "paac_window_fold: stats_first=%d outside [0, steps]", in->stats_first);
   launch_k(window_fold_kernel, dim3(1), dim3(kWinThreads), (hipStream_t)stream, PROF_WHOLE, *in, acc_f, acc_i);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_feature_constants(int32_t* out, int n) {
+  PAAC_REQUIRE(out && n >= 5, "paac_feature_constants: five words");
+  const int32_t v[5] = {kFeatChunkRows, kFeatSplitsMax, kFeatUnitWgs, 1 /* unit sums: every term is converted to fp64 */,
+                        kFeatScalars};
+  for (int i = 0; i < 5; ++i) out[i] = v[i];
+  return 0;
+}
+
+int paac_feature_fields(int arch, int64_t* n_f, int64_t* n_i) {
+  PAAC_REQUIRE(arch == PAAC_ARCH_NIPS || arch == PAAC_ARCH_NATURE || arch == PAAC_ARCH_USER, "paac_feature_fields: arch %d", arch);
+  const ArchSpec spec = arch_spec(arch);
+  PAAC_REQUIRE(spec.nconv >= 1, "paac_feature_fields: the library holds no geometry for arch %d", arch);
+  int units[4], positions[4];
+  feat_units_of(spec, units, positions);
+  const FeatLayout L = feat_layout(units);
+  if (n_f) *n_f = L.n_f;
+  if (n_i) *n_i = L.n_i;
+  return 0;
+}
+
+int paac_feature_fold(const paac_feature_inputs* in, double* acc_f, int64_t* acc_i, paac_stream_t stream) {
+  return feature_fold("paac_feature_fold", in, acc_f, acc_i, (hipStream_t)stream);
+}
+
+int paac_feature_fold_ctx(paac_ctx* ctx, int rows, double* acc_f, int64_t* acc_i, paac_stream_t stream) {
+  PAAC_REQUIRE(ctx, "paac_feature_fold_ctx: ctx is null");
+  PAAC_REQUIRE(rows >= 1 && rows <= ctx->max_batch, "paac_feature_fold_ctx: rows=%d outside [1, max_batch=%d]", rows,
+               ctx->max_batch);
+  PAAC_REQUIRE(ctx->heads_pending_rows == 0, "paac_feature_fold_ctx: the training set's %d rows are still pending (a trunk-only "
+               "training forward or kept acting rows have left no finished fc activations there): run their backward or the "
+               "record pass first", ctx->heads_pending_rows);
+  paac_feature_inputs in{};
+  feat_units_of(ctx->spec, in.units, in.positions);
+  for (int l = 0; l < 4; ++l) in.act[l] = train_activation(ctx, l);
+  in.rows = rows;
+  return feature_fold("paac_feature_fold_ctx", &in, acc_f, acc_i, (hipStream_t)stream);
+}
+
+int paac_feature_finish(const int32_t* units, const double* acc_f, const int64_t* acc_i, double tau, double* out_scalars,
+                        paac_stream_t stream) {
+  PAAC_REQUIRE(units && acc_f && acc_i && out_scalars, "paac_feature_finish: null argument");
+  PAAC_REQUIRE(units[3] >= 64 && units[3] % 64 == 0 && units[3] <= 1024, "paac_feature_finish: fc width %d is not a multiple of "
+               "64 up to 1024", units[3]);
+  for (int l = 0; l < 3; ++l)
+    PAAC_REQUIRE(units[l] >= 0 && units[l] % 16 == 0 && units[l] <= 1024, "paac_feature_finish: layer %d has %d channels", l + 1,
+                 units[l]);
+  PAAC_REQUIRE(tau >= 0.0 && tau <= 1.0, "paac_feature_finish: tau %g outside [0, 1]", tau);      // (NaN fails)
+  const FeatLayout L = feat_layout(units);
+  PAAC_REQUIRE(!feat_overlaps(out_scalars, kFeatScalars * 8, acc_f, (size_t)L.n_f * 8) &&
+               !feat_overlaps(out_scalars, kFeatScalars * 8, acc_i, (size_t)L.n_i * 8), "paac_feature_finish: out_scalars overlaps "
+               "the block");
+  ProfScope ps(g_prof_ctx, F_MISC, units[3], (hipStream_t)stream);
+  launch_k(feature_finish_kernel, dim3(1), dim3(256), (hipStream_t)stream, PROF_WHOLE, L, acc_f, acc_i, tau, out_scalars);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -561,6 +561,11 @@ class Context(object):
         return out[:n].clone()
 
     # -- timing hooks ----------------------------------------------------------------------------
+    def feature_fold(self, lay, acc_f, acc_i, rows):
+        """--feature_stats on the training activation set's rows [0, rows) (include/paac_hip.h: paac_feature_fold_ctx)."""
+        _lib.check(self.lib.paac_feature_fold_ctx(self.handle, int(rows), *_feature_block_ptrs(lay, acc_f, acc_i), _stream()),
+                   "paac_feature_fold_ctx")
+
     def prof_enable(self, on=True):
         _lib.check(self.lib.paac_prof_enable(self.handle, 1 if on else 0), "paac_prof_enable")
 
@@ -690,6 +695,88 @@ def window_fold(acc_f, acc_i, values, rewards, masks, actions, y, adv, num_actio
         _ptr(finished, torch.int32, FINISHED_RING_BYTES // 4, "finished", True))
     _lib.check(_lib.load().paac_window_fold(ctypes.byref(block), _ptr(acc_f, torch.float64, window_stats.N_F, "acc_f"),
                                             _ptr(acc_i, torch.int64, window_stats.N_I, "acc_i"), _stream()), "paac_window_fold")
+
+
+def feature_constants():
+    """-> (chunk rows, groups of chunks at most, workgroups per layer at most, fp32 terms of a unit sum, finish scalars) the
+    library was compiled with (include/paac_hip.h: paac_feature_constants)."""
+    out = (ctypes.c_int32 * 5)()
+    _lib.check(_lib.load().paac_feature_constants(out, 5), "paac_feature_constants")
+    return tuple(int(v) for v in out)
+
+
+class _FeatureConstant(object):
+    """A module attribute read from the library on first use: FEATURE_CHUNK_ROWS, FEATURE_UNIT_FP32_TERMS."""
+
+    def __init__(self, index):
+        self.index = index
+
+    def __index__(self):
+        return feature_constants()[self.index]
+
+    __int__ = __index__
+
+
+def feature_layout(arch=None, units=None):
+    """The --feature_stats block's layout (feature_stats.Layout) of `arch` in the loaded library, or of the four unit counts
+    `units`; the spec's constants and, for an architecture, its two lengths are checked against the compiled ones."""
+    from . import feature_stats as fs
+    if feature_constants() != (fs.CHUNK_ROWS, fs.GRAM_SPLITS_MAX, fs.UNIT_WGS, fs.UNIT_FP32_TERMS, fs.FINISH_SCALARS):
+        raise _lib.PaacHipError("feature_stats' constants differ from the library's %r" % (feature_constants(),))
+    if units is not None:
+        return fs.Layout(units)
+    lay = fs.Layout.of_geometry(*arch_geometry(arch))
+    n_f, n_i = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(_lib.load().paac_feature_fields(int(arch), ctypes.byref(n_f), ctypes.byref(n_i)), "paac_feature_fields")
+    if (int(n_f.value), int(n_i.value)) != (lay.N_F, lay.N_I):
+        raise _lib.PaacHipError("feature_stats.Layout holds %d / %d fields, the library was compiled for %d / %d"
+                                % (lay.N_F, lay.N_I, n_f.value, n_i.value))
+    return lay
+
+
+def feature_block(device, arch=None, units=None):
+    """An empty --feature_stats block on `device` -> (acc_f float64[N_F], acc_i int64[N_I], layout)."""
+    lay = feature_layout(arch, units)
+    return (torch.zeros(lay.N_F, dtype=torch.float64, device=device), torch.zeros(lay.N_I, dtype=torch.int64, device=device), lay)
+
+
+def _feature_block_ptrs(lay, acc_f, acc_i):
+    return _ptr(acc_f, torch.float64, lay.N_F, "acc_f"), _ptr(acc_i, torch.int64, lay.N_I, "acc_i")
+
+
+def feature_fold(lay, acc_f, acc_i, activations):
+    """--feature_stats: one cycle's activations folded into the block (include/paac_hip.h: paac_feature_fold; spec:
+    paac_amd/feature_stats.py).  activations: one float32 tensor per layer slot -- conv outputs [R, OH, OW, C] or None, fc
+    activations [R, H]."""
+    h = activations[3]
+    if h is None or h.dim() != 2 or h.shape[1] != lay.H:
+        raise ValueError("the fc activations must be [rows, %d]" % lay.H)
+    R = h.shape[0]
+    block = _lib.FeatureInputs()
+    block.rows = R
+    for l in range(4):
+        a = activations[l]
+        block.units[l] = lay.units[l]
+        if a is None:
+            continue
+        if a.shape[0] != R or a.shape[-1] != lay.units[l] or a.dim() not in ((2,) if l == 3 else (3, 4)):
+            raise ValueError("layer %d: shape %s, expected [%d, ..., %d]" % (l + 1, tuple(a.shape), R, lay.units[l]))
+        block.positions[l] = a.numel() // (R * lay.units[l])
+        block.act[l] = _ptr(a, torch.float32, a.numel(), "activations[%d]" % l).value
+    _lib.check(_lib.load().paac_feature_fold(ctypes.byref(block), *_feature_block_ptrs(lay, acc_f, acc_i), _stream()),
+               "paac_feature_fold")
+
+
+def feature_finish(lay, acc_f, acc_i, tau, out):
+    """--feature_stats: the window's scalars, out float64[FINISH_SCALARS] (include/paac_hip.h: paac_feature_finish)."""
+    from . import feature_stats as fs
+    units = (ctypes.c_int32 * 4)(*lay.units)
+    _lib.check(_lib.load().paac_feature_finish(units, *_feature_block_ptrs(lay, acc_f, acc_i), float(tau),
+                                               _ptr(out, torch.float64, fs.FINISH_SCALARS, "out"), _stream()), "paac_feature_finish")
+
+
+FEATURE_CHUNK_ROWS = _FeatureConstant(0)          # rows whose products the Gram kernel sums in fp32 (int(...) reads the library)
+FEATURE_UNIT_FP32_TERMS = _FeatureConstant(3)     # terms of a unit sum added in fp32 before fp64 takes over
 
 
 def uses_gae(gae_lambda):

@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from . import hip_ops, logger_utils, parallel, sticky, window_stats
+from . import feature_stats, hip_ops, logger_utils, parallel, sticky, window_stats
 from .actor_learner import ActorLearner
 from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Runners
 
@@ -92,6 +92,7 @@ class DeviceRollout(object):
     act_pipeline = False   # the small act_step route as two launches per step (act_step_pipe), set by __init__ only where it applies
     prev = None        # --sticky_action_p: the ring of previously executed actions, allocated by __init__ only with P > 0 and a game
     sticky_p = 0.0
+    features = None    # --feature_stats: the (acc_f, acc_i, layout) block (paac_amd/feature_stats.py), allocated by __init__ only with the flag on
     window_f = window_i = None   # --window_stats: the accumulator block (paac_amd/window_stats.py), allocated by __init__ only with the flag on
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
@@ -177,6 +178,12 @@ class DeviceRollout(object):
             if parallel.collectives_active():
                 raise ValueError(window_stats.DATA_PARALLEL_REFUSAL)
             self.window_f, self.window_i = hip_ops.window_block(dev)
+        # --feature_stats: the block one fold per cycle adds to, where the training set holds the rollout rows as forwarded on the
+        # pre-update weights (_rollout_and_backward).  Off: no block, no launch, the same graphs
+        if getattr(L, "feature_stats", False):
+            if parallel.collectives_active():
+                raise ValueError(feature_stats.DATA_PARALLEL_REFUSAL)
+            self.features = hip_ops.feature_block(dev, L.network.arch_id)
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
         if env_spec.get("raw_frames"):
@@ -345,6 +352,14 @@ class DeviceRollout(object):
                                    nxt, *records, stack_out2=wrap, raw_scratch=self.raw)
 
     def _rollout_and_backward(self, parity):
+        """The cycle up to its first gradient; --feature_stats: the cycle's fold where the training set's heads are finished and
+        nothing has overwritten its T * N rollout rows -- behind the first backward, or (--ppo_minibatches) behind the record
+        pass, whose first minibatch forward writes over them."""
+        self._rollout_and_first_backward(parity)
+        if self.features is not None and not self.L.minibatch_on:
+            self.L.feature_fold(self.features, self.T * self.N)
+
+    def _rollout_and_first_backward(self, parity):
         L, T, N = self.L, self.T, self.N
         params = L.network.params
         keep = self.reuse_acting
@@ -392,6 +407,8 @@ class DeviceRollout(object):
         L, T, N = self.L, self.T, self.N
         B = T * N
         L.minibatch_record(self.actions.view(-1), B + N)
+        if self.features is not None:
+            L.feature_fold(self.features, B)
         v_boot = L.v_rec[B:]
         if L.adv_norm:
             hip_ops.returns_norm_tick(v_boot, self.rewards, self.masks, self.values, L.gamma, self.y, self.adv, L.adv_n,
@@ -720,6 +737,9 @@ class PAACLearner(ActorLearner):
         self.host_truncated_steps = None   # host loop under --bootstrap_truncated: ones in the last rollout's truncation plane
         self.host_window = None            # host loop under --window_stats: its (acc_f, acc_i) block
         self.host_window_episodes = ([], [])   # ... and the (returns, lengths) of the episodes finished since the last record
+        self.host_features = None          # host loop under --feature_stats: its (acc_f, acc_i, layout) block
+        self.feature_windows = 0           # --feature_stats: `features` records written so far (--feature_rank_every counts them)
+        self.feature_scalars = None        # ... and where the finish launch leaves a window's scalars
 
     def _open_metrics(self):
         """metrics.jsonl in the debugging folder (rank 0 only): what the reference sends to TensorBoard."""
@@ -794,6 +814,38 @@ class PAACLearner(ActorLearner):
                             loss0=self.loss_dev if ppo and not self.minibatch_on else None,
                             ppo_stats=self.ppo_stats if ppo else None, stats_first=0 if self.minibatch_on else 1,
                             applied=self.ppo_applied, finished=finished)
+
+    def feature_fold(self, block, rows):
+        """--feature_stats: the training set's rows [0, rows) folded into the block (acc_f, acc_i, layout)."""
+        acc_f, acc_i, lay = block
+        self.ctx.feature_fold(lay, acc_f, acc_i, rows)
+
+    def _feature_read(self, block):
+        """--feature_stats at a progress record, on the current stream (the caller has synchronised): the finish launch, its
+        scalars copied out -- and the Gram matrix at every --feature_rank_every-th window, for the host's eigenvalues -- and the
+        block's live part emptied -> (the `features` record's fields, what the log line gains)."""
+        acc_f, acc_i, lay = block
+        if self.feature_scalars is None:
+            self.feature_scalars = torch.zeros(feature_stats.FINISH_SCALARS, dtype=torch.float64, device=acc_f.device)
+        hip_ops.feature_finish(lay, acc_f, acc_i, self.dormant_tau, self.feature_scalars)
+        scalars = self.feature_scalars.cpu().numpy()
+        self.feature_windows += 1
+        gram = None
+        if self.feature_rank_every and self.feature_windows % self.feature_rank_every == 0:
+            at, n = lay.FIELDS_F["gram"]
+            gram = acc_f[at:at + n].cpu().numpy().reshape(lay.H, lay.H)
+        acc_f[:lay.LIVE_F].zero_()
+        acc_i[:lay.LIVE_I].zero_()
+        record = feature_stats.summary(lay, scalars, self.dormant_tau, gram=gram)
+        pr = record["fc_participation_ratio"]
+        return record, ", fc dormant {:.4f}, participation ratio {}".format(
+            record["layers"]["fc"]["dormant_fraction"], "n/a" if pr is None else "%.2f" % pr)
+
+    def _features_record(self, record):
+        """The `features` record behind the `progress` record."""
+        if self.metrics is not None:
+            self.metrics.write("features", global_step=int(self.global_step), **record)
+            self.metrics.flush()
 
     def _window_loss_rows(self):
         """The loss scalars a cycle's fold read, one row per optimizer step (what window_fold hands over, on the host)."""
@@ -970,6 +1022,11 @@ class PAACLearner(ActorLearner):
                 if self.rollout.window_f is not None:
                     with torch.cuda.stream(self.rollout.stream):
                         window, window_text = self._window_read(self.rollout.window_f, self.rollout.window_i)
+                features = None
+                if self.rollout.features is not None:
+                    with torch.cuda.stream(self.rollout.stream):
+                        features, text = self._feature_read(self.rollout.features)
+                    window_text += text
                 logging.info("Ran {} steps, at {} steps/s ({} steps/s avg), last 10 rewards avg {}{}"
                              .format(self.global_step, chunk * steps_per_cycle / (curr_time - loop_start_time),
                                      (self.global_step - global_step_start) / (curr_time - start_time), last_ten, window_text))
@@ -981,6 +1038,8 @@ class PAACLearner(ActorLearner):
                                           (self.global_step - global_step_start) / (curr_time - start_time), last_ten)
                 if window is not None:
                     self._window_record(window)
+                if features is not None:
+                    self._features_record(features)
             if pool is not None and pool.schedule.due(self.global_step):
                 # a pool event, between two run_cycles calls and on the rollout's stream: two device-to-device copies and the
                 # repack, queued behind the cycles already issued -- nothing here waits for the GPU
@@ -1104,6 +1163,11 @@ class PAACLearner(ActorLearner):
         if self.window_stats and parallel.collectives_active():
             raise ValueError(window_stats.DATA_PARALLEL_REFUSAL)
         self.host_window = hip_ops.window_block(dev) if self.window_stats else None
+        # --feature_stats: the block, folded eagerly once per cycle where the training set holds the rollout rows on the
+        # pre-update weights
+        if self.feature_stats and parallel.collectives_active():
+            raise ValueError(feature_stats.DATA_PARALLEL_REFUSAL)
+        self.host_features = hip_ops.feature_block(dev, self.network.arch_id) if self.feature_stats else None
         rewards = np.zeros((T, N), dtype=np.float32)
         masks = np.zeros((T, N), dtype=np.float32)
         # the sampled action indices come back through a page-locked buffer: an asynchronous copy + an event instead of a
@@ -1230,6 +1294,8 @@ class PAACLearner(ActorLearner):
                 rows, acts = d_states.view(T * N, 84, 84, 4), d_actions.view(-1)
                 self.ctx.train_forward_trunk(params, rows)
                 self.minibatch_record(acts, T * N)
+                if self.host_features is not None:
+                    self.feature_fold(self.host_features, T * N)
                 mb_step.fill_((counter + 1) * T)
                 self.minibatch_perms(getattr(self.args, "sampler_seed", 42), mb_step)
                 for k in range(self.ppo_steps):
@@ -1242,6 +1308,8 @@ class PAACLearner(ActorLearner):
                                        p_old_out=self.p_old if self.ppo_epochs > 1 else None)
                 if self.vclip_on:         # v_old = the values epoch 1's heads just computed
                     self.ctx.train_values_into(self.v_old, T * N)
+                if self.host_features is not None:
+                    self.feature_fold(self.host_features, T * N)
                 self._allreduce_grad()
                 self.apply_gradients(0)
                 for k in range(1, self.ppo_epochs):      # epochs 2..K on the frozen y / adv / p_old (/ v_old), the same lr
@@ -1278,6 +1346,11 @@ class PAACLearner(ActorLearner):
                     host_stream.synchronize()
                     window, window_text = self._window_read(*self.host_window, episodes=self.host_window_episodes)
                     self.host_window_episodes = ([], [])
+                features = None
+                if self.host_features is not None:
+                    host_stream.synchronize()
+                    features, text = self._feature_read(self.host_features)
+                    window_text += text
                 logging.info("Ran {} steps, at {} steps/s ({} steps/s avg), last 10 rewards avg {}{}"
                              .format(self.global_step, T * N * world / (curr_time - loop_start_time),
                                      (self.global_step - global_step_start) / (curr_time - start_time), last_ten, window_text))
@@ -1285,6 +1358,8 @@ class PAACLearner(ActorLearner):
                                       (self.global_step - global_step_start) / (curr_time - start_time), last_ten)
                 if window is not None:
                     self._window_record(window)
+                if features is not None:
+                    self._features_record(features)
             self.save_vars()
         host_stream.synchronize()
         ctx_stream.__exit__(None, None, None)

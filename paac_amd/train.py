@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import duel_pool, environment_creator, evaluation, logger_utils, match, parallel, sticky, window_stats
+from . import duel_pool, environment_creator, evaluation, feature_stats, logger_utils, match, parallel, sticky, window_stats
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -133,6 +133,18 @@ BUILD_FLAGS = (
      "'window' record in metrics.jsonl: explained variance of the critic, value / return / advantage moments, action "
      "frequencies, the loss scalars and gradient norm averaged over all updates, and the statistics of all episodes finished "
      "in the window; one GPU only (refused under data parallelism).  Training is bit-identical with it on or off"),
+    (("--feature_stats",), "feature_stats", False, bool_arg,
+     "off by default; true = the trunk's activations of every cycle's training rows (on the pre-update weights) are folded on "
+     "the GPU into per-unit sums and the Gram matrix of the fc features (paac_amd/feature_stats.py; device and host loops), "
+     "and every 'progress' record is followed by a 'features' record in metrics.jsonl: per layer the dormant, dead and active "
+     "fractions of its units, and the participation ratio of the fc features; one GPU only (refused under data "
+     "parallelism).  Training is bit-identical with it on or off"),
+    (("--dormant_tau",), "dormant_tau", 0.025, float,
+     "--feature_stats: a unit is dormant when its mean activation over the layer's mean of means is at most this (in [0, 1]; "
+     "the default is the value of Sokar et al., arXiv 2302.12902)"),
+    (("--feature_rank_every",), "feature_rank_every", 64, int,
+     "--feature_stats: at every W-th 'features' record the Gram matrix is copied out and the record gains fc_srank (Kumar et "
+     "al., arXiv 2010.14498) and fc_top_eigen_share from its eigenvalues, computed on the host; 0 = never"),
     (("--eval_every",), "eval_every", 0, int,
      "device loop, --emulator catch|bricks|rally: score the current policy on --eval_count held-out game instances (seed random_seed "
      "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "
@@ -248,6 +260,7 @@ def main(args):
     match.check_train_flags(args)                 # ... and --eval_match's
     duel_pool.check_train_flags(args, world)      # ... and --duel_pool's
     window_stats.check_flags(args, world)         # ... and --window_stats'
+    feature_stats.check_flags(args, world)        # ... and --feature_stats'
     sticky.check_flags(args)                      # ... and --sticky_action_p's
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)

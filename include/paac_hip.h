@@ -665,6 +665,31 @@ int paac_feature_fold_ctx(paac_ctx* ctx, int rows, double* acc_f, int64_t* acc_i
 int paac_feature_finish(const int32_t* units, const double* acc_f, const int64_t* acc_i, double tau, double* out_scalars,
                         paac_stream_t stream);
 
+/* --redo_every (spec and numpy twin: paac_amd/redo.py): dormant units recycled (ReDo, Sokar et al., arXiv 2302.12902).  Eager,
+ * three parts on `stream`:
+ *   mask     one launch, one workgroup per layer slot of `units` (the four unit counts of the --feature_stats block, which must
+ *            be the context's geometry).  From the per-unit sums at the head of acc_f: unit u of a layer is recycled when
+ *            sum[u] * units <= tau * total, total = the layer's sums added in index order in fp64 (paac_feature_finish's dormant
+ *            rule and order); a layer whose total is 0 is skipped (nothing recycled).  mask_out device int32[sum of units],
+ *            counts_out device int32[12] = {recycled, units, skipped} per layer slot.  It only reads the block.
+ *   apply    one launch over the flat parameter buffer (paac_param_layout) and the optimizer's two slot buffers of the same
+ *            layout.  Weight element [..., o] of a layer whose unit o is recycled is drawn afresh from U(-d, d), d =
+ *            float32(1 / sqrt(fan-in)): philox4x32-10, counter {flat index lo, flat index hi, event, 0x5245444F}, key {seed lo,
+ *            seed hi}, x = -d + (d + d) * ((word0 >> 8) * 2^-24) in fp32, product rounded before the sum; its bias becomes 0;
+ *            element [..., c, :] of the NEXT layer's weights (conv: the input-channel slice; fc: rows p * C + c; actor and
+ *            critic: row c) becomes 0, and outgoing wins where both apply.  A rewritten element's slots take a fresh run's
+ *            values: PAAC_REDO_RMSPROP slot0 = 1, slot1 = 0; PAAC_REDO_ADAM both 0.  Every other element and all padding keep
+ *            their bits; untouched 16-byte quads are neither loaded nor stored.
+ *   repack   what paac_pack_weights launches, so every derived copy of the context describes the new weights.
+ * Refused with a message, without a launch: a null pointer; tau outside [0, 1]; another optimizer id; event == 0 (recycles are
+ * counted from 1) or above 2^32 - 1; units that are not the context's geometry; a context whose deferred conv-gradient slab
+ * reduction is still pending (paac_loss_backward phase 3 without its optimizer step); a context that owes an acting sample
+ * (paac_act_step_pending). */
+enum { PAAC_REDO_RMSPROP = 0, PAAC_REDO_ADAM = 1 };
+int paac_redo(paac_ctx* ctx, float* params, float* slot0, float* slot1, int optimizer, const int32_t* units,
+              const double* acc_f, double tau, uint64_t seed, uint64_t event, int32_t* mask_out, int32_t* counts_out,
+              paac_stream_t stream);
+
 /* paac.py:34-45 bit-exact: probs - float32.epsneg, then numpy legacy multinomial(1, p) per env in
  * index order on ONE MT19937 stream.  mt_state: device uint32[625] = numpy key[624] + pos, advanced
  * in place (import/export with np.random.get_state()/set_state()).  scratch: device, >=

@@ -133,6 +133,8 @@ _SIGNATURES = {
     "paac_feature_fold": (c_int, [POINTER(FeatureInputs), c_void_p, c_void_p, c_void_p]),
     "paac_feature_fold_ctx": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "paac_feature_finish": (c_int, [POINTER(c_int32), c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
+    "paac_redo": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p, c_double, c_uint64, c_uint64,
+                          c_void_p, c_void_p, c_void_p]),
     "paac_game_step": (c_int, [c_int, c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),

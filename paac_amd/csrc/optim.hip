@@ -1,9 +1,11 @@
 // The optimizer step on gfx950: gradient clip (ignore / global norm / per-tensor norm), TF RMSProp / Adam over the flat
-// parameter buffer with the packed weight copies kept current, the --ppo_target_kl gate, gradient statistics.
+// parameter buffer with the packed weight copies kept current, the --ppo_target_kl gate, gradient statistics; the recycle of
+// dormant units (--redo_every, csrc/redo.h), which writes the same parameters and slots.
 #include <type_traits>
 
 #include "common.h"
 #include "tower.h"
+#include "redo.h"
 
 namespace paac {
 
@@ -863,6 +865,43 @@ int paac_grad_tensor_stats(paac_ctx* ctx, float* out, paac_stream_t stream) {
   PAAC_REQUIRE(np > 0 && fill_local_spec(ctx, na, np, &ls), "paac_grad_tensor_stats: no local norm layout");
   hipLaunchKernelGGL(grad_tensor_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ctx->partials, ls,
                      out);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_redo(paac_ctx* ctx, float* params, float* slot0, float* slot1, int optimizer, const int32_t* units,
+              const double* acc_f, double tau, uint64_t seed, uint64_t event, int32_t* mask_out, int32_t* counts_out,
+              paac_stream_t stream) {
+  PAAC_REQUIRE(ctx && params && slot0 && slot1 && units && acc_f && mask_out && counts_out, "paac_redo: null argument");
+  PAAC_REQUIRE(tau >= 0.0 && tau <= 1.0, "paac_redo: tau %g outside [0, 1]", tau);      // (NaN fails)
+  PAAC_REQUIRE(optimizer == PAAC_REDO_RMSPROP || optimizer == PAAC_REDO_ADAM, "paac_redo: optimizer %d (PAAC_REDO_RMSPROP = 0, "
+               "PAAC_REDO_ADAM = 1)", optimizer);
+  PAAC_REQUIRE(event >= 1 && event <= 0xFFFFFFFFull, "paac_redo: event %llu: recycles are counted from 1 (one 32-bit counter "
+               "word)", (unsigned long long)event);
+  RedoArgs args;
+  RedoLayers layers;
+  int have[4], unit_off[4];
+  redo_units_of(ctx->spec, have, unit_off);
+  PAAC_REQUIRE(units[0] == have[0] && units[1] == have[1] && units[2] == have[2] && units[3] == have[3],
+               "paac_redo: units {%d, %d, %d, %d} do not match the context's geometry {%d, %d, %d, %d}", units[0], units[1],
+               units[2], units[3], have[0], have[1], have[2], have[3]);
+  PAAC_REQUIRE(redo_fill_args(ctx, &args, &layers), "paac_redo: the geometry has a unit axis wider than %d", kRedoMaxUnits);
+  PAAC_REQUIRE(ctx->pending_fin_grad == nullptr, "paac_redo: the conv weight gradients' slab reduction is still pending (a "
+               "phase-3 paac_loss_backward no optimizer step has consumed): recycle behind the optimizer step");
+  PAAC_REQUIRE(!paac_act_step_pending(ctx), "paac_redo: the last paac_act_step_pipe's sample is still pending (it was computed "
+               "on the weights a recycle would rewrite): pay it with paac_act_step_flush first");
+  const hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(ctx, F_MISC, (int)(ctx->layout.total / 4), s);
+  // `sum` is the first field of the block (feature_stats.Layout), laid out by the same unit offsets as the mask
+  launch_k(redo_mask_kernel, dim3((unsigned)layers.n), dim3(256), s, PROF_FIRST, layers, acc_f, tau, mask_out, counts_out);
+  launch_k(redo_apply_kernel, dim3((unsigned)args.nblocks), dim3(256), s, PROF_LAST, args, params, slot0, slot1,
+           (const int32_t*)mask_out, optimizer == PAAC_REDO_RMSPROP ? 1.0f : 0.0f, (uint32_t)seed, (uint32_t)(seed >> 32),
+           (uint32_t)event);
+  PAAC_CHECK_HIP(hipGetLastError());
+  // every derived copy the context keeps (fc fragments, the conv towers' bf16 planes, the data-gradient planes): what
+  // paac_pack_weights launches (untimed launches: the scope above times the two recycle kernels)
+  const int rc = launch_pack_weights(ctx, params, s);
+  if (rc != 0) return rc;
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

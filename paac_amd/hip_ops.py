@@ -468,6 +468,18 @@ class Context(object):
         _lib.check(self.lib.paac_pack_weights(self.handle, _ptr(params, torch.float32, self.layout["total"], "params"),
                                               _stream()), "paac_pack_weights")
 
+    def redo(self, params, slot0, slot1, optimizer, lay, acc_f, tau, seed, event, mask_out, counts_out):
+        """--redo_every: one recycle of the units the window in acc_f counts as dormant at `tau` (include/paac_hip.h: paac_redo;
+        spec: paac_amd/redo.py).  params and the optimizer's two slot buffers are rewritten in place and the context's derived
+        weight copies refreshed; lay: the block's feature_stats.Layout; mask_out int32[lay.U], counts_out int32[12]."""
+        n = self.layout["total"]
+        units = (ctypes.c_int32 * 4)(*lay.units)
+        _lib.check(self.lib.paac_redo(self.handle, _ptr(params, torch.float32, n, "params"), _ptr(slot0, torch.float32, n, "slot0"),
+                                      _ptr(slot1, torch.float32, n, "slot1"), int(optimizer), units,
+                                      _ptr(acc_f, torch.float64, lay.N_F, "acc_f"), float(tau), int(seed), int(event),
+                                      _ptr(mask_out, torch.int32, lay.U, "mask_out"),
+                                      _ptr(counts_out, torch.int32, 12, "counts_out"), _stream()), "paac_redo")
+
     def set_managed_weights(self, on=True):
         """Managed mode: only clip_rmsprop / pack_weights refresh the pre-split copy; acting forwards keep no conv1 /
         conv2 activations (include/paac_hip.h: paac_set_managed_weights)."""

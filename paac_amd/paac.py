@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from . import feature_stats, hip_ops, logger_utils, parallel, sticky, window_stats
+from . import feature_stats, hip_ops, logger_utils, parallel, redo, sticky, window_stats
 from .actor_learner import ActorLearner
 from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Runners
 
@@ -740,6 +740,9 @@ class PAACLearner(ActorLearner):
         self.host_features = None          # host loop under --feature_stats: its (acc_f, acc_i, layout) block
         self.feature_windows = 0           # --feature_stats: `features` records written so far (--feature_rank_every counts them)
         self.feature_scalars = None        # ... and where the finish launch leaves a window's scalars
+        self.redo_events = 0               # --redo_every: recycles so far (the draw's event number counts from 1)
+        self.redo_record = None            # ... the `redo` record of the window just read, if it led to a recycle
+        self.redo_mask = self.redo_counts = None      # ... and paac_redo's two outputs, allocated at the first recycle
 
     def _open_metrics(self):
         """metrics.jsonl in the debugging folder (rank 0 only): what the reference sends to TensorBoard."""
@@ -834,17 +837,44 @@ class PAACLearner(ActorLearner):
         if self.feature_rank_every and self.feature_windows % self.feature_rank_every == 0:
             at, n = lay.FIELDS_F["gram"]
             gram = acc_f[at:at + n].cpu().numpy().reshape(lay.H, lay.H)
+        # --redo_every: every W-th window's recycle, decided from the block before it is emptied
+        self.redo_record, redo_text = None, ""
+        if self.redo_every and self.feature_windows % self.redo_every == 0:
+            self.redo_record = self._redo(block)
+            redo_text = ", recycled " + " ".join("%s %d" % (name, layer["recycled"])
+                                                 for name, layer in self.redo_record["layers"].items())
         acc_f[:lay.LIVE_F].zero_()
         acc_i[:lay.LIVE_I].zero_()
         record = feature_stats.summary(lay, scalars, self.dormant_tau, gram=gram)
         pr = record["fc_participation_ratio"]
-        return record, ", fc dormant {:.4f}, participation ratio {}".format(
-            record["layers"]["fc"]["dormant_fraction"], "n/a" if pr is None else "%.2f" % pr)
+        return record, ", fc dormant {:.4f}, participation ratio {}{}".format(
+            record["layers"]["fc"]["dormant_fraction"], "n/a" if pr is None else "%.2f" % pr, redo_text)
+
+    def _redo(self, block):
+        """--redo_every at a progress record, on the current stream (the caller has synchronised, so the last cycle's optimizer
+        step has consumed its backward's slab reduction and its bootstrap forward has paid the pipelined acting sample: neither
+        of paac_redo's two context refusals applies here; a sample still owed would be flushed as before a checkpoint): one
+        recycle on the training context from the window in `block` -> the `redo` record's fields."""
+        acc_f, _, lay = block
+        if self.redo_mask is None:
+            self.redo_mask = torch.zeros(lay.U, dtype=torch.int32, device=acc_f.device)
+            self.redo_counts = torch.zeros(12, dtype=torch.int32, device=acc_f.device)
+        if self.ctx.act_step_pending():
+            self.ctx.act_step_flush()
+        self.redo_events += 1
+        (_, slot0), (_, slot1) = self._slot_tensors()
+        self.ctx.redo(self.network.params, slot0, slot1, redo.OPTIMIZERS[self.optimizer], lay, acc_f, self.dormant_tau,
+                      int(getattr(self.args, "random_seed", 3)), self.redo_events, self.redo_mask, self.redo_counts)
+        layers = redo.layers_of_counts(lay, self.redo_counts.cpu().numpy())
+        counts = redo.parameter_counts(self.network.layout, self.redo_mask.cpu().numpy())
+        return redo.record(layers, counts, self.dormant_tau, self.redo_events)
 
     def _features_record(self, record):
-        """The `features` record behind the `progress` record."""
+        """The `features` record behind the `progress` record, and the `redo` record of the recycle that window led to."""
         if self.metrics is not None:
             self.metrics.write("features", global_step=int(self.global_step), **record)
+            if self.redo_record is not None:
+                self.metrics.write("redo", global_step=int(self.global_step), **self.redo_record)
             self.metrics.flush()
 
     def _window_loss_rows(self):

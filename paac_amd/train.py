@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import duel_pool, environment_creator, evaluation, feature_stats, logger_utils, match, parallel, sticky, window_stats
+from . import duel_pool, environment_creator, evaluation, feature_stats, logger_utils, match, parallel, redo, sticky, window_stats
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -145,6 +145,13 @@ BUILD_FLAGS = (
     (("--feature_rank_every",), "feature_rank_every", 64, int,
      "--feature_stats: at every W-th 'features' record the Gram matrix is copied out and the record gains fc_srank (Kumar et "
      "al., arXiv 2010.14498) and fc_top_eigen_share from its eigenvalues, computed on the host; 0 = never"),
+    (("--redo_every",), "redo_every", 0, int,
+     "--feature_stats true: 0 = off; W > 0 = every W-th 'features' record is followed by one recycle of the units that record "
+     "counted as dormant at --dormant_tau (ReDo, Sokar et al., arXiv 2302.12902; paac_amd/redo.py): on the GPU their incoming "
+     "weights are drawn afresh from the layer's initialisation law (a counter-based draw keyed by random_seed), their bias and "
+     "outgoing weights are zeroed and their optimizer slots reset, and a 'redo' record goes to metrics.jsonl; a layer whose "
+     "units are all silent is left alone; device and host loops, one GPU only.  A recycle costs one log boundary every W "
+     "windows and nothing per cycle; evaluation does not read the flag"),
     (("--eval_every",), "eval_every", 0, int,
      "device loop, --emulator catch|bricks|rally: score the current policy on --eval_count held-out game instances (seed random_seed "
      "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "
@@ -261,6 +268,7 @@ def main(args):
     duel_pool.check_train_flags(args, world)      # ... and --duel_pool's
     window_stats.check_flags(args, world)         # ... and --window_stats'
     feature_stats.check_flags(args, world)        # ... and --feature_stats'
+    redo.check_flags(args, world)                 # ... and --redo_every's
     sticky.check_flags(args)                      # ... and --sticky_action_p's
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)

@@ -690,6 +690,28 @@ int paac_redo(paac_ctx* ctx, float* params, float* slot0, float* slot1, int opti
               const double* acc_f, double tau, uint64_t seed, uint64_t event, int32_t* mask_out, int32_t* counts_out,
               paac_stream_t stream);
 
+/* --explore_bonus (spec and numpy twin: paac_amd/explore.py): a count-based exploration bonus on a SimHash of the observation
+ * ("#Exploration", Tang et al., arXiv 1611.04717).  Kernels and their design: csrc/explore.h.
+ *   signs    one launch, once per run: the +-1 matrix S[28224, 64] of `seed` -- bit j % 32 of word 0 of philox4x32-10 on counter
+ *            {k, j / 32, 0, 0x4558504C}, key {seed lo, seed hi}; set = +1 -- as int8 in the projection's fragment order.
+ *            signs_out: device, PAAC_EXPLORE_SIGN_BYTES bytes, 16-byte aligned.
+ *   bonus    ONE launch on `stream`, capturable, no host synchronisation.  states: device uint8[rows][28224], 16-byte aligned.
+ *            Row r: P[j] = sum_k int8(x[k] ^ 0x80) * S[k][j] exactly in int32 (int8 matrix instructions); code = sum over j < bits
+ *            of (P[j] >= 0) << j; slot = splitmix64's finaliser of the code >> (64 - table_bits).  Every row adds 1 to
+ *            counts[slot] (device int32[2^table_bits], the caller's, persistent); then every row reads n = counts[slot] with all
+ *            of the call's increments in it, bonus_out[r] = beta / sqrt(float(n)) in correctly rounded fp32 and rewards[r] +=
+ *            bonus_out[r].  codes_out: device uint64[rows] or null.  scratch: device int32[paac_explore_scratch_words(rows)],
+ *            zero before the first call; every call leaves it zero.  The result does not depend on the order of rows or
+ *            workgroups; two calls on the same inputs and table give the same bits, eager or replayed.
+ * Refused with a message, without a launch: a null pointer (codes_out excepted); rows <= 0; bits outside [1, 64]; table_bits
+ * outside [4, 26]; a beta that is negative or not finite; states or signs not 16-byte aligned. */
+#define PAAC_EXPLORE_SIGN_BYTES (28224 * 64)
+int64_t paac_explore_scratch_words(int rows);
+int paac_explore_signs(uint64_t seed, void* signs_out, paac_stream_t stream);
+int paac_explore_bonus(const uint8_t* states, int rows, int bits, int table_bits, const void* signs, int32_t* counts,
+                       int32_t* scratch, float beta, float* rewards, float* bonus_out, uint64_t* codes_out,
+                       paac_stream_t stream);
+
 /* paac.py:34-45 bit-exact: probs - float32.epsneg, then numpy legacy multinomial(1, p) per env in
  * index order on ONE MT19937 stream.  mt_state: device uint32[625] = numpy key[624] + pos, advanced
  * in place (import/export with np.random.get_state()/set_state()).  scratch: device, >=

@@ -22,6 +22,8 @@ PPO_STEPS_MAX = 64             # PAAC_PPO_STEPS_MAX: optimizer steps (epochs x m
 MINIBATCH_MAX_ROWS = 8192      # PAAC_MINIBATCH_MAX_ROWS
 EVAL_CATCH, EVAL_BRICKS, EVAL_RALLY = 0, 1, 2          # PAAC_EVAL_CATCH, PAAC_EVAL_BRICKS, PAAC_EVAL_RALLY
 EVAL_USER = 3                  # PAAC_EVAL_USER: the user's game, in a library built with one (paac_amd/user_game.py)
+EXPLORE_K = 84 * 84 * 4        # bytes of one stack: the depth of --explore_bonus' projection
+EXPLORE_SIGN_BYTES = EXPLORE_K * 64          # PAAC_EXPLORE_SIGN_BYTES
 
 
 class Layout(ctypes.Structure):
@@ -135,6 +137,10 @@ _SIGNATURES = {
     "paac_feature_finish": (c_int, [POINTER(c_int32), c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
     "paac_redo": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p, c_double, c_uint64, c_uint64,
                           c_void_p, c_void_p, c_void_p]),
+    "paac_explore_scratch_words": (c_int64, [c_int]),
+    "paac_explore_signs": (c_int, [c_uint64, c_void_p, c_void_p]),
+    "paac_explore_bonus": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
     "paac_game_step": (c_int, [c_int, c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),

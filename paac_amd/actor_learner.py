@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, feature_stats, hip_ops, parallel, redo, window_stats
+from . import _lib, explore, feature_stats, hip_ops, parallel, redo, window_stats
 from .networks import Placeholder
 from .session import Saver, Session, checkpoint_key, tensor_of_key
 
@@ -84,6 +84,8 @@ class ActorLearner(object):
         self.feature_stats, self.dormant_tau, self.feature_rank_every = feature_stats.check_flags(args)
         # --redo_every W (paac_amd/redo.py): likewise; W > 0 needs the flag above
         self.redo_every = redo.check_flags(args)
+        # --explore_bonus BETA / --explore_bits / --explore_table_bits (paac_amd/explore.py): likewise; BETA = 0 is off
+        self.explore_beta, self.explore_bits, self.explore_table_bits = explore.check_flags(args)
         self.ppo_vclip = float(getattr(args, "ppo_vclip", 0.0))
         if not (0.0 <= self.ppo_vclip and math.isfinite(self.ppo_vclip)):          # (NaN fails the comparison)
             raise ValueError("ppo_vclip %r: expected a finite value >= 0 (0 = off)" % (self.ppo_vclip,))

@@ -6,6 +6,7 @@
 #include "fc_heads.h"
 #include "heads.h"
 #include "feature_stats.h"
+#include "explore.h"
 
 namespace paac {
 
@@ -2004,6 +2005,49 @@ int paac_feature_finish(const int32_t* units, const double* acc_f, const int64_t
                "the block");
   ProfScope ps(g_prof_ctx, F_MISC, units[3], (hipStream_t)stream);
   launch_k(feature_finish_kernel, dim3(1), dim3(256), (hipStream_t)stream, PROF_WHOLE, L, acc_f, acc_i, tau, out_scalars);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// --explore_bonus: the SimHash count bonus (kernels and their design: explore.h, instantiated here alone; spec and numpy twin:
+// paac_amd/explore.py; contract: include/paac_hip.h).
+int64_t paac_explore_scratch_words(int rows) { return rows >= 1 ? explore_scratch_words(rows) : 0; }
+
+int paac_explore_signs(uint64_t seed, void* signs_out, paac_stream_t stream) {
+  PAAC_REQUIRE(signs_out, "paac_explore_signs: null argument");
+  PAAC_REQUIRE(((uintptr_t)signs_out & 15) == 0, "paac_explore_signs: signs_out is not 16-byte aligned");
+  static_assert(PAAC_EXPLORE_SIGN_BYTES == kExpSteps * 4 * 64 * 16, "the sign operand's bytes");
+  hipLaunchKernelGGL(explore_signs_kernel, dim3(kExpSteps), dim3(256), 0, (hipStream_t)stream, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), reinterpret_cast<i32x4*>(signs_out));
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int paac_explore_bonus(const uint8_t* states, int rows, int bits, int table_bits, const void* signs, int32_t* counts,
+                       int32_t* scratch, float beta, float* rewards, float* bonus_out, uint64_t* codes_out,
+                       paac_stream_t stream) {
+  PAAC_REQUIRE(states && signs && counts && scratch && rewards && bonus_out, "paac_explore_bonus: null argument");
+  PAAC_REQUIRE(rows >= 1, "paac_explore_bonus: rows=%d (< 1)", rows);
+  PAAC_REQUIRE(bits >= 1 && bits <= 64, "paac_explore_bonus: bits=%d outside [1, 64]", bits);
+  PAAC_REQUIRE(table_bits >= 4 && table_bits <= 26, "paac_explore_bonus: table_bits=%d outside [4, 26]", table_bits);
+  PAAC_REQUIRE(beta >= 0.f && beta <= 3.402823466e38f, "paac_explore_bonus: beta %g is negative or not finite", (double)beta);   // (NaN fails)
+  PAAC_REQUIRE((((uintptr_t)states | (uintptr_t)signs) & 15) == 0, "paac_explore_bonus: states or signs not 16-byte aligned");
+  ExploreArgs a{};
+  a.states = states;
+  a.signs = reinterpret_cast<const i32x4*>(signs);
+  a.counts = counts;
+  a.scratch = scratch;
+  a.rewards = rewards;
+  a.bonus_out = bonus_out;
+  a.codes_out = codes_out;
+  a.rows = rows;
+  a.bits = bits;
+  a.table_bits = table_bits;
+  a.ksplit = explore_ksplit(rows);
+  a.groups = (rows + kExpRowsWg - 1) / kExpRowsWg;
+  a.beta = beta;
+  ProfScope ps(g_prof_ctx, F_MISC, rows, (hipStream_t)stream);
+  launch_k(explore_kernel, dim3((unsigned)(a.groups * a.ksplit)), dim3(256), (hipStream_t)stream, PROF_WHOLE, a);
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

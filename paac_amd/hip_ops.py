@@ -787,6 +787,43 @@ def feature_finish(lay, acc_f, acc_i, tau, out):
                                                _ptr(out, torch.float64, fs.FINISH_SCALARS, "out"), _stream()), "paac_feature_finish")
 
 
+class ExploreBlock(object):
+    """What --explore_bonus keeps on the device for a run: the packed sign operand of its seed, the table of visit counts and the
+    projection's scratch for calls of up to `rows` rows."""
+
+    def __init__(self, signs, counts, scratch, bits, table_bits, rows):
+        self.signs, self.counts, self.scratch = signs, counts, scratch
+        self.bits, self.table_bits, self.rows = bits, table_bits, rows
+
+
+def explore_block(device, seed, bits, table_bits, rows):
+    """An empty --explore_bonus block on `device` with the sign operand of `seed` built (include/paac_hip.h: paac_explore_signs;
+    spec: paac_amd/explore.py)."""
+    lib = _lib.load()
+    signs = torch.empty(_lib.EXPLORE_SIGN_BYTES, dtype=torch.int8, device=device)
+    _lib.check(lib.paac_explore_signs(int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(signs, torch.int8, name="signs"), _stream()),
+               "paac_explore_signs")
+    words = int(lib.paac_explore_scratch_words(int(rows)))
+    if words <= 0:
+        raise ValueError("explore_block: rows=%d (< 1)" % rows)
+    return ExploreBlock(signs, torch.zeros(1 << int(table_bits), dtype=torch.int32, device=device),
+                        torch.zeros(words, dtype=torch.int32, device=device), int(bits), int(table_bits), int(rows))
+
+
+def explore_bonus(block, states, beta, rewards, bonus_out, codes_out=None):
+    """--explore_bonus: one call (include/paac_hip.h: paac_explore_bonus).  states uint8 [rows, 84, 84, 4] (any shape of
+    rows * 28224 bytes); rewards (added to in place) and bonus_out float32 of `rows` elements; codes_out int64[rows] (the
+    codes' 64 bits) or None."""
+    rows = states.numel() // _lib.EXPLORE_K
+    if rows < 1 or rows > block.rows or states.numel() != rows * _lib.EXPLORE_K:
+        raise ValueError("explore_bonus: %d bytes of states are not 1..%d stacks of %d" % (states.numel(), block.rows, _lib.EXPLORE_K))
+    _lib.check(_lib.load().paac_explore_bonus(
+        _ptr(states, torch.uint8, name="states"), rows, block.bits, block.table_bits, _ptr(block.signs, torch.int8, name="signs"),
+        _ptr(block.counts, torch.int32, 1 << block.table_bits, "counts"), _ptr(block.scratch, torch.int32, name="scratch"),
+        float(beta), _ptr(rewards, torch.float32, rows, "rewards"), _ptr(bonus_out, torch.float32, rows, "bonus_out"),
+        _ptr(codes_out, torch.int64, rows, "codes_out", optional=True), _stream()), "paac_explore_bonus")
+
+
 FEATURE_CHUNK_ROWS = _FeatureConstant(0)          # rows whose products the Gram kernel sums in fp32 (int(...) reads the library)
 FEATURE_UNIT_FP32_TERMS = _FeatureConstant(3)     # terms of a unit sum added in fp32 before fp64 takes over
 

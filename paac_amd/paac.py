@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from . import feature_stats, hip_ops, logger_utils, parallel, redo, sticky, window_stats
+from . import explore, feature_stats, hip_ops, logger_utils, parallel, redo, sticky, window_stats
 from .actor_learner import ActorLearner
 from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Runners
 
@@ -93,6 +93,7 @@ class DeviceRollout(object):
     prev = None        # --sticky_action_p: the ring of previously executed actions, allocated by __init__ only with P > 0 and a game
     sticky_p = 0.0
     features = None    # --feature_stats: the (acc_f, acc_i, layout) block (paac_amd/feature_stats.py), allocated by __init__ only with the flag on
+    explore = None     # --explore_bonus: the hip_ops.ExploreBlock (paac_amd/explore.py), created by __init__ only with BETA > 0
     window_f = window_i = None   # --window_stats: the accumulator block (paac_amd/window_stats.py), allocated by __init__ only with the flag on
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
@@ -184,6 +185,14 @@ class DeviceRollout(object):
             if parallel.collectives_active():
                 raise ValueError(feature_stats.DATA_PARALLEL_REFUSAL)
             self.features = hip_ops.feature_block(dev, L.network.arch_id)
+        # --explore_bonus BETA: the sign operand of random_seed, the table of visit counts and the plane the cycle's one launch
+        # leaves its bonuses in (_rollout_and_first_backward).  Off: no block, no launch, the same graphs
+        if getattr(L, "explore_beta", 0.0) > 0.0:
+            if parallel.collectives_active():
+                raise ValueError(explore.DATA_PARALLEL_REFUSAL)
+            self.explore = hip_ops.explore_block(dev, int(getattr(getattr(L, "args", None), "random_seed", 3)), L.explore_bits,
+                                                 L.explore_table_bits, T * N)
+            self.bonus = torch.zeros((T, N), dtype=torch.float32, device=dev)
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
         if env_spec.get("raw_frames"):
@@ -372,6 +381,12 @@ class DeviceRollout(object):
             L.ctx.bootstrap_forward_trunk(params, self.states[self._slot(parity, T)], T * N)
         else:
             L.ctx.train_forward_trunk(params, self.states[parity * T:(parity + 1) * T + 1].view((T + 1) * N, 84, 84, 4))
+        # --explore_bonus: the cycle's one launch, on the T * N stacks the steps arrived in (ring slots parity * T + 1 .. + T),
+        # in front of everything that reads the rewards plane.  Behind the bootstrap forward, not the last acting step: the
+        # pipelined act_step route writes the last step's rewards from that forward's fc launch
+        if self.explore is not None:
+            hip_ops.explore_bonus(self.explore, self.states[parity * T + 1:parity * T + T + 1], L.explore_beta, self.rewards,
+                                  self.bonus)
         phase = ((0 if self.single_exchange else 1) if self.phased else 3)
         if L.minibatch_on:
             self._record_and_first_minibatch(parity, phase)
@@ -1070,6 +1085,14 @@ class PAACLearner(ActorLearner):
                     self._window_record(window)
                 if features is not None:
                     self._features_record(features)
+                if self.rollout.explore is not None and self.metrics is not None:
+                    # --explore_bonus: the `explore` record (the loop has synchronised: two small eager reads)
+                    with torch.cuda.stream(self.rollout.stream):
+                        occupied = int(torch.count_nonzero(self.rollout.explore.counts).item())
+                        plane = self.rollout.bonus.cpu().numpy()
+                    self.metrics.write("explore", global_step=int(self.global_step),
+                                       **explore.record(self.explore_beta, self.explore_bits, self.explore_table_bits, plane, occupied))
+                    self.metrics.flush()
             if pool is not None and pool.schedule.due(self.global_step):
                 # a pool event, between two run_cycles calls and on the rollout's stream: two device-to-device copies and the
                 # repack, queued behind the cycles already issued -- nothing here waits for the GPU
@@ -1127,6 +1150,9 @@ class PAACLearner(ActorLearner):
 
     # -- host-environment loop (the reference's structure, kernels instead of session.run) ------------
     def _train_host(self):
+        if self.explore_beta > 0.0:          # (--host_environments true was refused at start-up; this is an emulator without a device twin)
+            raise ValueError("--explore_bonus %g needs the device loop: the host loop keeps no observation ring on the GPU"
+                             % self.explore_beta)
         dev = self.torch_device
         N, T, A = self.emulator_counts, self.max_local_steps, self.num_actions
         counter = 0

@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import duel_pool, environment_creator, evaluation, feature_stats, logger_utils, match, parallel, redo, sticky, window_stats
+from . import duel_pool, environment_creator, evaluation, explore, feature_stats, logger_utils, match, parallel, redo, sticky, window_stats
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -152,6 +152,16 @@ BUILD_FLAGS = (
      "outgoing weights are zeroed and their optimizer slots reset, and a 'redo' record goes to metrics.jsonl; a layer whose "
      "units are all silent is left alone; device and host loops, one GPU only.  A recycle costs one log boundary every W "
      "windows and nothing per cycle; evaluation does not read the flag"),
+    (("--explore_bonus",), "explore_bonus", 0.0, float,
+     "device loop: 0 = off; BETA > 0 = every reward of the rollout gains BETA / sqrt(n), n = how often a SimHash code of the "
+     "observation the step arrived in has been seen in this run (\"#Exploration\", Tang et al., arXiv 1611.04717; "
+     "paac_amd/explore.py), computed on the GPU in one launch per cycle; every device emulator (duel: every learner row); the "
+     "returns and --window_stats read the shaped rewards, episode scores and --eval_every stay extrinsic; an 'explore' record "
+     "follows every 'progress' record; the table is not checkpointed; refused with --host_environments true and on more than "
+     "one GPU; evaluation does not read the flag"),
+    (("--explore_bits",), "explore_bits", 32, int, "--explore_bonus: bits of the SimHash code, 1 to 64"),
+    (("--explore_table_bits",), "explore_table_bits", 20, int,
+     "--explore_bonus: the table of visit counts has 2^B int32 entries, B in 4 to 26; colliding codes share a counter"),
     (("--eval_every",), "eval_every", 0, int,
      "device loop, --emulator catch|bricks|rally: score the current policy on --eval_count held-out game instances (seed random_seed "
      "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "
@@ -269,6 +279,7 @@ def main(args):
     window_stats.check_flags(args, world)         # ... and --window_stats'
     feature_stats.check_flags(args, world)        # ... and --feature_stats'
     redo.check_flags(args, world)                 # ... and --redo_every's
+    explore.check_flags(args, world)              # ... and --explore_bonus'
     sticky.check_flags(args)                      # ... and --sticky_action_p's
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)

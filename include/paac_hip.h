@@ -712,6 +712,31 @@ int paac_explore_bonus(const uint8_t* states, int rows, int bits, int table_bits
                        int32_t* scratch, float beta, float* rewards, float* bonus_out, uint64_t* codes_out,
                        paac_stream_t stream);
 
+/* --explore_kind rnd (spec and float64 numpy twin: paac_amd/rnd.py): a Random Network Distillation bonus (Burda et al., arXiv
+ * 1810.12894).  Kernels and their design: csrc/rnd.h.  THREE launches on `stream`, capturable, no host synchronisation.
+ *   nets     target (read only), predictor and the Adam slots adam_m / adam_v: device float[PAAC_RND_NET_FLOATS] each, flat
+ *            W1 [196, 256] | b1 [256] | W2 [256, 64] | b2 [64]; h = relu(u W1 + b1), o = h W2 + b2.  The caller fills both nets
+ *            (the twin draws them) and zeroes the slots.
+ *   input    states: device uint8[rows][28224], 16-byte aligned.  u[r][14 cy + cx] = float(the sum of the 6 x 6 bytes
+ *            x[r][6 cy + dy][6 cx + dx][3]) / 9180.
+ *   call     raw_out[r] = (1 / 64) sum_j (o_p - o_t)[r][j]^2 on the predictor's pre-step weights.  norm: device double[2], m and
+ *            the call count, zero before the first call: m = mean_r raw^2 on the first call, 0.99 m + 0.01 mean_r raw^2 after
+ *            it (the mean in float64 in a fixed order).  bonus_out[r] = float(beta * raw / (sqrt(m) + 1e-8)), rewards[r] +=
+ *            bonus_out[r].  Then the predictor takes one bias-corrected Adam step (lr, beta1, beta2, eps; t = the call count)
+ *            on the exact gradient of L = (1 / rows) sum_r raw[r]; grad_out: device float[PAAC_RND_NET_FLOATS] or null, that
+ *            gradient.  scratch: device int32[the size query's words], 16-byte aligned; word 0 is a ticket, zero before
+ *            the first call and after every call; the rest is written before it is read.
+ *   Sums run on fp32 matrix instructions in a fixed order, without floating-point atomics: two calls on the same inputs and
+ *   state give the same bits, eager or replayed; against the float64 twin the difference is fp32 accumulation error.
+ * Refused with a message, without a launch: a null pointer (grad_out excepted); rows outside [1, 2^24]; a beta that is negative
+ * or not finite; lr or eps not finite and > 0; beta1 or beta2 outside [0, 1); states, target, predictor or scratch not 16-byte
+ * aligned. */
+#define PAAC_RND_NET_FLOATS 66880
+int64_t paac_rnd_scratch_words(int rows);
+int paac_rnd_bonus(const uint8_t* states, int rows, const float* target, float* predictor, float* adam_m, float* adam_v,
+                   double* norm, int32_t* scratch, double beta, double lr, double beta1, double beta2, double eps, float* rewards,
+                   float* bonus_out, float* raw_out, float* grad_out, paac_stream_t stream);
+
 /* paac.py:34-45 bit-exact: probs - float32.epsneg, then numpy legacy multinomial(1, p) per env in
  * index order on ONE MT19937 stream.  mt_state: device uint32[625] = numpy key[624] + pos, advanced
  * in place (import/export with np.random.get_state()/set_state()).  scratch: device, >=

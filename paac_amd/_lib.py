@@ -141,6 +141,8 @@ _SIGNATURES = {
     "paac_explore_signs": (c_int, [c_uint64, c_void_p, c_void_p]),
     "paac_explore_bonus": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
+    "paac_rnd_scratch_words": (c_int64, [c_int]),
+    "paac_rnd_bonus": (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_double] * 5 + [c_void_p] * 5),
     "paac_game_step": (c_int, [c_int, c_uint64, c_uint32, c_int] + [c_void_p] * 7 + [POINTER(EnvRecords), c_int, c_void_p]),
     "paac_grad_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "paac_grad_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, explore, feature_stats, hip_ops, parallel, redo, window_stats
+from . import _lib, explore, feature_stats, hip_ops, parallel, redo, rnd, window_stats
 from .networks import Placeholder
 from .session import Saver, Session, checkpoint_key, tensor_of_key
 
@@ -86,6 +86,11 @@ class ActorLearner(object):
         self.redo_every = redo.check_flags(args)
         # --explore_bonus BETA / --explore_bits / --explore_table_bits (paac_amd/explore.py): likewise; BETA = 0 is off
         self.explore_beta, self.explore_bits, self.explore_table_bits = explore.check_flags(args)
+        # --explore_kind simhash|rnd / --rnd_lr (paac_amd/rnd.py): what BETA scales; likewise
+        self.explore_kind, self.rnd_lr = rnd.check_flags(args)
+        if self.explore_beta > 0.0 and self.explore_kind == "rnd":
+            logging.info("--explore_kind rnd: --explore_bits %d and --explore_table_bits %d are SimHash's and are ignored",
+                         self.explore_bits, self.explore_table_bits)
         self.ppo_vclip = float(getattr(args, "ppo_vclip", 0.0))
         if not (0.0 <= self.ppo_vclip and math.isfinite(self.ppo_vclip)):          # (NaN fails the comparison)
             raise ValueError("ppo_vclip %r: expected a finite value >= 0 (0 = off)" % (self.ppo_vclip,))

@@ -7,6 +7,7 @@
 #include "heads.h"
 #include "feature_stats.h"
 #include "explore.h"
+#include "rnd.h"
 
 namespace paac {
 
@@ -2048,6 +2049,66 @@ int paac_explore_bonus(const uint8_t* states, int rows, int bits, int table_bits
   a.beta = beta;
   ProfScope ps(g_prof_ctx, F_MISC, rows, (hipStream_t)stream);
   launch_k(explore_kernel, dim3((unsigned)(a.groups * a.ksplit)), dim3(256), (hipStream_t)stream, PROF_WHOLE, a);
+  PAAC_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// --explore_kind rnd: the Random Network Distillation bonus (kernels and their design: rnd.h, instantiated here alone; spec and
+// float64 numpy twin: paac_amd/rnd.py; contract: include/paac_hip.h).
+int64_t paac_rnd_scratch_words(int rows) { return rows >= 1 ? rnd_scratch_words(rows) : 0; }
+
+int paac_rnd_bonus(const uint8_t* states, int rows, const float* target, float* predictor, float* adam_m, float* adam_v,
+                   double* norm, int32_t* scratch, double beta, double lr, double beta1, double beta2, double eps, float* rewards,
+                   float* bonus_out, float* raw_out, float* grad_out, paac_stream_t stream) {
+  PAAC_REQUIRE(states && target && predictor && adam_m && adam_v && norm && scratch && rewards && bonus_out && raw_out,
+               "paac_rnd_bonus: null argument");
+  PAAC_REQUIRE(rows >= 1 && rows <= (1 << 24), "paac_rnd_bonus: rows=%d outside [1, 2^24]", rows);
+  PAAC_REQUIRE(beta >= 0.0 && beta <= 3.402823466e38, "paac_rnd_bonus: beta %g is negative or not finite", beta);   // (NaN fails)
+  PAAC_REQUIRE(lr > 0.0 && lr <= 3.402823466e38, "paac_rnd_bonus: lr %g is not a finite value > 0", lr);
+  PAAC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "paac_rnd_bonus: beta1 %g or beta2 %g outside [0, 1)",
+               beta1, beta2);
+  PAAC_REQUIRE(eps > 0.0 && eps <= 3.402823466e38, "paac_rnd_bonus: eps %g is not a finite value > 0", eps);
+  PAAC_REQUIRE((((uintptr_t)states | (uintptr_t)target | (uintptr_t)predictor | (uintptr_t)scratch) & 15) == 0,
+               "paac_rnd_bonus: states, target, predictor or scratch not 16-byte aligned");
+  const int rp = rnd_padded_rows(rows), tiles = rp / 16;
+  RndArgs a{};
+  a.states = states;
+  a.target = target;
+  a.predictor = predictor;
+  a.mom = adam_m;
+  a.var = adam_v;
+  a.norm = norm;
+  a.ticket = scratch;
+  a.U = reinterpret_cast<float*>(scratch) + kRndHead;
+  a.HT = a.U + (size_t)rp * kRndUS;
+  a.HP = a.HT + (size_t)rp * kRndH;
+  a.DO = a.HP + (size_t)rp * kRndHS;
+  a.DH = a.DO + (size_t)rp * kRndO;
+  a.rewards = rewards;
+  a.bonus_out = bonus_out;
+  a.raw_out = raw_out;
+  a.grad_out = grad_out;
+  a.rows = rows;
+  a.rows_padded = rp;
+  a.do_scale = (float)(2.0 / ((double)kRndO * rows));
+  a.beta = beta;
+  a.lr = lr;
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  const hipStream_t s = (hipStream_t)stream;
+  {          // (one timing scope per launch: tools/probe_rnd.py reads the three)
+    ProfScope ps(g_prof_ctx, F_MISC, rows, s);
+    launch_k(rnd_hidden_kernel, dim3((unsigned)(tiles * 4)), dim3(256), s, PROF_WHOLE, a);
+  }
+  {
+    ProfScope ps(g_prof_ctx, F_MISC, rows, s);
+    launch_k(rnd_error_kernel, dim3((unsigned)tiles), dim3(256), s, PROF_WHOLE, a, tiles);
+  }
+  {
+    ProfScope ps(g_prof_ctx, F_MISC, rows, s);
+    launch_k(rnd_step_kernel, dim3(kRndTiles1 + kRndTiles2), dim3(256), s, PROF_WHOLE, a);
+  }
   PAAC_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -824,7 +824,47 @@ def explore_bonus(block, states, beta, rewards, bonus_out, codes_out=None):
         _ptr(codes_out, torch.int64, rows, "codes_out", optional=True), _stream()), "paac_explore_bonus")
 
 
-FEATURE_CHUNK_ROWS = _FeatureConstant(0)          # rows whose products the Gram kernel sums in fp32 (int(...) reads the library)
+class RndBlock(object):
+    """What --explore_kind rnd keeps on the device for a run: the target and predictor nets of its seed, the predictor's Adam
+    slots, the normaliser (m, the call count), the last call's raw errors and the scratch for calls of up to `rows` rows."""
+
+    def __init__(self, target, predictor, adam_m, adam_v, norm, raw, scratch, rows):
+        self.target, self.predictor, self.adam_m, self.adam_v = target, predictor, adam_m, adam_v
+        self.norm, self.raw, self.scratch, self.rows = norm, raw, scratch, rows
+
+
+def rnd_block(device, seed, rows):
+    """A fresh --explore_kind rnd block on `device`: both nets drawn on the host by the twin's law (paac_amd/rnd.py: draw) and
+    uploaded, everything else zero (include/paac_hip.h: paac_rnd_bonus)."""
+    from . import rnd
+    words = int(_lib.load().paac_rnd_scratch_words(int(rows)))
+    if words <= 0:
+        raise ValueError("rnd_block: rows=%d (< 1)" % rows)
+    nets = [torch.from_numpy(rnd.draw(seed, stream)).to(device) for stream in (rnd.TARGET_STREAM, rnd.PREDICTOR_STREAM)]
+    zeros = lambda n, dtype: torch.zeros(n, dtype=dtype, device=device)
+    return RndBlock(nets[0], nets[1], zeros(rnd.NET, torch.float32), zeros(rnd.NET, torch.float32), zeros(2, torch.float64),
+                    zeros(int(rows), torch.float32), zeros(words, torch.int32), int(rows))
+
+
+def rnd_bonus(block, states, beta, lr, rewards, bonus_out, grad_out=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    """--explore_kind rnd: one call, three launches (include/paac_hip.h: paac_rnd_bonus).  states uint8 [rows, 84, 84, 4] (any
+    shape of rows * 28224 bytes); rewards (added to in place) and bonus_out float32 of `rows` elements; the raw errors go to
+    block.raw[:rows]; grad_out float32[rnd.NET] (the predictor's gradient before Adam) or None."""
+    from . import rnd
+    rows = states.numel() // _lib.EXPLORE_K
+    if rows < 1 or rows > block.rows or states.numel() != rows * _lib.EXPLORE_K:
+        raise ValueError("rnd_bonus: %d bytes of states are not 1..%d stacks of %d" % (states.numel(), block.rows, _lib.EXPLORE_K))
+    net = lambda t, name: _ptr(t, torch.float32, rnd.NET, name)
+    _lib.check(_lib.load().paac_rnd_bonus(
+        _ptr(states, torch.uint8, name="states"), rows, net(block.target, "target"), net(block.predictor, "predictor"),
+        net(block.adam_m, "adam_m"), net(block.adam_v, "adam_v"), _ptr(block.norm, torch.float64, 2, "norm"),
+        _ptr(block.scratch, torch.int32, name="scratch"), float(beta), float(lr), float(beta1), float(beta2), float(eps),
+        _ptr(rewards, torch.float32, rows, "rewards"), _ptr(bonus_out, torch.float32, rows, "bonus_out"),
+        _ptr(block.raw, torch.float32, name="raw"), _ptr(grad_out, torch.float32, rnd.NET, "grad_out", optional=True), _stream()),
+        "paac_rnd_bonus")
+
+
+FEATURE_CHUNK_ROWS = _FeatureConstant(0)         # rows whose products the Gram kernel sums in fp32 (int(...) reads the library)
 FEATURE_UNIT_FP32_TERMS = _FeatureConstant(3)     # terms of a unit sum added in fp32 before fp64 takes over
 
 

@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from . import explore, feature_stats, hip_ops, logger_utils, parallel, redo, sticky, window_stats
+from . import explore, feature_stats, hip_ops, logger_utils, parallel, redo, rnd, sticky, window_stats
 from .actor_learner import ActorLearner
 from .runners import TRUNCATED_ATTRIBUTE, EmulatorRunner, RawEmulatorRunner, Runners
 
@@ -94,6 +94,7 @@ class DeviceRollout(object):
     sticky_p = 0.0
     features = None    # --feature_stats: the (acc_f, acc_i, layout) block (paac_amd/feature_stats.py), allocated by __init__ only with the flag on
     explore = None     # --explore_bonus: the hip_ops.ExploreBlock (paac_amd/explore.py), created by __init__ only with BETA > 0
+    rnd = None         # --explore_kind rnd: the hip_ops.RndBlock (paac_amd/rnd.py) in its place
     window_f = window_i = None   # --window_stats: the accumulator block (paac_amd/window_stats.py), allocated by __init__ only with the flag on
 
     def __init__(self, learner, env_spec, sampler="philox", sampler_seed=42, env_offset=0, use_graph=True,
@@ -190,8 +191,12 @@ class DeviceRollout(object):
         if getattr(L, "explore_beta", 0.0) > 0.0:
             if parallel.collectives_active():
                 raise ValueError(explore.DATA_PARALLEL_REFUSAL)
-            self.explore = hip_ops.explore_block(dev, int(getattr(getattr(L, "args", None), "random_seed", 3)), L.explore_bits,
-                                                 L.explore_table_bits, T * N)
+            seed = int(getattr(getattr(L, "args", None), "random_seed", 3))
+            if getattr(L, "explore_kind", "simhash") == "rnd":
+                # --explore_kind rnd: both nets of random_seed, the predictor's Adam slots and the normaliser instead; the same plane
+                self.rnd = hip_ops.rnd_block(dev, seed, T * N)
+            else:
+                self.explore = hip_ops.explore_block(dev, seed, L.explore_bits, L.explore_table_bits, T * N)
             self.bonus = torch.zeros((T, N), dtype=torch.float32, device=dev)
         # lets the large shards' sampler spread its walk over several workgroups (hip_ops.sample_mt_synth_step)
         self.walk_scratch = hip_ops.walk_scratch(N, A, dev) if N * (A - 1) <= hip_ops.FUSED_SAMPLE_MAX_DRAWS else None
@@ -387,6 +392,9 @@ class DeviceRollout(object):
         if self.explore is not None:
             hip_ops.explore_bonus(self.explore, self.states[parity * T + 1:parity * T + T + 1], L.explore_beta, self.rewards,
                                   self.bonus)
+        if self.rnd is not None:          # --explore_kind rnd: its three launches in the same place, on the same rows
+            hip_ops.rnd_bonus(self.rnd, self.states[parity * T + 1:parity * T + T + 1], L.explore_beta, L.rnd_lr, self.rewards,
+                              self.bonus)
         phase = ((0 if self.single_exchange else 1) if self.phased else 3)
         if L.minibatch_on:
             self._record_and_first_minibatch(parity, phase)
@@ -1092,6 +1100,14 @@ class PAACLearner(ActorLearner):
                         plane = self.rollout.bonus.cpu().numpy()
                     self.metrics.write("explore", global_step=int(self.global_step),
                                        **explore.record(self.explore_beta, self.explore_bits, self.explore_table_bits, plane, occupied))
+                    self.metrics.flush()
+                if self.rollout.rnd is not None and self.metrics is not None:
+                    # --explore_kind rnd: the `explore` record (the loop has synchronised: three small eager reads)
+                    with torch.cuda.stream(self.rollout.stream):
+                        plane, raw = self.rollout.bonus.cpu().numpy(), self.rollout.rnd.raw.cpu().numpy()
+                        m = float(self.rollout.rnd.norm[0].item())
+                    self.metrics.write("explore", global_step=int(self.global_step),
+                                       **rnd.record(self.explore_beta, self.rnd_lr, plane, raw, m))
                     self.metrics.flush()
             if pool is not None and pool.schedule.due(self.global_step):
                 # a pool event, between two run_cycles calls and on the rollout's stream: two device-to-device copies and the

@@ -13,7 +13,7 @@ import os
 import signal
 import sys
 
-from . import duel_pool, environment_creator, evaluation, explore, feature_stats, logger_utils, match, parallel, redo, sticky, window_stats
+from . import duel_pool, environment_creator, evaluation, explore, feature_stats, logger_utils, match, parallel, redo, rnd, sticky, window_stats
 from .paac import PAACLearner
 from .policy_v_network import NaturePolicyVNetwork, NIPSPolicyVNetwork
 
@@ -162,6 +162,14 @@ BUILD_FLAGS = (
     (("--explore_bits",), "explore_bits", 32, int, "--explore_bonus: bits of the SimHash code, 1 to 64"),
     (("--explore_table_bits",), "explore_table_bits", 20, int,
      "--explore_bonus: the table of visit counts has 2^B int32 entries, B in 4 to 26; colliding codes share a counter"),
+    (("--explore_kind",), "explore_kind", "simhash", None,
+     "--explore_bonus: what BETA scales -- 'simhash', the count bonus above, or 'rnd', Random Network Distillation (Burda et al., "
+     "arXiv 1810.12894; paac_amd/rnd.py): a predictor network is trained online on the GPU, inside the cycle, to match a fixed "
+     "random network on a 14 x 14 thumbnail of the newest frame, and its error, divided by a running RMS, is the bonus; three "
+     "launches per cycle; --explore_bits and --explore_table_bits are then ignored; the predictor is not checkpointed; the "
+     "same refusals as simhash; evaluation does not read the flag"),
+    (("--rnd_lr",), "rnd_lr", 1e-4, float,
+     "--explore_kind rnd: the predictor's Adam learning rate, finite and > 0 -- how fast novelty decays"),
     (("--eval_every",), "eval_every", 0, int,
      "device loop, --emulator catch|bricks|rally: score the current policy on --eval_count held-out game instances (seed random_seed "
      "+ 1, up to 30 no-op steps, whole episodes) at the first chunk boundary at or after every multiple of this many global "
@@ -205,9 +213,10 @@ def get_arg_parser():
         kwargs = dict(dest=dest, default=default, help=text)
         if kind is not None:
             kwargs["type"] = kind
-        if dest in ("sampler", "emulator", "checkpoint_format", "optimizer"):
+        if dest in ("sampler", "emulator", "checkpoint_format", "optimizer", "explore_kind"):
             kwargs["choices"] = {"sampler": ["philox", "numpy"], "emulator": ["synthetic", "catch", "bricks", "rally", "duel", "user", "ale"],
-                                 "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"]}[dest]
+                                 "checkpoint_format": ["npz", "tf"], "optimizer": ["rmsprop", "adam"],
+                                 "explore_kind": list(rnd.KINDS)}[dest]
         parser.add_argument(*options, **kwargs)
     return parser
 
@@ -280,6 +289,7 @@ def main(args):
     feature_stats.check_flags(args, world)        # ... and --feature_stats'
     redo.check_flags(args, world)                 # ... and --redo_every's
     explore.check_flags(args, world)              # ... and --explore_bonus'
+    rnd.check_flags(args, world)                  # ... and --explore_kind's
     sticky.check_flags(args)                      # ... and --sticky_action_p's
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args)
